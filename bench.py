@@ -2,7 +2,7 @@
 """Headline benchmark: CLIP-ViP video-text contrastive training step on MI355X (BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W
-    (N>1: the script starts its own N ranks -- `python bench.py --gpus 8` re-executes itself under torch.distributed.run
+    (N>1: the script starts its own N ranks -- `python bench.py --gpus 8` runs itself under torch.distributed.run
      with one process per GPU on 127.0.0.1; under an external launcher -- python -m torch.distributed.run --nnodes=1
      --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ..., WORLD_SIZE set -- it just joins the group)
 
@@ -12,7 +12,14 @@ all-reduce overlapped with backward -> global-norm clip 5.0 -> AdamW step, on BA
 B=8 pairs, T=12 frames 224x224, 32 text tokens, bf16 compute / fp32 master weights, synthetic inputs resident
 in HBM, random-init weights of the named architecture.  Weak scaling: per-GPU batch fixed.
 
-Prints ONE JSON line on rank 0 (metric/value/..., plus `roofline` for the dominant kernel and `cpu_baseline`).
+Prints ONE JSON line on rank 0: metric / value / unit / higher_is_better / dtype / ms_per_step of the timed steps.  A plain
+run does only that: set up, warm up, time --steps steps, write --dump-outputs, print the line.  --full adds what takes runs of
+its own: `roofline` / `roofline_bwd` for the dominant kernels, the ViT-forward probes, the data-parallel diagnostics and
+`cpu_baseline`.
+
+--dump-outputs DIR writes what the last timed step computed, as float32 .npy files: loss, vis_features, text_features (this
+rank's) and params_sample (a fixed, seeded sample of every updated parameter; every element of the small ones).  The inputs
+and the initial weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -100,6 +107,10 @@ def parse():
     ap.add_argument("--launch-check", action="store_true", help="start the ranks, join the process group, print the world size "
                     "measured by a collective and exit (no GPU work; backend gloo when there is no GPU) -- the launcher self-test")
     ap.add_argument("--cpu-baseline-batch", type=int, default=8)
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the roofline kernels, the ViT-forward "
+                    "probes, the data-parallel diagnostics and the CPU baseline (a plain run times the steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step to DIR/<name>.npy "
+                    "(float32): loss, vis_features, text_features, params_sample")
     return ap.parse_args()
 
 
@@ -263,10 +274,12 @@ def workload_tag(a, W):
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` without a launcher: become `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-    --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` (one rank per GPU; the reference is started as
-    `horovodrun -np $NUM_GPUS python src/pretrain/run_pretrain.py`, CLIP-ViP/README.md:58).  Does not return."""
+    """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+    --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a child process (one rank per GPU; the reference is
+    started as `horovodrun -np $NUM_GPUS python src/pretrain/run_pretrain.py`, CLIP-ViP/README.md:58) and exit with its status.
+    Does not return."""
     import socket
+    import subprocess
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -276,7 +289,7 @@ def self_launch(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def parse_rccl_log(text):
@@ -344,6 +357,59 @@ def dp_diagnostics(step, reducer, sync, dev, rank, W, n_seen, cu_budget, steps=3
     return [info]
 
 
+def result_line(a, W, n_seen, dt, final_loss, cu_budget, forced, opt_overlap, use_graph, t_enq, c_proc, c_main):
+    """The fields of the JSON line that the timed steps give (every run; --full adds its separate measurements)."""
+    import xpretrain_amd.functional as XF
+    from xpretrain_amd import workload as O
+    rows = a.batch * (4 + a.frames * (a.res // a.patch) ** 2)
+    two_chains = XF.FWD_SPLIT and XF.LAYER_CALLS and a.batch % 2 == 0 and rows >= XF.FWD_SPLIT_MIN_ROWS
+    f_vis, f_txt = O.flops_per_pair(a.frames, a.res, a.txt_len, a.patch)
+    pairs_s = W * a.batch * a.steps / dt
+    step_flops = 3.0 * (f_vis + f_txt) * a.batch                     # per GPU, fwd+bwd convention (BASELINE.md §3)
+    return {
+        "metric": "video-text pairs/sec", "value": round(pairs_s, 3), "unit": "pairs/s", "n_gpus": W,
+        "n_ranks_seen": n_seen,
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"CLIP-ViP ViT-B/{a.patch} video-text contrastive train step (fwd+loss+bwd+grad-sync+"
+                               f"clip+AdamW), {a.frames} frames {a.res}^2, {a.txt_len} text tokens, "
+                               f"local batch {a.batch}, " + workload_tag(a, W),
+                   "global_batch": W * a.batch, "parallelism": f"dp{W}", "final_loss": round(final_loss, 4),
+                   "gemm_cu_budget": cu_budget, "grad_wire": os.environ.get("XPRETRAIN_GRAD_WIRE", "fp32"),
+                   "forced_one_rank_collectives": forced,
+                   "prefetch": ({"loader": "xpretrain_amd.utils.prefetch.PrefetchLoader", "host_frames": a.prefetch_dtype,
+                                 "copy_stream": {1: "own", 2: "text tower's", 3: "auto"}[a.prefetch]} if a.prefetch else None),
+                   "video_forward_chains": 2 if two_chains else 1,
+                   "optimizer_overlaps_next_forward_from_layer": opt_overlap,
+                   "second_chain_stream": XF.second_chain_stream_mode() if two_chains else None,
+                   "launch": "hipGraph replay of the captured step" if use_graph else "eager", "profile_run": bool(a.profile_run)},
+        "step_tflops_per_gpu": round(step_flops / (dt / a.steps) / 1e12, 1),
+        "step_frac_of_bf16_peak": round(step_flops / (dt / a.steps) / 1e12 / PEAK_BF16_TFLOPS, 4),
+        "host_cpu_ms_per_step": round(c_proc / a.steps * 1e3, 3),              # CPU time of ALL host threads per step
+        "host_main_thread_cpu_ms_per_step": round(c_main / a.steps * 1e3, 3),  # forward + optimizer thread alone
+        "host_enqueue_wall_ms_per_step": round(t_enq / a.steps * 1e3, 3),      # wall incl. queue back-pressure; not a cost
+    }
+
+
+def dump_outputs(out_dir, loss, last, model, per_param=4096, seed=0):
+    """The outputs of the last timed step as float32 .npy files in out_dir: loss, this rank's vis_features / text_features,
+    and params_sample -- every parameter after the update, in model.parameters() order: all elements of a tensor of at most
+    `per_param` elements, else `per_param` elements at indices drawn from a generator seeded with `seed` (~7 MB at cfg #2)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+    pieces = []
+    for p in model.parameters():
+        v = p.detach().reshape(-1)
+        if v.numel() > per_param:
+            v = v[torch.randint(0, v.numel(), (per_param,), generator=g).to(v.device)]
+        pieces.append(v.float().cpu())
+    arrays = {"loss": loss.detach().float().reshape(1).cpu(), "vis_features": last["vis_features"].detach().float().cpu(),
+              "text_features": last["text_features"].detach().float().cpu(), "params_sample": torch.cat(pieces)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy().astype(np.float32))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -357,7 +423,7 @@ def main():
         os.environ.setdefault("NCCL_MAX_NCHANNELS", "32")
         os.environ.setdefault("NCCL_ALGO", "Ring")
         os.environ.setdefault("NCCL_PROTO", "Simple")
-    if a.gpus > 1 or os.environ.get("XPRETRAIN_BENCH_FORCE_COLLECTIVES", "") in ("1", "gather", "reducer"):
+    if a.full and (a.gpus > 1 or os.environ.get("XPRETRAIN_BENCH_FORCE_COLLECTIVES", "") in ("1", "gather", "reducer")):
         # what RCCL actually chose (channels, algorithm, protocol per message size) goes to a per-process file that dp_diagnostics()
         # parses after the timed region: the first multi-GPU run then shows whether the defaults above were honoured
         if os.environ.get("NCCL_DEBUG", "VERSION").upper() in ("VERSION", "WARN"):      # (the image exports NCCL_DEBUG=VERSION)
@@ -446,6 +512,7 @@ def main():
     video, ids, mask = video.to(dev), ids.to(dev), mask.to(dev)
     logit_scale = model.clipmodel.logit_scale
     params = [p for p in model.parameters()]
+    last = {}                                  # this rank's features of the latest step (--dump-outputs)
 
     def step():
         nonlocal video, ids, mask
@@ -460,6 +527,7 @@ def main():
         else:
             vis, txt = D.gather_features(out["vis_features"], out["text_features"])
         loss = loss_fn(vis, txt, logit_scale)
+        last["vis_features"], last["text_features"] = out["vis_features"], out["text_features"]
         loss.backward()
         reducer.synchronize()
         lr_t = get_lr_sched(sched_step[0], "cosine", LR, TOTAL_STEPS, warmup_ratio=0.01)   # run_video_retrieval.py:372-383
@@ -516,6 +584,16 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = t.item()
     final_loss = loss.item()
+    if a.dump_outputs and rank == 0:                 # before anything else runs a step: the outputs of the last TIMED step
+        dump_outputs(a.dump_outputs, loss, last, model)
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(result_line(a, W, n_seen, dt, final_loss, cu_budget, forced, opt_overlap, use_graph,
+                                         t_enq, c_proc, c_main)), flush=True)
+        if W > 1 or forced:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
     dp_diag = dp_diagnostics(step, reducer, sync, dev, rank, W, n_seen, cu_budget) if (W > 1 or (forced and fmode != "gather")) else None
 
     # the dominant forward kernel timed WHERE IT RUNS: three more training steps with the library's GEMM timer armed for the fc1
@@ -579,8 +657,6 @@ def main():
 
     if rank == 0:
         f_vis, f_txt = O.flops_per_pair(a.frames, a.res, a.txt_len, a.patch)
-        pairs_s = W * a.batch * a.steps / dt
-        step_flops = 3.0 * (f_vis + f_txt) * a.batch                     # per GPU, fwd+bwd convention
         rows = a.batch * (4 + a.frames * (a.res // a.patch) ** 2)
         dom = time_dominant_kernels(dev, rows) if not a.profile_run else {"fwd": (0.0, 0.0), "bwd": (0.0, 0.0)}
         (k_tf_iso, k_ms_iso), (b_tf, b_ms) = dom["fwd"], dom["bwd"]
@@ -601,28 +677,8 @@ def main():
         full = rows == 18848
         tr_f, note_f = pmc_traffic("NT_fc1_fwd") if full else (None, "PMC summary exists for the cfg #2 shape only")
         tr_b, note_b = pmc_traffic("SS_dw1") if full else (None, "PMC summary exists for the cfg #2 shape only")
-        res = {
-            "metric": "video-text pairs/sec", "value": round(pairs_s, 3), "unit": "pairs/s", "n_gpus": W,
-            "n_ranks_seen": n_seen,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": f"CLIP-ViP ViT-B/{a.patch} video-text contrastive train step (fwd+loss+bwd+grad-sync+"
-                                   f"clip+AdamW), {a.frames} frames {a.res}^2, {a.txt_len} text tokens, "
-                                   f"local batch {a.batch}, " + workload_tag(a, W),
-                       "global_batch": W * a.batch, "parallelism": f"dp{W}", "final_loss": round(final_loss, 4),
-                       "gemm_cu_budget": cu_budget, "grad_wire": os.environ.get("XPRETRAIN_GRAD_WIRE", "fp32"),
-                       "forced_one_rank_collectives": forced,
-                       "prefetch": ({"loader": "xpretrain_amd.utils.prefetch.PrefetchLoader", "host_frames": a.prefetch_dtype,
-                                     "copy_stream": {1: "own", 2: "text tower's", 3: "auto"}[a.prefetch]} if a.prefetch else None),
-                       "video_forward_chains": 2 if two_chains else 1,
-                       "optimizer_overlaps_next_forward_from_layer": opt_overlap,
-                       "second_chain_stream": XF.second_chain_stream_mode() if two_chains else None,
-                       "launch": "hipGraph replay of the captured step" if use_graph else "eager", "profile_run": bool(a.profile_run)},
-            "step_tflops_per_gpu": round(step_flops / (dt / a.steps) / 1e12, 1),
-            "step_frac_of_bf16_peak": round(step_flops / (dt / a.steps) / 1e12 / PEAK_BF16_TFLOPS, 4),
-            "host_cpu_ms_per_step": round(c_proc / a.steps * 1e3, 3),              # CPU time of ALL host threads per step
-            "host_main_thread_cpu_ms_per_step": round(c_main / a.steps * 1e3, 3),  # forward + optimizer thread alone
-            "host_enqueue_wall_ms_per_step": round(t_enq / a.steps * 1e3, 3),      # wall incl. queue back-pressure; not a cost
+        res = result_line(a, W, n_seen, dt, final_loss, cu_budget, forced, opt_overlap, use_graph, t_enq, c_proc, c_main)
+        res.update({
             # the ViT forward as the training step runs it (activations and the MLP pre-activation kept): north_star's 0.40 target
             "vit_forward_train_mode_ms": round(vit_fwd_train_ms, 3),
             "vit_forward_frac_of_bf16_peak": round(f_vis * a.batch / (vit_fwd_train_ms * 1e-3) / 1e12 / PEAK_BF16_TFLOPS, 4) if vit_fwd_train_ms else 0.0,
@@ -664,7 +720,7 @@ def main():
                                  "workgroups": 36 * dw1_split, "frac_of_held_cus": round(bw_tf / PEAK_BF16_TFLOPS * 256.0 / min(256, 36 * dw1_split), 4)},
                              "traffic": tr_b, "traffic_unit": "bytes/launch (GEMM kernel only)", "traffic_source": note_b,
                              "algorithmic_bytes": (rows * 3072 + rows * 768) * 2 + 3072 * 768 * 4},
-        }
+        })
         if dp_diag is not None:                        # one entry per rank: what the data-parallel machinery did on it
             res["data_parallel"] = dp_diag
         if not a.no_cpu_baseline and not a.profile_run and W == 1:           # reported baseline, rank 0 of the single-GPU run only

@@ -7,8 +7,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu via gpurun)")
@@ -16,11 +14,8 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import torch
-
-    def load(name):
-        return torch.load(os.path.join(GOLDEN, name), map_location="cpu", weights_only=False)
-    return load
+    from tests.gpu_util import load_golden
+    return load_golden
 
 
 # Run order of the GPU suite: per-kernel parity files first, then the model-level parity files, then the long full-size /

@@ -29,6 +29,14 @@ Fixtures (all fp32, CPU, torch.manual_seed'ed):
                      loss is identically 0.)
   optim.pt           src/optimization: AdamW.step x 6 with clip_grad_norm_ 5.0 and the warmup-cosine schedule
                      over the four build_e2e_optimizer_w_lr_mul groups; get_lr_sched tables.
+  reference_cfg1.pt  BASELINE cfg #1's architecture (ViT-B/32, 2 frames, 16 text tokens) at batch 2 through the reference
+                     VidCLIP.forward + NCELearnableTempLoss, weights rebuilt from a seed: features, loss and a fingerprint
+                     of the weights.
+  pretrain_vip_base_16.json  the reference's shipped pre-training config (src/configs/pretrain/), copied verbatim: settings only,
+                     read by tests/test_configs_cpu.py.
+
+A fixture larger than 1000 KiB is written as the byte pieces <name>.0, <name>.1, ... (tests/gpu_util.py::save_golden);
+the tests read every fixture through tests/gpu_util.py::load_golden.
 """
 import math
 import os
@@ -42,6 +50,7 @@ sys.path.insert(0, ROOT)
 
 from oracle import ref_import  # noqa: E402
 from oracle import clipvip_oracle as O  # noqa: E402
+from tests.gpu_util import save_golden  # noqa: E402
 
 TINY = dict(vision_hidden=128, vision_heads=2, vision_layers=2, vision_inter=192, patch=8, image=32,
             text_hidden=128, text_heads=2, text_layers=2, text_inter=192, vocab=120, max_pos=16, proj=64)
@@ -97,7 +106,7 @@ def tiny_e2e(ref):
         text_hidden=[h.detach() for h in to.hidden_states], text_last=to.last_hidden_state.detach(),
         text_pooled=to.pooler_output.detach(),
     )
-    torch.save(fx, os.path.join(HERE, "tiny_e2e.pt"))
+    save_golden(fx, "tiny_e2e.pt")
     print("tiny_e2e: loss", float(loss), "params", sum(p.numel() for p in model.parameters()))
 
 
@@ -148,9 +157,32 @@ def full_size(ref, name, frames, res, B=2, txt_len=32, patch=16, temporal_size=1
               vision_hidden=[h[:, rows].detach().half() for h in vo.hidden_states] if hidden else None,
               text_hidden=[h.detach().half() for h in to.hidden_states] if hidden else None,
               vision_pooled=vo.pooler_output.detach(), text_pooled=to.pooler_output.detach(), grads=grads, ref_bf16=ref_bf16)
-    torch.save(fx, os.path.join(HERE, name))
+    files = save_golden(fx, name)
     print(name, "reference bf16 autocast vs fp32:", ref_bf16)
-    print(name, "loss", float(loss), "size MB", os.path.getsize(os.path.join(HERE, name)) / 1e6)
+    print(name, "loss", float(loss), "size MB", sum(os.path.getsize(f) for f in files) / 1e6)
+
+
+def reference_cfg1(ref):
+    """BASELINE cfg #1's architecture (ViT-B/32, T=2, Lt=16) at B=2 through the reference VidCLIP.forward +
+    NCELearnableTempLoss: features and loss.  The weights are this repo's model class under manual_seed(1234) (loaded into the
+    reference, as in full_size); their fingerprint (tests/gpu_util.py::weight_fingerprint) is stored beside the outputs."""
+    from tests.gpu_util import ModelArgs, weight_fingerprint
+    from xpretrain_amd.modeling import VidCLIP
+    torch.manual_seed(1234)
+    cfgd = O.vit_b_config(patch=32)
+    ours = VidCLIP(ModelArgs(cfgd, 12))
+    with torch.no_grad():
+        ours.clipmodel.vision_model.embeddings.temporal_embedding.normal_(0, 0.02)
+    model = ref.VidCLIP.VidCLIP(ref_import.make_args(cfgd, add_cls_num=3, temporal_size=12))
+    model.load_state_dict(ours.state_dict(), strict=True)
+    del ours
+    video, ids, mask = O.synthetic_inputs(2, 2, 224, 16)
+    with torch.no_grad():
+        out = model(video, ids, mask)
+        loss = ref.loss.NCELearnableTempLoss(None)(out["vis_features"], out["text_features"], model.clipmodel.logit_scale)
+    save_golden(dict(vis_features=out["vis_features"].clone(), text_features=out["text_features"].clone(), loss=loss.clone(),
+                     weights=weight_fingerprint(model.state_dict())), "reference_cfg1.pt")
+    print("reference_cfg1: loss", float(loss))
 
 
 def _attn_module(ref, D, H, seed):
@@ -177,7 +209,7 @@ def attn_forward2(ref):
         y.backward(gy)
         cases.append(dict(size=(M, N, L), D=D, H=H, x=x.detach(), y=y.detach(), gy=gy, gx=x.grad.clone(),
                           sd={k: v.detach().clone() for k, v in m.state_dict().items()}))
-    torch.save(cases, os.path.join(HERE, "attn_forward2.pt"))
+    save_golden(cases, "attn_forward2.pt")
     print("attn_forward2:", [c["size"] for c in cases])
 
 
@@ -203,7 +235,7 @@ def text_attn(ref):
         y.backward(gy)
         cases.append(dict(D=D, H=H, mask=mask, x=x.detach(), y=y.detach(), gy=gy, gx=x.grad.clone(),
                           sd={k: v.detach().clone() for k, v in m.state_dict().items()}))
-    torch.save(cases, os.path.join(HERE, "text_attn.pt"))
+    save_golden(cases, "text_attn.pt")
     print("text_attn:", len(cases))
 
 
@@ -230,8 +262,7 @@ def temporal_interp(ref):
                           g_patch=emb.patch_embedding.weight.grad.clone(),
                           g_pos=emb.position_embedding.weight.grad.clone(),
                           g_cls=emb.class_embedding.grad.clone(), g_added=emb.added_cls.grad.clone()))
-    torch.save(dict(sd={k: v.detach().clone() for k, v in emb.state_dict().items()}, cases=cases),
-               os.path.join(HERE, "temporal_interp.pt"))
+    save_golden(dict(sd={k: v.detach().clone() for k, v in emb.state_dict().items()}, cases=cases), "temporal_interp.pt")
     print("temporal_interp:", [c["T"] for c in cases])
 
 
@@ -251,7 +282,7 @@ def loss(ref):
             cases.append(dict(n=n, d=d, log_scale=ls, feats=[f.detach() for f in feats],
                               nce=l1.detach(), nce_grads=[g.clone() for g in g1],
                               vsc_fc=l2.detach(), vsc_fc_grads=[g.clone() for g in g2]))
-    torch.save(cases, os.path.join(HERE, "loss.pt"))
+    save_golden(cases, "loss.pt")
     print("loss:", len(cases))
 
 
@@ -289,11 +320,11 @@ def optim(ref):
             lrs.append(lr_t)
     table = {d: [sched.get_lr_sched(t, d, 3e-4, 50, warmup_ratio=0.1) for t in range(0, 56)]
              for d in ("linear", "cosine", "invsqrt", "constant")}
-    torch.save(dict(names=names, init=init, grads=grads, norms=norms, lrs=lrs, lr_mul=lr_mul, weight_decay=wd,
-                    betas=(0.9, 0.98), group_idx=group_idx, final=[p.detach().clone() for p in params],
-                    exp_avg=[opt.state[p]["exp_avg"].clone() for p in params],
-                    exp_avg_sq=[opt.state[p]["exp_avg_sq"].clone() for p in params], sched_table=table),
-               os.path.join(HERE, "optim.pt"))
+    save_golden(dict(names=names, init=init, grads=grads, norms=norms, lrs=lrs, lr_mul=lr_mul, weight_decay=wd,
+                     betas=(0.9, 0.98), group_idx=group_idx, final=[p.detach().clone() for p in params],
+                     exp_avg=[opt.state[p]["exp_avg"].clone() for p in params],
+                     exp_avg_sq=[opt.state[p]["exp_avg_sq"].clone() for p in params], sched_table=table),
+                 "optim.pt")
     print("optim: steps", steps, "norms", [round(float(n), 3) for n in norms])
 
 
@@ -331,7 +362,7 @@ def retrieval(ref):
     img = frames.float()
     img.div_(255.)
     img = img.sub_(torch.tensor(mean).view(1, 1, 3, 1, 1)).div_(torch.tensor(std).view(1, 1, 3, 1, 1))
-    torch.save(dict(cases=cases, frames=frames, normed=img, mean=mean, std=std), os.path.join(HERE, "retrieval.pt"))
+    save_golden(dict(cases=cases, frames=frames, normed=img, mean=mean, std=std), "retrieval.pt")
     print("retrieval:", [(c["results"]["simple"]["t2v"][0], c["results"]["DSL"]["t2v"][0]) for c in cases])
 
 
@@ -355,6 +386,7 @@ if __name__ == "__main__":
     loss(ref)
     optim(ref)
     retrieval(ref)
+    reference_cfg1(ref)
     for f in sorted(os.listdir(HERE)):
-        if f.endswith(".pt"):
+        if f.endswith(".pt") or ".pt." in f:
             print(f, os.path.getsize(os.path.join(HERE, f)) // 1024, "KiB")

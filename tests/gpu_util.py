@@ -1,10 +1,52 @@
 """Shared helpers for the -m gpu parity tests."""
+import glob
+import io
 import json
 import os
 
 import torch
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# committed files stay below 1 MiB: a larger fixture is stored as the byte pieces <name>.0, <name>.1, ... of its torch.save stream
+GOLDEN_PART_BYTES = 1000 * 1024
+
+
+def _golden_parts(path):
+    parts = [p for p in glob.glob(glob.escape(path) + ".*") if p.rsplit(".", 1)[1].isdigit()]
+    return sorted(parts, key=lambda p: int(p.rsplit(".", 1)[1]))
+
+
+def load_golden(name):
+    """tests/golden/<name>: the file itself, or its pieces <name>.0, <name>.1, ... joined (save_golden)"""
+    path = os.path.join(GOLDEN, name)
+    if os.path.isfile(path):
+        return torch.load(path, map_location="cpu", weights_only=False)
+    parts = _golden_parts(path)
+    if not parts:
+        raise FileNotFoundError(path)
+    data = b"".join(open(p, "rb").read() for p in parts)
+    return torch.load(io.BytesIO(data), map_location="cpu", weights_only=False)
+
+
+def save_golden(obj, name):
+    """torch.save into tests/golden/<name>, split into pieces of GOLDEN_PART_BYTES when larger (load_golden joins them)"""
+    path = os.path.join(GOLDEN, name)
+    buf = io.BytesIO()
+    torch.save(obj, buf)
+    data = buf.getvalue()
+    for p in ([path] if os.path.isfile(path) else []) + _golden_parts(path):
+        os.remove(p)
+    if len(data) <= GOLDEN_PART_BYTES:
+        with open(path, "wb") as f:
+            f.write(data)
+        return [path]
+    out = []
+    for i, off in enumerate(range(0, len(data), GOLDEN_PART_BYTES)):
+        out.append(f"{path}.{i}")
+        with open(out[-1], "wb") as f:
+            f.write(data[off:off + GOLDEN_PART_BYTES])
+    return out
 
 
 def dump(name, obj):
@@ -128,6 +170,17 @@ def seeded_model(cfgd, temporal_size, seed=1234, perturb_seed=99):
             elif "layer_norm" in n or "layrnorm" in n or "layernorm" in n:
                 p.add_(0.1 * torch.randn(p.shape, generator=g))
     return model
+
+
+def weight_fingerprint(sd, n=16, seed=7):
+    """{name: (fp64 sum, n seeded elements)} of a state dict: pins that two model classes built the same weights"""
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for k in sorted(sd):
+        v = sd[k].detach().reshape(-1)
+        pick = torch.randint(0, v.numel(), (n,), generator=g)
+        out[k] = (v.double().sum().item(), v[pick].clone())
+    return out
 
 
 def sample_rows(S, M, n=28, seed=5):

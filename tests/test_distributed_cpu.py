@@ -159,7 +159,7 @@ def test_resume_broadcasts_optimizer_state(tmp_path):
 
 
 def test_bench_starts_its_own_ranks():
-    """`python bench.py --gpus 2` with no launcher around it re-executes itself under torch.distributed.run and both ranks join
+    """`python bench.py --gpus 2` with no launcher around it runs itself under torch.distributed.run and both ranks join
     the process group (gloo here: no GPU); --launch-check stops before any GPU work."""
     import json
     import subprocess

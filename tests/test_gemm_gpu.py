@@ -300,7 +300,7 @@ def test_gemm256_token_count_nn_and_f32():
 
 
 @pytest.mark.parametrize("M,N,K,split", [(3072, 768, 18848, 7), (768, 768, 18848, 27), (2304, 768, 9424, 9)])
-def test_dw_split_k_chunk_major_grid(M, N, K, split):
+def test_dw_split_k_chunk_major_grid(M, N, K, split, tmp_path):
     """Weight-gradient shapes of the step (dW1, dWo, dWqkv): the split-K launch walks a 1-D grid over (k-chunk, tile) pairs,
     chunk-major per XCD (csrc/gemm256.hip).  Against fp64, and bit-identical to the (tile, z) grid (XPRETRAIN_DEBUG=dw_tile_major
     in a fresh process: it computes the same slabs) -- the mapping changes which CU computes a slab, never the slab."""
@@ -315,10 +315,11 @@ def test_dw_split_k_chunk_major_grid(M, N, K, split):
     dw = H.splitk_reduce(slabs, torch.empty(M, N, device="cuda"))
     ref = Y.double().t() @ X.double()
     assert report(f"dW {M}x{N}x{K} split {split}", dw, ref, 2e-5) <= 2e-5
-    torch.save({"Y": Y.cpu(), "X": X.cpu(), "slabs": slabs.cpu()}, "/tmp/xp_chunk_major_case.pt")
+    case = str(tmp_path / "xp_chunk_major_case.pt")
+    torch.save({"Y": Y.cpu(), "X": X.cpu(), "slabs": slabs.cpu()}, case)
     code = ("import torch, sys; sys.path.insert(0, '.');\n"
             "from xpretrain_amd import hip_ops as H\n"
-            "d = torch.load('/tmp/xp_chunk_major_case.pt'); Y, X = d['Y'].cuda(), d['X'].cuda()\n"
+            f"d = torch.load({case!r}); Y, X = d['Y'].cuda(), d['X'].cuda()\n"
             f"s = H.gemm(Y, X, {M}, {N}, {K}, a_kstrided=True, b_kstrided=True, split_k={split})\n"
             "assert torch.equal(s.cpu(), d['slabs'])\nprint('same')\n")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

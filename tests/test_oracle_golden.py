@@ -1,12 +1,11 @@
 """CPU: pin oracle/clipvip_oracle.py against the fixtures produced by the UNMODIFIED
-reference (tests/golden/make_golden.py), and against the live reference when present."""
+reference (tests/golden/make_golden.py)."""
 import math
 
 import pytest
 import torch
 
 from oracle import clipvip_oracle as O
-from oracle import ref_import
 
 TOL = dict(rtol=1e-4, atol=5e-5)   # fp32 roundoff between two op orders; values are O(1-10)
 
@@ -119,25 +118,31 @@ def test_losses(golden):
             torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.skipif(not ref_import.available(), reason="reference tree not present (GPU box)")
-def test_live_reference_cfg1_shape():
-    """Live cross-check at BASELINE cfg #1's architecture (ViT-B/32, T=2, Lt=16) with B=2."""
-    ref = ref_import.load()
+def test_live_reference_cfg1_shape(golden):
+    """Cross-check at BASELINE cfg #1's architecture (ViT-B/32, T=2, Lt=16) with B=2 against the reference's own run of it
+    (tests/golden/reference_cfg1.pt, make_golden.py::reference_cfg1): the weights are rebuilt from the seed (the fingerprint pins
+    them to those the reference ran on), and the oracle on them gives the reference's features and loss."""
+    from tests.gpu_util import ModelArgs, weight_fingerprint
+    from xpretrain_amd.modeling import VidCLIP
+    fx = golden("reference_cfg1.pt")
     torch.manual_seed(1234)
     cfgd = O.vit_b_config(patch=32)
-    model = ref.VidCLIP.VidCLIP(ref_import.make_args(cfgd, add_cls_num=3, temporal_size=12))
+    model = VidCLIP(ModelArgs(cfgd, 12))
     with torch.no_grad():
         model.clipmodel.vision_model.embeddings.temporal_embedding.normal_(0, 0.02)
+    fp = weight_fingerprint(model.state_dict())
+    assert fp.keys() == fx["weights"].keys()
+    for k, (total, picked) in fx["weights"].items():
+        assert torch.equal(fp[k][1], picked), k
+        assert math.isclose(fp[k][0], total, rel_tol=1e-9, abs_tol=1e-9), k
     video, ids, mask = O.synthetic_inputs(2, 2, 224, 16)
-    out = model(video, ids, mask)
-    loss = ref.loss.NCELearnableTempLoss(None)(out["vis_features"], out["text_features"], model.clipmodel.logit_scale)
     cfg = O.OracleCfg.from_hf_dict(cfgd)
     sd = O.strip_prefix(model.state_dict())
     with torch.no_grad():
         l2, vis, txt = O.full_step(video, ids, mask, sd, cfg)
-    torch.testing.assert_close(vis, out["vis_features"], rtol=1e-4, atol=1e-5)
-    torch.testing.assert_close(txt, out["text_features"], rtol=1e-4, atol=1e-5)
-    torch.testing.assert_close(l2, loss, rtol=1e-4, atol=1e-4)
+    torch.testing.assert_close(vis, fx["vis_features"], rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(txt, fx["text_features"], rtol=1e-4, atol=1e-5)
+    torch.testing.assert_close(l2, fx["loss"], rtol=1e-4, atol=1e-4)
 
 
 @pytest.mark.parametrize("fixture", ["full_cfg2.pt", "full_cfg2_b8.pt"])

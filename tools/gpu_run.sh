@@ -25,7 +25,7 @@ case $TASK in
   tests)
     timeout 1500 python -m pytest tests -m gpu -q "$@" > $O/pytest.log 2>&1; echo "pytest exit $?"; tail -4 $O/pytest.log ;;
   bench)
-    timeout 900 python bench.py "$@" 2> $O/bench.err | grep "^{" > $O/bench.json
+    timeout 900 python bench.py --full "$@" 2> $O/bench.err | grep "^{" > $O/bench.json
     python3 -c "
 import json; d=json.load(open('$O/bench.json')); r=d['roofline']; b=d['roofline_bwd']
 print('bench', d['value'], 'pairs/s', d['ms_per_step'], 'ms/step; vit fwd', d['vit_forward_train_mode_ms'], d['vit_forward_ms'], '; roofline', r['frac'], r['kernel_ms'], '; bwd', b['frac'], b['kernel_ms'], '; cpu', d.get('cpu_baseline', {}).get('value'))" ;;
@@ -36,7 +36,7 @@ print('bench', d['value'], 'pairs/s', d['ms_per_step'], 'ms/step; vit fwd', d['v
     timeout 600 python tools/bench_kernels.py "${1:-all}" 2>&1 | grep -v amdgpu.ids | tee $O/kernels.txt ;;
   profile)
     rm -rf /tmp/prof_$TAG
-    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o p -- python bench.py --steps 10 --warmup 3 --profile-run "$@" > $O/bench_under_rocprof.log 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o p -- python bench.py --full --steps 10 --warmup 3 --profile-run "$@" > $O/bench_under_rocprof.log 2>&1
     grep "^{" $O/bench_under_rocprof.log > $O/bench_under_rocprof.json
     cp $(find /tmp/prof_$TAG -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
     python3 tools/kernel_by_grid.py $(find /tmp/prof_$TAG -name "*kernel_trace.csv" | head -1) > $O/kernel_by_grid.txt

@@ -7,7 +7,7 @@ VARIANT = name[@tree][:ENV=value[,ENV=value...]][/--bench-flag=value ...]
           e.g.   default   one:XPRETRAIN_FWD_SPLIT=0   r2@_ab_r2   pf:XPRETRAIN_BENCH_FORCE_COLLECTIVES=1/--prefetch=1/--prefetch-dtype=uint8
           (tree: another checkout of this repository with its library built, relative to the repository root; default: this one)
 
-Every round runs `python bench.py --no-cpu-baseline --steps N` once per variant, in the order given; the table lists pairs/s,
+Every round runs `python bench.py --full --no-cpu-baseline --steps N` once per variant, in the order given; the table lists pairs/s,
 ms/step and the two forward-only probes per round, then the per-variant median.  Boxes of the pool differ by +-3 % on one build and
 isolated kernel timings rank power-limited kernels differently from the step: only numbers from one invocation are comparable."""
 import argparse
@@ -29,7 +29,7 @@ def parse_variant(text):
 
 
 def run(tree, envs, steps, flags=()):
-    out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--steps", str(steps), *flags], cwd=tree, env=dict(os.environ, **envs),
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--steps", str(steps), *flags], cwd=tree, env=dict(os.environ, **envs),
                          capture_output=True, text=True, timeout=900)
     line = next((l for l in out.stdout.splitlines() if l.startswith("{")), None)
     if line is None:
@@ -50,7 +50,7 @@ def main():
         for name, tree, envs, flags in variants:
             res[name].append(run(tree, envs, a.steps, flags))
     keys = ("value", "ms_per_step", "vit_forward_ms", "vit_forward_train_mode_ms")
-    lines = [f"bench.py --steps {a.steps} --no-cpu-baseline, one box, {a.rounds} interleaved rounds: pairs/s ms/step vit_fwd_ms vit_fwd_train_mode_ms"]
+    lines = [f"bench.py --full --steps {a.steps} --no-cpu-baseline, one box, {a.rounds} interleaved rounds: pairs/s ms/step vit_fwd_ms vit_fwd_train_mode_ms"]
     w = max(len(v) for v in a.variants)
     for (name, _, _, _), text in zip(variants, a.variants):
         cells = [" ".join("-" if d.get(k) is None else f"{d[k]:.3f}" for k in keys) for d in res[name]]

@@ -11,7 +11,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import clipvip_oracle as O  # noqa: E402
-from tests.gpu_util import seeded_model  # noqa: E402
+from tests.gpu_util import load_golden, seeded_model  # noqa: E402
 
 MODE = {"m": "all"}
 orig_layer = O.encoder_layer
@@ -37,7 +37,7 @@ def layer(x, sd, pfx, heads, size, pad_mask):
 
 O.encoder_layer = layer
 for name in sys.argv[1:] or ["full_cfg2.pt"]:
-    fx = torch.load(os.path.join(ROOT, "tests", "golden", name), map_location="cpu", weights_only=False)
+    fx = load_golden(name)
     cfgd = O.vit_b_config(fx["patch"], fx["res"])
     model = seeded_model(cfgd, fx["temporal_size"])
     sd = {k: v.detach() for k, v in O.strip_prefix(model.state_dict()).items()}
