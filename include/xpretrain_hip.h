@@ -103,9 +103,10 @@ typedef struct XpGemmDesc {
 int xp_gemm(const XpGemmDesc* desc, void* stream);
 
 /* Split-K factor xp_gemm should be given for a weight-gradient-shaped problem (dW = dY^T X as computed by the
- * backward of nn.Linear inside CLIPEncoderLayer, modeling/CLIP_ViP.py:383-396,444-460): fills one resident round
- * of workgroups of the kernel family xp_gemm will pick for `desc` (desc->split_k and the data pointers are
- * ignored).  The value is always accepted by xp_gemm (whole k-steps per slab, no empty slab); 1 = no split. */
+ * backward of nn.Linear inside CLIPEncoderLayer, modeling/CLIP_ViP.py:383-396,444-460): the 256-wide family's split that
+ * fills one resident round of its workgroups, if the plan xp_gemm launches for `desc` with that split is 256-wide; else
+ * the 128x128 family's split, which the plan may still run on the 256-wide family (desc->split_k and the data pointers
+ * are ignored).  The value is always accepted by xp_gemm (whole k-steps per slab, no empty slab); 1 = no split. */
 int32_t xp_gemm_auto_split(const XpGemmDesc* desc);
 /* The same for a split-K launch that has SLACK: it runs on another stream beside the caller's work and nothing waits for it soon --
  * the first three weight-gradient GEMMs of an encoder layer's backward (fc2, fc1, out_proj: issued on the weight-gradient stream
@@ -117,10 +118,10 @@ int32_t xp_gemm_auto_split_slack(const XpGemmDesc* desc);
  * run_pretrain.py:224-227,379; RCCL's gfx950 kernels own a CU per workgroup) so that a dW launch still fits one round. */
 int xp_set_cu_budget(int32_t cus);
 int32_t xp_get_cu_budget(void);
-/* number of partial rows xp_gemm writes to desc->colsum_partials, or 0 if the fused column sums are not available
- * for this problem (desc->colsum_partials itself is ignored here) */
+/* number of partial rows xp_gemm writes to desc->colsum_partials, read from the plan xp_gemm launches, or 0 if the fused
+ * column sums are not available for this problem (desc->colsum_partials itself is ignored here) */
 int64_t xp_gemm_colsum_rows(const XpGemmDesc* desc);
-/* Output-tile height (rows) of the kernel family xp_gemm will run `desc` with: 256 for the 256-wide ping-pong family (the four
+/* Output-tile height (rows) of the kernel family in the plan xp_gemm launches for `desc`: 256 for the 256-wide ping-pong family (the four
  * Linear layers of CLIPEncoderLayer at video-tower sizes, modeling/CLIP_ViP.py:341-343,379,393-395), 128 for the 128x128 family.
  * desc->split_k is honoured; the data pointers are ignored. */
 int32_t xp_gemm_tile_rows(const XpGemmDesc* desc);

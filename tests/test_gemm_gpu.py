@@ -4,6 +4,7 @@ import pytest
 import torch
 
 from tests.gpu_util import report
+from tests.test_planning_cpu import _tile_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -226,22 +227,6 @@ def test_gemm_fused_colsum(epi):
 
 
 # ---------------------------------------------------------------------------------------------- the real token count
-def _tile_rows(M, N, K, b_kstrided=False, split_k=1, out_f32=False):
-    import ctypes as C
-    from xpretrain_amd import _lib as L
-    d = L.XpGemmDesc()
-    d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.ldr, d.ldaux = M, N, K, K, (N if b_kstrided else K), N, N, N
-    d.b_kstrided, d.in_dtype, d.out_dtype, d.split_k = int(b_kstrided), L.XP_BF16, (L.XP_F32 if out_f32 else L.XP_BF16), split_k
-    return int(L.lib().xp_gemm_tile_rows(C.byref(d)))
-
-
-def test_kernel_family_per_shape():
-    """the video-tower shapes of BASELINE cfg #2 / configs[3] run the 256-wide family, small problems the 128x128 family"""
-    assert _tile_rows(18848, 768, 768) == 256 and _tile_rows(18848, 3072, 768, b_kstrided=True) == 256
-    assert _tile_rows(50208, 768, 768) == 256 and _tile_rows(16384, 1024, 512) == 256
-    assert _tile_rows(256, 512, 768) == 128
-
-
 @pytest.mark.parametrize("M", [18848, 18848 + 40, 18848 - 200])
 def test_gemm256_token_count_all_epilogues(M):
     """The training step's row count (74 tiles of 256 rows, ragged last tile) through every fused epilogue of the family; rows past

@@ -78,6 +78,56 @@ def test_tile_height_planning():
     assert lib.xp_gemm_tile_rows(C.byref(_desc(18848, 768, 768, dtype=L.XP_F32, a_ks=False, b_ks=False))) == 128
 
 
+def _tile_rows(M, N, K, b_kstrided=False, split_k=1, out_f32=False):
+    d = L.XpGemmDesc()
+    d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.ldr, d.ldaux = M, N, K, K, (N if b_kstrided else K), N, N, N
+    d.b_kstrided, d.in_dtype, d.out_dtype, d.split_k = int(b_kstrided), L.XP_BF16, (L.XP_F32 if out_f32 else L.XP_BF16), split_k
+    return int(L.lib().xp_gemm_tile_rows(C.byref(d)))
+
+
+def test_kernel_family_per_shape():
+    """the video-tower shapes of BASELINE cfg #2 / configs[3] run the 256-wide family, small problems the 128x128 family"""
+    assert _tile_rows(18848, 768, 768) == 256 and _tile_rows(18848, 3072, 768, b_kstrided=True) == 256
+    assert _tile_rows(50208, 768, 768) == 256 and _tile_rows(16384, 1024, 512) == 256
+    assert _tile_rows(256, 512, 768) == 128
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+_SWEEP_ROWS = (300, 2356, 4609, 4712, 9424, 16384, 18848, 18848 - 200, 50208)
+_SWEEP_DIMS = (128, 512, 768, 1280, 1536, 2048, 2304, 3072)
+
+
+@pytest.mark.parametrize("rows", _SWEEP_ROWS)
+def test_plan_invariants(rows):
+    """What one plan guarantees to the callers that size buffers by the planning queries (hip_ops.gemm, csrc/layer.hip): fused column
+    sums only in the 256-wide family, one partial row per 128 output rows; split-K answers that xp_gemm accepts, the slack one never
+    with more slabs than the general one; the 256-wide family only where it can run the split (bf16, whole 64-deep k-tiles per slab,
+    >= 2 of them in the last slab).  (A split from the 128x128 family's formula may run on the 256-wide family.)"""
+    lib = L.lib()
+    for a, b in [(a, b) for a in _SWEEP_DIMS for b in _SWEEP_DIMS]:
+        for M, N, K, a_ks, b_ks in ((rows, a, b, False, False), (rows, a, b, False, True), (a, b, rows, True, True), (a, b, rows, True, False)):
+            for dtype, out in ((L.XP_BF16, L.XP_BF16), (L.XP_BF16, L.XP_F32), (L.XP_F32, L.XP_F32)):
+                for epi in (L.EPI_NONE, L.EPI_GELU_BWD, L.EPI_BIAS):
+                    d = _desc(M, N, K, a_ks=a_ks, b_ks=b_ks, dtype=dtype, out=out, epi=epi)
+                    if epi == L.EPI_GELU_BWD:
+                        d.resid, d.ldr = 1, N
+                    cs = lib.xp_gemm_colsum_rows(C.byref(d))
+                    if cs > 0:
+                        assert lib.xp_gemm_tile_rows(C.byref(d)) == 256 and cs == 2 * _cdiv(M, 256), (M, N, K, epi)
+                    s, slack = lib.xp_gemm_auto_split(C.byref(d)), lib.xp_gemm_auto_split_slack(C.byref(d))
+                    assert slack <= s, (M, N, K)
+                    for split in (s, slack):
+                        assert split == 1 or _valid_split(K, split, 64 if dtype == L.XP_BF16 else 32), (M, N, K, dtype, split)
+                        d.split_k = split
+                        if lib.xp_gemm_tile_rows(C.byref(d)) == 256:
+                            kps = _cdiv(_cdiv(K, split), 64) * 64
+                            assert dtype == L.XP_BF16 and _valid_split(K, split) and K - (split - 1) * kps > 64, (M, N, K, split)
+                    d.split_k = 1
+
+
 def test_cu_budget_shrinks_the_split():
     """xp_set_cu_budget: a data-parallel run reserves the CUs its collective kernels own (distributed.reserve_cus_for_collectives);
     the dW launches must then fit the remaining CUs in one round."""

@@ -444,19 +444,21 @@ bool glds_ok(const XpGemmDesc* d, int esz) {
   return true;
 }
 
+// the kernel families and variants plan_gemm chooses between
+enum class Family { G256, DIRECT, STAGED, FRAMES };      // 256x256 (gemm256.hip); 128x128 direct-to-LDS / register-staged / frame-gather
+
 template <typename T>
-int launch(const XpGemmDesc* d, const KParams& kp, dim3 grid, hipStream_t st) {
+void launch(Family f, const XpGemmDesc* d, const KParams& kp, dim3 grid, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
-    if (d->a_frames) {                  // A gathered from the frame tensor by the loader
+    if (f == Family::FRAMES) {          // A gathered from the frame tensor by the loader
       const size_t lds = 4 * TILE_BYTES;
       if (d->a_frames_u8) gemm_kernel<T, false, false, false, 2><<<grid, NT, lds, st>>>(kp);
       else                gemm_kernel<T, false, false, false, 1><<<grid, NT, lds, st>>>(kp);
-      return 0;
+      return;
     }
   }
-  if (glds_ok(d, sizeof(T))) launch2<T, true>(d, kp, grid, st);
-  else                       launch2<T, false>(d, kp, grid, st);
-  return 0;
+  if (f == Family::DIRECT) launch2<T, true>(d, kp, grid, st);
+  else                     launch2<T, false>(d, kp, grid, st);
 }
 
 // ---- split-K slab reduce, column sums ---------------------------------------------------------------
@@ -708,6 +710,62 @@ static int gemm_timer_slot(const XpGemmDesc* d, int split) {
   return slot;
 }
 
+// ---- planning: the one place that decides how a problem runs -----------------------------------------
+// xp_gemm launches the plan; xp_gemm_tile_rows, xp_gemm_colsum_rows and the split-K planning answer from the same plan.  The
+// switches are read once per plan, and on every call (tests flip them inside one process).
+struct GemmPlan {
+  Family family;
+  int tile_rows;
+  int split; int64_t k_per_split;
+  int tiles_m, tiles_n, group_n, xcd_remap, flat_split;
+  int wide, fast_epi;
+  int64_t colsum_rows;        // partial rows of the fused column sums (256 family, split 1, bf16 out, EPI_NONE / GELU_BWD), else 0
+  dim3 grid;
+};
+
+static GemmPlan plan_gemm(const XpGemmDesc* d, int split) {
+  GemmPlan p{};
+  p.split = split = split > 1 ? split : 1;
+  const int esz = d->in_dtype == XP_BF16 ? 2 : 4, ke = BKB / esz;
+  p.k_per_split = cdiv(cdiv(d->K, split), ke) * ke;
+  p.xcd_remap = 1;
+  p.wide = d->N % 8 == 0 && d->ldc % 8 == 0 && (!d->resid || d->ldr % 8 == 0) && (!d->aux || d->ldaux % 8 == 0);
+  // fast epilogue (gemm_common.h): identity row map, 32-bit buffer offsets that cannot wrap for any row of the last tile
+  const int64_t osz = d->out_dtype == XP_F32 ? 4 : esz, lim = (int64_t)EPI_OOB - 64, rows = d->M + 256;
+  p.fast_epi = p.wide && !xp_debug_flag("gemm_slow_epi") && d->c_grp == 0 && rows * d->ldc * osz < lim &&
+               (!d->resid || rows * d->ldr * esz < lim) && (!d->aux || rows * d->ldaux * osz < lim);
+  // the 256 family has only the fast epilogue, for the (epilogue, output type, column sums) combinations fast_epi_dispatch
+  // specialises: column sums with bf16 out after NONE / GELU_BWD, fp32 out after NONE, bf16 out after every kind but PATCH / SCALE
+  const int ep = d->epilogue;
+  const bool f32 = d->out_dtype == XP_F32, cs_epi = ep == XP_EPI_NONE || ep == XP_EPI_GELU_BWD;
+  const bool epi256 = p.fast_epi && (d->colsum_partials ? !f32 && cs_epi
+                                     : f32 ? ep == XP_EPI_NONE : ep >= XP_EPI_NONE && ep <= XP_EPI_GELU_BWD);
+  // XPRETRAIN_GEMM256: 0 = never, 1 = from 96 workgroups (default: a half-batch N = 768 GEMM of the forward's two chains is 111
+  // tiles and runs beside its twin), 2 = whenever legal.  The 256 family (bf16 only: ke == 64) needs whole k-tiles in every
+  // slab, no empty slab and >= 2 k-tiles in the last one (the pipeline depth).
+  const char* env = getenv("XPRETRAIN_GEMM256");
+  const int mode = env ? atoi(env) : 1;
+  const int64_t k_last = d->K - (int64_t)(split - 1) * p.k_per_split;
+  if (mode != 0 && xp_gemm256_legal(d) && epi256 && (mode != 1 || cdiv(d->M, 256) * cdiv(d->N, 256) * split >= 96) &&
+      cdiv(k_last, 64) >= 2 && (split == 1 || cdiv(d->K, p.k_per_split) == split)) {      // (K <= 0: the k-tail test fails first)
+    p.family = Family::G256; p.tile_rows = 256;
+    p.tiles_m = (int)cdiv(d->M, 256); p.tiles_n = (int)cdiv(d->N, 256);
+    p.group_n = split > 1 ? p.tiles_n : xp_gemm256_group_n(d, p.tiles_n);
+    const bool chunk_major = split > 1 && !xp_debug_flag("dw_tile_major");     // (test facility: the (tile, z) grid of rounds 1-3, bit-identical slabs)
+    p.flat_split = chunk_major ? split : 0;
+    p.colsum_rows = split == 1 && !f32 && cs_epi ? 2 * cdiv(d->M, 256) : 0;      // one partial row per wave row block (128 rows)
+    p.grid = dim3(p.tiles_m * p.tiles_n * (chunk_major ? split : 1), 1, chunk_major ? 1 : split);
+    return p;
+  }
+  p.family = d->in_dtype == XP_BF16 && d->a_frames ? Family::FRAMES : glds_ok(d, esz) ? Family::DIRECT : Family::STAGED;
+  p.tile_rows = BM;
+  p.tiles_m = (int)cdiv(d->M, BM); p.tiles_n = (int)cdiv(d->N, BN);
+  const int gmax = 4;                     // L2 super-tile groups of <= 4 tile columns (A/B in round 2: profiles/r02_gemm256_ab_groupn_storepolicy.txt)
+  p.group_n = (int)cdiv(p.tiles_n, cdiv(p.tiles_n, gmax));
+  p.grid = dim3(p.tiles_m * p.tiles_n, 1, split);
+  return p;
+}
+
 extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
   XP_REQUIRE(d && (d->A || d->a_frames) && d->B && d->C, "xp_gemm: null operand");
   XP_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "xp_gemm: empty problem M=%lld N=%lld K=%lld",
@@ -743,23 +801,23 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
   if (split > 1) XP_REQUIRE(ep == XP_EPI_NONE && d->out_dtype == XP_F32 && d->c_grp == 0 && d->ldc == d->N,
                             "xp_gemm: split_k needs EPI_NONE, f32 output, dense C");
 
+  const GemmPlan plan = plan_gemm(d, split);
   KParams kp;
   kp.A = d->A; kp.B = d->B; kp.C = d->C;
   kp.M = d->M; kp.N = d->N; kp.K = d->K; kp.lda = d->lda; kp.ldb = d->ldb; kp.ldc = d->ldc;
   kp.amap = Remap{d->a_grp, d->a_grp_stride, d->a_off};
   kp.cmap = Remap{d->c_grp, d->c_grp_stride, d->c_off};
   kp.epilogue = ep; kp.out_f32 = d->out_dtype == XP_F32;
-  const int ke = BKB / esz;
-  kp.k_per_split = cdiv(cdiv(d->K, split), ke) * ke;
+  kp.k_per_split = plan.k_per_split;
   kp.bias = d->bias; kp.scale = d->scale; kp.scale_cols = d->scale_cols;
   kp.resid = d->resid; kp.ldr = d->ldr; kp.aux = d->aux; kp.ldaux = d->ldaux;
   kp.tab1 = d->tab1; kp.tab2 = d->tab2; kp.tab_L = d->tab_L;
-  kp.dbg = g_gemm_trace; kp.flat_split = 0;
+  kp.dbg = g_gemm_trace;
   kp.im_src = d->a_frames; kp.im_u8 = d->a_frames_u8; kp.im_H = d->fr_H; kp.im_W = d->fr_W; kp.im_P = d->fr_P;
   kp.im_gw = d->fr_P > 0 ? d->fr_W / d->fr_P : 1; kp.im_L = d->fr_P > 0 ? (d->fr_H / d->fr_P) * kp.im_gw : 1;
   for (int c = 0; c < 3; ++c) { kp.im_mean[c] = d->fr_mean[c]; kp.im_std[c] = d->fr_std[c]; }
-  kp.wide = (d->N % 8 == 0 && d->ldc % 8 == 0 && (!d->resid || d->ldr % 8 == 0) && (!d->aux || d->ldaux % 8 == 0)) ? 1 : 0;
-  kp.fast_epi = (kp.wide && xp_gemm_fast_epi_ok(d)) ? 1 : 0;
+  kp.tiles_m = plan.tiles_m; kp.tiles_n = plan.tiles_n; kp.group_n = plan.group_n; kp.xcd_remap = plan.xcd_remap;
+  kp.flat_split = plan.flat_split; kp.wide = plan.wide; kp.fast_epi = plan.fast_epi;
   kp.colsum = d->colsum_partials;
   kp.rside = d->resid_side; kp.oside = d->out_side; kp.side_S = (unsigned)d->side_S; kp.side_M = (unsigned)d->side_M;
   if (d->resid_side || d->out_side)
@@ -767,57 +825,37 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
                d->side_S > 0 && d->side_M > 0 && d->side_M <= d->side_S && d->M + 512 < ((int64_t)1 << 24) && d->N % 8 == 0,
                "xp_gemm: resid_side / out_side need both pointers, EPI_BIAS_RESID, an unmapped output, 0 < side_M <= side_S, M < 2^24");
   if (d->colsum_partials)
-    XP_REQUIRE(xp_gemm_colsum_rows(d) > 0, "xp_gemm: fused column sums are not available for this problem "
+    XP_REQUIRE(plan.colsum_rows > 0, "xp_gemm: fused column sums are not available for this problem "
                "(xp_gemm_colsum_rows() == 0): use xp_colsum / xp_colsum_partials");
-  kp.tiles_m = (int)cdiv(d->M, BM); kp.tiles_n = (int)cdiv(d->N, BN);
-  {
-    const int gmax = 4;                   // L2 super-tile groups of <= 4 tile columns (A/B in round 2: profiles/r02_gemm256_ab_groupn_storepolicy.txt)
-    const int ngroups = (int)cdiv(kp.tiles_n, gmax);
-    kp.group_n = (int)cdiv(kp.tiles_n, ngroups);
-    kp.xcd_remap = 1;
-  }
-  const int zsplits = (int)cdiv(d->K, kp.k_per_split);
+  const int zsplits = (int)cdiv(d->K, plan.k_per_split);
   XP_REQUIRE(split == 1 || zsplits == split, "xp_gemm: split_k=%d leaves empty slabs for K=%lld (use <= %d)",
              split, (long long)d->K, zsplits);
-  dim3 grid(kp.tiles_m * kp.tiles_n, 1, split);
   hipStream_t st = (hipStream_t)stream;
   const int tslot = gemm_timer_slot(d, split);                       // (debug: in-step timing of one shape)
   if (tslot >= 0) (void)hipEventRecord(g_timer.ev[tslot], st);
   struct Stop { int slot; hipStream_t st; ~Stop() { if (slot >= 0) (void)hipEventRecord(g_timer.ev[slot + 1], st); } } stop{tslot, st};
-  if (xp_gemm256_try(d, kp, st)) {     // large dense problems: 256x256 ping-pong family
+  if (plan.family == Family::G256) {
+    // No fall-back to the 128x128 family: the planning queries have already answered for this one (the 128x128 family has no
+    // fused column sums).  The library is built for gfx950 only, whose 160 KiB of LDS per CU always admit the 128 KiB opt-in.
+    if (!xp_gemm256_launch(d, kp, plan.grid, st)) {
+      xp_set_error("xp_gemm: the 256x256 family cannot launch: no current device with an index below 64, "
+                   "or its 128 KiB dynamic-LDS opt-in was refused");
+      return XP_ERR_LAUNCH;
+    }
     XP_CHECK_LAUNCH("xp_gemm(256)");
     return XP_OK;
   }
-  if (d->in_dtype == XP_BF16) launch<bf16_t>(d, kp, grid, st);
-  else                        launch<float>(d, kp, grid, st);
+  if (d->in_dtype == XP_BF16) launch<bf16_t>(plan.family, d, kp, plan.grid, st);
+  else                        launch<float>(plan.family, d, kp, plan.grid, st);
   XP_CHECK_LAUNCH("xp_gemm");
   return XP_OK;
 }
 
-// fast epilogue (gemm_common.h): identity row map, 32-bit buffer offsets that cannot wrap for any row of the last tile
-bool xp_gemm_fast_epi_ok(const XpGemmDesc* d) {
-  if (xp_debug_flag("gemm_slow_epi")) return false;
-  const int64_t esz = d->in_dtype == XP_BF16 ? 2 : 4, osz = d->out_dtype == XP_F32 ? 4 : esz, lim = (int64_t)EPI_OOB - 64;
-  const int64_t rows = d->M + 256;
-  const bool wide = d->N % 8 == 0 && d->ldc % 8 == 0 && (!d->resid || d->ldr % 8 == 0) && (!d->aux || d->ldaux % 8 == 0);
-  return wide && d->c_grp == 0 && rows * d->ldc * osz < lim && (!d->resid || rows * d->ldr * esz < lim) &&
-         (!d->aux || rows * d->ldaux * osz < lim);
-}
-
-extern "C" int64_t xp_gemm_colsum_rows(const XpGemmDesc* d) {
-  if (!d || d->split_k > 1 || d->in_dtype != XP_BF16 || d->out_dtype != XP_BF16) return 0;
-  if (d->epilogue != XP_EPI_NONE && d->epilogue != XP_EPI_GELU_BWD) return 0;
-  if (!xp_gemm_fast_epi_ok(d) || !xp_gemm256_wanted(d, 1) || cdiv(d->K, 64) < 2) return 0;
-  return xp_gemm256_colsum_rows(d);          // one partial row per wave row block of the tile height the launcher will pick
-}
+extern "C" int64_t xp_gemm_colsum_rows(const XpGemmDesc* d) { return d ? plan_gemm(d, d->split_k).colsum_rows : 0; }
 
 extern "C" int32_t xp_gemm_tile_rows(const XpGemmDesc* d) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;
-  const int split = d->split_k > 1 ? d->split_k : 1;
-  const int64_t k_per = cdiv(cdiv(d->K, split), 64) * 64;
-  if (xp_gemm256_wanted(d, split) && cdiv(d->K - (int64_t)(split - 1) * k_per, 64) >= 2 && (split == 1 || cdiv(d->K, k_per) == split))
-    return 256;
-  return BM;
+  return plan_gemm(d, d->split_k).tile_rows;
 }
 
 // split s0 rounded to one xp_gemm accepts (whole k-steps per slab, no empty slab)
@@ -883,7 +921,7 @@ static int32_t auto_split_fill(const XpGemmDesc* d, int64_t fill) {
   const int64_t cus = g_cu_budget < fill ? g_cu_budget : fill;
   int64_t s0 = cus / t256 < d->K / 512 ? cus / t256 : d->K / 512;
   const int s256 = valid_split(d->K, s0, 64);
-  if (xp_gemm256_wanted(d, s256)) return s256;
+  if (plan_gemm(d, s256).family == Family::G256) return s256;
   const int64_t t128 = cdiv(d->M, BM) * cdiv(d->N, BN);
   if (t128 >= 256) return 1;
   s0 = 512 / t128 < d->K / 512 ? 512 / t128 : d->K / 512;

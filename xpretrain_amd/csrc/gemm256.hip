@@ -1,5 +1,5 @@
 // 256x256-tile MFMA GEMM, 8-wave ping-pong main loop: the kernel family of every video-tower GEMM (XPRETRAIN_GEMM256=0|1|2, see
-// xp_gemm256_wanted).  ONE family since round 4: round 3's second set (direct LDS-free epilogue through an N-side row permutation,
+// gemm.hip::plan_gemm).  ONE family since round 4: round 3's second set (direct LDS-free epilogue through an N-side row permutation,
 // 224-row tiles, persistent tile loop) won isolated launches by 2-6 % and lost 0.5 ms per training step on one box
 // (profiles/r03v..r03x) -- it was removed; the in-step calibration against the vendor library (profiles/r04a_vendor_library_in_step_calibration.txt)
 // has this kernel within 10 % of the vendor's hand-written 256x256x64 stream-K kernel on the forward shapes, level on dX, 2-4x ahead on dW.
@@ -32,7 +32,6 @@
 //   k-strided    half [64 k][256 B]:      32-byte block' = block ^ ((k&3) | ((k>>3)&1)<<2)   (ds_read_b64_tr_b16)
 #include "common.h"
 #include "gemm_common.h"
-#include <stdlib.h>
 #include <mutex>
 
 namespace {
@@ -306,7 +305,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
       }
     }
   });
-  (void)fast;          // the launcher admits only (epilogue, output type) pairs the fast path specialises (epi_supported)
+  (void)fast;          // the planner admits only (epilogue, output type) pairs the fast path specialises (gemm.hip::plan_gemm)
   if (trace && lane == 0) tr[3] = __builtin_amdgcn_s_memtime();
   if (tline) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tr[64 + bid * 4 + 2] = __builtin_amdgcn_s_memrealtime(); }
 }
@@ -325,7 +324,7 @@ bool launch_one(const KParams& kp, dim3 grid, hipStream_t st) {
     if (!configured[dev])
       configured[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                             LDS_BYTES) == hipSuccess ? 1 : -1;
-    if (configured[dev] < 0) return false;          // (a device without 128 KiB of LDS per workgroup: the 128x128 family serves it)
+    if (configured[dev] < 0) return false;          // (gfx950 has 160 KiB per CU: xp_gemm reports a refusal as an error)
   }
   kern<<<grid, NTH, LDS_BYTES, st>>>(kp);
   return true;
@@ -339,21 +338,7 @@ template __global__ void gemm256_kernel<true, false>(KParams);
 
 }  // namespace
 
-// the (epilogue, output type, column sums) combinations the fast epilogue is specialised for (fast_epi_dispatch); everything
-// else goes to the 128x128 family
-static bool epi_supported(const XpGemmDesc* d) {
-  if (!xp_gemm_fast_epi_ok(d)) return false;
-  const bool f32 = d->out_dtype == XP_F32;
-  if (d->colsum_partials) return !f32 && (d->epilogue == XP_EPI_NONE || d->epilogue == XP_EPI_GELU_BWD);
-  if (f32) return d->epilogue == XP_EPI_NONE;
-  switch (d->epilogue) {
-    case XP_EPI_NONE: case XP_EPI_BIAS: case XP_EPI_BIAS_QSCALE: case XP_EPI_BIAS_GELU: case XP_EPI_BIAS_RESID: case XP_EPI_GELU_BWD:
-      return true;
-    default: return false;
-  }
-}
-
-// preconditions of the family that do not depend on split_k
+// Layout preconditions of the family; the planner (gemm.hip::plan_gemm) adds the epilogue, workgroup-count, split and k-tail rules.
 bool xp_gemm256_legal(const XpGemmDesc* d) {
   if (d->in_dtype != XP_BF16 || d->a_grp != 0 || d->a_frames) return false;      // (a_frames: the register-staged 128x128 loader gathers)
   const int64_t a_rows = d->a_kstrided ? d->K : d->M, b_rows = d->b_kstrided ? d->K : d->N;
@@ -362,18 +347,7 @@ bool xp_gemm256_legal(const XpGemmDesc* d) {
   if (d->a_kstrided && (d->M % TM != 0 || d->lda != d->M)) return false;
   if (d->b_kstrided && (d->N % TN != 0 || d->ldb != d->N)) return false;
   const int64_t lim = (int64_t)0xFFFFFFF0u - 512 * 1024 * 1024;
-  if ((a_rows + TM) * d->lda * 2 >= lim || (b_rows + TN) * d->ldb * 2 >= lim) return false;
-  return epi_supported(d);
-}
-
-// XPRETRAIN_GEMM256: 0 = never, 1 = from 96 workgroups (default: a half-batch N = 768 GEMM of the forward's two chains is 111 tiles and
-// runs beside its twin), 2 = whenever legal.
-bool xp_gemm256_wanted(const XpGemmDesc* d, int split) {
-  const char* env = getenv("XPRETRAIN_GEMM256");
-  const int mode = env ? atoi(env) : 1;
-  if (mode == 0 || !xp_gemm256_legal(d)) return false;
-  if (mode == 1 && cdiv(d->M, TM) * cdiv(d->N, TN) * split < 96) return false;
-  return true;
+  return (a_rows + TM) * d->lda * 2 < lim && (b_rows + TN) * d->ldb * 2 < lim;
 }
 
 // Tile columns per L2 group (gemm_common.h::tile_of walks column groups, columns fastest inside a group; the XCD-contiguous id
@@ -392,22 +366,8 @@ int xp_gemm256_group_n(const XpGemmDesc* d, int tiles_n) {
   return (int)cdiv(tiles_n, groups);
 }
 
-// fused column sums: one partial row per wave row block (128 rows)
-int64_t xp_gemm256_colsum_rows(const XpGemmDesc* d) { return 2 * cdiv(d->M, TM); }
-
-bool xp_gemm256_try(const XpGemmDesc* d, const xpgemm::KParams& kp_base, hipStream_t st) {
-  const int split = d->split_k > 1 ? d->split_k : 1;
-  if (!xp_gemm256_wanted(d, split)) return false;
-  xpgemm::KParams kp = kp_base;
-  kp.k_per_split = cdiv(cdiv(d->K, split), KE) * KE;
-  if (split > 1 && cdiv(d->K, kp.k_per_split) != split) return false;
-  const int64_t k_last = d->K - (int64_t)(split - 1) * kp.k_per_split;
-  if (cdiv(k_last, KE) < 2) return false;                                         // the pipeline needs >= 2 k-tiles
-  kp.tiles_m = (int)cdiv(d->M, TM); kp.tiles_n = (int)cdiv(d->N, TN);
-  kp.group_n = split > 1 ? kp.tiles_n : xp_gemm256_group_n(d, kp.tiles_n);
-  const bool chunk_major = !xp_debug_flag("dw_tile_major");      // (test facility: the (tile, z) grid of rounds 1-3, bit-identical slabs)
-  kp.flat_split = (split > 1 && chunk_major) ? split : 0;
-  dim3 grid(kp.tiles_m * kp.tiles_n * (kp.flat_split ? split : 1), 1, kp.flat_split ? 1 : split);
+// Launches a problem gemm.hip::plan_gemm gave to this family (kp and grid as planned).  false: the dynamic-LDS opt-in was refused.
+bool xp_gemm256_launch(const XpGemmDesc* d, const xpgemm::KParams& kp, dim3 grid, hipStream_t st) {
   if (!d->a_kstrided && !d->b_kstrided)      return launch_one<false, false>(kp, grid, st);
   else if (!d->a_kstrided && d->b_kstrided)  return launch_one<false, true>(kp, grid, st);
   else if (d->a_kstrided && d->b_kstrided)   return launch_one<true, true>(kp, grid, st);
