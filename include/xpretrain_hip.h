@@ -420,6 +420,28 @@ int32_t xp_debug_gemm_timer_read(float* ms, int32_t cap);
 int xp_debug_set_attn_trace(void* device_buffer);
 /* resident workgroups per CU of the default bf16 GEMM kernel at `lds_bytes` of dynamic LDS (occupancy API) */
 int xp_debug_gemm_occupancy(int lds_bytes);
+/* The plan xp_gemm launches for `desc` (desc->split_k honoured), from the same planner: host only, launches nothing, reads the
+ * environment switches (XPRETRAIN_GEMM256, XPRETRAIN_DEBUG) and the CU budget as xp_gemm would.  The data pointers are read only as
+ * present / absent (resid, aux, colsum_partials, a_frames).  The descriptor's arguments are not validated: a descriptor xp_gemm
+ * rejects still gets the plan it would have had. */
+enum { XP_GEMM_FAMILY_256 = 0,       /* 256x256 ping-pong tiles (gemm256.hip) */
+       XP_GEMM_FAMILY_DIRECT = 1,    /* 128x128, operands staged global -> LDS directly */
+       XP_GEMM_FAMILY_STAGED = 2,    /* 128x128, operands staged through registers */
+       XP_GEMM_FAMILY_FRAMES = 3 };  /* 128x128, A gathered from a frame tensor (XpGemmDesc::a_frames) */
+enum { XP_GEMM_EPI_FAST = 0,         /* straight-line buffer-addressed epilogue, 8 columns per lane */
+       XP_GEMM_EPI_ROW8 = 1,         /* generic epilogue, 8 columns per lane */
+       XP_GEMM_EPI_ROW4 = 2 };       /* generic epilogue, 4 columns per lane */
+typedef struct XpGemmPlanInfo {
+  int32_t family, tile_rows;            /* XP_GEMM_FAMILY_*; output tile height (as xp_gemm_tile_rows)      */
+  int32_t split, flat_split;            /* k slabs; > 0: split-K on the 1-D chunk-major grid (256 family)   */
+  int64_t k_per_split;                  /* k of every slab but the last                                     */
+  int32_t tiles_m, tiles_n, group_n;    /* output tiles; tile columns per L2 group                           */
+  int32_t epi_impl;                     /* XP_GEMM_EPI_*                                                     */
+  int32_t grid[3];                      /* launch grid (x, y, z)                                            */
+  int32_t reserved;
+  int64_t colsum_rows;                  /* partial rows of the fused column sums (as xp_gemm_colsum_rows)    */
+} XpGemmPlanInfo;
+int xp_debug_gemm_plan(const XpGemmDesc* desc, XpGemmPlanInfo* out);
 int xp_probe_mfma_bf16(const void* a, const void* b, float* c, void* stream);
 int xp_probe_mfma_f32(const float* a, const float* b, float* c, void* stream);
 /* packed-fp32 self-check (csrc/probe.hip): err[(variant*64 + lane)*2 + half] += mismatches between one v_pk_*_f32 form and

@@ -1,8 +1,10 @@
 """GPU: MFMA GEMM family vs torch fp64 matmul on bf16-rounded / fp32 inputs (the kernel's own inputs),
-every operand layout, every epilogue, ragged M/N/K tails, split-K."""
+every operand layout, every epilogue, ragged M/N/K tails, split-K.  Every case first asserts the kernel variant the planner runs it
+on (tests/test_gemm_plans_gpu.py covers every variant systematically)."""
 import pytest
 import torch
 
+from tests import gemm_cases as G
 from tests.gpu_util import report
 from tests.test_planning_cpu import _tile_rows
 
@@ -17,12 +19,23 @@ def _mk(shape, dtype, scale=1.0):
     return (torch.randn(shape, device="cuda") * scale).to(dtype)
 
 
+def _plan(A, B, M, N, K, family, impl=None, **kw):
+    """assert the variant (gemm_cases.FAMILIES) and epilogue implementation (IMPLS) the planner picks for this call"""
+    from xpretrain_amd import hip_ops as H
+    p = H.gemm(A, B, M, N, K, plan_only=True, **kw)
+    got = (G.FAMILIES[p["family"]], G.IMPLS[p["epi_impl"]])
+    assert got[0] == family and (impl is None or got[1] == impl), (M, N, K, kw.keys(), got, family, impl)
+    return p
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 768), (204, 132, 200), (8, 512, 768), (1000, 2304, 768)])
 def test_nt_plain(dtype, M, N, K):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(M + N + K)
     A, B = _mk((M, K), dtype), _mk((N, K), dtype)
+    # ragged k-tiles (K = 200) take the register-staged loader, N % 8 == 4 the 4-column epilogue
+    _plan(A, B, M, N, K, "staged" if K == 200 else "direct", "row4" if N % 8 else "fast")
     C = H.gemm(A, B, M, N, K)
     ref = A.double() @ B.double().t()
     assert report(f"gemm_nt {dtype} {M}x{N}x{K}", C, ref, TOL[dtype]) <= TOL[dtype]
@@ -35,6 +48,7 @@ def test_nn_b_kstrided(dtype, M, N, K):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(1)
     A, W = _mk((M, K), dtype), _mk((K, N), dtype)
+    _plan(A, W, M, N, K, "staged" if N % 128 else "direct", "fast", b_kstrided=True)      # (k-strided B: N % 128 for DIRECT)
     C = H.gemm(A, W, M, N, K, b_kstrided=True)
     ref = A.double() @ W.double()
     assert report(f"gemm_nn {dtype} {M}x{N}x{K}", C, ref, TOL[dtype]) <= TOL[dtype]
@@ -47,6 +61,9 @@ def test_tn_both_kstrided(dtype, M, N, K, split):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(2)
     Y, X = _mk((K, M), dtype), _mk((K, N), dtype)
+    # (768 x 768 x 4000 in 8 slabs: 72 workgroups of the 256 family, below its default threshold of 96)
+    _plan(Y, X, M, N, K, "staged" if M % 128 or N % 128 else "direct", "fast", a_kstrided=True, b_kstrided=True,
+          out_dtype=torch.float32, split_k=split)
     if split == 1:
         C = H.gemm(Y, X, M, N, K, a_kstrided=True, b_kstrided=True, out_dtype=torch.float32)
     else:
@@ -68,6 +85,10 @@ def test_epilogues(dtype):
     R = _mk((M, N), dtype)
     acc = A.double() @ B.double().t()
     tol = TOL[dtype]
+    impl = "fast" if dtype == torch.bfloat16 else "row8"      # (fp32 output: the fast epilogue exists for EPI_NONE only)
+    for epi in (L.EPI_BIAS, L.EPI_BIAS_QSCALE, L.EPI_BIAS_GELU, L.EPI_BIAS_RESID, L.EPI_GELU_BWD):
+        _plan(A, B, M, N, K, "direct", impl, epilogue=epi, bias=bias, resid=R)
+    _plan(A, B, M, N, K, "direct", "row8", epilogue=L.EPI_SCALE, out_dtype=torch.float32)
     C = H.gemm(A, B, M, N, K, epilogue=L.EPI_BIAS, bias=bias)
     assert report(f"epi_bias {dtype}", C, acc + bias.double(), tol) <= tol
     C = H.gemm(A, B, M, N, K, epilogue=L.EPI_BIAS_QSCALE, bias=bias, scale=0.125, scale_cols=128)
@@ -98,6 +119,8 @@ def test_patch_epilogue_and_row_remap(dtype):
     A, W = _mk((Bsz * T * Lp, K), dtype, 0.3), _mk((D, K), dtype, 0.3)
     tab_t, tab_l = torch.randn(T, D, device="cuda"), torch.randn(Lp, D, device="cuda")
     x = torch.zeros(Bsz * S, D, dtype=dtype, device="cuda")
+    _plan(A, W, Bsz * T * Lp, D, K, "direct", "row8", out=x, epilogue=L.EPI_PATCH, tab1=tab_t, tab2=tab_l, tab_L=Lp,
+          c_remap=(T * Lp, S, Mp))
     H.gemm(A, W, Bsz * T * Lp, D, K, out=x, epilogue=L.EPI_PATCH, tab1=tab_t, tab2=tab_l, tab_L=Lp,
            c_remap=(T * Lp, S, Mp))
     ref = (A.double() @ W.double().t()).view(Bsz, T, Lp, D) + tab_t.double()[None, :, None] + tab_l.double()[None, None]
@@ -106,6 +129,8 @@ def test_patch_epilogue_and_row_remap(dtype):
     assert report(f"epi_patch {dtype}", x.view(Bsz, S, D), full, TOL[dtype]) <= TOL[dtype]
     # dW with the A operand's k-rows remapped the same way (token rows -> patch rows)
     dx = _mk((Bsz * S, D), dtype)
+    _plan(dx, A, D, K, Bsz * T * Lp, "staged", "fast", a_kstrided=True, b_kstrided=True, lda=D, ldb=K, out_dtype=torch.float32,
+          a_remap=(T * Lp, S, Mp))
     dW = H.gemm(dx, A, D, K, Bsz * T * Lp, a_kstrided=True, b_kstrided=True, lda=D, ldb=K, out_dtype=torch.float32,
                 a_remap=(T * Lp, S, Mp))
     ref = dx.double().view(Bsz, S, D)[:, Mp:].reshape(-1, D).t() @ A.double()
@@ -133,26 +158,63 @@ def force_gemm256(monkeypatch):
     monkeypatch.setenv("XPRETRAIN_GEMM256", "2")     # use the 256x256 family whenever its preconditions hold
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("M,N,K", [(256, 256, 64), (1280, 512, 768), (1100, 768, 256), (300, 260, 96), (2356, 768, 3072)])
+def _params(shapes, bf16_fallback=()):
+    """(M, N, K, dtype) with the ids of a stacked (M,N,K) x dtype parametrisation; the bf16 cases of `bf16_fallback` left out (they
+    are test_gemm256_falls_back_to_128's)"""
+    return [pytest.param(*s, dt, id="-".join(map(str, s)) + f"-dtype{i}") for s in shapes for i, dt in enumerate(DTYPES)
+            if not (dt == torch.bfloat16 and s in bf16_fallback)]
+
+
+def _family256(dtype):
+    """the family a forced-256 test runs: the 256 family is bf16 only, fp32 parametrisations run the 128x128 family"""
+    return "g256" if dtype == torch.bfloat16 else "direct"
+
+
+@pytest.mark.parametrize("M,N,K,dtype", _params([(256, 256, 128), (1280, 512, 768), (1100, 768, 256), (304, 264, 128),
+                                                  (2356, 768, 3072), (256, 256, 64), (300, 260, 96)],
+                                                 bf16_fallback=[(256, 256, 64), (300, 260, 96)]))
 def test_gemm256_nt(force_gemm256, dtype, M, N, K):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(M + N + K)
     A, B = _mk((M, K), dtype), _mk((N, K), dtype)
+    _plan(A, B, M, N, K, _family256(dtype), "row4" if N % 8 else "fast")
     C = H.gemm(A, B, M, N, K)
     ref = A.double() @ B.double().t()
     assert report(f"gemm256_nt {dtype} {M}x{N}x{K}", C, ref, TOL[dtype]) <= TOL[dtype]
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("M,N,K", [(1280, 768, 2304), (520, 256, 72), (2356, 3072, 768)])
+@pytest.mark.parametrize("M,N,K,dtype", _params([(1280, 768, 2304), (512, 256, 128), (2356, 3072, 768), (520, 256, 72)],
+                                                 bf16_fallback=[(520, 256, 72)]))
 def test_gemm256_nn(force_gemm256, dtype, M, N, K):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(1)
     A, W = _mk((M, K), dtype), _mk((K, N), dtype)
+    _plan(A, W, M, N, K, "staged" if K % 32 else _family256(dtype), "fast", b_kstrided=True)
     C = H.gemm(A, W, M, N, K, b_kstrided=True)
     ref = A.double() @ W.double()
     assert report(f"gemm256_nn {dtype} {M}x{N}x{K}", C, ref, TOL[dtype]) <= TOL[dtype]
+
+
+@pytest.mark.parametrize("layout,M,N,K,family,impl", [
+    # one k-tile: the 256 family's pipeline needs >= 2 k-tiles in the last slab
+    pytest.param("nt", 256, 256, 64, "direct", "fast", id="nt-256-256-64"),
+    # N % 8 == 4: no 8-column epilogue, and the 256 family has only the fast one; K % 64 != 0 as well (ragged k-tile: staged)
+    pytest.param("nt", 300, 260, 96, "staged", "row4", id="nt-300-260-96"),
+    # K % 64 != 0 with a k-contiguous A (xp_gemm256_legal)
+    pytest.param("nn", 520, 256, 72, "staged", "fast", id="nn-520-256-72"),
+])
+def test_gemm256_falls_back_to_128(force_gemm256, layout, M, N, K, family, impl):
+    """bf16 problems the 256 family does not admit even when forced (XPRETRAIN_GEMM256=2): the planner runs them on the 128x128
+    family.  (These were test_gemm256_nt / _nn cases; those now hold 256-admissible neighbours.)"""
+    from xpretrain_amd import hip_ops as H
+    bf = torch.bfloat16
+    torch.manual_seed(M + N + K if layout == "nt" else 1)
+    bks = layout == "nn"
+    A, B = _mk((M, K), bf), _mk((K, N) if bks else (N, K), bf)
+    _plan(A, B, M, N, K, family, impl, b_kstrided=bks)
+    C = H.gemm(A, B, M, N, K, b_kstrided=bks)
+    ref = A.double() @ (B.double() if bks else B.double().t())
+    assert report(f"gemm256 fallback {layout} {M}x{N}x{K}", C, ref, TOL[bf]) <= TOL[bf]
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -161,6 +223,7 @@ def test_gemm256_tn(force_gemm256, dtype, M, N, K, split):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(2)
     Y, X = _mk((K, M), dtype), _mk((K, N), dtype)
+    _plan(Y, X, M, N, K, _family256(dtype), "fast", a_kstrided=True, b_kstrided=True, out_dtype=torch.float32, split_k=split)
     if split == 1:
         C = H.gemm(Y, X, M, N, K, a_kstrided=True, b_kstrided=True, out_dtype=torch.float32)
     else:
@@ -181,6 +244,8 @@ def test_gemm256_epilogues(force_gemm256, dtype):
     R = _mk((M, N), dtype)
     acc = A.double() @ B.double().t()
     tol = TOL[dtype]
+    for epi in (L.EPI_BIAS_QSCALE, L.EPI_BIAS_GELU, L.EPI_BIAS_RESID, L.EPI_GELU_BWD):
+        _plan(A, B, M, N, K, _family256(dtype), "fast" if dtype == torch.bfloat16 else "row8", epilogue=epi, bias=bias, resid=R)
     C = H.gemm(A, B, M, N, K, epilogue=L.EPI_BIAS_QSCALE, bias=bias, scale=0.125, scale_cols=128)
     ref = acc + bias.double(); ref[:, :128] *= 0.125
     assert report(f"g256 epi_qscale {dtype}", C, ref, tol) <= tol
@@ -210,6 +275,7 @@ def test_gemm_fused_colsum(epi):
     pre = torch.randn(M, N, device="cuda").to(bf)
     defer = H.DeferredReduce(dY.device)
     kw = dict(epilogue=L.EPI_GELU_BWD, resid=pre) if epi == "gelu_bwd" else {}
+    assert _plan(dY, W, M, N, K, "g256", "fast", b_kstrided=True, colsum_defer=defer, **kw)["colsum_rows"] == 2 * ((M + 255) // 256)
     out, cs = H.gemm(dY, W, M, N, K, b_kstrided=True, colsum_defer=defer, **kw)
     assert len(defer.segs) == 1 and defer.segs[0].nrows == 2 * ((M + 255) // 256)      # the fused path was taken (256-row tiles)
     defer.flush()
@@ -240,6 +306,8 @@ def test_gemm256_token_count_all_epilogues(M):
     A, B = _mk((M, K), bf, 0.5), _mk((N, K), bf, 0.2)
     bias = torch.randn(N, device="cuda")
     R = _mk((M, N), bf)
+    for epi in range(L.EPI_GELU_BWD + 1):
+        _plan(A, B, M, N, K, "g256", "fast", epilogue=epi, bias=bias, resid=R)
     acc = A.double() @ B.double().t()
     tol = TOL[bf]
     C = H.gemm(A, B, M, N, K)
@@ -274,6 +342,7 @@ def test_gemm256_token_count_nn_and_f32():
     M, N, K = 18848, 768, 256
     assert _tile_rows(M, N, K, b_kstrided=True) == 256
     A, W = _mk((M, K), bf, 0.5), _mk((K, N), bf, 0.2)
+    _plan(A, W, M, N, K, "g256", "fast", b_kstrided=True, out_dtype=torch.float32)
     C = H.gemm(A, W, M, N, K, b_kstrided=True)
     ref = A.double() @ W.double()
     assert report("g256 nn", C, ref, TOL[bf]) <= TOL[bf]
@@ -285,6 +354,7 @@ def test_gemm256_token_count_nn_and_f32():
 
 
 @pytest.mark.parametrize("M,N,K,split", [(3072, 768, 18848, 7), (768, 768, 18848, 27), (2304, 768, 9424, 9)])
+# (the splits of earlier rounds; the planner's own splits of the step, and the grid identity at them: test_gemm_plans_gpu.py)
 def test_dw_split_k_chunk_major_grid(M, N, K, split, tmp_path):
     """Weight-gradient shapes of the step (dW1, dWo, dWqkv): the split-K launch walks a 1-D grid over (k-chunk, tile) pairs,
     chunk-major per XCD (csrc/gemm256.hip).  Against fp64, and bit-identical to the (tile, z) grid (XPRETRAIN_DEBUG=dw_tile_major
@@ -296,6 +366,7 @@ def test_dw_split_k_chunk_major_grid(M, N, K, split, tmp_path):
     torch.manual_seed(M + split)
     bf = torch.bfloat16
     Y, X = _mk((K, M), bf, 0.3), _mk((K, N), bf, 0.3)
+    assert _plan(Y, X, M, N, K, "g256", "fast", a_kstrided=True, b_kstrided=True, split_k=split)["flat_split"] == split
     slabs = H.gemm(Y, X, M, N, K, a_kstrided=True, b_kstrided=True, split_k=split)
     dw = H.splitk_reduce(slabs, torch.empty(M, N, device="cuda"))
     ref = Y.double().t() @ X.double()
@@ -317,7 +388,7 @@ def test_dw_split_k_chunk_major_grid(M, N, K, split, tmp_path):
 def test_resid_epilogue_with_fp32_side_rows(M, N, K, S, Ms):
     """EPI_BIAS_RESID with the fp32 side rows of the residual stream (XpGemmDesc::resid_side / out_side): rows m with m % S < Ms take
     their residual operand from the fp32 side buffer and leave their fp32 result there as well as the rounded C row; all other rows
-    are untouched by the feature.  256-wide family (K = 768-like and K = 3072) and the 128x128 family."""
+    are untouched by the feature.  256-wide family (the step's row count) and the 128x128 family (the smaller row counts)."""
     from xpretrain_amd import hip_ops as H
     from xpretrain_amd import _lib as L
     torch.manual_seed(M + N)
@@ -328,6 +399,8 @@ def test_resid_epilogue_with_fp32_side_rows(M, N, K, S, Ms):
     nb = (M + S - 1) // S
     rs = torch.randn(nb * Ms, N, device="cuda")
     os_ = torch.full((nb * Ms, N), float("nan"), device="cuda")
+    _plan(A, B, M, N, K, "g256" if -(-M // 256) * -(-N // 256) >= 96 else "direct", "fast", epilogue=L.EPI_BIAS_RESID, bias=bias,
+          resid=R)      # (the 256 family from 96 workgroups by default)
     C = H.gemm(A, B, M, N, K, epilogue=L.EPI_BIAS_RESID, bias=bias, resid=R, resid_side=rs, out_side=os_, side=(S, Ms))
     plain = H.gemm(A, B, M, N, K, epilogue=L.EPI_BIAS_RESID, bias=bias, resid=R)
     acc = A.double() @ B.double().t() + bias.double()

@@ -1,6 +1,7 @@
 """CPU: the host-side planning entry points of the C ABI (no kernel is launched, no GPU needed): split-K planning,
 fused-column-sum availability, partial-row counts and workspace sizes."""
 import ctypes as C
+import os
 
 import pytest
 
@@ -200,3 +201,174 @@ def test_encoder_layer_rejects_bad_arguments():
     b = L.XpLayerBwd()
     b.dims = _dims(8 * 32, 512, 2048, 8, 32, 8, None)
     assert lib.xp_encoder_layer_bwd(C.byref(b), None) != 0 and b"null pointer" in lib.xp_last_error()
+
+
+# ---------------------------------------------------------------------------------------------- the plan query and the case table
+from tests import gemm_cases as G      # noqa: E402  (plain data)
+
+
+def case_desc(c):
+    d = L.XpGemmDesc()
+    for k, v in G.desc_fields(c).items():
+        setattr(d, k, v)
+    return d
+
+
+def set_case_env(c, monkeypatch):
+    """the case's XPRETRAIN_GEMM256 / XPRETRAIN_DEBUG (the library reads both at every call); the CU budget is set by case_budget"""
+    if c["gemm256"] is None:
+        monkeypatch.delenv("XPRETRAIN_GEMM256", raising=False)
+    else:
+        monkeypatch.setenv("XPRETRAIN_GEMM256", str(c["gemm256"]))
+    if c["debug"]:
+        monkeypatch.setenv("XPRETRAIN_DEBUG", ",".join(c["debug"]))
+    else:
+        monkeypatch.delenv("XPRETRAIN_DEBUG", raising=False)
+
+
+class case_budget:
+    """xp_set_cu_budget(case budget) for the duration of a with-block, the previous budget restored after"""
+
+    def __init__(self, c):
+        self.budget = c["budget"]
+
+    def __enter__(self):
+        self.prev = L.lib().xp_get_cu_budget()
+        assert L.lib().xp_set_cu_budget(self.budget) == 0
+        return self
+
+    def __exit__(self, *exc):
+        L.lib().xp_set_cu_budget(self.prev)
+
+
+def resolve_split(c, d):
+    """the case's split: its int, or what xp_gemm_auto_split / _slack answer for its descriptor"""
+    if c["split"] == "general":
+        return int(L.lib().xp_gemm_auto_split(C.byref(d)))
+    if c["split"] == "slack":
+        return int(L.lib().xp_gemm_auto_split_slack(C.byref(d)))
+    return int(c["split"])
+
+
+def check_plan(c, plan, split):
+    """the plan the case declares"""
+    e = c["expect"]
+    got = dict(family=G.FAMILIES[plan["family"]], impl=G.IMPLS[plan["epi_impl"]], split=split)
+    assert got == e, (c["id"], got, e)
+    assert plan["split"] == split and plan["tile_rows"] == G.TILE_ROWS[e["family"]], (c["id"], plan)
+    assert plan["colsum_rows"] > 0 or not c["colsum"], (c["id"], plan)
+
+
+@pytest.mark.parametrize("c", G.CASES, ids=[c["id"] for c in G.CASES])
+def test_case_table_plans(c, monkeypatch):
+    """every case of tests/gemm_cases.py gets the plan (kernel family / loader, epilogue implementation, split) it declares"""
+    from xpretrain_amd import hip_ops as H
+    set_case_env(c, monkeypatch)
+    with case_budget(c):
+        d = case_desc(c)
+        split = resolve_split(c, d)
+        d.split_k = split
+        plan = H.gemm_plan_of(d)
+    check_plan(c, plan, split)
+
+
+def _sweep_descs():
+    for rows in _SWEEP_ROWS:
+        for a, b in [(a, b) for a in _SWEEP_DIMS for b in _SWEEP_DIMS]:
+            for M, N, K, a_ks, b_ks in ((rows, a, b, False, False), (rows, a, b, False, True), (a, b, rows, True, True),
+                                        (a, b, rows, True, False)):
+                for dtype, out in ((L.XP_BF16, L.XP_BF16), (L.XP_BF16, L.XP_F32), (L.XP_F32, L.XP_F32)):
+                    yield _desc(M, N, K, a_ks=a_ks, b_ks=b_ks, dtype=dtype, out=out)
+
+
+@pytest.mark.parametrize("rows", _SWEEP_ROWS)
+def test_plan_query_agrees_with_the_planning_queries(rows):
+    """xp_debug_gemm_plan answers from the plan the other planning queries read: tile rows, column-sum rows, the auto splits; its
+    grid covers every tile and every slab exactly once"""
+    from xpretrain_amd import hip_ops as H
+    lib = L.lib()
+    for d in _sweep_descs():
+        if d.M != rows and d.K != rows:
+            continue
+        for epi in (L.EPI_NONE, L.EPI_GELU_BWD, L.EPI_BIAS):
+            d.epilogue, d.resid, d.ldr, d.split_k = epi, (1 if epi == L.EPI_GELU_BWD else 0), d.N, 1
+            for cs in (0, 1):
+                d.colsum_partials = cs
+                p = H.gemm_plan_of(d)
+                assert p["colsum_rows"] == lib.xp_gemm_colsum_rows(C.byref(d)), (d.M, d.N, d.K, epi)
+            d.colsum_partials = 0
+            for split in (1, lib.xp_gemm_auto_split(C.byref(d)), lib.xp_gemm_auto_split_slack(C.byref(d))):
+                d.split_k = split
+                p = H.gemm_plan_of(d)
+                assert p["tile_rows"] == lib.xp_gemm_tile_rows(C.byref(d)) and p["split"] == split, (d.M, d.N, d.K, split, p)
+                assert p["tiles_m"] == _cdiv(d.M, p["tile_rows"]) and p["tiles_n"] == _cdiv(d.N, p["tile_rows"])
+                assert (split - 1) * p["k_per_split"] < d.K <= split * p["k_per_split"], (d.M, d.N, d.K, split, p)
+                tiles = p["tiles_m"] * p["tiles_n"]
+                assert p["grid"] == ((tiles * split, 1, 1) if p["flat_split"] else (tiles, 1, split)), p
+                assert p["flat_split"] in (0, split) and (p["flat_split"] == 0 or (p["family"] == L.GEMM_FAMILY_256 and split > 1))
+                assert p["family"] == L.GEMM_FAMILY_256 or p["colsum_rows"] == 0
+
+
+def _accepted(d):
+    """the argument rules of xp_gemm that do not concern data (csrc/gemm.hip::xp_gemm)"""
+    epc = 8 if d.in_dtype == L.XP_BF16 else 4
+    a_contig, b_contig = (d.M if d.a_kstrided else d.K), (d.N if d.b_kstrided else d.K)
+    return (a_contig % epc == 0 and b_contig % epc == 0 and d.lda % epc == 0 and d.ldb % epc == 0 and d.N % 4 == 0 and
+            d.ldc % 4 == 0 and (d.out_dtype == d.in_dtype or d.out_dtype == L.XP_F32))
+
+
+_LAYOUT_NAME = {v: k for k, v in G.LAYOUTS.items()}
+
+
+def planner_combinations():
+    """(variant, layout, epilogue kind, epilogue implementation, output dtype) of every plan over the _SWEEP_* grid, every epilogue
+    kind, under each switch (XPRETRAIN_GEMM256=2, gemm_no_glds, gemm_slow_epi) and with the descriptor changes that move a problem
+    to another variant (a pitch that is not a multiple of 8, a row-remapped output, a padded / remapped A)"""
+    lib = L.lib()
+    info = L.XpGemmPlanInfo()
+    found = set()
+    perturb = [(lo, ep) for lo in (None, "lda", "a_remap") for ep in (None, "ldc", "c_remap")]
+    envs = [dict(), dict(XPRETRAIN_GEMM256="2"), dict(XPRETRAIN_DEBUG="gemm_no_glds"), dict(XPRETRAIN_DEBUG="gemm_slow_epi")]
+    saved = {k: os.environ.get(k) for k in ("XPRETRAIN_GEMM256", "XPRETRAIN_DEBUG")}
+    try:
+        for env in envs:
+            for k in saved:
+                os.environ.pop(k, None)
+            os.environ.update(env)
+            for d in _sweep_descs():
+                lay = _LAYOUT_NAME[(d.a_kstrided, d.b_kstrided)]
+                out = "bf16" if d.out_dtype == L.XP_BF16 else "f32"
+                for lo, ep in (perturb if not env else [(None, None)]):
+                    d.lda, d.ldc = (d.M if d.a_kstrided else d.K), d.N
+                    d.a_grp = d.c_grp = 0
+                    if ep == "ldc":
+                        d.ldc = d.N + 4
+                    elif ep == "c_remap":
+                        d.c_grp, d.c_grp_stride, d.c_off = 64, 96, 16
+                    if lo == "lda":
+                        d.lda += 8
+                    elif lo == "a_remap":
+                        d.a_grp, d.a_grp_stride, d.a_off = 64, 80, 16
+                    if not _accepted(d):
+                        continue
+                    for epi in range(8):
+                        d.epilogue = epi
+                        d.resid, d.ldr = (1 if epi in (L.EPI_BIAS_RESID, L.EPI_GELU_BWD) else 0), d.N
+                        assert lib.xp_debug_gemm_plan(C.byref(d), C.byref(info)) == 0
+                        found.add((G.FAMILIES[info.family], lay, G.EPIS[epi], G.IMPLS[info.epi_impl], out))
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+    return found
+
+
+def test_case_table_covers_every_plan():
+    """Coverage: every (variant, layout, epilogue kind, epilogue implementation, output dtype) the planner produces over the sweep
+    has a case in tests/gemm_cases.py.  If the planner stops routing a case's problem to its variant, test_case_table_plans fails;
+    if it starts producing a new combination, this does -- the GPU tests never quietly run something else than they name."""
+    found = planner_combinations()
+    have = {(c["expect"]["family"], c["layout"], c["epi"], c["expect"]["impl"], c["out"]) for c in G.CASES}
+    missing = sorted(found - have)
+    assert not missing, f"{len(missing)} planner combinations without a case in tests/gemm_cases.py, e.g. {missing[:10]}"

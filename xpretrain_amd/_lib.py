@@ -46,6 +46,16 @@ class XpGemmDesc(C.Structure):
     ]
 
 
+class XpGemmPlanInfo(C.Structure):
+    _fields_ = [("family", i32), ("tile_rows", i32), ("split", i32), ("flat_split", i32), ("k_per_split", i64),
+                ("tiles_m", i32), ("tiles_n", i32), ("group_n", i32), ("epi_impl", i32), ("grid", i32 * 3), ("reserved", i32),
+                ("colsum_rows", i64)]
+
+
+GEMM_FAMILY_256, GEMM_FAMILY_DIRECT, GEMM_FAMILY_STAGED, GEMM_FAMILY_FRAMES = range(4)
+GEMM_EPI_FAST, GEMM_EPI_ROW8, GEMM_EPI_ROW4 = range(3)
+
+
 class XpReduceSeg(C.Structure):
     _fields_ = [("in_", vp), ("out", vp), ("stride", i64), ("nrows", i32), ("width", i32), ("accumulate", i32),
                 ("reserved", i32)]
@@ -154,6 +164,7 @@ SIGNATURES = {
     "xp_debug_gemm_timer_read": (i32, [C.POINTER(C.c_float), i32]),
     "xp_debug_set_attn_trace": (i32, [vp]),
     "xp_debug_gemm_occupancy": (i32, [i32]),
+    "xp_debug_gemm_plan": (i32, [C.POINTER(XpGemmDesc), C.POINTER(XpGemmPlanInfo)]),
     "xp_probe_mfma_bf16": (i32, [vp, vp, vp, vp]),
     "xp_probe_mfma_f32": (i32, [vp, vp, vp, vp]),
     "xp_probe_tr16": (i32, [vp, vp, vp, vp]),

@@ -719,6 +719,7 @@ struct GemmPlan {
   int split; int64_t k_per_split;
   int tiles_m, tiles_n, group_n, xcd_remap, flat_split;
   int wide, fast_epi;
+  int epi_impl;               // XP_GEMM_EPI_*: the epilogue the kernel takes (gemm_common.h::epi_impl, as fast_epi_dispatch decides)
   int64_t colsum_rows;        // partial rows of the fused column sums (256 family, split 1, bf16 out, EPI_NONE / GELU_BWD), else 0
   dim3 grid;
 };
@@ -735,11 +736,11 @@ static GemmPlan plan_gemm(const XpGemmDesc* d, int split) {
   p.fast_epi = p.wide && !xp_debug_flag("gemm_slow_epi") && d->c_grp == 0 && rows * d->ldc * osz < lim &&
                (!d->resid || rows * d->ldr * esz < lim) && (!d->aux || rows * d->ldaux * osz < lim);
   // the 256 family has only the fast epilogue, for the (epilogue, output type, column sums) combinations fast_epi_dispatch
-  // specialises: column sums with bf16 out after NONE / GELU_BWD, fp32 out after NONE, bf16 out after every kind but PATCH / SCALE
+  // specialises (gemm_common.h::fast_epi_specialised)
   const int ep = d->epilogue;
   const bool f32 = d->out_dtype == XP_F32, cs_epi = ep == XP_EPI_NONE || ep == XP_EPI_GELU_BWD;
-  const bool epi256 = p.fast_epi && (d->colsum_partials ? !f32 && cs_epi
-                                     : f32 ? ep == XP_EPI_NONE : ep >= XP_EPI_NONE && ep <= XP_EPI_GELU_BWD);
+  p.epi_impl = epi_impl(p.fast_epi, p.wide, ep, f32, d->colsum_partials != nullptr);
+  const bool epi256 = p.epi_impl == XP_GEMM_EPI_FAST;
   // XPRETRAIN_GEMM256: 0 = never, 1 = from 96 workgroups (default: a half-batch N = 768 GEMM of the forward's two chains is 111
   // tiles and runs beside its twin), 2 = whenever legal.  The 256 family (bf16 only: ke == 64) needs whole k-tiles in every
   // slab, no empty slab and >= 2 k-tiles in the last one (the pipeline depth).
@@ -852,6 +853,21 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
 }
 
 extern "C" int64_t xp_gemm_colsum_rows(const XpGemmDesc* d) { return d ? plan_gemm(d, d->split_k).colsum_rows : 0; }
+
+extern "C" int xp_debug_gemm_plan(const XpGemmDesc* d, XpGemmPlanInfo* out) {
+  XP_REQUIRE(d && out, "xp_debug_gemm_plan: null argument");
+  const GemmPlan p = plan_gemm(d, d->split_k);
+  static_assert((int)Family::G256 == XP_GEMM_FAMILY_256 && (int)Family::DIRECT == XP_GEMM_FAMILY_DIRECT &&
+                (int)Family::STAGED == XP_GEMM_FAMILY_STAGED && (int)Family::FRAMES == XP_GEMM_FAMILY_FRAMES, "XP_GEMM_FAMILY_*");
+  *out = XpGemmPlanInfo{};
+  out->family = (int)p.family; out->tile_rows = p.tile_rows;
+  out->split = p.split; out->flat_split = p.flat_split; out->k_per_split = p.k_per_split;
+  out->tiles_m = p.tiles_m; out->tiles_n = p.tiles_n; out->group_n = p.group_n;
+  out->epi_impl = p.epi_impl;
+  out->grid[0] = (int)p.grid.x; out->grid[1] = (int)p.grid.y; out->grid[2] = (int)p.grid.z;
+  out->colsum_rows = p.colsum_rows;
+  return XP_OK;
+}
 
 extern "C" int32_t xp_gemm_tile_rows(const XpGemmDesc* d) {
   if (!d || d->M <= 0 || d->N <= 0 || d->K <= 0) return 0;

@@ -56,14 +56,22 @@ struct SideRows {
   }
 };
 
+// EPI_BIAS_QSCALE's factor of columns n .. n+3: scale where n + e < scale_cols, 1 elsewhere (per column: scale_cols need not be a
+// multiple of the 4 or 8 columns a lane owns)
+__device__ __forceinline__ f32x4 qscale4(float scale, int64_t scale_cols, int64_t n) {
+  return f32x4{n < scale_cols ? scale : 1.f, n + 1 < scale_cols ? scale : 1.f, n + 2 < scale_cols ? scale : 1.f,
+               n + 3 < scale_cols ? scale : 1.f};
+}
+
 // Per-lane epilogue constants: the lane owns columns n .. n+3 of every row it stores.
 struct EpiLane {
-  f32x4 bias; float colscale;
+  f32x4 bias, colscale;
   __device__ __forceinline__ EpiLane(const KParams& p, int64_t n) {
     const int ep = p.epilogue;
     const bool has_bias = ep == XP_EPI_BIAS || ep == XP_EPI_BIAS_QSCALE || ep == XP_EPI_BIAS_GELU || ep == XP_EPI_BIAS_RESID;
     bias = has_bias ? load4(p.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-    colscale = ep == XP_EPI_SCALE ? p.scale : ((ep == XP_EPI_BIAS_QSCALE && n < p.scale_cols) ? p.scale : 1.0f);
+    colscale = ep == XP_EPI_SCALE ? f32x4{p.scale, p.scale, p.scale, p.scale}
+             : ep == XP_EPI_BIAS_QSCALE ? qscale4(p.scale, p.scale_cols, n) : f32x4{1.f, 1.f, 1.f, 1.f};
   }
 };
 
@@ -99,16 +107,16 @@ __device__ __forceinline__ void epi_row(const KParams& p, const EpiLane& el, f32
 
 // 8-column variant: half as many (16-byte) store instructions -- the epilogue is store-ISSUE bound.
 struct EpiLane8 {
-  f32x8 bias; float cs_lo, cs_hi;
+  f32x8 bias, cs;
   __device__ __forceinline__ EpiLane8(const KParams& p, int64_t n) {
     const EpiLane a(p, n), b(p, n + 4);
-    bias = f32x8{a.bias, b.bias}; cs_lo = a.colscale; cs_hi = b.colscale;
+    bias = f32x8{a.bias, b.bias}; cs = f32x8{a.colscale, b.colscale};
   }
 };
 template <typename T>
 __device__ __forceinline__ void epi_row8(const KParams& p, const EpiLane8& el, f32x8 v, int64_t m, int64_t n, float* Cf, T* Ct) {
   const int ep = p.epilogue;
-  v.lo = (v.lo + el.bias.lo) * el.cs_lo; v.hi = (v.hi + el.bias.hi) * el.cs_hi;
+  v.lo = (v.lo + el.bias.lo) * el.cs.lo; v.hi = (v.hi + el.bias.hi) * el.cs.hi;
   const int64_t crow = p.cmap(m);
   if (ep == XP_EPI_BIAS_GELU) {
     if (!p.aux) {}                                   // forward-only: the pre-activation is not kept
@@ -191,7 +199,7 @@ struct FastEpi {
   using Tr = EpiTraits<EPI>;
   static constexpr unsigned OSZ = F32 ? 4 : sizeof(T);
   __amdgpu_buffer_rsrc_t rc, rx;
-  f32x8 bias; float cs_lo, cs_hi;
+  f32x8 bias, cs;
   unsigned ld_c, ld_x;      // row pitch in bytes
   unsigned col_c, col_x;    // byte offset of column n
   bool ok, keep_aux;
@@ -210,15 +218,15 @@ struct FastEpi {
       ld_x = (unsigned)(p.ldr * sizeof(T)); col_x = (unsigned)(nn * sizeof(T));
     } else { rx = rc; ld_x = 0; col_x = 0; }
     if constexpr (Tr::bias) bias = f32x8{load4(p.bias + nn), load4(p.bias + nn + 4)};
-    if constexpr (EPI == XP_EPI_SCALE) cs_lo = cs_hi = p.scale;
-    if constexpr (EPI == XP_EPI_BIAS_QSCALE) { cs_lo = nn < p.scale_cols ? p.scale : 1.f; cs_hi = nn + 4 < p.scale_cols ? p.scale : 1.f; }
+    if constexpr (EPI == XP_EPI_SCALE) cs = f32x8{f32x4{p.scale, p.scale, p.scale, p.scale}, f32x4{p.scale, p.scale, p.scale, p.scale}};
+    if constexpr (EPI == XP_EPI_BIAS_QSCALE) cs = f32x8{qscale4(p.scale, p.scale_cols, nn), qscale4(p.scale, p.scale_cols, nn + 4)};
   }
   __device__ __forceinline__ unsigned off_c(unsigned m) const { return ok ? m * ld_c + col_c : EPI_OOB; }
   __device__ __forceinline__ unsigned off_x(unsigned m) const { return ok ? m * ld_x + col_x : EPI_OOB; }
   __device__ __forceinline__ Raw8<T> load_pre(unsigned m) const { return bload8<T>(rx, off_x(m)); }
   __device__ __forceinline__ f32x8 finish(f32x8 v, const Raw8<T>& pre, unsigned m) const {
     if constexpr (Tr::bias) { v.lo += bias.lo; v.hi += bias.hi; }
-    if constexpr (Tr::scale) { v.lo *= cs_lo; v.hi *= cs_hi; }
+    if constexpr (Tr::scale) { v.lo *= cs.lo; v.hi *= cs.hi; }
     if constexpr (EPI == XP_EPI_BIAS_GELU) {
       if (keep_aux) bstore8<T, F32>(rx, off_x(m), v);
 #pragma unroll
@@ -243,6 +251,21 @@ struct FastEpi {
   }
 };
 
+// The (epilogue, output type, column sums) combinations the fast epilogue specialises: column sums with bf16 out after NONE /
+// GELU_BWD, fp32 out after NONE, bf16 out after every kind but PATCH / SCALE.  The one predicate of both sides: the planner
+// (gemm.hip::plan_gemm, which gives the 256 family only these) and fast_epi_dispatch below.
+__host__ __device__ inline bool fast_epi_specialised(int epilogue, bool out_f32, bool colsum) {
+  if (colsum) return !out_f32 && (epilogue == XP_EPI_NONE || epilogue == XP_EPI_GELU_BWD);
+  return out_f32 ? epilogue == XP_EPI_NONE : epilogue >= XP_EPI_NONE && epilogue <= XP_EPI_GELU_BWD;
+}
+
+// The epilogue implementation a kernel of the plan runs (XP_GEMM_EPI_* in include/xpretrain_hip.h): the fast one where the plan
+// allows it (KParams::fast_epi) and the pair is specialised, else the generic epi_row8 (8 columns per lane) or epi_row (4).
+__host__ __device__ inline int epi_impl(int fast_epi, int wide, int epilogue, bool out_f32, bool colsum) {
+  if (fast_epi && fast_epi_specialised(epilogue, out_f32, colsum)) return XP_GEMM_EPI_FAST;
+  return wide ? XP_GEMM_EPI_ROW8 : XP_GEMM_EPI_ROW4;
+}
+
 // Calls f(integral_constant<int, EPI>, bool_constant<F32>, bool_constant<COLSUM>) for the (epilogue, output type) pairs the
 // fast path specialises; returns false for any other pair (the caller then runs the generic epilogue).  COLSUM (column
 // sums of the finished outputs, i.e. the bias gradient of the layer that produced this GEMM's input gradient) exists for
@@ -250,15 +273,15 @@ struct FastEpi {
 template <typename F>
 __device__ __forceinline__ bool fast_epi_dispatch(const KParams& p, F&& f) {
   using std::integral_constant; using std::bool_constant;
-  if (!p.fast_epi) return false;
+  if (epi_impl(p.fast_epi, p.wide, p.epilogue, p.out_f32, p.colsum != nullptr) != XP_GEMM_EPI_FAST) return false;
   if (p.colsum) {
     if (p.epilogue == XP_EPI_GELU_BWD) f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<true>{});
     else                               f(integral_constant<int, XP_EPI_NONE>{}, bool_constant<false>{}, bool_constant<true>{});
     return true;
   }
   if (p.out_f32) {
-    if (p.epilogue == XP_EPI_NONE) { f(integral_constant<int, XP_EPI_NONE>{}, bool_constant<true>{}, bool_constant<false>{}); return true; }
-    return false;
+    f(integral_constant<int, XP_EPI_NONE>{}, bool_constant<true>{}, bool_constant<false>{});
+    return true;
   }
   switch (p.epilogue) {
     case XP_EPI_NONE:        f(integral_constant<int, XP_EPI_NONE>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
@@ -266,8 +289,7 @@ __device__ __forceinline__ bool fast_epi_dispatch(const KParams& p, F&& f) {
     case XP_EPI_BIAS_QSCALE: f(integral_constant<int, XP_EPI_BIAS_QSCALE>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
     case XP_EPI_BIAS_GELU:   f(integral_constant<int, XP_EPI_BIAS_GELU>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
     case XP_EPI_BIAS_RESID:  f(integral_constant<int, XP_EPI_BIAS_RESID>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
-    case XP_EPI_GELU_BWD:    f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
-    default: return false;
+    default:                 f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
   }
 }
 

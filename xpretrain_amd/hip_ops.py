@@ -60,8 +60,10 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
          a_kstrided=False, b_kstrided=False, out_dtype=None, epilogue=L.EPI_NONE, bias=None, scale=1.0,
          scale_cols=0, resid=None, ldr=None, aux=None, ldaux=None, tab1=None, tab2=None, tab_L=0,
          a_remap=(0, 0, 0), c_remap=(0, 0, 0), split_k=1, out_rows=None, colsum_defer=None, colsum_name="gemm_colsum",
-         resid_side=None, out_side=None, side=None, frames=None, frame_patch=0, frame_norm=None):
+         resid_side=None, out_side=None, side=None, frames=None, frame_patch=0, frame_norm=None, plan_only=False):
     """C[M,N] = epilogue(sum_k A(m,k) B(n,k)); see include/xpretrain_hip.h::XpGemmDesc.
+
+    ``plan_only``: launch nothing and return the plan xp_gemm would launch for this call's descriptor (``gemm_plan_of``).
 
     ``frames`` ([BT,3,H,W] fp32 or uint8, contiguous) with ``frame_patch`` = P: A is the patch matrix of the frames, gathered by the
     operand loader (no im2col pass; pass ``A=None``); uint8 frames need ``frame_norm = (mean3, std3)``.
@@ -116,6 +118,10 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
         if not (resid_side.is_contiguous() and out_side.is_contiguous()) or resid_side.numel() < need or out_side.numel() < need:
             raise ValueError("gemm: resid_side / out_side are too small or not contiguous")
         d.resid_side, d.out_side, d.side_S, d.side_M = resid_side.data_ptr(), out_side.data_ptr(), S_, M_
+    if plan_only:
+        if colsum_defer is not None and L.lib().xp_gemm_colsum_rows(C.byref(d)) > 0:
+            d.colsum_partials = 1          # (the planner reads the pointer only as present / absent)
+        return gemm_plan_of(d)
     if colsum_defer is None:
         L.check(L.lib().xp_gemm(C.byref(d), _stream()), "xp_gemm")
         return out
@@ -129,6 +135,14 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
     L.check(L.lib().xp_gemm(C.byref(d), _stream()), "xp_gemm")
     colsum_defer.add(part, 0, cs, nrows, N, N)
     return out, cs
+
+
+def gemm_plan_of(d: L.XpGemmDesc) -> dict:
+    """The plan xp_gemm launches for descriptor ``d`` (xp_debug_gemm_plan: host only, nothing launched) as a dict of the
+    XpGemmPlanInfo fields."""
+    info = L.XpGemmPlanInfo()
+    L.check(L.lib().xp_debug_gemm_plan(C.byref(d), C.byref(info)), "xp_debug_gemm_plan")
+    return {f: (tuple(getattr(info, f)) if f == "grid" else getattr(info, f)) for f, _ in info._fields_ if f != "reserved"}
 
 
 def gemm_auto_split(M: int, N: int, K: int, dtype: torch.dtype, *, a_kstrided=True, b_kstrided=True, lda=None,
