@@ -442,6 +442,28 @@ typedef struct XpGemmPlanInfo {
   int64_t colsum_rows;                  /* partial rows of the fused column sums (as xp_gemm_colsum_rows)    */
 } XpGemmPlanInfo;
 int xp_debug_gemm_plan(const XpGemmDesc* desc, XpGemmPlanInfo* out);
+/* The plan xp_attn_fwd (backward == 0) / xp_attn_bwd2 (backward != 0) launches for these arguments, from the same planner: host
+ * only, launches nothing, reads XPRETRAIN_DEBUG as the call would.  cus > 0: planned for a device of that many CUs that grants every
+ * dynamic-LDS opt-in (no GPU needed); cus <= 0: for the current device, as a launch plans it (XP_ERR_LAUNCH if there is none or it
+ * refuses the planned kernel's opt-in).  The arguments are not validated. */
+enum { XP_ATTN_KERNEL_FWD = 0,        /* attn_fwd_kernel: one 7-wave workgroup per (problem, 112 query rows) */
+       XP_ATTN_KERNEL_FWD3 = 1,       /* attn_fwd3_kernel: persistent, problems of one LDS group (M + L <= 208) */
+       XP_ATTN_KERNEL_FWD4 = 2,       /* attn_fwd4_kernel: persistent, wider problems, one workgroup per CU */
+       XP_ATTN_KERNEL_BWD_PAIR = 3,   /* attn_bwd_dq_kernel, then attn_bwd_dkv_kernel */
+       XP_ATTN_KERNEL_BWD5 = 4,       /* attn_bwd5_kernel: dQ, dK, dV in one persistent launch */
+       XP_ATTN_KERNEL_F32 = 5 };      /* the fp32 compute mode's kernels (attention_f32.hip, which sizes their grids) */
+typedef struct XpAttnPlanInfo {
+  int32_t kernel;                       /* XP_ATTN_KERNEL_*                                                       */
+  int32_t grid, lds_bytes;              /* main launch (each kernel of the pair): workgroups, dynamic LDS; f32: 0  */
+  int32_t reduce_grid;                  /* proxy merge (forward) / proxy reduce (backward) workgroups; 0: none     */
+  int32_t uses_counter;                 /* the fused backward's problem counter is reset and used                 */
+  int32_t reserved;
+  int64_t part[2], delta[2], dq[2], dkv[2], counter[2];  /* workspace regions (byte offset, bytes); 0 bytes: not used   */
+  int64_t workspace_bytes;              /* this direction's regions (xp_attn_workspace_bytes: the larger direction) */
+  int64_t colsum_rows;                  /* as xp_attn_bwd_colsum_rows                                             */
+} XpAttnPlanInfo;
+int xp_debug_attn_plan(int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
+                       int32_t has_pad_mask, int32_t backward, int32_t cus, XpAttnPlanInfo* out);
 int xp_probe_mfma_bf16(const void* a, const void* b, float* c, void* stream);
 int xp_probe_mfma_f32(const float* a, const float* b, float* c, void* stream);
 /* packed-fp32 self-check (csrc/probe.hip): err[(variant*64 + lane)*2 + half] += mismatches between one v_pk_*_f32 form and

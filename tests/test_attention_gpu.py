@@ -9,14 +9,42 @@ from tests.gpu_util import report
 
 pytestmark = pytest.mark.gpu
 
+# The kernels each case runs on an MI355X (256 CUs), forward / backward (hip_ops.attn_plan names).  Every case asserts them on the
+# device; tests/test_planning_cpu.py plans these tables for 256 CUs on the host and fails if a case names other kernels or if a kernel
+# of XP_ATTN_KERNEL_* is run by no case.
+FUSED, WIDE, GENERAL, F32 = ("fwd3", "bwd5"), ("fwd4", "bwd_pair"), ("fwd", "bwd_pair"), ("f32", "f32")
+PROXY_CASES = {((4, 2, 49), 2, 2): FUSED, ((4, 12, 196), 1, 2): FUSED, ((1, 3, 5), 2, 1): FUSED, ((4, 3, 70), 1, 3): FUSED,
+               ((2, 5, 16), 2, 3): FUSED, ((4, 1, 196), 1, 1): FUSED, ((4, 2, 784), 1, 1): WIDE, ((4, 32, 196), 1, 1): FUSED,
+               ((20, 3, 49), 1, 2): GENERAL, ((17, 2, 180), 1, 1): GENERAL,     # > 16 proxy tokens: outside the persistent kernels' mask
+               ((4, 3, 300), 2, 2): WIDE, ((2, 2, 500), 1, 3): WIDE, ((4, 5, 208), 1, 2): WIDE, ((1, 2, 1023), 1, 1): WIDE,
+               ((4, 9, 784), 2, 3): WIDE}      # multi-group persistent kernel: 2..5 key groups, 2..4 query blocks, many problems
+RESCALE_CASE = ((4, 3, 196), 1, 2)                                                                             # FUSED
+CAUSAL_CASES = [(3, 12, 2, "ragged"), (2, 32, 8, "ragged"), (2, 7, 1, "none"), (2, 77, 2, "ragged"), (2, 16, 2, "allpad"),
+                (1, 130, 1, "ragged")]                                                                         # GENERAL
+PROXY_F32_CASES = [((4, 2, 49), 2, 2), ((4, 12, 196), 1, 2), ((1, 3, 5), 2, 1), ((4, 2, 784), 1, 1)]        # F32
+CAUSAL_F32_CASES = [(3, 12, 2, "ragged"), (2, 77, 2, "ragged"), (2, 16, 2, "allpad"), (1, 130, 1, "none")]    # F32
+COLSUM_CASES = [(4, 12, 196), (4, 2, 49), (1, 3, 5), None]                        # B 2, H 3: FUSED; None: causal, padded, GENERAL
+FUSED_VS_SPLIT_CASES = [((4, 12, 196), 2, 3), ((4, 2, 49), 2, 2), ((1, 3, 5), 2, 1), ((16, 3, 192), 1, 2), ((4, 7, 204), 1, 2),
+                        ((3, 40, 100), 3, 5)]                                                                  # FUSED
+
+
+def check_kernels(kernels, B, S, H, *, size=None, pad=False, dtype=torch.bfloat16, cus=0):
+    """the call runs `kernels` (forward, backward): what the planner gives its arguments on the current device (cus=0) or on a device
+    of `cus` CUs"""
+    from xpretrain_amd import hip_ops as Hh
+    got = tuple(Hh.attn_plan(B, S, H, size=size, pad_mask=(True if pad else None), dtype=dtype, backward=b, cus=cus)["kernel"]
+                for b in (False, True))
+    assert got == kernels, f"B{B} S{S} H{H} size{size} pad{pad} {dtype}: plans {got}, the case names {kernels}"
+
 
 def _split(qkv, B, S, H):
     q, k, v = qkv.view(B, S, 3, H, 64).double().unbind(2)          # [B,S,H,64]
     return [t.transpose(1, 2) for t in (q, k, v)]                  # [B,H,S,64]
 
 
-def _run(B, H, size, S, pad_mask, seed, scale=1.0, spike=False, q_scale=1.0, dtype=torch.bfloat16):
+def _run(B, H, size, S, pad_mask, seed, kernels, scale=1.0, spike=False, q_scale=1.0, dtype=torch.bfloat16):
     from xpretrain_amd import hip_ops as Hh
+    check_kernels(kernels, B, S, H, size=size, pad=pad_mask is not None, dtype=dtype)
     torch.manual_seed(seed)
     tf, tb = (1.2e-2, 2e-2) if dtype == torch.bfloat16 else (2e-5, 1e-4)     # fp32 mode: exact-arithmetic kernels
     qkv = (torch.randn(B * S, 3 * H * 64, device="cuda") * scale).to(dtype)
@@ -43,23 +71,18 @@ def _run(B, H, size, S, pad_mask, seed, scale=1.0, spike=False, q_scale=1.0, dty
     assert torch.isfinite(dqkv.float()).all()
 
 
-@pytest.mark.parametrize("size,B,H", [((4, 2, 49), 2, 2), ((4, 12, 196), 1, 2), ((1, 3, 5), 2, 1), ((4, 3, 70), 1, 3),
-                                      ((2, 5, 16), 2, 3), ((4, 1, 196), 1, 1), ((4, 2, 784), 1, 1), ((4, 32, 196), 1, 1),
-                                      ((20, 3, 49), 1, 2), ((17, 2, 180), 1, 1),       # > 16 proxy tokens: outside the persistent kernel's mask
-                                      ((4, 3, 300), 2, 2), ((2, 2, 500), 1, 3), ((4, 5, 208), 1, 2), ((1, 2, 1023), 1, 1),
-                                      ((4, 9, 784), 2, 3)])      # multi-group persistent kernel: 2..5 key groups, 2..4 query blocks, many problems
-
+@pytest.mark.parametrize("size,B,H", list(PROXY_CASES))
 def test_proxy_attention(size, B, H):
     M, N, L = size
-    _run(B, H, size, M + N * L, None, seed=M + N + L)
+    _run(B, H, size, M + N * L, None, seed=M + N + L, kernels=PROXY_CASES[(size, B, H)])
 
 
 def test_proxy_attention_rescale_and_qscale():
-    _run(1, 2, (4, 3, 196), 4 + 3 * 196, None, seed=5, scale=2.0, spike=True, q_scale=0.125)
+    (M, N, L), B, H = RESCALE_CASE
+    _run(B, H, (M, N, L), M + N * L, None, seed=5, kernels=FUSED, scale=2.0, spike=True, q_scale=0.125)
 
 
-@pytest.mark.parametrize("B,S,H,mode", [(3, 12, 2, "ragged"), (2, 32, 8, "ragged"), (2, 7, 1, "none"), (2, 77, 2, "ragged"),
-                                        (2, 16, 2, "allpad"), (1, 130, 1, "ragged")])
+@pytest.mark.parametrize("B,S,H,mode", CAUSAL_CASES)
 def test_causal_attention(B, S, H, mode):
     torch.manual_seed(S)
     if mode == "none":
@@ -70,17 +93,17 @@ def test_causal_attention(B, S, H, mode):
         if mode == "allpad":
             mask[1] = 0
         mask = mask.cuda()
-    _run(B, H, None, S, mask, seed=S + 1)
+    _run(B, H, None, S, mask, seed=S + 1, kernels=GENERAL)
 
 
-@pytest.mark.parametrize("size,B,H", [((4, 2, 49), 2, 2), ((4, 12, 196), 1, 2), ((1, 3, 5), 2, 1), ((4, 2, 784), 1, 1)])
+@pytest.mark.parametrize("size,B,H", PROXY_F32_CASES)
 def test_proxy_attention_fp32_mode(size, B, H):
     """the fp32 compute mode's attention kernels (csrc/attention_f32.hip) against the fp64 oracle core"""
     M, N, L = size
-    _run(B, H, size, M + N * L, None, seed=M + N + L, dtype=torch.float32, q_scale=0.125)
+    _run(B, H, size, M + N * L, None, seed=M + N + L, kernels=F32, dtype=torch.float32, q_scale=0.125)
 
 
-@pytest.mark.parametrize("B,S,H,mode", [(3, 12, 2, "ragged"), (2, 77, 2, "ragged"), (2, 16, 2, "allpad"), (1, 130, 1, "none")])
+@pytest.mark.parametrize("B,S,H,mode", CAUSAL_F32_CASES)
 def test_causal_attention_fp32_mode(B, S, H, mode):
     torch.manual_seed(S)
     mask = None
@@ -90,7 +113,7 @@ def test_causal_attention_fp32_mode(B, S, H, mode):
         if mode == "allpad":
             mask[1] = 0
         mask = mask.cuda()
-    _run(B, H, None, S, mask, seed=S + 1, dtype=torch.float32)
+    _run(B, H, None, S, mask, seed=S + 1, kernels=F32, dtype=torch.float32)
 
 
 def test_attention_rejects_bad_shapes():
@@ -100,7 +123,7 @@ def test_attention_rejects_bad_shapes():
         Hh.attn_fwd(qkv, 3, 10, 1, size=(4, 2, 2))
 
 
-@pytest.mark.parametrize("geom", [(4, 12, 196), (4, 2, 49), (1, 3, 5), None])
+@pytest.mark.parametrize("geom", COLSUM_CASES)
 def test_backward_emits_the_qkv_bias_column_sums(geom):
     """xp_attn_bwd2: the bias gradients of q/k/v_proj (column sums of dqkv as stored) come out of the backward kernels -- frame rows
     from the dQ / dKV workgroups, proxy rows from the proxy reduce -- and equal a separate pass over dqkv; the causal text pattern
@@ -114,6 +137,7 @@ def test_backward_emits_the_qkv_bias_column_sums(geom):
     else:
         M, N, Lp = geom
         S, size, pad = M + N * Lp, geom, None
+    check_kernels(GENERAL if geom is None else FUSED, B, S, Hh, size=size, pad=pad is not None)
     qkv = (torch.randn(B * S, 3 * Hh * 64, device="cuda") * 0.7).to(torch.bfloat16)
     out, stats = H.attn_fwd(qkv, B, S, Hh, size=size, pad_mask=pad)
     dout = torch.randn_like(out)
@@ -127,8 +151,7 @@ def test_backward_emits_the_qkv_bias_column_sums(geom):
     assert report(f"attn bwd fused colsum {geom}", cs, want, 1e-5, scale_floor=1e-3) <= 1e-5
 
 
-@pytest.mark.parametrize("geom,B,Hh", [((4, 12, 196), 2, 3), ((4, 2, 49), 2, 2), ((1, 3, 5), 2, 1), ((16, 3, 192), 1, 2), ((4, 7, 204), 1, 2),
-                                       ((3, 40, 100), 3, 5)])
+@pytest.mark.parametrize("geom,B,Hh", FUSED_VS_SPLIT_CASES)
 def test_fused_backward_against_the_two_kernel_path(geom, B, Hh, monkeypatch):
     """attn_bwd5_kernel (one launch: dQ, dK, dV, the bias column sums; problems handed out by a device counter) against the dQ / dKV
     kernel pair on identical inputs (XPRETRAIN_DEBUG=attn_bwd_split): same operands, same rounding points, different summation order
@@ -137,6 +160,7 @@ def test_fused_backward_against_the_two_kernel_path(geom, B, Hh, monkeypatch):
     from xpretrain_amd import hip_ops as H
     M, N, Lp = geom
     S = M + N * Lp
+    check_kernels(FUSED, B, S, Hh, size=geom)
     torch.manual_seed(3)
     qkv = (torch.randn(B * S, 3 * Hh * 64, device="cuda") * 0.7).to(torch.bfloat16)
     out, stats = H.attn_fwd(qkv, B, S, Hh, size=geom)
@@ -147,6 +171,7 @@ def test_fused_backward_against_the_two_kernel_path(geom, B, Hh, monkeypatch):
     again = H.attn_bwd(qkv, out, dout, stats, B, S, Hh, size=geom, q_scale=0.125)
     assert torch.equal(got, again)
     monkeypatch.setenv("XPRETRAIN_DEBUG", "attn_bwd_split")
+    check_kernels(("fwd3", "bwd_pair"), B, S, Hh, size=geom)
     want = H.attn_bwd(qkv, out, dout, stats, B, S, Hh, size=geom, q_scale=0.125)
     monkeypatch.delenv("XPRETRAIN_DEBUG")
     assert torch.isfinite(got.float()).all()

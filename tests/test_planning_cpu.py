@@ -1,7 +1,8 @@
 """CPU: the host-side planning entry points of the C ABI (no kernel is launched, no GPU needed): split-K planning,
-fused-column-sum availability, partial-row counts and workspace sizes."""
+fused-column-sum availability, partial-row counts and workspace sizes, the GEMM and attention plans."""
 import ctypes as C
 import os
+import re
 
 import pytest
 
@@ -372,3 +373,101 @@ def test_case_table_covers_every_plan():
     have = {(c["expect"]["family"], c["layout"], c["epi"], c["expect"]["impl"], c["out"]) for c in G.CASES}
     missing = sorted(found - have)
     assert not missing, f"{len(missing)} planner combinations without a case in tests/gemm_cases.py, e.g. {missing[:10]}"
+
+
+# ---------------------------------------------------------------------------------------------- attention plans
+from tests import test_attention_gpu as AG      # noqa: E402  (its case tables)
+
+_PERSISTENT = ("fwd3", "fwd4", "bwd5")
+
+
+def _attn_rule(mode, B, H, S, M, N, Lp, f32, pad, bwd, cus, split):
+    """(kernel, main grid) by the rules of csrc/attention.hip::plan_attn, restated"""
+    if f32:
+        return "f32", 0
+    R, nprob = (M + Lp if mode == L.ATTN_PROXY else S), B * H * N
+    persistent = mode == L.ATTN_PROXY and M <= 16 and not pad
+    if not bwd and persistent and R <= 208:
+        return "fwd3", min(nprob, cus)
+    if not bwd and persistent and cus % 8 == 0 and cus // 8 >= _cdiv(_cdiv(R, 16), 16):
+        return "fwd4", cus
+    if bwd and persistent and R <= 208 and not split:
+        return "bwd5", min(nprob, cus)
+    return ("bwd_pair" if bwd else "fwd"), _cdiv(nprob, 8) * 8 * _cdiv(R, 112)
+
+
+def _attn_geoms():
+    """(mode, B, H, S, M, N, L): proxy rows R = M + L on both sides of 208, M on both sides of 16, and causal problems"""
+    for B, H in ((1, 1), (2, 3), (8, 12)):
+        for M in (1, 4, 16, 17, 20):
+            for N in (1, 3, 12):
+                for Lp in (5, 49, 192, 196, 204, 205, 300, 784, 1023):
+                    yield L.ATTN_PROXY, B, H, M + N * Lp, M, N, Lp
+        for S in (7, 32, 77, 130, 300):
+            yield L.ATTN_CAUSAL, B, H, S, 0, 1, S
+
+
+@pytest.mark.parametrize("split", [False, True])
+def test_attention_plan_rules(split, monkeypatch):
+    """xp_debug_attn_plan over geometries, padding, CU counts, dtypes and both directions: the kernel and grids of the rules above;
+    dynamic LDS exactly for the persistent kernels; the problem counter exactly for attn_bwd5; workspace regions of the sizes the
+    kernels write, 4-byte aligned, disjoint and inside xp_attn_workspace_bytes, which keeps its formula; column-sum rows as
+    xp_attn_bwd_colsum_rows"""
+    import torch
+    from xpretrain_amd import hip_ops as H
+    lib = L.lib()
+    if split:
+        monkeypatch.setenv("XPRETRAIN_DEBUG", "attn_bwd_split")
+    else:
+        monkeypatch.delenv("XPRETRAIN_DEBUG", raising=False)
+    for mode, B, Hh, S, M, N, Lp in _attn_geoms():
+        P = B * Hh * N
+        size = (M, N, Lp) if mode == L.ATTN_PROXY else None
+        ws = lib.xp_attn_workspace_bytes(mode, B, Hh, M, N, Lp)
+        assert ws == (4 * max(P * M * 66, B * Hh * S + P * M * 192 + 64) if size else 4 * B * Hh * S), (size, B, Hh)
+        for f32 in (False, True):
+            dtype = L.XP_F32 if f32 else L.XP_BF16
+            rows = lib.xp_attn_bwd_colsum_rows(mode, B, Hh, S, M, N, Lp, dtype)
+            for pad in (False, True):
+                for cus in (256, 80, 36, 8):
+                    for bwd in (False, True):
+                        p = H.attn_plan(B, S, Hh, size=size, pad_mask=(True if pad else None),
+                                        dtype=(torch.float32 if f32 else torch.bfloat16), backward=bwd, cus=cus)
+                        case = (size, B, Hh, S, f32, pad, cus, bwd, p)
+                        assert (p["kernel"], p["grid"]) == _attn_rule(mode, B, Hh, S, M, N, Lp, f32, pad, bwd, cus, split), case
+                        assert (p["lds_bytes"] > 0) == (p["kernel"] in _PERSISTENT) and p["lds_bytes"] <= 160 * 1024, case
+                        assert p["uses_counter"] == (p["kernel"] == "bwd5"), case
+                        assert p["reduce_grid"] == (B * Hh * M if size and not f32 else 0), case
+                        assert p["colsum_rows"] == rows, case
+                        want = (dict(part=0, delta=4 * B * Hh * S, dq=4 * P * M * 64, dkv=4 * P * M * 128, counter=256 if size else 0)
+                                if bwd else dict(part=4 * P * M * 66, delta=0, dq=0, dkv=0, counter=0))
+                        assert {r: p[r][1] for r in want} == want, case
+                        used = sorted(p[r] for r in want if p[r][1])
+                        assert all(off % 4 == 0 and n % 4 == 0 for off, n in used), case
+                        assert all(a[0] + a[1] <= b[0] for a, b in zip(used, used[1:])), case
+                        end = used[-1][0] + used[-1][1] if used else 0
+                        assert p["workspace_bytes"] == end <= ws, case
+
+
+def test_attention_gpu_cases_name_the_kernels_they_run():
+    """Every case of tests/test_attention_gpu.py names the kernels the planner gives it at 256 CUs (an MI355X), and every
+    XP_ATTN_KERNEL_* is run by some case.  If the planner moves a case to another kernel, or a kernel loses its last case, this
+    fails -- the GPU tests never quietly run something else than they name."""
+    import torch
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "xpretrain_hip.h")).read()
+    declared = {int(v): n.lower() for n, v in re.findall(r"XP_ATTN_KERNEL_(\w+) = (\d+)", header)}
+    assert declared == dict(enumerate(L.ATTN_KERNELS))
+    run = set()
+
+    def check(kernels, B, S, H, **kw):
+        AG.check_kernels(kernels, B, S, H, cus=256, **kw)
+        run.update(kernels)
+    for (size, B, H), kernels in list(AG.PROXY_CASES.items()) + [(AG.RESCALE_CASE, AG.FUSED)] + \
+            [(c, AG.FUSED) for c in AG.FUSED_VS_SPLIT_CASES]:
+        check(kernels, B, size[0] + size[1] * size[2], H, size=size)
+    for size, B, H in AG.PROXY_F32_CASES:
+        check(AG.F32, B, size[0] + size[1] * size[2], H, size=size, dtype=torch.float32)
+    for (B, S, H, mode), kernels in [(c, AG.GENERAL) for c in AG.CAUSAL_CASES] + [(c, AG.F32) for c in AG.CAUSAL_F32_CASES]:
+        check(kernels, B, S, H, pad=mode != "none", dtype=(torch.float32 if kernels == AG.F32 else torch.bfloat16))
+    missing = sorted(set(L.ATTN_KERNELS) - run)
+    assert not missing, f"no case of tests/test_attention_gpu.py runs XP_ATTN_KERNEL_{'/'.join(m.upper() for m in missing)}"

@@ -56,6 +56,16 @@ GEMM_FAMILY_256, GEMM_FAMILY_DIRECT, GEMM_FAMILY_STAGED, GEMM_FAMILY_FRAMES = ra
 GEMM_EPI_FAST, GEMM_EPI_ROW8, GEMM_EPI_ROW4 = range(3)
 
 
+class XpAttnPlanInfo(C.Structure):
+    _fields_ = [("kernel", i32), ("grid", i32), ("lds_bytes", i32), ("reduce_grid", i32), ("uses_counter", i32), ("reserved", i32),
+                ("part", i64 * 2), ("delta", i64 * 2), ("dq", i64 * 2), ("dkv", i64 * 2), ("counter", i64 * 2),
+                ("workspace_bytes", i64), ("colsum_rows", i64)]
+
+
+# XP_ATTN_KERNEL_* by value, lower case
+ATTN_KERNELS = ("fwd", "fwd3", "fwd4", "bwd_pair", "bwd5", "f32")
+
+
 class XpReduceSeg(C.Structure):
     _fields_ = [("in_", vp), ("out", vp), ("stride", i64), ("nrows", i32), ("width", i32), ("accumulate", i32),
                 ("reserved", i32)]
@@ -165,6 +175,7 @@ SIGNATURES = {
     "xp_debug_set_attn_trace": (i32, [vp]),
     "xp_debug_gemm_occupancy": (i32, [i32]),
     "xp_debug_gemm_plan": (i32, [C.POINTER(XpGemmDesc), C.POINTER(XpGemmPlanInfo)]),
+    "xp_debug_attn_plan": (i32, [i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, C.POINTER(XpAttnPlanInfo)]),
     "xp_probe_mfma_bf16": (i32, [vp, vp, vp, vp]),
     "xp_probe_mfma_f32": (i32, [vp, vp, vp, vp]),
     "xp_probe_tr16": (i32, [vp, vp, vp, vp]),

@@ -24,7 +24,6 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
@@ -1591,6 +1590,67 @@ int check_common(const char* name, int32_t mode, int64_t B, int64_t H, int64_t S
   return XP_OK;
 }
 
+// ============================================================================================ planning
+// plan_attn decides how an attention call runs: kernel, grids, dynamic LDS, workspace layout, bias column-sum rows.  xp_attn_fwd /
+// xp_attn_bwd2 launch the plan; xp_attn_workspace_bytes, xp_attn_bwd_colsum_rows and xp_debug_attn_plan answer from it.
+struct AttnCall { int32_t mode; int64_t B, H, S, M, N, L; int32_t dtype; bool pad, bwd; };
+struct Region { int64_t off, bytes; float* in(void* ws) const { return reinterpret_cast<float*>(static_cast<char*>(ws) + off); } };
+struct AttnPlan {
+  AP geo;                            // the kernel parameters the geometry decides: mode .. L, R, nq, nprob, cs_main
+  int kernel, lds; const void* lds_kernel;   // XP_ATTN_KERNEL_*; dynamic LDS of the main launch, lds_kernel's opt-in
+  unsigned grid, reduce_grid;        // main launch (each kernel of the pair; fp32: attention_f32.hip's own); proxy merge / reduce, 0: none
+  bool uses_counter;                 // the fused backward takes its problems from the workspace counter
+  Region part, delta, dq, dkv, counter;      // workspace bytes: by problem and direction only
+  int64_t ws_bytes, colsum_rows;     // colsum_rows: 0 in fp32 mode (callers run xp_colsum_partials)
+};
+
+// cus: the device's CUs (the persistent kernels' grids, attn_fwd4's admission).  CAUSAL is planned as M = 0, N = 1, L = S.
+AttnPlan plan_attn(AttnCall c, int cus) {
+  AttnPlan p{};
+  const bool proxy = c.mode == XP_ATTN_PROXY;
+  if (!proxy) { c.M = 0; c.N = 1; c.L = c.S; }
+  const int64_t P = c.B * c.H * c.N, R = proxy ? c.M + c.L : c.S, nq = cdiv(R, FQ);
+  AP& g = p.geo;
+  g.mode = c.mode; g.B = (int)c.B; g.H = (int)c.H; g.S = (int)c.S; g.M = (int)c.M; g.N = (int)c.N; g.L = (int)c.L;
+  g.R = (int)R; g.nq = (int)nq; g.nprob = (int)P; g.cs_main = (int)(c.B * c.N * nq);
+  if (!c.bwd) p.part = {0, P * c.M * PART * 4};                       // the proxy rows' (m, l, O) per problem
+  else {                                                                // delta, the proxy rows' dQ and dK / dV per problem, counter
+    p.delta = {0, c.B * c.H * c.S * 4};
+    p.dq = {p.delta.bytes, P * c.M * DH * 4};
+    p.dkv = {p.dq.off + p.dq.bytes, P * c.M * 2 * DH * 4};
+    p.counter = {p.dkv.off + p.dkv.bytes, proxy ? 64 * 4 : 0};         // (4 of the 256 bytes used)
+  }
+  p.ws_bytes = c.bwd ? p.counter.off + p.counter.bytes : p.part.bytes;
+  p.colsum_rows = c.dtype == XP_BF16 && (proxy || c.mode == XP_ATTN_CAUSAL) ? c.B * c.N * nq + c.B * c.M : 0;
+  if (c.dtype == XP_F32) { p.kernel = XP_ATTN_KERNEL_F32; return p; }
+  // The persistent kernels: proxy problems, no padding mask, at most 16 proxy rows (their proxy x proxy mask lives in query tile 0 /
+  // key sub-tile 0 only).  One LDS group (R <= 208): attn_fwd3 / attn_bwd5 (XPRETRAIN_DEBUG=attn_bwd_split keeps the two-kernel
+  // backward: A/B and the cross-check test); wider problems: attn_fwd4 where every XCD gets whole quads of workgroups.
+  const bool persistent = proxy && c.M <= 16 && !c.pad;
+  const unsigned per_cu = (unsigned)(P < cus ? P : cus);
+  if (!c.bwd && persistent && R <= FG) {
+    p.kernel = XP_ATTN_KERNEL_FWD3; p.grid = per_cu; p.lds = F3_LDS; p.lds_kernel = reinterpret_cast<const void*>(attn_fwd3_kernel);
+  } else if (!c.bwd && persistent && cus % 8 == 0 && cus / 8 >= cdiv(cdiv(R, 16), 2 * F3W)) {
+    p.kernel = XP_ATTN_KERNEL_FWD4; p.grid = (unsigned)cus; p.lds = F3_LDS; p.lds_kernel = reinterpret_cast<const void*>(attn_fwd4_kernel);
+  } else if (c.bwd && persistent && R <= FG && !xp_debug_flag("attn_bwd_split")) {
+    p.kernel = XP_ATTN_KERNEL_BWD5; p.grid = per_cu; p.lds = B5_LDS; p.lds_kernel = reinterpret_cast<const void*>(attn_bwd5_kernel);
+    p.uses_counter = true;
+  } else {                           // the 7-wave kernels: the query blocks of one problem get workgroup ids 8 apart
+    p.kernel = c.bwd ? XP_ATTN_KERNEL_BWD_PAIR : XP_ATTN_KERNEL_FWD; p.grid = (unsigned)(cdiv(P, 8) * 8 * nq);
+  }
+  p.reduce_grid = proxy ? (unsigned)(c.B * c.H * c.M) : 0;
+  return p;
+}
+
+// plan_attn for the current device (cus <= 0): its CU count, and the planned kernel's dynamic-LDS opt-in granted (gfx950 grants the
+// 104 / ~156 of its 160 KiB per CU they ask for); cus > 0 (xp_debug_attn_plan): a device of that many CUs that grants every opt-in
+int plan_attn_for(const AttnCall& c, int cus, AttnPlan& p) {
+  const bool device = cus <= 0;
+  if (device && !(cus = xp_device_cus())) return XP_ERR_LAUNCH;
+  p = plan_attn(c, cus);
+  return device && p.lds && !xp_device_cus(p.lds_kernel, p.lds) ? XP_ERR_LAUNCH : XP_OK;
+}
+
 }  // namespace
 
 // fp32 compute mode (attention_f32.hip): exact-arithmetic kernels, same layout / statistics / workspace contract
@@ -1604,13 +1664,10 @@ static void* g_attn_trace = nullptr;
 extern "C" int xp_debug_set_attn_trace(void* device_buffer) { g_attn_trace = device_buffer; return XP_OK; }
 
 extern "C" size_t xp_attn_workspace_bytes(int32_t mode, int64_t B, int64_t H, int64_t M, int64_t N, int64_t L) {
-  // S is M + N*L for PROXY; for CAUSAL callers pass M=0, N=1, L=S
-  const int64_t S = M + N * L;
-  const int64_t delta = B * H * S;
-  if (mode != XP_ATTN_PROXY) return (size_t)delta * sizeof(float);
-  const int64_t P = B * H * N;
-  const int64_t fwd = P * M * PART, bwd = delta + P * M * DH + P * M * 2 * DH + 64;      // (+ the fused backward's problem counter)
-  return (size_t)(fwd > bwd ? fwd : bwd) * sizeof(float);
+  // the larger direction, whatever the dtype (S is M + N*L for PROXY; for CAUSAL callers pass M=0, N=1, L=S)
+  const int64_t fwd = plan_attn(AttnCall{mode, B, H, M + N * L, M, N, L, XP_BF16, false, false}, 0).ws_bytes;
+  const int64_t bwd = plan_attn(AttnCall{mode, B, H, M + N * L, M, N, L, XP_BF16, false, true}, 0).ws_bytes;
+  return (size_t)(fwd > bwd ? fwd : bwd);
 }
 
 extern "C" int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, float* stats,
@@ -1624,60 +1681,25 @@ extern "C" int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ld
   if (dtype == XP_F32) return xp_attn_f32_fwd(qkv, ldqkv, out, ldo, stats, pad_mask, mode, B, H, S, M, N, L, (hipStream_t)stream);
   XP_REQUIRE(mode == XP_ATTN_CAUSAL || (workspace && workspace_bytes >= xp_attn_workspace_bytes(mode, B, H, M, N, L)),
              "xp_attn_fwd: workspace too small");
-  AP p{};
+  AttnPlan pl;
+  if ((rc = plan_attn_for(AttnCall{mode, B, H, S, M, N, L, dtype, pad_mask != nullptr, false}, 0, pl))) return rc;
+  AP p = pl.geo;
   p.qkv = (const bf16_t*)qkv; p.ldqkv = ldqkv; p.out = (bf16_t*)out; p.ldo = ldo; p.stats = stats; p.pad = pad_mask;
-  p.mode = mode; p.B = (int)B; p.H = (int)H; p.S = (int)S; p.M = (int)M; p.N = (int)N; p.L = (int)L;
-  p.R = mode == XP_ATTN_PROXY ? (int)(M + L) : (int)S;
-  p.ws0 = (float*)workspace;
-  p.ws2 = (float*)g_attn_trace;
+  p.ws0 = pl.part.in(workspace); p.ws2 = (float*)g_attn_trace;
   hipStream_t st = (hipStream_t)stream;
-  p.nq = (int)cdiv(p.R, FQ); p.nprob = (int)(B * H * N);
-  // the persistent kernel: proxy problems that fit one LDS group, no padding mask, at most 16 proxy rows (its proxy x proxy mask
-  // lives in query tile 0 / key sub-tile 0 only), and a device that grants the 104 KiB dynamic-LDS opt-in (configured per device)
-  bool use3 = mode == XP_ATTN_PROXY && p.R <= FG && p.M <= 16 && !pad_mask;
-  // the multi-group persistent kernel: proxy problems wider than one LDS group (448^2 frames), same conditions otherwise
-  bool use4 = mode == XP_ATTN_PROXY && p.R > FG && p.M <= 16 && !pad_mask;
-  int ncu = 256;
-  if (use3 || use4) {
-    static std::mutex mu;
-    static int configured[64] = {0};                  // per device -- 0: not yet, > 0: CU count, -1: refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) use3 = use4 = false;
-    else {
-      std::lock_guard<std::mutex> lock(mu);
-      if (!configured[dev]) {
-        int n = 256;
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            F3_LDS) == hipSuccess &&
-                        hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            F3_LDS) == hipSuccess;
-        configured[dev] = ok ? (n > 0 ? n : 256) : -1;
-      }
-      if (configured[dev] < 0) use3 = use4 = false; else ncu = configured[dev];
-      if (use4 && (ncu % 8 != 0 || ncu / 8 < (int)cdiv(cdiv(p.R, 16), 2 * F3W))) use4 = false;      // needs whole quads per XCD
-    }
-  }
-  if (use3) {
-    attn_fwd3_kernel<<<(unsigned)(p.nprob < ncu ? p.nprob : ncu), F3THR, F3_LDS, st>>>(p);
-  } else if (use4) {
-    attn_fwd4_kernel<<<(unsigned)ncu, F3THR, F3_LDS, st>>>(p);      // persistent: one workgroup per CU (ncu is a multiple of 8 here)
-  } else {
-    attn_fwd_kernel<<<(unsigned)(cdiv(p.nprob, 8) * 8 * p.nq), FTHR, 0, st>>>(p);
-  }
+  if (pl.kernel == XP_ATTN_KERNEL_FWD3)      attn_fwd3_kernel<<<pl.grid, F3THR, pl.lds, st>>>(p);
+  else if (pl.kernel == XP_ATTN_KERNEL_FWD4) attn_fwd4_kernel<<<pl.grid, F3THR, pl.lds, st>>>(p);
+  else                                       attn_fwd_kernel<<<pl.grid, FTHR, 0, st>>>(p);
   XP_CHECK_LAUNCH("xp_attn_fwd");
-  if (mode == XP_ATTN_PROXY) {
-    attn_fwd_merge_kernel<<<(unsigned)(B * H * M), 256, 0, st>>>(p);
+  if (pl.reduce_grid) {
+    attn_fwd_merge_kernel<<<pl.reduce_grid, 256, 0, st>>>(p);
     XP_CHECK_LAUNCH("xp_attn_fwd(merge)");
   }
   return XP_OK;
 }
 
 extern "C" int64_t xp_attn_bwd_colsum_rows(int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype) {
-  if (dtype != XP_BF16) return 0;                    // the fp32 kernels do not produce them: callers run xp_colsum_partials
-  if (mode == XP_ATTN_CAUSAL) { M = 0; N = 1; L = S; }
-  else if (mode != XP_ATTN_PROXY) return 0;
-  return B * N * cdiv(M + L, FQ) + B * M;
+  return plan_attn(AttnCall{mode, B, H, S, M, N, L, dtype, false, true}, 0).colsum_rows;
 }
 
 extern "C" int xp_attn_bwd(const void* qkv, int64_t ldqkv, const void* out, const void* dout, int64_t ldo,
@@ -1702,54 +1724,40 @@ extern "C" int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, con
   if (dtype == XP_F32)
     return xp_attn_f32_bwd(qkv, ldqkv, out, dout, ldo, stats, pad_mask, dqkv, q_scale, mode, B, H, S, M, N, L, (float*)workspace,
                            (hipStream_t)stream);
-  AP p{};
+  AttnPlan pl;
+  if ((rc = plan_attn_for(AttnCall{mode, B, H, S, M, N, L, dtype, pad_mask != nullptr, true}, 0, pl))) return rc;
+  AP p = pl.geo;
   p.qkv = (const bf16_t*)qkv; p.ldqkv = ldqkv; p.out = (bf16_t*)out; p.dout = (const bf16_t*)dout; p.ldo = ldo;
   p.dqkv = (bf16_t*)dqkv; p.stats = const_cast<float*>(stats); p.pad = pad_mask; p.q_scale = q_scale;
-  p.mode = mode; p.B = (int)B; p.H = (int)H; p.S = (int)S; p.M = (int)M; p.N = (int)N; p.L = (int)L;
-  p.R = mode == XP_ATTN_PROXY ? (int)(M + L) : (int)S;
-  const int64_t P = B * H * N;
-  p.ws0 = (float*)workspace; p.ws1 = p.ws0 + B * H * S; p.ws2 = p.ws1 + P * M * DH;
+  p.ws0 = pl.delta.in(workspace); p.ws1 = pl.dq.in(workspace); p.ws2 = pl.dkv.in(workspace);
+  p.cs = dqkv_colsum_partials; p.tr = reinterpret_cast<unsigned long long*>(g_attn_trace);
   hipStream_t st = (hipStream_t)stream;
-  p.nq = (int)cdiv(p.R, FQ); p.nprob = (int)P;
-  p.cs = dqkv_colsum_partials; p.cs_main = (int)(B * N * p.nq);
-  p.tr = reinterpret_cast<unsigned long long*>(g_attn_trace);
-  // the fused kernel: the problems of attn_fwd3_kernel (one LDS group, at most 16 proxy rows, no padding mask) on a device that
-  // grants the dynamic-LDS opt-in; XPRETRAIN_DEBUG=attn_bwd_split keeps the two-kernel path (A/B and the cross-check test)
-  bool use5 = mode == XP_ATTN_PROXY && p.R <= FG && p.M <= 16 && !pad_mask && !xp_debug_flag("attn_bwd_split");
-  int ncu = 256;
-  if (use5) {
-    static std::mutex mu;
-    static int configured[64] = {0};                    // per device -- 0: not yet, > 0: CU count, -1: refused
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) use5 = false;
-    else {
-      std::lock_guard<std::mutex> lock(mu);
-      if (!configured[dev]) {
-        int n = 256;
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd5_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            B5_LDS) == hipSuccess;
-        configured[dev] = ok ? (n > 0 ? n : 256) : -1;
-      }
-      if (configured[dev] < 0) use5 = false; else ncu = configured[dev];
-    }
-  }
-  if (use5) {
-    int* counter = reinterpret_cast<int*>(p.ws2 + P * M * 2 * DH);
-    if (xp_debug_flag("attn_bwd_static")) counter = nullptr;          // (A/B: problems b, b + grid, ... per workgroup, no counter)
-    else if (hipMemsetAsync(counter, 0, sizeof(int), st) != hipSuccess) { xp_set_error("xp_attn_bwd: counter reset failed"); return XP_ERR_LAUNCH; }
-    attn_bwd5_kernel<<<(unsigned)(p.nprob < ncu ? p.nprob : ncu), B5THR, B5_LDS, st>>>(p, counter);
+  int* counter = reinterpret_cast<int*>(pl.counter.in(workspace));
+  if (pl.uses_counter && hipMemsetAsync(counter, 0, sizeof(int), st) != hipSuccess) { xp_set_error("xp_attn_bwd: counter reset failed"); return XP_ERR_LAUNCH; }
+  if (pl.kernel == XP_ATTN_KERNEL_BWD5) {
+    attn_bwd5_kernel<<<pl.grid, B5THR, pl.lds, st>>>(p, counter);
     XP_CHECK_LAUNCH("xp_attn_bwd(fused)");
   } else {
-    const unsigned grid = (unsigned)(cdiv(p.nprob, 8) * 8 * p.nq);
-    attn_bwd_dq_kernel<<<grid, FTHR, 0, st>>>(p);          // also computes delta = rowsum(dO * O) into ws0
+    attn_bwd_dq_kernel<<<pl.grid, FTHR, 0, st>>>(p);          // also computes delta = rowsum(dO * O) into ws0
     XP_CHECK_LAUNCH("xp_attn_bwd(dq)");
-    attn_bwd_dkv_kernel<<<grid, FTHR, 0, st>>>(p);
+    attn_bwd_dkv_kernel<<<pl.grid, FTHR, 0, st>>>(p);
     XP_CHECK_LAUNCH("xp_attn_bwd(dkv)");
   }
-  if (mode == XP_ATTN_PROXY) {
-    attn_bwd_proxy_reduce_kernel<<<(unsigned)(B * H * M), 256, 0, st>>>(p);
+  if (pl.reduce_grid) {
+    attn_bwd_proxy_reduce_kernel<<<pl.reduce_grid, 256, 0, st>>>(p);
     XP_CHECK_LAUNCH("xp_attn_bwd(proxy reduce)");
   }
+  return XP_OK;
+}
+
+extern "C" int xp_debug_attn_plan(int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
+                                  int32_t has_pad_mask, int32_t backward, int32_t cus, XpAttnPlanInfo* out) {
+  XP_REQUIRE(out, "xp_debug_attn_plan: null argument");
+  AttnPlan p;
+  const int rc = plan_attn_for(AttnCall{mode, B, H, S, M, N, L, dtype, has_pad_mask != 0, backward != 0}, cus, p);
+  if (rc) return rc;
+  *out = XpAttnPlanInfo{p.kernel, (int32_t)p.grid, p.lds, (int32_t)p.reduce_grid, p.uses_counter, 0, {p.part.off, p.part.bytes},
+                        {p.delta.off, p.delta.bytes}, {p.dq.off, p.dq.bytes}, {p.dkv.off, p.dkv.bytes},
+                        {p.counter.off, p.counter.bytes}, p.ws_bytes, p.colsum_rows};
   return XP_OK;
 }

@@ -839,8 +839,7 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
     // No fall-back to the 128x128 family: the planning queries have already answered for this one (the 128x128 family has no
     // fused column sums).  The library is built for gfx950 only, whose 160 KiB of LDS per CU always admit the 128 KiB opt-in.
     if (!xp_gemm256_launch(d, kp, plan.grid, st)) {
-      xp_set_error("xp_gemm: the 256x256 family cannot launch: no current device with an index below 64, "
-                   "or its 128 KiB dynamic-LDS opt-in was refused");
+      xp_set_error("xp_gemm: the 256x256 family cannot launch: no current device, or its 128 KiB dynamic-LDS opt-in was refused");
       return XP_ERR_LAUNCH;
     }
     XP_CHECK_LAUNCH("xp_gemm(256)");

@@ -32,7 +32,6 @@
 //   k-strided    half [64 k][256 B]:      32-byte block' = block ^ ((k&3) | ((k>>3)&1)<<2)   (ds_read_b64_tr_b16)
 #include "common.h"
 #include "gemm_common.h"
-#include <mutex>
 
 namespace {
 
@@ -313,19 +312,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
 template <bool AKS, bool BKS>
 bool launch_one(const KParams& kp, dim3 grid, hipStream_t st) {
   auto kern = gemm256_kernel<AKS, BKS>;
-  // the 128 KiB dynamic-LDS opt-in is per device: configured once for every device this process launches on
-  // (forward thread and autograd thread may both arrive first)
-  static std::mutex mu;
-  static int configured[64] = {0};                  // 0: not yet, 1: ok, -1: refused
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (!configured[dev])
-      configured[dev] = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            LDS_BYTES) == hipSuccess ? 1 : -1;
-    if (configured[dev] < 0) return false;          // (gfx950 has 160 KiB per CU: xp_gemm reports a refusal as an error)
-  }
+  if (!xp_device_cus(reinterpret_cast<const void*>(kern), LDS_BYTES)) return false;      // the 128 KiB opt-in (xp_gemm reports a refusal)
   kern<<<grid, NTH, LDS_BYTES, st>>>(kp);
   return true;
 }

@@ -493,6 +493,20 @@ def attn_fwd(qkv: torch.Tensor, B: int, S: int, H: int, *, size=None, pad_mask=N
     return out, stats
 
 
+def attn_plan(B: int, S: int, H: int, *, size=None, pad_mask=None, dtype=torch.bfloat16, backward=False, cus=0) -> dict:
+    """The plan attn_fwd (``backward``: attn_bwd) launches for these arguments (xp_debug_attn_plan: host only, nothing launched) as
+    a dict of the XpAttnPlanInfo fields, ``kernel`` by name (_lib.ATTN_KERNELS); ``pad_mask`` counts as present or absent.  ``cus``
+    > 0: a device of that many CUs that grants every dynamic-LDS opt-in (no GPU needed); <= 0: the current device."""
+    mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
+    M, N, Lp = size if size is not None else (0, 1, S)
+    info = L.XpAttnPlanInfo()
+    L.check(L.lib().xp_debug_attn_plan(mode, B, H, S, M, N, Lp, _DT[dtype], int(pad_mask is not None), int(backward), cus,
+                                       C.byref(info)), "xp_debug_attn_plan")
+    plan = {f: getattr(info, f) for f, _ in info._fields_ if f != "reserved"}
+    plan.update({f: tuple(plan[f]) for f in ("part", "delta", "dq", "dkv", "counter")}, kernel=L.ATTN_KERNELS[info.kernel])
+    return plan
+
+
 def attn_bwd(qkv, out, dout, stats, B, S, H, *, size=None, pad_mask=None, q_scale=1.0, colsum_defer=None,
              colsum_name="dbqkv"):
     """dqkv; with ``colsum_defer`` (a DeferredReduce) also the column sums of dqkv (the q/k/v bias gradients) as ``(dqkv, colsum)``:
