@@ -234,6 +234,27 @@ int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, const void* do
                  int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
                  void* workspace, size_t workspace_bytes, float* dqkv_colsum_partials, void* stream);
 
+/* Single-query proxy attention (csrc/attention_pooled.hip): what the LAST layer of the video tower needs when only the pooled
+ * feature leaves it (pooled_output = last_hidden_state[:, 0], modeling/CLIP_ViP.py:360-366).  Query row 0 of every sample is a
+ * proxy row and attends all S keys (CLIPAttention.forward2): B*H problems of one query against S keys, a memory-bound pass over
+ * K and V.  q[B, H*64] (already scaled); kv[B, S, 2, H, 64] = the packed K/V projection output (row stride ldkv elements);
+ * out[B, H*64]; stats[B, H, 2] fp32 = (row max, log row sum).  Keys are cut into chunks so that B*H*chunks workgroups fill the
+ * chip; chunk partials are combined in chunk order (no atomics: bit-identical run to run).  bf16 storage or fp32, fp32
+ * arithmetic either way.  head_dim 64; no padding mask, no XP_ATTN_CAUSAL (the text tower pools at a per-sample EOS index and
+ * is 0.6 % of the step's FLOPs). */
+size_t xp_attn_pooled_workspace_bytes(int64_t B, int64_t H, int64_t S, int32_t dtype);
+int xp_attn_pooled_fwd(const void* q, const void* kv, int64_t ldkv, void* out, float* stats, int64_t B, int64_t H, int64_t S,
+                       int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
+/* dq[b*lddq + h*64 + d] (already multiplied by q_scale, as xp_attn_bwd defines dq) and dkv[B, S, 2, H, 64] (row stride lddkv) for
+ * ALL keys, in one pass over K/V.  dkv_colsum_partials (NULL: skipped): the column sums of the dkv rows as stored, one partial
+ * row of 2*H*64 floats per (sample, chunk) -- xp_attn_pooled_colsum_rows() rows on the current device (0: no device), never more
+ * than xp_attn_pooled_colsum_rows_max(); finish with xp_reduce_rows_batch (the k_proj / v_proj bias gradients). */
+int64_t xp_attn_pooled_colsum_rows(int64_t B, int64_t H, int64_t S, int32_t dtype);
+int64_t xp_attn_pooled_colsum_rows_max(int64_t B, int64_t S);
+int xp_attn_pooled_bwd(const void* q, const void* kv, int64_t ldkv, const void* out, const void* dout, const float* stats,
+                       void* dq, int64_t lddq, void* dkv, int64_t lddkv, float q_scale, int64_t B, int64_t H, int64_t S,
+                       int32_t dtype, void* workspace, size_t workspace_bytes, float* dkv_colsum_partials, void* stream);
+
 /* --------------------------------------------------------------------------------- Embeddings / glue
  * CLIPVisionViPEmbeddings.forward (modeling/CLIP_ViP.py:168-197).
  */
@@ -398,6 +419,48 @@ typedef struct XpLayerBwd {
 } XpLayerBwd;
 size_t xp_encoder_layer_bwd_workspace_bytes(const XpLayerDims* dims);
 int xp_encoder_layer_bwd(const XpLayerBwd* args, void* stream);
+/* The LAST video-tower layer when only the pooled feature (token 0 of every sample, a proxy row) leaves the tower: the same
+ * function of x as row b*S of xp_encoder_layer_fwd's x3, computed without the dead rows.  LayerNorm 1 and the K/V projection
+ * (Wqkv rows D..3D) see every row, because token 0 attends all S keys; the Q projection, the single-query attention
+ * (xp_attn_pooled_fwd), out_proj + residual, LayerNorm 2 and the MLP run on the B pooled rows.  XP_ATTN_PROXY only (M >= 1), no
+ * padding mask.  Same conventions as xp_encoder_layer_fwd / _bwd: caller-owned saved activations, pre == NULL for a forward-only
+ * pass, NULL gradient pointer = frozen parameter, the weight-gradient GEMMs on the library's stream joined before return.
+ * The backward's dx is dense [rows, D]: LayerNorm 1' over all rows, fed by dkv . Wkv on all rows plus dq . Wq and the residual
+ * on the pooled rows; every parameter of the layer receives its gradient.
+ * Side rows (bf16): side_in is the layer's usual [B*M, D] fp32 buffer (read by LayerNorm 1; its row b*M is the pooled row's
+ * residual operand); side_x2 / side_out are [B, D] fp32, one row per sample (side_x2 NULL: kept in the workspace). */
+typedef struct XpLayerPooledFwd {
+  XpLayerDims dims;
+  const void* x; const void* Wqkv; const void* Wo; const void* W1; const void* W2;
+  const float* ln1_w; const float* ln1_b; const float* bqkv; const float* bo;
+  const float* ln2_w; const float* ln2_b; const float* b1; const float* b2;
+  /* every row: h1 [rows, D], kv [rows, 2D], mean1 / rstd1 [rows] */
+  void* h1; void* kv; float* mean1; float* rstd1;
+  /* the pooled rows: h1p, q, attn_o, x2, h2, x3 [B, D]; pre, act [B, Dff]; mean1p, rstd1p, mean2, rstd2 [B]; stats [B, heads, 2] */
+  void* h1p; void* q; void* attn_o; void* x2; void* h2; void* pre; void* act; void* x3;
+  float* mean1p; float* rstd1p; float* mean2; float* rstd2; float* stats;
+  void* workspace; size_t workspace_bytes;                        /* >= xp_encoder_layer_pooled_fwd_workspace_bytes */
+  const float* side_in; float* side_out; float* side_x2;
+} XpLayerPooledFwd;
+size_t xp_encoder_layer_pooled_fwd_workspace_bytes(const XpLayerDims* dims);
+int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* args, void* stream);
+
+typedef struct XpLayerPooledBwd {
+  XpLayerDims dims;
+  /* saved by the forward */
+  const void* x; const void* h1; const void* kv; const void* h1p; const void* q; const void* attn_o; const void* x2;
+  const void* h2; const void* pre; const void* act; const void* Wqkv; const void* Wo; const void* W1; const void* W2;
+  const float* ln1_w; const float* ln2_w; const float* mean1; const float* rstd1; const float* mean1p; const float* rstd1p;
+  const float* mean2; const float* rstd2; const float* stats;
+  const void* dx3;                      /* gradient of the pooled output rows [B, D]                                   */
+  void* dx;                             /* gradient of the layer input [rows, D]                                      */
+  float* dln1_w; float* dln1_b; float* dwqkv; float* dbqkv; float* dwo; float* dbo;
+  float* dln2_w; float* dln2_b; float* dw1; float* db1; float* dw2; float* db2;
+  void* workspace; size_t workspace_bytes;                        /* >= xp_encoder_layer_pooled_bwd_workspace_bytes */
+  const float* side_in; const float* side_x2;
+} XpLayerPooledBwd;
+size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* dims);
+int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* args, void* stream);
 /* The library's second stream of the current device (the one xp_encoder_layer_bwd issues the weight-gradient GEMMs on; created at the
  * device's highest priority on first use), or NULL when XPRETRAIN_WGRAD_STREAM=0.  It is idle outside xp_encoder_layer_bwd calls: the
  * host side runs the second half-batch chain of the video tower's forward on it instead of creating one more stream (a process gets few
@@ -464,6 +527,18 @@ typedef struct XpAttnPlanInfo {
 } XpAttnPlanInfo;
 int xp_debug_attn_plan(int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
                        int32_t has_pad_mask, int32_t backward, int32_t cus, XpAttnPlanInfo* out);
+/* The plan xp_attn_pooled_fwd (backward == 0) / xp_attn_pooled_bwd (backward != 0) launches: host only, launches nothing.
+ * cus > 0: planned for a device of that many CUs (no GPU needed); cus <= 0: for the current device (XP_ERR_LAUNCH if none). */
+typedef struct XpAttnPooledPlanInfo {
+  int32_t chunks, chunk_keys;           /* chunk c covers keys [c*chunk_keys, min(S, (c+1)*chunk_keys))             */
+  int32_t grid, combine_grid;           /* main launch: B*H*chunks workgroups; combine launch: B*H                  */
+  int64_t part_ml[2], part_acc[2];      /* forward workspace regions (byte offset, bytes): (m, l) and O partials    */
+  int64_t part_dq[2];                   /* backward workspace region: dq partials; 0 bytes: not used                */
+  int64_t workspace_bytes;              /* this direction's regions (<= xp_attn_pooled_workspace_bytes)             */
+  int64_t colsum_rows;                  /* as xp_attn_pooled_colsum_rows                                            */
+} XpAttnPooledPlanInfo;
+int xp_debug_attn_pooled_plan(int64_t B, int64_t H, int64_t S, int32_t dtype, int32_t backward, int32_t cus,
+                              XpAttnPooledPlanInfo* out);
 int xp_probe_mfma_bf16(const void* a, const void* b, float* c, void* stream);
 int xp_probe_mfma_f32(const float* a, const float* b, float* c, void* stream);
 /* packed-fp32 self-check (csrc/probe.hip): err[(variant*64 + lane)*2 + half] += mismatches between one v_pk_*_f32 form and

@@ -97,6 +97,28 @@ class XpLayerBwd(C.Structure):
                 + [("workspace_bytes", sz), ("side_in", vp), ("side_x2", vp), ("side_S", i64), ("side_M", i32), ("reserved", i32)])
 
 
+class XpLayerPooledFwd(C.Structure):
+    _fields_ = ([("dims", XpLayerDims)]
+                + [(n, vp) for n in ("x", "Wqkv", "Wo", "W1", "W2", "ln1_w", "ln1_b", "bqkv", "bo", "ln2_w", "ln2_b", "b1", "b2",
+                                     "h1", "kv", "mean1", "rstd1", "h1p", "q", "attn_o", "x2", "h2", "pre", "act", "x3",
+                                     "mean1p", "rstd1p", "mean2", "rstd2", "stats", "workspace")]
+                + [("workspace_bytes", sz), ("side_in", vp), ("side_out", vp), ("side_x2", vp)])
+
+
+class XpLayerPooledBwd(C.Structure):
+    _fields_ = ([("dims", XpLayerDims)]
+                + [(n, vp) for n in ("x", "h1", "kv", "h1p", "q", "attn_o", "x2", "h2", "pre", "act", "Wqkv", "Wo", "W1", "W2",
+                                     "ln1_w", "ln2_w", "mean1", "rstd1", "mean1p", "rstd1p", "mean2", "rstd2", "stats", "dx3", "dx",
+                                     "dln1_w", "dln1_b", "dwqkv", "dbqkv", "dwo", "dbo", "dln2_w", "dln2_b", "dw1", "db1",
+                                     "dw2", "db2", "workspace")]
+                + [("workspace_bytes", sz), ("side_in", vp), ("side_x2", vp)])
+
+
+class XpAttnPooledPlanInfo(C.Structure):
+    _fields_ = [("chunks", i32), ("chunk_keys", i32), ("grid", i32), ("combine_grid", i32), ("part_ml", i64 * 2),
+                ("part_acc", i64 * 2), ("part_dq", i64 * 2), ("workspace_bytes", i64), ("colsum_rows", i64)]
+
+
 class XpAdamTensor(C.Structure):
     _fields_ = [("p", vp), ("m", vp), ("v", vp), ("shadow", vp), ("numel", i64), ("shadow_dtype", i32), ("reserved", i32)]
 
@@ -143,6 +165,11 @@ SIGNATURES = {
     "xp_attn_bwd": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, f32, i32, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp]),
     "xp_attn_bwd2": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, f32, i32, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp, vp]),
     "xp_attn_bwd_colsum_rows": (i64, [i32, i64, i64, i64, i64, i64, i64, i32]),
+    "xp_attn_pooled_workspace_bytes": (sz, [i64, i64, i64, i32]),
+    "xp_attn_pooled_fwd": (i32, [vp, vp, i64, vp, vp, i64, i64, i64, i32, vp, sz, vp]),
+    "xp_attn_pooled_colsum_rows": (i64, [i64, i64, i64, i32]),
+    "xp_attn_pooled_colsum_rows_max": (i64, [i64, i64]),
+    "xp_attn_pooled_bwd": (i32, [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, f32, i64, i64, i64, i32, vp, sz, vp, vp]),
     "xp_im2col": (i32, [vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_im2col_u8": (i32, [vp, C.POINTER(f32), C.POINTER(f32), vp, i64, i64, i64, i64, i32, vp]),
     "xp_vip_proxy_rows": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
@@ -168,6 +195,10 @@ SIGNATURES = {
     "xp_encoder_layer_fwd": (i32, [C.POINTER(XpLayerFwd), vp]),
     "xp_encoder_layer_bwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),
     "xp_encoder_layer_bwd": (i32, [C.POINTER(XpLayerBwd), vp]),
+    "xp_encoder_layer_pooled_fwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),
+    "xp_encoder_layer_pooled_fwd": (i32, [C.POINTER(XpLayerPooledFwd), vp]),
+    "xp_encoder_layer_pooled_bwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),
+    "xp_encoder_layer_pooled_bwd": (i32, [C.POINTER(XpLayerPooledBwd), vp]),
     "xp_side_stream": (vp, []),
     "xp_debug_set_gemm_trace": (i32, [vp]),
     "xp_debug_gemm_timer_arm": (i32, [i64, i64, i64, i32, i32, i32, i32, i32]),
@@ -176,6 +207,7 @@ SIGNATURES = {
     "xp_debug_gemm_occupancy": (i32, [i32]),
     "xp_debug_gemm_plan": (i32, [C.POINTER(XpGemmDesc), C.POINTER(XpGemmPlanInfo)]),
     "xp_debug_attn_plan": (i32, [i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, C.POINTER(XpAttnPlanInfo)]),
+    "xp_debug_attn_pooled_plan": (i32, [i64, i64, i64, i32, i32, i32, C.POINTER(XpAttnPooledPlanInfo)]),
     "xp_probe_mfma_bf16": (i32, [vp, vp, vp, vp]),
     "xp_probe_mfma_f32": (i32, [vp, vp, vp, vp]),
     "xp_probe_tr16": (i32, [vp, vp, vp, vp]),

@@ -28,27 +28,35 @@ XpGemmDesc gemm_desc(const void* A, const void* B, void* C, int64_t M, int64_t N
   return d;
 }
 
-// dW[n_out, n_in] = dY[rows, n_out]^T . X[rows, n_in], fp32: both operands k-strided, split-K chosen by the library
+// dW[n_out, n_in] = dY[k, n_out]^T . X[k, n_in], fp32: both operands k-strided (row pitches lddy / ldx), split-K chosen by the library
+XpGemmDesc wgrad_desc(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t k, int64_t n_out, int64_t n_in,
+                      int dtype) {
+  XpGemmDesc d = gemm_desc(dy, x, dw, n_out, n_in, k, dtype);
+  d.a_kstrided = d.b_kstrided = 1; d.lda = lddy; d.ldb = ldx; d.out_dtype = XP_F32;
+  return d;
+}
 // slack: nothing waits for this launch soon (xp_gemm_auto_split_slack: fewer, longer slabs)
-int wgrad(const void* dy, const void* x, float* dw, int64_t rows, int64_t n_out, int64_t n_in, int dtype, float* slabs,
-          size_t slab_bytes, void* st, bool slack) {
-  XpGemmDesc d = gemm_desc(dy, x, dw, n_out, n_in, rows, dtype);
-  d.a_kstrided = d.b_kstrided = 1; d.lda = n_out; d.ldb = n_in; d.out_dtype = XP_F32;
+int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, bool slack) {
   const int split = slack ? xp_gemm_auto_split_slack(&d) : xp_gemm_auto_split(&d);
   if (split <= 1) return xp_gemm(&d, st);
-  XP_REQUIRE(slab_bytes >= (size_t)split * n_out * n_in * sizeof(float), "xp_encoder_layer_bwd: split-K slab space too small");
+  XP_REQUIRE(slab_bytes >= (size_t)split * d.M * d.N * sizeof(float), "encoder layer backward: split-K slab space too small");
+  float* dw = (float*)d.C;
   d.C = slabs; d.split_k = split;
   int rc = xp_gemm(&d, st);
   if (rc) return rc;
   if (xp_debug_flag("skip_splitk_reduce")) return XP_OK;      // measurement only (wrong gradients): what the four reduces of a layer cost the step
-  return xp_splitk_reduce(slabs, dw, n_out * n_in, split, 0, st);
+  return xp_splitk_reduce(slabs, dw, d.M * d.N, split, 0, st);
 }
-
-size_t wgrad_slab_bytes(int64_t rows, int64_t n_out, int64_t n_in, int dtype) {
-  XpGemmDesc d = gemm_desc(nullptr, nullptr, nullptr, n_out, n_in, rows, dtype);
-  d.a_kstrided = d.b_kstrided = 1; d.lda = n_out; d.ldb = n_in; d.out_dtype = XP_F32;
+size_t wgrad_desc_slab_bytes(XpGemmDesc d) {
   const int a = xp_gemm_auto_split(&d), b = xp_gemm_auto_split_slack(&d), split = a > b ? a : b;
-  return split <= 1 ? 0 : (size_t)split * n_out * n_in * sizeof(float);
+  return split <= 1 ? 0 : (size_t)split * d.M * d.N * sizeof(float);
+}
+int wgrad(const void* dy, const void* x, float* dw, int64_t rows, int64_t n_out, int64_t n_in, int dtype, float* slabs,
+          size_t slab_bytes, void* st, bool slack) {
+  return run_wgrad(wgrad_desc(dy, n_out, x, n_in, dw, rows, n_out, n_in, dtype), slabs, slab_bytes, st, slack);
+}
+size_t wgrad_slab_bytes(int64_t rows, int64_t n_out, int64_t n_in, int dtype) {
+  return wgrad_desc_slab_bytes(wgrad_desc(nullptr, n_out, nullptr, n_in, nullptr, rows, n_out, n_in, dtype));
 }
 
 struct Defer {             // the layer's deferred second-level reductions (bias / LayerNorm-parameter gradients)
@@ -305,6 +313,229 @@ extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
     // (XPRETRAIN_DEBUG=no_wgrad_join: measurement only -- races on the shared workspace -- what a lazy join could be worth at most)
     if (hipEventRecord(wsd->done, wsd->side) != hipSuccess || hipStreamWaitEvent(mst, wsd->done, 0) != hipSuccess) {
       xp_set_error("xp_encoder_layer_bwd: joining the weight-gradient stream failed");
+      return XP_ERR_LAUNCH;
+    }
+  }
+  return XP_OK;
+}
+
+// ================================================================================== pooled last layer (video tower)
+// The last layer when only token 0 of every sample (a proxy row) leaves the tower: LayerNorm 1 and the K/V projection on every
+// row, everything else on the B pooled rows (include/xpretrain_hip.h: XpLayerPooledFwd).  Host-side sequencing again: the one
+// kernel pair of its own is the single-query attention (attention_pooled.hip).  Row b*S of a [rows, .] matrix is addressed as
+// row b of a matrix with pitch S*D (LayerNorm, the residual operand) or through the GEMM's A-row remap (1, S, 0).
+namespace {
+
+int check_pooled_dims(const char* name, const XpLayerDims& d) {
+  int rc = check_dims(name, d);
+  if (rc) return rc;
+  XP_REQUIRE(d.attn_mode == XP_ATTN_PROXY && d.M >= 1 && d.N >= 1 && d.L >= 1 && d.S == d.M + d.N * d.L,
+             "%s: the pooled layer is the video tower's (XP_ATTN_PROXY, M >= 1, S == M + N*L)", name);
+  return XP_OK;
+}
+
+struct PooledBwdPlan {
+  size_t esz, dpre, dhp, dqkv, dh1, slabs, cs_pre, ln2, cs_q, cs_kv, ln1, ln1p, red, attn, total;
+  int64_t cs_pre_rows, cs_q_rows, ln_rows, lnp_rows;
+};
+PooledBwdPlan plan_pooled_bwd(const XpLayerDims& d) {
+  PooledBwdPlan p;
+  memset(&p, 0, sizeof(p));
+  const int64_t rows = d.rows, D = d.D, Dff = d.Dff, B = d.B, S = d.S;
+  const int dt = d.dtype;
+  p.esz = dt == XP_BF16 ? 2 : 4;
+  p.dpre = align256(B * Dff * p.esz); p.dhp = align256(B * D * p.esz);
+  p.dqkv = align256(rows * 3 * D * p.esz); p.dh1 = align256(rows * D * p.esz);
+  size_t s = wgrad_desc_slab_bytes(wgrad_desc(nullptr, D, nullptr, Dff, nullptr, B, D, Dff, dt));
+  size_t t = wgrad_desc_slab_bytes(wgrad_desc(nullptr, Dff, nullptr, D, nullptr, B, Dff, D, dt)); if (t > s) s = t;
+  t = wgrad_desc_slab_bytes(wgrad_desc(nullptr, D, nullptr, D, nullptr, B, D, D, dt)); if (t > s) s = t;
+  XpGemmDesc g = wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, B, D, D, dt);
+  g.a_grp = 1; g.a_grp_stride = S;
+  t = wgrad_desc_slab_bytes(g); if (t > s) s = t;
+  t = wgrad_desc_slab_bytes(wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, rows, 2 * D, D, dt)); if (t > s) s = t;
+  p.slabs = align256(s);
+  p.cs_pre_rows = xp_colsum_partial_rows(B, Dff);
+  p.cs_pre = align256(p.cs_pre_rows * Dff * sizeof(float));
+  p.cs_q_rows = xp_colsum_partial_rows(B, D);
+  p.cs_q = align256(p.cs_q_rows * D * sizeof(float));
+  p.cs_kv = align256(xp_attn_pooled_colsum_rows_max(B, S) * 2 * D * sizeof(float));
+  p.ln_rows = xp_layernorm_bwd_partial_rows(rows); p.lnp_rows = xp_layernorm_bwd_partial_rows(B);
+  p.ln1 = align256(xp_layernorm_bwd_workspace_bytes(rows, D));
+  p.ln2 = p.ln1p = align256(xp_layernorm_bwd_workspace_bytes(B, D));
+  p.red = align256((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16);
+  p.attn = align256(xp_attn_pooled_workspace_bytes(B, d.heads, S, dt));
+  p.total = p.dpre + 3 * p.dhp + p.dqkv + p.dh1 + p.slabs + p.cs_pre + p.ln2 + p.cs_q + p.cs_kv + p.ln1 + p.ln1p + p.red + p.attn + 256;
+  return p;
+}
+
+}  // namespace
+
+extern "C" size_t xp_encoder_layer_pooled_fwd_workspace_bytes(const XpLayerDims* d) {
+  if (!d || d->B <= 0 || d->D <= 0 || d->S <= 0 || d->heads <= 0) return 0;
+  // the attention partials + two [B, D] fp32 side buffers (the pooled rows of side_in; side_x2 of a forward-only pass)
+  return align256(xp_attn_pooled_workspace_bytes(d->B, d->heads, d->S, d->dtype)) + 2 * align256((size_t)d->B * d->D * sizeof(float)) + 256;
+}
+
+extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) {
+  XP_REQUIRE(a, "xp_encoder_layer_pooled_fwd: null argument");
+  const XpLayerDims& d = a->dims;
+  int rc = check_pooled_dims("xp_encoder_layer_pooled_fwd", d);
+  if (rc) return rc;
+  XP_REQUIRE(a->x && a->Wqkv && a->Wo && a->W1 && a->W2 && a->ln1_w && a->ln1_b && a->bqkv && a->bo && a->ln2_w && a->ln2_b &&
+             a->b1 && a->b2 && a->h1 && a->kv && a->mean1 && a->rstd1 && a->h1p && a->q && a->attn_o && a->x2 && a->h2 && a->act &&
+             a->x3 && a->mean1p && a->rstd1p && a->mean2 && a->rstd2 && a->stats, "xp_encoder_layer_pooled_fwd: null pointer");
+  const int64_t rows = d.rows, D = d.D, Dff = d.Dff, B = d.B, S = d.S;
+  const int dt = d.dtype;
+  const bool sided = a->side_in != nullptr;
+  XP_REQUIRE(!sided || (a->side_out && dt == XP_BF16), "xp_encoder_layer_pooled_fwd: side rows need side_in and side_out, and bf16");
+  const size_t attn_ws = align256(xp_attn_pooled_workspace_bytes(B, d.heads, S, dt)), side_b = align256((size_t)B * D * sizeof(float));
+  XP_REQUIRE(a->workspace && a->workspace_bytes >= attn_ws + 2 * side_b, "xp_encoder_layer_pooled_fwd: workspace too small");
+  float* side0 = !sided ? nullptr : reinterpret_cast<float*>(static_cast<char*>(a->workspace) + attn_ws);
+  float* side_x2 = !sided ? nullptr : a->side_x2 ? a->side_x2 : reinterpret_cast<float*>(static_cast<char*>(a->workspace) + attn_ws + side_b);
+  const int64_t sS = sided ? S : 0;
+  const int32_t sM = sided ? (int32_t)d.M : 0, s1 = sided ? 1 : 0;
+  const size_t esz = dt == XP_BF16 ? 2 : 4;
+  // h1 = LN1(x) on every row; the pooled rows once more as a [B, D] matrix of their own (the Q projection's operand)
+  if ((rc = xp_layernorm_fwd_side(a->x, D, a->ln1_w, a->ln1_b, a->h1, D, a->mean1, a->rstd1, rows, D, d.ln_eps, dt,
+                                  a->side_in, nullptr, sS, sM, sM, st))) return rc;
+  if (sided && (rc = xp_gather_rows(a->side_in, nullptr, side0, B, d.M, D, XP_F32, st))) return rc;
+  if ((rc = xp_layernorm_fwd_side(a->x, S * D, a->ln1_w, a->ln1_b, a->h1p, D, a->mean1p, a->rstd1p, B, D, d.ln_eps, dt,
+                                  side0, nullptr, s1, s1, s1, st))) return rc;
+  // kv = h1 Wkv^T + bkv on every row (token 0 attends all S keys); q = (h1p Wq^T + bq) * dh^-0.5 on the pooled rows
+  XpGemmDesc g = gemm_desc(a->h1, static_cast<const char*>(a->Wqkv) + (size_t)D * D * esz, a->kv, rows, 2 * D, D, dt);
+  g.epilogue = XP_EPI_BIAS; g.bias = a->bqkv + D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  g = gemm_desc(a->h1p, a->Wqkv, a->q, B, D, D, dt);
+  g.epilogue = XP_EPI_BIAS_QSCALE; g.bias = a->bqkv; g.scale = d.q_scale; g.scale_cols = D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if ((rc = xp_attn_pooled_fwd(a->q, a->kv, 2 * D, a->attn_o, a->stats, B, d.heads, S, dt, a->workspace, attn_ws, st))) return rc;
+  // x2 = x[pooled] + attn_o Wo^T + bo
+  g = gemm_desc(a->attn_o, a->Wo, a->x2, B, D, D, dt);
+  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a->bo; g.resid = a->x; g.ldr = S * D;
+  if (sided) { g.resid_side = side0; g.out_side = side_x2; g.side_S = 1; g.side_M = 1; }
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if ((rc = xp_layernorm_fwd_side(a->x2, D, a->ln2_w, a->ln2_b, a->h2, D, a->mean2, a->rstd2, B, D, d.ln_eps, dt,
+                                  side_x2, nullptr, s1, s1, s1, st))) return rc;
+  g = gemm_desc(a->h2, a->W1, a->act, B, Dff, D, dt);
+  g.epilogue = XP_EPI_BIAS_GELU; g.bias = a->b1; g.aux = a->pre;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  g = gemm_desc(a->act, a->W2, a->x3, B, D, Dff, dt);
+  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a->b2; g.resid = a->x2;
+  if (sided) { g.resid_side = side_x2; g.out_side = a->side_out; g.side_S = 1; g.side_M = 1; }
+  return xp_gemm(&g, st);
+}
+
+extern "C" size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* d) {
+  if (!d || d->rows <= 0 || d->B <= 0 || d->D <= 0 || d->Dff <= 0 || d->S <= 0 || d->heads <= 0) return 0;
+  return plan_pooled_bwd(*d).total;
+}
+
+extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) {
+  XP_REQUIRE(a, "xp_encoder_layer_pooled_bwd: null argument");
+  const XpLayerDims& d = a->dims;
+  int rc = check_pooled_dims("xp_encoder_layer_pooled_bwd", d);
+  if (rc) return rc;
+  XP_REQUIRE(a->x && a->h1 && a->kv && a->h1p && a->q && a->attn_o && a->x2 && a->h2 && a->pre && a->act && a->Wqkv && a->Wo &&
+             a->W1 && a->W2 && a->ln1_w && a->ln2_w && a->mean1 && a->rstd1 && a->mean1p && a->rstd1p && a->mean2 && a->rstd2 &&
+             a->stats && a->dx3 && a->dx, "xp_encoder_layer_pooled_bwd: null pointer");
+  XP_REQUIRE((!a->side_in && !a->side_x2) || (a->side_in && a->side_x2 && d.dtype == XP_BF16),
+             "xp_encoder_layer_pooled_bwd: side rows need side_in and side_x2, and bf16");
+  const PooledBwdPlan p = plan_pooled_bwd(d);
+  XP_REQUIRE(a->workspace && a->workspace_bytes >= p.total, "xp_encoder_layer_pooled_bwd: workspace too small (%zu < %zu)",
+             a->workspace_bytes, p.total);
+  Carver ws{(char*)a->workspace, 0, a->workspace_bytes};
+  void* dpre = ws.take(p.dpre); void* dh2 = ws.take(p.dhp); void* dx2 = ws.take(p.dhp); void* dattn = ws.take(p.dhp);
+  char* dqkv = (char*)ws.take(p.dqkv); void* dh1 = ws.take(p.dh1);
+  float* slabs = (float*)ws.take(p.slabs);
+  float* cs_pre = (float*)ws.take(p.cs_pre); float* ln2_part = (float*)ws.take(p.ln2); float* cs_q = (float*)ws.take(p.cs_q);
+  float* cs_kv = (float*)ws.take(p.cs_kv); float* ln1_part = (float*)ws.take(p.ln1); float* ln1p_part = (float*)ws.take(p.ln1p);
+  void* red_ws = ws.take(p.red); void* attn_ws = ws.take(p.attn);
+  const int64_t rows = d.rows, D = d.D, Dff = d.Dff, B = d.B, S = d.S;
+  const int dt = d.dtype;
+  const bool sided = a->side_in != nullptr;
+  const int64_t sS = sided ? S : 0;
+  const int32_t sM = sided ? (int32_t)d.M : 0, s1 = sided ? 1 : 0;
+  void* dkv = dqkv + (size_t)D * p.esz;      // dqkv[rows, 3D]: the k / v columns of every row, the q columns of the pooled rows only
+  Defer df;
+  WgradSide* wsd = rows >= 4096 ? wgrad_side() : nullptr;
+  hipStream_t mst = (hipStream_t)st;
+  void* wst = wsd ? (void*)wsd->side : st;
+  auto mark = [&](int i) -> int {           // side stream: everything the main stream has enqueued so far must finish first
+    if (!wsd) return XP_OK;
+    if (hipEventRecord(wsd->ev[i], mst) != hipSuccess || hipStreamWaitEvent(wsd->side, wsd->ev[i], 0) != hipSuccess) {
+      xp_set_error("xp_encoder_layer_pooled_bwd: event hand-off to the weight-gradient stream failed");
+      return XP_ERR_LAUNCH;
+    }
+    return XP_OK;
+  };
+  if ((rc = mark(0))) return rc;
+
+  // ---- MLP on the pooled rows
+  XpGemmDesc g = gemm_desc(a->dx3, a->W2, dpre, B, Dff, D, dt);               // dpre = (dx3 . W2) * quick_gelu'(pre)
+  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.resid = a->pre; g.ldr = Dff;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a->db1) {
+    if ((rc = xp_colsum_partials(dpre, B, Dff, Dff, dt, cs_pre, p.cs_pre, st))) return rc;
+    df.add(cs_pre, a->db1, Dff, (int)p.cs_pre_rows, (int)Dff);
+  }
+  if (a->dw2 && (rc = run_wgrad(wgrad_desc(a->dx3, D, a->act, Dff, a->dw2, B, D, Dff, dt), slabs, p.slabs, wst, true))) return rc;
+  if ((rc = mark(1))) return rc;
+  g = gemm_desc(dpre, a->W1, dh2, B, D, Dff, dt);                             // dh2 = dpre . W1
+  g.b_kstrided = 1; g.ldb = D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a->dw1 && (rc = run_wgrad(wgrad_desc(dpre, Dff, a->h2, D, a->dw1, B, Dff, D, dt), slabs, p.slabs, wst, true))) return rc;
+  // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)]
+  if ((rc = xp_layernorm_bwd_partials_side(dh2, D, a->x2, D, a->ln2_w, a->mean2, a->rstd2, a->dx3, D, dx2, D, 2, B, D, dt,
+                                           a->side_x2, s1, s1, s1, ln2_part, p.ln2, st))) return rc;
+  df.add(ln2_part, a->dln2_w, 4 * D, (int)p.lnp_rows, (int)D);
+  df.add(ln2_part + D, a->dln2_b, 4 * D, (int)p.lnp_rows, (int)D);
+  df.add(ln2_part + 2 * D, a->dbo, 4 * D, (int)p.lnp_rows, (int)D);
+  df.add(ln2_part + 3 * D, a->db2, 4 * D, (int)p.lnp_rows, (int)D);
+  if ((rc = mark(2))) return rc;
+  // ---- attention
+  g = gemm_desc(dx2, a->Wo, dattn, B, D, D, dt);                              // dattn = dx2 . Wo
+  g.b_kstrided = 1; g.ldb = D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a->dwo && (rc = run_wgrad(wgrad_desc(dx2, D, a->attn_o, D, a->dwo, B, D, D, dt), slabs, p.slabs, wst, true))) return rc;
+  // dq lands in the q columns of the pooled rows of dqkv, dk / dv in the k / v columns of every row
+  if ((rc = xp_attn_pooled_bwd(a->q, a->kv, 2 * D, a->attn_o, dattn, a->stats, dqkv, S * 3 * D, dkv, 3 * D, d.q_scale, B, d.heads,
+                               S, dt, attn_ws, p.attn, a->dbqkv ? cs_kv : nullptr, st))) return rc;
+  if ((rc = mark(3))) return rc;
+  // dh1 = dkv . Wkv on every row, then the pooled rows again with their q columns: dqkv[b*S] . Wqkv
+  g = gemm_desc(dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * p.esz, dh1, rows, D, 2 * D, dt);
+  g.lda = 3 * D; g.b_kstrided = 1; g.ldb = D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  g = gemm_desc(dqkv, a->Wqkv, dh1, B, D, 3 * D, dt);
+  g.a_grp = 1; g.a_grp_stride = S; g.b_kstrided = 1; g.ldb = D; g.c_grp = 1; g.c_grp_stride = S;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a->dwqkv) {
+    g = wgrad_desc(dqkv, 3 * D, a->h1p, D, a->dwqkv, B, D, D, dt);            // dWq = dq^T . h1p
+    g.a_grp = 1; g.a_grp_stride = S;
+    if ((rc = run_wgrad(g, slabs, p.slabs, wst, true))) return rc;
+    if ((rc = run_wgrad(wgrad_desc(dkv, 3 * D, a->h1, D, a->dwqkv + D * D, rows, 2 * D, D, dt), slabs, p.slabs, wst, false))) return rc;
+  }
+  if (a->dbqkv) {
+    const int64_t kv_rows = xp_attn_pooled_colsum_rows(B, d.heads, S, dt);
+    XP_REQUIRE(kv_rows > 0, "xp_encoder_layer_pooled_bwd: no current device");
+    if ((rc = xp_colsum_partials(dqkv, B, D, S * 3 * D, dt, cs_q, p.cs_q, st))) return rc;
+    df.add(cs_q, a->dbqkv, D, (int)p.cs_q_rows, (int)D);
+    df.add(cs_kv, a->dbqkv + D, 2 * D, (int)kv_rows, (int)(2 * D));
+  }
+  // dx = LN1'(dh1) on every row; the pooled rows once more with their residual gradient dx2 (the parameter-gradient partial
+  // rows of that second pass are dropped: the first pass has counted those rows)
+  if ((rc = xp_layernorm_bwd_partials_side(dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, nullptr, D, a->dx, D, 0, rows, D, dt,
+                                           a->side_in, sS, sM, sM, ln1_part, p.ln1, st))) return rc;
+  df.add(ln1_part, a->dln1_w, 2 * D, (int)p.ln_rows, (int)D);
+  df.add(ln1_part + D, a->dln1_b, 2 * D, (int)p.ln_rows, (int)D);
+  if ((rc = xp_layernorm_bwd_partials_side(dh1, S * D, a->x, S * D, a->ln1_w, a->mean1p, a->rstd1p, dx2, D, a->dx, S * D, 0, B, D, dt,
+                                           a->side_in, s1, s1, sM, ln1p_part, p.ln1p, st))) return rc;
+  if (df.n) {
+    XP_REQUIRE(xp_reduce_rows_batch_workspace_bytes(df.segs, df.n) <= p.red, "xp_encoder_layer_pooled_bwd: reduce scratch too small");
+    if ((rc = xp_reduce_rows_batch(df.segs, df.n, red_ws, p.red, st))) return rc;
+  }
+  if (wsd) {      // join: the weight gradients (and every workspace the side stream read) belong to the main stream again
+    if (hipEventRecord(wsd->done, wsd->side) != hipSuccess || hipStreamWaitEvent(mst, wsd->done, 0) != hipSuccess) {
+      xp_set_error("xp_encoder_layer_pooled_bwd: joining the weight-gradient stream failed");
       return XP_ERR_LAUNCH;
     }
   }

@@ -612,6 +612,250 @@ class EncoderLayerFn(torch.autograd.Function):
                 keep(12, dln2_b), dw1, db1, dw2, keep(16, db2), None, None, None, None, None, None, None, None)
 
 
+# ------------------------------------------------------------------------------------------ pooled last layer (video tower)
+class _PooledLayerPlan:
+    """Sizes / offsets of one (shape, dtype) of the pooled last layer (xp_encoder_layer_pooled_fwd / _bwd): every-row pieces
+    (h1, kv, LayerNorm-1 statistics) and the pooled rows' pieces ([B, .])."""
+
+    def __init__(self, rows, D, Dff, B, S, heads, size, dtype):
+        base = _layer_plan(rows, D, Dff, B, S, heads, size, dtype)
+        self.dims, self.gsizes, self.gnames, self.gtotal = base.dims, base.gsizes, base.gnames, base.gtotal
+        es = _ES[dtype]
+        self.off, o = {}, 0
+        for name, n in (("h1", rows * D * es), ("kv", rows * 2 * D * es), ("mean1", rows * 4), ("rstd1", rows * 4),
+                        ("h1p", B * D * es), ("q", B * D * es), ("attn_o", B * D * es), ("x2", B * D * es), ("h2", B * D * es),
+                        ("pre", B * Dff * es), ("act", B * Dff * es), ("mean1p", B * 4), ("rstd1p", B * 4), ("mean2", B * 4),
+                        ("rstd2", B * 4), ("stats", B * heads * 2 * 4)):
+            self.off[name] = o
+            o += _a256(n)
+        self.arena_bytes = o
+        lib = L.lib()
+        self.fwd_ws = int(lib.xp_encoder_layer_pooled_fwd_workspace_bytes(C.byref(self.dims)))
+        self.bwd_ws = int(lib.xp_encoder_layer_pooled_bwd_workspace_bytes(C.byref(self.dims)))
+
+
+def _pooled_plan(rows, D, Dff, B, S, heads, size, dtype) -> _PooledLayerPlan:
+    key = ("pooled", rows, D, Dff, B, S, heads, size, dtype)
+    p = _PLANS.get(key)
+    if p is None:
+        p = _PLANS[key] = _PooledLayerPlan(rows, D, Dff, B, S, heads, size, dtype)
+    return p
+
+
+_POOLED_SAVED = ("h1", "kv", "h1p", "q", "attn_o", "x2", "h2", "pre", "act", "mean1", "rstd1", "mean1p", "rstd1p", "mean2", "rstd2",
+                 "stats")
+
+
+class PooledEncoderLayerFn(torch.autograd.Function):
+    """The LAST CLIPEncoderLayer of the video tower when only the pooled feature leaves it (``pooled_output =
+    last_hidden_state[:, 0]``, modeling/CLIP_ViP.py:360-366): returns row ``b*S`` of ``EncoderLayerFn``'s output for every sample
+    -- ``[B, D]`` (and, with ``side``, those rows in fp32) -- computed without the dead rows.  LayerNorm 1 and the K/V projection
+    see every row (token 0 is a proxy row: it attends all S keys, CLIPAttention.forward2); the Q projection, the single-query
+    attention (csrc/attention_pooled.hip), out_proj, LayerNorm 2 and the MLP run on B rows.  The backward's ``dx`` is dense and
+    every parameter receives its gradient.  Exactly the function of the dense layer, not bit-equal to it in bf16: the dense
+    attention rounds P and dS to bf16 as matrix-core operands, the single-query kernel keeps them in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2,
+                B: int, S: int, heads: int, size: Tuple[int, int, int], training: bool = True, side: Optional[torch.Tensor] = None):
+        dt = x.dtype
+        rows, D = x.shape
+        M = size[0]
+        if side is not None and (dt != torch.bfloat16 or side.dtype != torch.float32 or not side.is_contiguous() or side.device != x.device
+                                 or tuple(side.shape) != (B * M, D)):
+            raise TypeError("PooledEncoderLayerFn: side rows must be a contiguous fp32 [B*M, D] tensor beside a bf16 stream")
+        Dff = w1.shape[0]
+        if D // heads != 64:
+            raise RuntimeError(f"xpretrain_amd attention kernels are built for head_dim 64, got {D // heads}")
+        if M < 1 or S != M + size[1] * size[2] or rows != B * S:
+            raise RuntimeError(f"PooledEncoderLayerFn: token 0 must be a proxy row of a [B*S, D] stream (size={size}, S={S}, rows={rows})")
+        q_scale = 64 ** -0.5
+        Wqkv = WEIGHTS.fused((wq, wk, wv), dt)
+        bqkv = WEIGHTS.fused((bq, bk, bv), torch.float32)
+        Wo, W1, W2 = WEIGHTS.get(wo, dt), WEIGHTS.get(w1, dt), WEIGHTS.get(w2, dt)
+        dev = x.device
+        x3 = torch.empty((B, D), dtype=dt, device=dev)
+        side_out = side_x2 = None
+        if side is not None:
+            side_out = torch.empty((B, D), dtype=torch.float32, device=dev)
+            side_x2 = torch.empty((B, D), dtype=torch.float32, device=dev)
+        if LAYER_CALLS and _native_ok(x, (ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2), (Wqkv, Wo, W1, W2), None):
+            plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt)
+            arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
+            ws = H.workspace(plan.fwd_ws, dev, "layer_pooled_fwd")
+            a = L.XpLayerPooledFwd()
+            a.dims = plan.dims
+            a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
+            a.ln1_w, a.ln1_b, a.bqkv, a.bo = ln1_w.data_ptr(), ln1_b.data_ptr(), bqkv.data_ptr(), bo.data_ptr()
+            a.ln2_w, a.ln2_b, a.b1, a.b2 = ln2_w.data_ptr(), ln2_b.data_ptr(), b1.data_ptr(), b2.data_ptr()
+            base = arena.data_ptr()
+            for name in _POOLED_SAVED:
+                setattr(a, name, base + plan.off[name])
+            if not training:        # forward-only pass: the MLP pre-activation is not written
+                a.pre = 0
+            a.x3 = x3.data_ptr()
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+            if side is not None:
+                a.side_in, a.side_out, a.side_x2 = side.data_ptr(), side_out.data_ptr(), side_x2.data_ptr()
+            L.check(L.lib().xp_encoder_layer_pooled_fwd(C.byref(a), H._stream()), "xp_encoder_layer_pooled_fwd")
+            ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2)
+            ctx.plan = plan
+            if GRAD_SINKS:
+                ctx.sink_params = (ln1_w, ln1_b, wq, wk, wv, bq, bk, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
+                ctx.sink_key = grad_sink_key(ctx.sink_params)
+            else:
+                ctx.sink_params, ctx.sink_key = (), None
+        else:
+            # op by op: the same entry points in the same order with the same arguments as csrc/layer.hip issues them
+            ctx.plan = None
+            lns, p1 = (None, None) if side is None else ((S, M, M), (1, 1, 1))
+            h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
+            side0 = None if side is None else H.gather_rows(side, None, B, M, D)
+            h1p, mean1p, rstd1p = H.layernorm_fwd(x, ln1_w, ln1_b, B, D, ldx=S * D, x_side=side0, side=p1)
+            kv = H.gemm(h1, Wqkv[D:], rows, 2 * D, D, epilogue=L.EPI_BIAS, bias=bqkv[D:])
+            q = H.gemm(h1p, Wqkv, B, D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
+            attn_o, stats = H.attn_pooled_fwd(q, kv, B, S, heads)
+            sd = None if side is None else (1, 1)
+            x2 = H.gemm(attn_o, Wo, B, D, D, epilogue=L.EPI_BIAS_RESID, bias=bo.detach(), resid=x, ldr=S * D,
+                        resid_side=side0, out_side=side_x2, side=sd)
+            h2, mean2, rstd2 = H.layernorm_fwd(x2, ln2_w, ln2_b, B, D, x_side=side_x2, side=p1)
+            pre = torch.empty((B, Dff), dtype=dt, device=dev) if training else None
+            act = H.gemm(h2, W1, B, Dff, D, epilogue=L.EPI_BIAS_GELU, bias=b1.detach(), aux=pre)
+            H.gemm(act, W2, B, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2, out=x3,
+                   resid_side=side_x2, out_side=side_out, side=sd)
+            if training:
+                ctx.save_for_backward(x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2,
+                                      h2, pre, act, Wqkv, Wo, W1, W2, side, side_x2)
+        ctx.meta = (B, S, heads, M, q_scale, D, Dff)
+        if side is not None:
+            ctx.mark_non_differentiable(side_out)
+            ctx.set_materialize_grads(False)
+            return x3, side_out
+        return x3
+
+    @staticmethod
+    def backward(ctx, dx3, _dside=None):
+        if dx3 is None:
+            return (None,) * 23
+        B, S, heads, M, q_scale, D, Dff = ctx.meta
+        need = ctx.needs_input_grad
+        saved = ctx.saved_tensors          # (read once: a checkpointed layer's tensors unpack once)
+        x = saved[0]
+        if dx3.dtype != x.dtype or dx3.device != x.device or tuple(dx3.shape) != (B, D):
+            raise TypeError(f"PooledEncoderLayerFn.backward: incoming gradient is {dx3.dtype} {tuple(dx3.shape)} on {dx3.device}, "
+                            f"expected {x.dtype} {(B, D)} on {x.device}")
+        dx3 = dx3.contiguous()
+        rows, dev = x.shape[0], x.device
+        dx = torch.empty_like(x)
+        pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
+        if ctx.plan is not None:
+            x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2 = saved
+            plan = ctx.plan
+            flat = None
+            if GRAD_SINKS and ctx.sink_key is not None and all(need[1:17]):
+                flat = _claim_sink(ctx.sink_key, GRAD_SINKS.get(ctx.sink_key), plan.gtotal, dev, ctx.sink_params)
+            if flat is None:
+                flat = torch.empty(plan.gtotal, dtype=torch.float32, device=dev)
+            parts = flat.split_with_sizes(plan.gsizes)
+            ws = H.workspace(plan.bwd_ws, dev, "layer_pooled_bwd")
+            a = L.XpLayerPooledBwd()
+            a.dims = plan.dims
+            base = arena.data_ptr()
+            for name in _POOLED_SAVED:
+                setattr(a, name, base + plan.off[name])
+            a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
+            a.ln1_w, a.ln2_w = ln1_w.data_ptr(), ln2_w.data_ptr()
+            a.dx3, a.dx = dx3.data_ptr(), dx.data_ptr()
+            want = dict(dln1_w=need[1], dln1_b=need[2], dwqkv=need[3] or need[5] or need[7], dbqkv=need[4] or need[6] or need[8],
+                        dwo=need[9], dbo=need[10], dln2_w=need[11], dln2_b=need[12], dw1=need[13], db1=need[14], dw2=need[15],
+                        db2=need[16])
+            g = {}
+            for name, t in zip(plan.gnames, parts):
+                if want[name]:
+                    g[name] = t
+                    setattr(a, name, t.data_ptr())
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+            if side is not None:
+                a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
+            L.check(L.lib().xp_encoder_layer_pooled_bwd(C.byref(a), H._stream()), "xp_encoder_layer_pooled_bwd")
+            gw = lambda n, shape: g[n].view(shape) if n in g else None
+            dwqkv, dbqkv = gw("dwqkv", (3 * D, D)), g.get("dbqkv")
+            return (dx, g.get("dln1_w"), g.get("dln1_b"),
+                    pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]), pick(dbqkv, 1, need[6]),
+                    pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"),
+                    g.get("dln2_b"), gw("dw1", (Dff, D)), g.get("db1"), gw("dw2", (D, Dff)), g.get("db2"),
+                    None, None, None, None, None, None)
+        (x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
+         Wqkv, Wo, W1, W2, side, side_x2) = saved
+        dt = x.dtype
+        lns, p1, pM = (None, None, None) if side is None else ((S, M, M), (1, 1, 1), (1, 1, M))
+
+        def wgrad(dy, lddy, xx, ldx, K, n_out, n_in, out, a_remap=(0, 0, 0), slack=True):
+            split = H.gemm_auto_split(n_out, n_in, K, dt, lda=lddy, ldb=ldx, a_remap=a_remap, slack=slack)
+            if split <= 1:
+                H.gemm(dy, xx, n_out, n_in, K, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=out,
+                       out_dtype=torch.float32, a_remap=a_remap)
+            else:
+                ws = H.workspace(split * n_out * n_in * 4, dev, "splitk")
+                H.gemm(dy, xx, n_out, n_in, K, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=ws, split_k=split,
+                       a_remap=a_remap)
+                H.splitk_reduce(ws, out, splits=split)
+            return out
+
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        defer = H.DeferredReduce(dev)
+        dpre = H.gemm(dx3, W2, B, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre)
+        db1 = H.colsum_deferred(dpre, B, Dff, defer, name="db1") if need[14] else None
+        dw2 = wgrad(dx3, D, act, Dff, B, D, Dff, f32(D, Dff)) if need[15] else None
+        dh2 = H.gemm(dpre, W1, B, D, Dff, b_kstrided=True)
+        dw1 = wgrad(dpre, Dff, h2, D, B, Dff, D, f32(Dff, D)) if need[13] else None
+        dx2, dln2_w, dln2_b, dbo, db2 = H.layernorm_bwd(dh2, x2, ln2_w, mean2, rstd2, B, D, dres=dx3, defer=defer, dx_colsum=True,
+                                                        dres_colsum=True, name="ln2", x_side=side_x2, side=p1)
+        dattn = H.gemm(dx2, Wo, B, D, D, b_kstrided=True)
+        dwo = wgrad(dx2, D, attn_o, D, B, D, D, f32(D, D)) if need[9] else None
+        # dqkv [rows, 3D]: dk / dv in the k / v columns of every row, dq in the q columns of the pooled rows only
+        dqkv = torch.empty((rows, 3 * D), dtype=dt, device=dev)
+        dq_view, dkv = dqkv.view(B, S * 3 * D)[:, :D], dqkv[:, D:]
+        want_b = need[4] or need[6] or need[8]
+        dbqkv = f32(3 * D) if want_b else None
+        if want_b:
+            H.attn_pooled_bwd(q, kv, attn_o, dattn, stats, B, S, heads, q_scale=q_scale, dq=dq_view, dkv=dkv,
+                              colsum_defer=defer, colsum_name="dbkv", colsum_out=dbqkv[D:])
+        else:
+            H.attn_pooled_bwd(q, kv, attn_o, dattn, stats, B, S, heads, q_scale=q_scale, dq=dq_view, dkv=dkv)
+        dh1 = H.gemm(dkv, Wqkv[D:], rows, D, 2 * D, lda=3 * D, b_kstrided=True, ldb=D)
+        H.gemm(dqkv, Wqkv, B, D, 3 * D, b_kstrided=True, ldb=D, a_remap=(1, S, 0), c_remap=(1, S, 0), out=dh1)
+        dwqkv = None
+        if need[3] or need[5] or need[7]:
+            dwqkv = f32(3 * D, D)
+            wgrad(dqkv, 3 * D, h1p, D, B, D, D, dwqkv[:D], a_remap=(1, S, 0))
+            wgrad(dkv, 3 * D, h1, D, rows, 2 * D, D, dwqkv[D:], slack=False)
+        if want_b:
+            nq = L.lib().xp_colsum_partial_rows(B, D)
+            part = defer.slot(nq * D * 4, "dbq")
+            L.check(L.lib().xp_colsum_partials(H._p(dqkv), B, D, S * 3 * D, H._dt(dqkv), H._p(part), part.numel(), H._stream()),
+                    "xp_colsum_partials")
+            defer.add(part, 0, dbqkv, nq, D, D)
+        _, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dx=dx, defer=defer, name="ln1", x_side=side, side=lns)
+        # the pooled rows once more, with their residual gradient (the parameter-gradient partial rows of this pass are dropped)
+        ws = H.workspace(L.lib().xp_layernorm_bwd_workspace_bytes(B, D), dev, "ln1_pooled")
+        L.check(L.lib().xp_layernorm_bwd_partials_side(H._p(dh1), S * D, H._p(x), S * D, H._p(ln1_w), H._p(mean1p), H._p(rstd1p),
+                                                       H._p(dx2), D, H._p(dx), S * D, 0, B, D, H._dt(x), H._p(side),
+                                                       *((1, 1, M) if side is not None else (0, 0, 0)), H._p(ws), ws.numel(),
+                                                       H._stream()), "xp_layernorm_bwd_partials_side")
+        defer.flush()
+        keep = lambda i, t: t if need[i] else None
+        return (dx, keep(1, dln1_w), keep(2, dln1_b), pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]),
+                pick(dbqkv, 1, need[6]), pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), dwo, keep(10, dbo), keep(11, dln2_w),
+                keep(12, dln2_b), dw1, db1, dw2, keep(16, db2), None, None, None, None, None, None)
+
+
+def pooled_encoder_layer(x, layer, B, S, heads, size, side=None):
+    """Apply ``PooledEncoderLayerFn`` with the parameters of a ``CLIPEncoderLayer`` module: ``[B, D]`` (with ``side``: also the fp32
+    rows)."""
+    return PooledEncoderLayerFn.apply(x, *_layer_params(layer), B, S, heads, tuple(size), torch.is_grad_enabled(), side)
+
+
 # ------------------------------------------------------------------------------------------ fp32 side rows (proxy tokens)
 # XPRETRAIN_PROXY_FP32=1 (default): the video tower's M proxy tokens of every sample keep their residual stream in fp32 beside the
 # bf16 rows ([B*M, D] fp32 "side rows": read by the LayerNorms, read / written by the residual GEMM epilogues).  Measured with the

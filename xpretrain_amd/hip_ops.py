@@ -527,3 +527,65 @@ def attn_bwd(qkv, out, dout, stats, B, S, H, *, size=None, pad_mask=None, q_scal
     cs = torch.empty(3 * H * 64, dtype=torch.float32, device=qkv.device)
     colsum_defer.add(part, 0, cs, nrows, 3 * H * 64, 3 * H * 64)
     return dqkv, cs
+
+
+# --------------------------------------------------------------------------------------- single-query proxy attention
+def _rows_ld(t: torch.Tensor, name: str, width: int) -> int:
+    """row pitch of a 2-D operand whose rows are contiguous (a column slice of a wider matrix is fine: kv = qkv[:, D:])"""
+    _chk(t, name)
+    if t.dim() != 2 or t.stride(1) != 1 or t.shape[1] < width:
+        raise TypeError(f"{name}: expected a [rows, >= {width}] matrix with contiguous rows, got {tuple(t.shape)} strides {t.stride()}")
+    return t.stride(0)
+
+
+def attn_pooled_fwd(q: torch.Tensor, kv: torch.Tensor, B: int, S: int, H: int):
+    """Token 0 of every sample against all S keys (the pooled last layer of the video tower).  q [B, H*64] (pre-scaled), kv
+    [B*S, 2*H*64] = [k | v] rows (any row pitch).  Returns (out [B, H*64], stats [B, H, 2])."""
+    _chk(q, "q")
+    ld = _rows_ld(kv, "kv", 2 * H * 64)
+    if not q.is_contiguous() or tuple(q.shape) != (B, H * 64) or kv.shape[0] != B * S or kv.dtype != q.dtype:
+        raise TypeError("attn_pooled_fwd: q must be a contiguous [B, H*64] matrix and kv [B*S, 2*H*64] of the same dtype")
+    out = torch.empty_like(q)
+    stats = torch.empty((B, H, 2), dtype=torch.float32, device=q.device)
+    ws = workspace(L.lib().xp_attn_pooled_workspace_bytes(B, H, S, _dt(q)), q.device, "attn_pooled")
+    L.check(L.lib().xp_attn_pooled_fwd(_p(q), _p(kv), ld, _p(out), _p(stats), B, H, S, _dt(q), _p(ws), ws.numel(), _stream()),
+            "xp_attn_pooled_fwd")
+    return out, stats
+
+
+def attn_pooled_bwd(q, kv, out, dout, stats, B, S, H, *, q_scale=1.0, dq=None, dkv=None, colsum_defer=None, colsum_name="dbkv",
+                    colsum_out=None):
+    """(dq [B, H*64] -- times q_scale --, dkv [B*S, 2*H*64]); with ``colsum_defer`` also the column sums of dkv (the k / v bias
+    gradients, final after ``flush()``; written to ``colsum_out`` if given).  ``dq`` / ``dkv``: optional outputs with contiguous
+    rows (any row pitch)."""
+    ld = _rows_ld(kv, "kv", 2 * H * 64)
+    if dq is None:
+        dq = torch.empty_like(q)
+    if dkv is None:
+        dkv = torch.empty((B * S, 2 * H * 64), dtype=q.dtype, device=q.device)
+    lddq, lddkv = _rows_ld(dq, "dq", H * 64), _rows_ld(dkv, "dkv", 2 * H * 64)
+    for t, n in ((out, "out"), (dout, "dout")):
+        _chk(t, n, q.dtype)
+        if not t.is_contiguous() or t.shape != q.shape:
+            raise TypeError(f"attn_pooled_bwd: {n} must be contiguous and shaped like q")
+    lib = L.lib()
+    ws = workspace(lib.xp_attn_pooled_workspace_bytes(B, H, S, _dt(q)), q.device, "attn_pooled")
+    nrows = int(lib.xp_attn_pooled_colsum_rows(B, H, S, _dt(q))) if colsum_defer is not None else 0
+    part = colsum_defer.slot(nrows * 2 * H * 64 * 4, colsum_name) if nrows else None
+    L.check(lib.xp_attn_pooled_bwd(_p(q), _p(kv), ld, _p(out), _p(dout), _p(stats), _p(dq), lddq, _p(dkv), lddkv, float(q_scale),
+                                   B, H, S, _dt(q), _p(ws), ws.numel(), _p(part), _stream()), "xp_attn_pooled_bwd")
+    if colsum_defer is None:
+        return dq, dkv
+    cs = torch.empty(2 * H * 64, dtype=torch.float32, device=q.device) if colsum_out is None else colsum_out
+    colsum_defer.add(part, 0, cs, nrows, 2 * H * 64, 2 * H * 64)
+    return dq, dkv, cs
+
+
+def attn_pooled_plan(B: int, S: int, H: int, *, dtype=torch.bfloat16, backward=False, cus=0) -> dict:
+    """The plan attn_pooled_fwd (``backward``: attn_pooled_bwd) launches (xp_debug_attn_pooled_plan: host only, nothing launched) as
+    a dict of the XpAttnPooledPlanInfo fields.  ``cus`` > 0: a device of that many CUs (no GPU needed); <= 0: the current device."""
+    info = L.XpAttnPooledPlanInfo()
+    L.check(L.lib().xp_debug_attn_pooled_plan(B, H, S, _DT[dtype], int(backward), cus, C.byref(info)), "xp_debug_attn_pooled_plan")
+    plan = {f: getattr(info, f) for f, _ in info._fields_}
+    plan.update({f: tuple(plan[f]) for f in ("part_ml", "part_acc", "part_dq")})
+    return plan

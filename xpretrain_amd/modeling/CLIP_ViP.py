@@ -238,11 +238,23 @@ class CLIPEncoder(nn.Module):
         self.layers = nn.ModuleList([CLIPEncoderLayer(config) for _ in range(config.num_hidden_layers)])
         self.gradient_checkpointing = False
 
-    def forward(self, x, B, S, inputs_size=None, pad_mask=None, collect=None, side=None, collect_side=None):
+    def pools_last(self, x, inputs_size, pad_mask, collect) -> bool:
+        """whether ``forward(pooled_last=True)`` runs the last layer in its pooled form: the video tower on the GPU, token 0 a proxy
+        row, nobody else looking at that layer's output (no padding mask, no ``collect``, no forward hooks on it)"""
+        return (inputs_size is not None and inputs_size[0] >= 1 and pad_mask is None and collect is None and x.is_cuda
+                and len(self.layers) > 0 and not _has_forward_hooks(self.layers[-1:]))
+
+    def forward(self, x, B, S, inputs_size=None, pad_mask=None, collect=None, side=None, collect_side=None, pooled_last=False):
         """``side``: the proxy rows of ``x`` in fp32 (video tower, bf16 compute: XF.PROXY_SIDE); returns ``(x, side)`` then.
         ``collect`` / ``collect_side``: lists that receive every layer output (compute dtype, as ``last_hidden_state``) and its
-        fp32 side rows (``output_hidden_states``)."""
+        fp32 side rows (``output_hidden_states``).
+        ``pooled_last``: the caller reads token 0 of every sample only.  Layers 0..n-2 run as ever, the two chains join, and the
+        last layer runs in its pooled form (XF.PooledEncoderLayerFn): the encoder then returns the ``[B, D]`` rows of token 0
+        (and their ``[B, D]`` fp32 side rows) instead of the ``[B*S, D]`` stream.  Ignored -- dense last layer, dense result --
+        unless ``pools_last``: callers test that to know what they got."""
         ckpt = self.gradient_checkpointing and self.training and torch.is_grad_enabled()
+        pooled_last = bool(pooled_last) and self.pools_last(x, inputs_size, pad_mask, collect)
+        last = len(self.layers) - 1
         # video tower: two half-batch chains on two streams (functional.ForwardSplit), joined after the last layer.  Training passes
         # keep every layer's buffers in the autograd graph; forward-only passes (and layers without a node: everything frozen under
         # grad mode) have the split hold them until the join.
@@ -254,6 +266,21 @@ class CLIPEncoder(nn.Module):
             if keeps or 12 * len(self.layers) * x.numel() * x.element_size() <= XF.FWD_SPLIT_HOLD_BYTES:
                 split = XF.ForwardSplit(x.device)
         for li, layer in enumerate(self.layers):
+            if pooled_last and li == last:
+                if split is not None:       # the pooled layer reads every row of both chains
+                    split.join()
+                    split = None
+                if XF.LATE_WEIGHTS["event"] is not None:
+                    XF.wait_late_weights(li)
+                heads = layer.num_heads
+                if ckpt:
+                    from torch.utils.checkpoint import checkpoint
+                    if side is None:
+                        return checkpoint(lambda t, _l=layer: XF.pooled_encoder_layer(t, _l, B, S, heads, inputs_size), x,
+                                          use_reentrant=False)
+                    return checkpoint(lambda t, sd, _l=layer: XF.pooled_encoder_layer(t, _l, B, S, heads, inputs_size, sd), x, side,
+                                      use_reentrant=False)
+                return XF.pooled_encoder_layer(x, layer, B, S, heads, inputs_size, side)
             if XF.LATE_WEIGHTS["event"] is not None and x.is_cuda:      # the optimizer's overlapped update of the layers >= K (XF.LATE_WEIGHTS)
                 XF.wait_late_weights(li, *((torch.cuda.current_stream(x.device), split.stream) if split is not None else ()))
             if ckpt:
@@ -340,7 +367,10 @@ class CLIPVisionTransformer(nn.Module):
         self.post_layernorm = nn.LayerNorm(config.hidden_size)
         self.compute_dtype = torch.bfloat16
 
-    def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+    def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None, pooled_only=False):
+        """``pooled_only`` (CLIPModel.pooled_last_layer): the caller reads ``pooler_output`` alone, so the last encoder layer may
+        compute token 0 of every sample only; ``last_hidden_state`` is then ``None``.  Without it -- every direct call -- and with
+        ``output_hidden_states`` the tower is dense."""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
         if output_attentions:
@@ -356,16 +386,21 @@ class CLIPVisionTransformer(nn.Module):
             side = XF.proxy_side_rows(emb.class_embedding, emb.added_cls, emb.position_embedding.weight, B, M)
             x, side = XF.LayerNormFn.apply(x, self.pre_layrnorm.weight, self.pre_layrnorm.bias, side, (S, M, M), True)
             hs, hside = ([x], [side]) if output_hidden_states else (None, None)
-            x, side = self.encoder(x, B, S, size, None, hs, side, hside)
-            pooled = XF.LayerNormFn.apply(XF.GatherRowsFn.apply(x, None, B, S), self.post_layernorm.weight,
-                                          self.post_layernorm.bias, side, (1, 1, M))
+            pooled_only = bool(pooled_only) and self.encoder.pools_last(x, size, None, hs)
+            x, side = self.encoder(x, B, S, size, None, hs, side, hside, pooled_only)
+            if pooled_only:         # x, side: token 0 of every sample already
+                pooled = XF.LayerNormFn.apply(x, self.post_layernorm.weight, self.post_layernorm.bias, side, (1, 1, 1))
+            else:
+                pooled = XF.LayerNormFn.apply(XF.GatherRowsFn.apply(x, None, B, S), self.post_layernorm.weight,
+                                              self.post_layernorm.bias, side, (1, 1, M))
         else:
             x = XF.LayerNormFn.apply(x, self.pre_layrnorm.weight, self.pre_layrnorm.bias)
             hs, hside = ([x] if output_hidden_states else None), None
-            x = self.encoder(x, B, S, size, None, hs)
-            pooled = XF.LayerNormFn.apply(XF.GatherRowsFn.apply(x, None, B, S), self.post_layernorm.weight,
+            pooled_only = bool(pooled_only) and self.encoder.pools_last(x, size, None, hs)
+            x = self.encoder(x, B, S, size, None, hs, pooled_last=pooled_only)
+            pooled = XF.LayerNormFn.apply(x if pooled_only else XF.GatherRowsFn.apply(x, None, B, S), self.post_layernorm.weight,
                                           self.post_layernorm.bias)
-        out = BaseModelOutputWithPooling(last_hidden_state=x.view(B, S, D), pooler_output=pooled,
+        out = BaseModelOutputWithPooling(last_hidden_state=None if pooled_only else x.view(B, S, D), pooler_output=pooled,
                                          hidden_states=None if hs is None else tuple(h.view(B, S, D) for h in hs),
                                          hidden_side_rows=None if hside is None else tuple(h.view(B, M, D) for h in hside),
                                          attentions=None)
@@ -563,7 +598,7 @@ class CLIPModel(CLIPPreTrainedModel):
     def get_image_features(self, pixel_values=None, output_attentions=None, output_hidden_states=None,
                            return_dict=None, if_norm=None):
         out = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                output_hidden_states=output_hidden_states)
+                                output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer)
         feats = XF.ProjectionFn.apply(out["pooler_output"], self.visual_projection.weight)
         return XF.L2NormFn.apply(feats) if if_norm else feats.float()
 
@@ -586,14 +621,14 @@ class CLIPModel(CLIPPreTrainedModel):
                 text_done.record(side)                          # the join below waits for the TOWER, not for what is queued behind it
                 CLIPModel.run_deferred_text_stream_work()       # (e.g. the loader's copy of the NEXT batch: behind the text tower's forward)
             vision_outputs = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                               output_hidden_states=output_hidden_states)
+                                               output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer)
             image_embeds = XF.L2NormFn.apply(XF.ProjectionFn.apply(vision_outputs["pooler_output"], self.visual_projection.weight))
             main.wait_event(text_done)
             text_embeds.record_stream(main)
             return self._finish(image_embeds, text_embeds, text_outputs, vision_outputs, return_loss, return_dict,
                                 output_hidden_states)
         vision_outputs = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                           output_hidden_states=output_hidden_states)
+                                           output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer)
         text_outputs = self.text_model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                        output_attentions=output_attentions, output_hidden_states=output_hidden_states)
         image_embeds = XF.L2NormFn.apply(XF.ProjectionFn.apply(vision_outputs["pooler_output"], self.visual_projection.weight))
@@ -602,6 +637,12 @@ class CLIPModel(CLIPPreTrainedModel):
                             output_hidden_states)
 
     overlap_text_tower = True          # class attribute: False runs the text tower on the caller's stream (A/B: DESIGN_HISTORY.md 6.0)
+    # Opt-in (class attribute, settable per model; XPRETRAIN_POOLED_LAST=1 turns it on for every model): forward() and
+    # get_image_features() read the video tower's pooler_output only, so its LAST encoder layer computes token 0 of every sample
+    # alone (XF.PooledEncoderLayerFn: the same function, without the rows nobody reads).  The one visible
+    # difference: forward()'s vision_model_output.last_hidden_state is None.  output_hidden_states, forward hooks on the last
+    # layer, and any direct call of vision_model / CLIPVisionModel keep the dense layer.
+    pooled_last_layer = os.environ.get("XPRETRAIN_POOLED_LAST", "0") not in ("", "0")
     _text_streams = {}          # one per device, shared by every model instance (and by utils.prefetch.PrefetchLoader(stream="text"))
 
     @staticmethod
