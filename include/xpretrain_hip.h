@@ -11,8 +11,8 @@
  *   - plain pointers + sizes; no torch types.  Every pointer is a DEVICE pointer unless named host_*.
  *   - never allocates, never synchronises, never owns memory; launches only on `stream`
  *     (a hipStream_t passed as void*); re-entrant (forward thread + autograd thread).
- *     The three deviations an integrator must know, all documented at the entry point concerned: (1) xp_encoder_layer_bwd runs a
- *     layer's weight-gradient GEMMs on ONE library-owned stream per device (xp_side_stream(), created on first use, ordered against
+ *     The three deviations an integrator must know, all documented at the entry point concerned: (1) xp_encoder_layer_bwd (and
+ *     xp_encoder_layer_pooled_bwd) runs a layer's weight-gradient GEMMs on ONE library-owned stream per device (xp_side_stream(), created on first use, ordered against
  *     `stream` by library-owned events, joined before the call returns); (2) xp_set_cu_budget() is process-global planning state;
  *     (3) xp_attn_bwd / xp_attn_bwd2 enqueue one 4-byte hipMemsetAsync on `stream` (the fused backward's problem counter, inside the
  *     caller's workspace).
@@ -461,10 +461,11 @@ typedef struct XpLayerPooledBwd {
 } XpLayerPooledBwd;
 size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* dims);
 int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* args, void* stream);
-/* The library's second stream of the current device (the one xp_encoder_layer_bwd issues the weight-gradient GEMMs on; created at the
- * device's highest priority on first use), or NULL when XPRETRAIN_WGRAD_STREAM=0.  It is idle outside xp_encoder_layer_bwd calls: the
- * host side runs the second half-batch chain of the video tower's forward on it instead of creating one more stream (a process gets few
- * hardware queues). */
+/* The library's second stream of the current device (the one xp_encoder_layer_bwd and xp_encoder_layer_pooled_bwd issue the
+ * weight-gradient GEMMs on; created at the DEFAULT priority on first use -- a high-priority queue starves the critical chain as soon
+ * as a collective library's streams run beside it), or NULL when XPRETRAIN_WGRAD_STREAM=0.  It is idle outside those
+ * two calls: the host side runs the second half-batch chain of the video tower's forward on it instead of creating one more stream
+ * (a process gets few hardware queues). */
 void* xp_side_stream(void);
 
 /* -------------------------------------------------------------------------------------- Diagnostics

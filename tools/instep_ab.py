@@ -46,9 +46,10 @@ def main():
     a = ap.parse_args()
     variants = [parse_variant(v) for v in a.variants]
     res = {name: [] for name, _, _, _ in variants}
-    for _ in range(a.rounds):
+    for r in range(a.rounds):
         for name, tree, envs, flags in variants:
             res[name].append(run(tree, envs, a.steps, flags))
+            print(f"round {r + 1}/{a.rounds} {name}: {res[name][-1]['ms_per_step']:.3f} ms/step", file=sys.stderr, flush=True)   # (progress: a run takes minutes)
     keys = ("value", "ms_per_step", "vit_forward_ms", "vit_forward_train_mode_ms")
     lines = [f"bench.py --full --steps {a.steps} --no-cpu-baseline, one box, {a.rounds} interleaved rounds: pairs/s ms/step vit_fwd_ms vit_fwd_train_mode_ms"]
     w = max(len(v) for v in a.variants)

@@ -3,11 +3,16 @@
 // code.  Pure host-side sequencing over the public entry points of this library (xp_layernorm_*, xp_gemm, xp_attn_*,
 // xp_colsum_partials, xp_splitk_reduce, xp_reduce_rows_batch) -- no kernel of its own -- so the arithmetic is identical,
 // launch for launch, to driving those entry points one by one (the Python op-by-op path, functional.EncoderLayerFn with
-// XPRETRAIN_LAYER_CALLS=0; tests compare the two bit for bit).  Why: ~810 launches per training step cost 13.6 ms of
+// XPRETRAIN_DEBUG=op_by_op; tests compare the two bit for bit).  Why: ~810 launches per training step cost 13.6 ms of
 // Python / ctypes time against 16.7 ms of GPU time (BENCH_r01); from C++ a launch costs 3-4 us.
+// The dense layer (xp_encoder_layer_fwd / _bwd) and the pooled last layer (xp_encoder_layer_pooled_fwd / _bwd) are the same
+// sequence from out_proj onward, over `rows` rows or over the B pooled rows: those stages (out_proj_mlp_fwd, mlp_out_proj_bwd,
+// finish_bwd) are written once and read the fields the argument structs have in common; LayerNorm 1, the projections, the
+// attention call and their backward stay with each entry point.
 #include "common.h"
 #include <string.h>
 #include <stdlib.h>
+#include <initializer_list>
 #include <mutex>
 
 namespace {
@@ -47,16 +52,18 @@ int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, bool slac
   if (xp_debug_flag("skip_splitk_reduce")) return XP_OK;      // measurement only (wrong gradients): what the four reduces of a layer cost the step
   return xp_splitk_reduce(slabs, dw, d.M * d.N, split, 0, st);
 }
-size_t wgrad_desc_slab_bytes(XpGemmDesc d) {
-  const int a = xp_gemm_auto_split(&d), b = xp_gemm_auto_split_slack(&d), split = a > b ? a : b;
-  return split <= 1 ? 0 : (size_t)split * d.M * d.N * sizeof(float);
+// both operands dense: dY[k, n_out], X[k, n_in]
+XpGemmDesc wgrad_desc(const void* dy, const void* x, float* dw, int64_t k, int64_t n_out, int64_t n_in, int dtype) {
+  return wgrad_desc(dy, n_out, x, n_in, dw, k, n_out, n_in, dtype);
 }
-int wgrad(const void* dy, const void* x, float* dw, int64_t rows, int64_t n_out, int64_t n_in, int dtype, float* slabs,
-          size_t slab_bytes, void* st, bool slack) {
-  return run_wgrad(wgrad_desc(dy, n_out, x, n_in, dw, rows, n_out, n_in, dtype), slabs, slab_bytes, st, slack);
-}
-size_t wgrad_slab_bytes(int64_t rows, int64_t n_out, int64_t n_in, int dtype) {
-  return wgrad_desc_slab_bytes(wgrad_desc(nullptr, n_out, nullptr, n_in, nullptr, rows, n_out, n_in, dtype));
+// split-K slab space that serves every one of `ds` under either split rule (and at least `s` bytes)
+size_t max_slab_bytes(size_t s, std::initializer_list<XpGemmDesc> ds) {
+  for (XpGemmDesc d : ds) {
+    const int a = xp_gemm_auto_split(&d), b = xp_gemm_auto_split_slack(&d), split = a > b ? a : b;
+    const size_t t = split <= 1 ? 0 : (size_t)split * d.M * d.N * sizeof(float);
+    if (t > s) s = t;
+  }
+  return s;
 }
 
 struct Defer {             // the layer's deferred second-level reductions (bias / LayerNorm-parameter gradients)
@@ -104,6 +111,138 @@ WgradSide* wgrad_side() {
   return w.ok ? &w : nullptr;
 }
 
+// One backward call's ordering against that stream (side == nullptr: the dW GEMMs stay on the caller's stream, nothing to order)
+struct WgradOrder {
+  WgradSide* side; hipStream_t main; const char* name;      // name: the entry point, for error text
+  void* stream() const { return side ? (void*)side->side : (void*)main; }
+  int mark(int i) const {           // side stream: everything the main stream has enqueued so far must finish first
+    if (!side) return XP_OK;
+    if (hipEventRecord(side->ev[i], main) != hipSuccess || hipStreamWaitEvent(side->side, side->ev[i], 0) != hipSuccess) {
+      xp_set_error("%s: event hand-off to the weight-gradient stream failed", name);
+      return XP_ERR_LAUNCH;
+    }
+    return XP_OK;
+  }
+  int join() const {                // the weight gradients (and every workspace the side stream read) belong to the main stream again
+    // (XPRETRAIN_DEBUG=no_wgrad_join: measurement only -- races on the shared workspace -- what a lazy join could be worth at most)
+    if (!side || xp_debug_flag("no_wgrad_join")) return XP_OK;
+    if (hipEventRecord(side->done, side->side) != hipSuccess || hipStreamWaitEvent(main, side->done, 0) != hipSuccess) {
+      xp_set_error("%s: joining the weight-gradient stream failed", name);
+      return XP_ERR_LAUNCH;
+    }
+    return XP_OK;
+  }
+};
+
+// ---- the stages a dense and a pooled layer share: out_proj onward, over n rows (n = rows / n = B) --------------------------
+// `Args`: XpLayerFwd / XpLayerPooledFwd (XpLayerBwd / XpLayerPooledBwd): only the fields the two have in common are read.
+// Side rows: (sS, sM) is the geometry of the n rows' fp32 side rows, stored with stride sM (dense: side_S, side_M; pooled: 1, 1).
+
+// x2 = resid + attn_o Wo^T + bo (resid: x with row pitch ldr, its side rows in side_x) ; x3 = x2 + fc2(quick_gelu(fc1(LN2(x2))))
+template <class Args>
+int out_proj_mlp_fwd(const Args& a, int64_t n, int64_t ldr, const float* side_x, float* side_x2, float* side_out, int64_t sS,
+                     int32_t sM, void* st) {
+  const XpLayerDims& d = a.dims;
+  const int64_t D = d.D, Dff = d.Dff;
+  const int dt = d.dtype;
+  int rc;
+  XpGemmDesc g = gemm_desc(a.attn_o, a.Wo, a.x2, n, D, D, dt);
+  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a.bo; g.resid = a.x; g.ldr = ldr;
+  if (side_x) { g.resid_side = side_x; g.out_side = side_x2; g.side_S = sS; g.side_M = sM; }
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if ((rc = xp_layernorm_fwd_side(a.x2, D, a.ln2_w, a.ln2_b, a.h2, D, a.mean2, a.rstd2, n, D, d.ln_eps, dt,
+                                  side_x2, nullptr, sS, sM, sM, st))) return rc;
+  // pre = h2 W1^T + b1 ; act = quick_gelu(pre)
+  g = gemm_desc(a.h2, a.W1, a.act, n, Dff, D, dt);
+  g.epilogue = XP_EPI_BIAS_GELU; g.bias = a.b1; g.aux = a.pre;
+  if (xp_debug_flag("fc1_no_pre")) g.aux = nullptr;      // measurement only (tools/fc1_one_output.py): the backward then reads garbage
+  if ((rc = xp_gemm(&g, st))) return rc;
+  // x3 = x2 + act W2^T + b2
+  g = gemm_desc(a.act, a.W2, a.x3, n, D, Dff, dt);
+  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a.b2; g.resid = a.x2;
+  if (side_x) { g.resid_side = side_x2; g.out_side = side_out; g.side_S = sS; g.side_M = sM; }
+  return xp_gemm(&g, st);
+}
+
+// The part of a backward workspace the shared stages use, for n rows: [dpre | dh2 | dx2 | dattn] activation-gradient temporaries,
+// fc1's bias-gradient partial rows, the second LayerNorm's partial rows, the batched-reduce scratch.
+struct TailBwdPlan {
+  size_t esz, dpre, dh, cs_pre, ln2, red, bytes, slabs;     // slabs: what the stage's three dW GEMMs need (not part of bytes)
+  int64_t db1_fused_rows, cs_pre_rows, ln_rows;
+};
+struct TailBwdWs { void *dpre, *dh2, *dx2, *dattn, *red; float *cs_pre, *ln2_part; };
+// db1_fused_rows: partial rows of fc1's bias gradient out of the dpre GEMM's epilogue (xp_gemm_colsum_rows), 0 = a separate
+// column-sum pass over dpre
+TailBwdPlan plan_tail_bwd(int64_t n, int64_t D, int64_t Dff, int dt, int64_t db1_fused_rows) {
+  TailBwdPlan p;
+  memset(&p, 0, sizeof(p));
+  p.esz = dt == XP_BF16 ? 2 : 4;
+  p.dpre = align256(n * Dff * p.esz); p.dh = align256(n * D * p.esz);
+  p.db1_fused_rows = db1_fused_rows;
+  p.cs_pre_rows = db1_fused_rows > 0 ? db1_fused_rows : xp_colsum_partial_rows(n, Dff);
+  p.cs_pre = align256(p.cs_pre_rows * Dff * sizeof(float));
+  p.ln_rows = xp_layernorm_bwd_partial_rows(n);
+  p.ln2 = align256(xp_layernorm_bwd_workspace_bytes(n, D));
+  p.red = align256((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16);
+  p.bytes = p.dpre + 3 * p.dh + p.cs_pre + p.ln2 + p.red;
+  p.slabs = max_slab_bytes(0, {wgrad_desc(nullptr, nullptr, nullptr, n, D, Dff, dt), wgrad_desc(nullptr, nullptr, nullptr, n, Dff, D, dt),
+                               wgrad_desc(nullptr, nullptr, nullptr, n, D, D, dt)});
+  return p;
+}
+TailBwdWs carve_tail_bwd(Carver& ws, const TailBwdPlan& p) {
+  TailBwdWs w;
+  w.dpre = ws.take(p.dpre); w.dh2 = ws.take(p.dh); w.dx2 = ws.take(p.dh); w.dattn = ws.take(p.dh);
+  w.cs_pre = (float*)ws.take(p.cs_pre); w.ln2_part = (float*)ws.take(p.ln2); w.red = ws.take(p.red);
+  return w;
+}
+
+// x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))) and x2 = resid + out_proj(attn_o), backwards: leaves dx2 and dattn in the workspace,
+// issues dW2, dW1, dWo and defers db1, dln2_w, dln2_b, dbo, db2.  Marks 1 and 2 of the weight-gradient stream.
+template <class Args>
+int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwdPlan& p, const TailBwdWs& w, float* slabs, size_t slab_bytes, int64_t sS,
+                     int32_t sM, Defer& df, const WgradOrder& wg, void* st) {
+  const int64_t D = a.dims.D, Dff = a.dims.Dff;
+  const int dt = a.dims.dtype;
+  int rc;
+  XpGemmDesc g = gemm_desc(a.dx3, a.W2, w.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * quick_gelu'(pre)
+  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.resid = a.pre; g.ldr = Dff;
+  if (a.db1 && p.db1_fused_rows > 0) g.colsum_partials = w.cs_pre;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a.db1) {
+    if (p.db1_fused_rows == 0 && (rc = xp_colsum_partials(w.dpre, n, Dff, Dff, dt, w.cs_pre, p.cs_pre, st))) return rc;
+    df.add(w.cs_pre, a.db1, Dff, (int)p.cs_pre_rows, (int)Dff);
+  }
+  if (a.dw2 && (rc = run_wgrad(wgrad_desc(a.dx3, a.act, a.dw2, n, D, Dff, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  if ((rc = wg.mark(1))) return rc;                                           // dpre is ready for dW1
+  g = gemm_desc(w.dpre, a.W1, w.dh2, n, D, Dff, dt);                          // dh2 = dpre . W1
+  g.b_kstrided = 1; g.ldb = D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a.dw1 && (rc = run_wgrad(wgrad_desc(w.dpre, a.h2, a.dw1, n, Dff, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)] -- out_proj's and fc2's bias gradients
+  if ((rc = xp_layernorm_bwd_partials_side(w.dh2, D, a.x2, D, a.ln2_w, a.mean2, a.rstd2, a.dx3, D, w.dx2, D, 2, n, D, dt,
+                                           a.side_x2, sS, sM, sM, w.ln2_part, p.ln2, st))) return rc;
+  df.add(w.ln2_part, a.dln2_w, 4 * D, (int)p.ln_rows, (int)D);
+  df.add(w.ln2_part + D, a.dln2_b, 4 * D, (int)p.ln_rows, (int)D);
+  df.add(w.ln2_part + 2 * D, a.dbo, 4 * D, (int)p.ln_rows, (int)D);
+  df.add(w.ln2_part + 3 * D, a.db2, 4 * D, (int)p.ln_rows, (int)D);
+  if ((rc = wg.mark(2))) return rc;                                           // dx2 is ready for dWo
+  g = gemm_desc(w.dx2, a.Wo, w.dattn, n, D, D, dt);                           // dattn = dx2 . Wo
+  g.b_kstrided = 1; g.ldb = D;
+  if ((rc = xp_gemm(&g, st))) return rc;
+  if (a.dwo && (rc = run_wgrad(wgrad_desc(w.dx2, a.attn_o, a.dwo, n, D, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  return XP_OK;
+}
+
+// the layer's deferred reductions in one batched launch pair, then the weight-gradient stream joins the caller's
+int finish_bwd(const Defer& df, void* red_ws, size_t red_bytes, const WgradOrder& wg, void* st) {
+  if (df.n) {
+    XP_REQUIRE(xp_reduce_rows_batch_workspace_bytes(df.segs, df.n) <= red_bytes, "%s: reduce scratch too small", wg.name);
+    int rc = xp_reduce_rows_batch(df.segs, df.n, red_ws, red_bytes, st);
+    if (rc) return rc;
+  }
+  return wg.join();
+}
+
 int check_dims(const char* name, const XpLayerDims& d) {
   XP_REQUIRE(d.rows > 0 && d.D > 0 && d.Dff > 0 && d.B > 0 && d.S > 0 && d.heads > 0, "%s: empty dimension", name);
   XP_REQUIRE(d.rows == d.B * d.S && d.D == d.heads * 64, "%s: rows != B*S or D != heads*64", name);
@@ -133,7 +272,7 @@ extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
   XP_REQUIRE(a->x && a->Wqkv && a->Wo && a->W1 && a->W2 && a->ln1_w && a->ln1_b && a->bqkv && a->bo && a->ln2_w && a->ln2_b &&
              a->b1 && a->b2 && a->h1 && a->qkv && a->attn_o && a->x2 && a->h2 && a->act && a->x3 && a->mean1 &&
              a->rstd1 && a->mean2 && a->rstd2 && a->stats, "xp_encoder_layer_fwd: null pointer");
-  const int64_t rows = d.rows, D = d.D, Dff = d.Dff;
+  const int64_t rows = d.rows, D = d.D;
   const int dt = d.dtype;
   // fp32 side rows of the residual stream (the M proxy tokens of every sample): x rows in side_in, x2 rows in the workspace,
   // x3 rows in side_out
@@ -155,62 +294,38 @@ extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
   if ((rc = xp_gemm(&g, st))) return rc;
   if ((rc = xp_attn_fwd(a->qkv, 3 * D, a->attn_o, D, a->stats, a->pad_mask, d.attn_mode, d.B, d.heads, d.S, d.M, d.N, d.L, dt,
                         a->workspace, a->workspace_bytes, st))) return rc;
-  // x2 = x + attn_o Wo^T + bo
-  g = gemm_desc(a->attn_o, a->Wo, a->x2, rows, D, D, dt);
-  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a->bo; g.resid = a->x;
-  if (sided) { g.resid_side = a->side_in; g.out_side = side_x2; g.side_S = sS; g.side_M = sM; }
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if ((rc = xp_layernorm_fwd_side(a->x2, D, a->ln2_w, a->ln2_b, a->h2, D, a->mean2, a->rstd2, rows, D, d.ln_eps, dt,
-                                  side_x2, nullptr, sS, sM, sM, st))) return rc;
-  // pre = h2 W1^T + b1 ; act = quick_gelu(pre)
-  g = gemm_desc(a->h2, a->W1, a->act, rows, Dff, D, dt);
-  g.epilogue = XP_EPI_BIAS_GELU; g.bias = a->b1; g.aux = a->pre;
-  if (xp_debug_flag("fc1_no_pre")) g.aux = nullptr;      // measurement only (tools/fc1_one_output.py): the backward then reads garbage
-  if ((rc = xp_gemm(&g, st))) return rc;
-  // x3 = x2 + act W2^T + b2
-  g = gemm_desc(a->act, a->W2, a->x3, rows, D, Dff, dt);
-  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a->b2; g.resid = a->x2;
-  if (sided) { g.resid_side = side_x2; g.out_side = a->side_out; g.side_S = sS; g.side_M = sM; }
-  return xp_gemm(&g, st);
+  return out_proj_mlp_fwd(*a, rows, D, a->side_in, side_x2, a->side_out, sS, sM, st);
 }
 
-// workspace layout of the backward: [dpre | dh2 | dx2 | dattn | dqkv | dh1] activations-gradient temporaries, split-K slabs,
-// six deferred partial-row slots, the batched-reduce scratch, the attention workspace
+// workspace of the backward: the shared stages' part (TailBwdPlan), [dqkv | dh1], split-K slabs, the q/k/v bias-gradient and first
+// LayerNorm's partial rows, the attention workspace
 namespace {
 struct BwdPlan {
-  size_t esz, dpre, dh, dqkv, slabs, cs_pre, cs_dx3, ln2, cs_qkv, ln1, red, attn, total;
-  int64_t cs_pre_rows, cs_dx3_rows, cs_qkv_rows, ln_rows;
+  TailBwdPlan t;
+  size_t dqkv, slabs, cs_qkv, ln1, attn, total;
+  int64_t cs_qkv_rows;
   bool cs_qkv_fused;
 };
 BwdPlan plan_bwd(const XpLayerDims& d) {
   BwdPlan p;
   memset(&p, 0, sizeof(p));
   const int64_t rows = d.rows, D = d.D, Dff = d.Dff;
-  p.esz = d.dtype == XP_BF16 ? 2 : 4;
-  p.dpre = align256(rows * Dff * p.esz); p.dh = align256(rows * D * p.esz); p.dqkv = align256(rows * 3 * D * p.esz);
-  size_t s = wgrad_slab_bytes(rows, D, Dff, d.dtype);
-  size_t t = wgrad_slab_bytes(rows, Dff, D, d.dtype); if (t > s) s = t;
-  t = wgrad_slab_bytes(rows, D, D, d.dtype); if (t > s) s = t;
-  t = wgrad_slab_bytes(rows, 3 * D, D, d.dtype); if (t > s) s = t;
-  p.slabs = align256(s);
   // fc1's bias gradient: fused into the dX GEMM epilogue where the library offers it, else a column-sum pass over dpre
   XpGemmDesc g = gemm_desc(nullptr, nullptr, nullptr, rows, Dff, D, d.dtype);
   g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.ldr = Dff;
   g.resid = &g;                          // (only tested for non-NULL by the planning queries)
-  p.cs_pre_rows = xp_gemm_colsum_rows(&g);
-  const int64_t pre_rows = p.cs_pre_rows > 0 ? p.cs_pre_rows : xp_colsum_partial_rows(rows, Dff);
-  p.cs_pre = align256(pre_rows * Dff * sizeof(float));
-  p.cs_dx3_rows = 0; p.cs_dx3 = 0;           // fc2's bias gradient = column sums of dx3: taken by the second LayerNorm's backward
+  p.t = plan_tail_bwd(rows, D, Dff, d.dtype, xp_gemm_colsum_rows(&g));
+  // (fc2's bias gradient = column sums of dx3: taken by the second LayerNorm's backward)
+  p.dqkv = align256(rows * 3 * D * p.t.esz);
+  p.slabs = align256(max_slab_bytes(p.t.slabs, {wgrad_desc(nullptr, nullptr, nullptr, rows, 3 * D, D, d.dtype)}));
   // the q/k/v bias gradients: out of the attention backward kernels where they offer it, else a column-sum pass over dqkv
   p.cs_qkv_rows = xp_attn_bwd_colsum_rows(d.attn_mode, d.B, d.heads, d.S, d.M, d.N, d.L, d.dtype);
   p.cs_qkv_fused = p.cs_qkv_rows > 0;
   if (!p.cs_qkv_fused) p.cs_qkv_rows = xp_colsum_partial_rows(rows, 3 * D);
   p.cs_qkv = align256(p.cs_qkv_rows * 3 * D * sizeof(float));
-  p.ln_rows = xp_layernorm_bwd_partial_rows(rows);
-  p.ln2 = p.ln1 = align256(xp_layernorm_bwd_workspace_bytes(rows, D));
-  p.red = align256((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16);
+  p.ln1 = p.t.ln2;                       // (both LayerNorms run over the same [rows, D])
   p.attn = align256(xp_attn_workspace_bytes(d.attn_mode, d.B, d.heads, d.M, d.N, d.L));
-  p.total = p.dpre + 4 * p.dh + p.dqkv + p.slabs + p.cs_pre + p.cs_dx3 + p.ln2 + p.cs_qkv + p.ln1 + p.red + p.attn + 256;
+  p.total = p.t.bytes + p.dqkv + p.t.dh + p.slabs + p.cs_qkv + p.ln1 + p.attn + 256;
   return p;
 }
 }  // namespace
@@ -235,88 +350,36 @@ extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
   XP_REQUIRE(a->workspace && a->workspace_bytes >= p.total, "xp_encoder_layer_bwd: workspace too small (%zu < %zu)",
              a->workspace_bytes, p.total);
   Carver ws{(char*)a->workspace, 0, a->workspace_bytes};
-  void* dpre = ws.take(p.dpre); void* dh2 = ws.take(p.dh); void* dx2 = ws.take(p.dh); void* dattn = ws.take(p.dh);
-  void* dqkv = ws.take(p.dqkv); void* dh1 = ws.take(p.dh);
+  const TailBwdWs w = carve_tail_bwd(ws, p.t);
+  void* dqkv = ws.take(p.dqkv); void* dh1 = ws.take(p.t.dh);
   float* slabs = (float*)ws.take(p.slabs);
-  float* cs_pre = (float*)ws.take(p.cs_pre); float* cs_dx3 = (float*)ws.take(p.cs_dx3);
-  float* ln2_part = (float*)ws.take(p.ln2); float* cs_qkv = (float*)ws.take(p.cs_qkv); float* ln1_part = (float*)ws.take(p.ln1);
-  void* red_ws = ws.take(p.red); void* attn_ws = ws.take(p.attn);
-  const int64_t rows = d.rows, D = d.D, Dff = d.Dff;
+  float* cs_qkv = (float*)ws.take(p.cs_qkv); float* ln1_part = (float*)ws.take(p.ln1);
+  void* attn_ws = ws.take(p.attn);
+  const int64_t rows = d.rows, D = d.D;
   const int dt = d.dtype;
   Defer df;
   // dW GEMMs beside the dX chain (video tower only: the text tower is 256 rows on a side stream of its own already)
-  WgradSide* wsd = (d.attn_mode == XP_ATTN_PROXY && rows >= 4096) ? wgrad_side() : nullptr;
-  hipStream_t mst = (hipStream_t)st;
-  void* wst = wsd ? (void*)wsd->side : st;
-  auto mark = [&](int i) -> int {           // side stream: everything the main stream has enqueued so far must finish first
-    if (!wsd) return XP_OK;
-    if (hipEventRecord(wsd->ev[i], mst) != hipSuccess || hipStreamWaitEvent(wsd->side, wsd->ev[i], 0) != hipSuccess) {
-      xp_set_error("xp_encoder_layer_bwd: event hand-off to the weight-gradient stream failed");
-      return XP_ERR_LAUNCH;
-    }
-    return XP_OK;
-  };
-  if ((rc = mark(0))) return rc;
-
-  // ---- MLP: x3 = x2 + fc2(quick_gelu(fc1(LN2(x2))))
-  XpGemmDesc g = gemm_desc(a->dx3, a->W2, dpre, rows, Dff, D, dt);            // dpre = (dx3 . W2) * quick_gelu'(pre)
-  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.resid = a->pre; g.ldr = Dff;
-  if (a->db1 && p.cs_pre_rows > 0) g.colsum_partials = cs_pre;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->db1) {
-    if (p.cs_pre_rows > 0) df.add(cs_pre, a->db1, Dff, (int)p.cs_pre_rows, (int)Dff);
-    else {
-      const int64_t r = xp_colsum_partial_rows(rows, Dff);
-      if ((rc = xp_colsum_partials(dpre, rows, Dff, Dff, dt, cs_pre, p.cs_pre, st))) return rc;
-      df.add(cs_pre, a->db1, Dff, (int)r, (int)Dff);
-    }
-  }
-  if (a->dw2 && (rc = wgrad(a->dx3, a->act, a->dw2, rows, D, Dff, dt, slabs, p.slabs, wst, true))) return rc;
-  if ((rc = mark(1))) return rc;                                              // dpre is ready for dW1
-  g = gemm_desc(dpre, a->W1, dh2, rows, D, Dff, dt);                          // dh2 = dpre . W1
-  g.b_kstrided = 1; g.ldb = D;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dw1 && (rc = wgrad(dpre, a->h2, a->dw1, rows, Dff, D, dt, slabs, p.slabs, wst, true))) return rc;
-  // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)] -- out_proj's and fc2's bias gradients
-  if ((rc = xp_layernorm_bwd_partials_side(dh2, D, a->x2, D, a->ln2_w, a->mean2, a->rstd2, a->dx3, D, dx2, D, 2, rows, D, dt,
-                                           a->side_x2, a->side_S, a->side_M, a->side_M, ln2_part, p.ln2, st))) return rc;
-  df.add(ln2_part, a->dln2_w, 4 * D, (int)p.ln_rows, (int)D);
-  df.add(ln2_part + D, a->dln2_b, 4 * D, (int)p.ln_rows, (int)D);
-  df.add(ln2_part + 2 * D, a->dbo, 4 * D, (int)p.ln_rows, (int)D);
-  df.add(ln2_part + 3 * D, a->db2, 4 * D, (int)p.ln_rows, (int)D);
-  if ((rc = mark(2))) return rc;                                              // dx2 is ready for dWo
-  // ---- attention: x2 = x + out_proj(attn(qkv(LN1(x))))
-  g = gemm_desc(dx2, a->Wo, dattn, rows, D, D, dt);                           // dattn = dx2 . Wo
-  g.b_kstrided = 1; g.ldb = D;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dwo && (rc = wgrad(dx2, a->attn_o, a->dwo, rows, D, D, dt, slabs, p.slabs, wst, true))) return rc;
-  if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, dattn, D, a->stats, a->pad_mask, dqkv, d.q_scale, d.attn_mode, d.B, d.heads,
+  const WgradOrder wg{(d.attn_mode == XP_ATTN_PROXY && rows >= 4096) ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_bwd"};
+  if ((rc = wg.mark(0))) return rc;
+  // ---- MLP: x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))), then dattn = dx2 . Wo of x2 = x + out_proj(attn(qkv(LN1(x))))
+  if ((rc = mlp_out_proj_bwd(*a, rows, p.t, w, slabs, p.slabs, a->side_S, a->side_M, df, wg, st))) return rc;
+  // ---- attention
+  if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, w.dattn, D, a->stats, a->pad_mask, dqkv, d.q_scale, d.attn_mode, d.B, d.heads,
                          d.S, d.M, d.N, d.L, dt, attn_ws, p.attn, (a->dbqkv && p.cs_qkv_fused) ? cs_qkv : nullptr, st))) return rc;
-  if ((rc = mark(3))) return rc;                                              // dqkv is ready for dWqkv
-  g = gemm_desc(dqkv, a->Wqkv, dh1, rows, D, 3 * D, dt);                      // dh1 = dqkv . Wqkv
+  if ((rc = wg.mark(3))) return rc;                                           // dqkv is ready for dWqkv
+  XpGemmDesc g = gemm_desc(dqkv, a->Wqkv, dh1, rows, D, 3 * D, dt);           // dh1 = dqkv . Wqkv
   g.b_kstrided = 1; g.ldb = D;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dwqkv && (rc = wgrad(dqkv, a->h1, a->dwqkv, rows, 3 * D, D, dt, slabs, p.slabs, wst, false))) return rc;
+  if (a->dwqkv && (rc = run_wgrad(wgrad_desc(dqkv, a->h1, a->dwqkv, rows, 3 * D, D, dt), slabs, p.slabs, wg.stream(), false))) return rc;
   if (a->dbqkv) {
     if (!p.cs_qkv_fused && (rc = xp_colsum_partials(dqkv, rows, 3 * D, 3 * D, dt, cs_qkv, p.cs_qkv, st))) return rc;
     df.add(cs_qkv, a->dbqkv, 3 * D, (int)p.cs_qkv_rows, (int)(3 * D));
   }
-  if ((rc = xp_layernorm_bwd_partials_side(dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, dx2, D, a->dx, D, 0, rows, D, dt,
+  if ((rc = xp_layernorm_bwd_partials_side(dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, w.dx2, D, a->dx, D, 0, rows, D, dt,
                                            a->side_in, a->side_S, a->side_M, a->side_M, ln1_part, p.ln1, st))) return rc;
-  df.add(ln1_part, a->dln1_w, 2 * D, (int)p.ln_rows, (int)D);
-  df.add(ln1_part + D, a->dln1_b, 2 * D, (int)p.ln_rows, (int)D);
-  if (df.n) {
-    XP_REQUIRE(xp_reduce_rows_batch_workspace_bytes(df.segs, df.n) <= p.red, "xp_encoder_layer_bwd: reduce scratch too small");
-    if ((rc = xp_reduce_rows_batch(df.segs, df.n, red_ws, p.red, st))) return rc;
-  }
-  if (wsd && !xp_debug_flag("no_wgrad_join")) {      // join: the weight gradients (and every workspace the side stream read) belong to the main stream again
-    // (XPRETRAIN_DEBUG=no_wgrad_join: measurement only -- races on the shared workspace -- what a lazy join could be worth at most)
-    if (hipEventRecord(wsd->done, wsd->side) != hipSuccess || hipStreamWaitEvent(mst, wsd->done, 0) != hipSuccess) {
-      xp_set_error("xp_encoder_layer_bwd: joining the weight-gradient stream failed");
-      return XP_ERR_LAUNCH;
-    }
-  }
-  return XP_OK;
+  df.add(ln1_part, a->dln1_w, 2 * D, (int)p.t.ln_rows, (int)D);
+  df.add(ln1_part + D, a->dln1_b, 2 * D, (int)p.t.ln_rows, (int)D);
+  return finish_bwd(df, w.red, p.t.red, wg, st);
 }
 
 // ================================================================================== pooled last layer (video tower)
@@ -335,36 +398,28 @@ int check_pooled_dims(const char* name, const XpLayerDims& d) {
 }
 
 struct PooledBwdPlan {
-  size_t esz, dpre, dhp, dqkv, dh1, slabs, cs_pre, ln2, cs_q, cs_kv, ln1, ln1p, red, attn, total;
-  int64_t cs_pre_rows, cs_q_rows, ln_rows, lnp_rows;
+  TailBwdPlan t;             // the shared stages over the B pooled rows
+  size_t dqkv, dh1, slabs, cs_q, cs_kv, ln1, ln1p, attn, total;
+  int64_t cs_q_rows, ln_rows;
 };
 PooledBwdPlan plan_pooled_bwd(const XpLayerDims& d) {
   PooledBwdPlan p;
   memset(&p, 0, sizeof(p));
-  const int64_t rows = d.rows, D = d.D, Dff = d.Dff, B = d.B, S = d.S;
+  const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
   const int dt = d.dtype;
-  p.esz = dt == XP_BF16 ? 2 : 4;
-  p.dpre = align256(B * Dff * p.esz); p.dhp = align256(B * D * p.esz);
-  p.dqkv = align256(rows * 3 * D * p.esz); p.dh1 = align256(rows * D * p.esz);
-  size_t s = wgrad_desc_slab_bytes(wgrad_desc(nullptr, D, nullptr, Dff, nullptr, B, D, Dff, dt));
-  size_t t = wgrad_desc_slab_bytes(wgrad_desc(nullptr, Dff, nullptr, D, nullptr, B, Dff, D, dt)); if (t > s) s = t;
-  t = wgrad_desc_slab_bytes(wgrad_desc(nullptr, D, nullptr, D, nullptr, B, D, D, dt)); if (t > s) s = t;
-  XpGemmDesc g = wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, B, D, D, dt);
-  g.a_grp = 1; g.a_grp_stride = S;
-  t = wgrad_desc_slab_bytes(g); if (t > s) s = t;
-  t = wgrad_desc_slab_bytes(wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, rows, 2 * D, D, dt)); if (t > s) s = t;
-  p.slabs = align256(s);
-  p.cs_pre_rows = xp_colsum_partial_rows(B, Dff);
-  p.cs_pre = align256(p.cs_pre_rows * Dff * sizeof(float));
+  p.t = plan_tail_bwd(B, D, d.Dff, dt, 0);      // fc1's bias gradient: always a column-sum pass over dpre
+  p.dqkv = align256(rows * 3 * D * p.t.esz); p.dh1 = align256(rows * D * p.t.esz);
+  XpGemmDesc gq = wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, B, D, D, dt);       // dWq: dq of the pooled rows of dqkv
+  gq.a_grp = 1; gq.a_grp_stride = S;
+  p.slabs = align256(max_slab_bytes(p.t.slabs, {gq, wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, rows, 2 * D, D, dt)}));
   p.cs_q_rows = xp_colsum_partial_rows(B, D);
   p.cs_q = align256(p.cs_q_rows * D * sizeof(float));
   p.cs_kv = align256(xp_attn_pooled_colsum_rows_max(B, S) * 2 * D * sizeof(float));
-  p.ln_rows = xp_layernorm_bwd_partial_rows(rows); p.lnp_rows = xp_layernorm_bwd_partial_rows(B);
+  p.ln_rows = xp_layernorm_bwd_partial_rows(rows);
   p.ln1 = align256(xp_layernorm_bwd_workspace_bytes(rows, D));
-  p.ln2 = p.ln1p = align256(xp_layernorm_bwd_workspace_bytes(B, D));
-  p.red = align256((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16);
+  p.ln1p = p.t.ln2;                             // (LayerNorm 1 once more over the [B, D] pooled rows)
   p.attn = align256(xp_attn_pooled_workspace_bytes(B, d.heads, S, dt));
-  p.total = p.dpre + 3 * p.dhp + p.dqkv + p.dh1 + p.slabs + p.cs_pre + p.ln2 + p.cs_q + p.cs_kv + p.ln1 + p.ln1p + p.red + p.attn + 256;
+  p.total = p.t.bytes + p.dqkv + p.dh1 + p.slabs + p.cs_q + p.cs_kv + p.ln1 + p.ln1p + p.attn + 256;
   return p;
 }
 
@@ -384,7 +439,7 @@ extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) 
   XP_REQUIRE(a->x && a->Wqkv && a->Wo && a->W1 && a->W2 && a->ln1_w && a->ln1_b && a->bqkv && a->bo && a->ln2_w && a->ln2_b &&
              a->b1 && a->b2 && a->h1 && a->kv && a->mean1 && a->rstd1 && a->h1p && a->q && a->attn_o && a->x2 && a->h2 && a->act &&
              a->x3 && a->mean1p && a->rstd1p && a->mean2 && a->rstd2 && a->stats, "xp_encoder_layer_pooled_fwd: null pointer");
-  const int64_t rows = d.rows, D = d.D, Dff = d.Dff, B = d.B, S = d.S;
+  const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
   const int dt = d.dtype;
   const bool sided = a->side_in != nullptr;
   XP_REQUIRE(!sided || (a->side_out && dt == XP_BF16), "xp_encoder_layer_pooled_fwd: side rows need side_in and side_out, and bf16");
@@ -409,20 +464,8 @@ extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) 
   g.epilogue = XP_EPI_BIAS_QSCALE; g.bias = a->bqkv; g.scale = d.q_scale; g.scale_cols = D;
   if ((rc = xp_gemm(&g, st))) return rc;
   if ((rc = xp_attn_pooled_fwd(a->q, a->kv, 2 * D, a->attn_o, a->stats, B, d.heads, S, dt, a->workspace, attn_ws, st))) return rc;
-  // x2 = x[pooled] + attn_o Wo^T + bo
-  g = gemm_desc(a->attn_o, a->Wo, a->x2, B, D, D, dt);
-  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a->bo; g.resid = a->x; g.ldr = S * D;
-  if (sided) { g.resid_side = side0; g.out_side = side_x2; g.side_S = 1; g.side_M = 1; }
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if ((rc = xp_layernorm_fwd_side(a->x2, D, a->ln2_w, a->ln2_b, a->h2, D, a->mean2, a->rstd2, B, D, d.ln_eps, dt,
-                                  side_x2, nullptr, s1, s1, s1, st))) return rc;
-  g = gemm_desc(a->h2, a->W1, a->act, B, Dff, D, dt);
-  g.epilogue = XP_EPI_BIAS_GELU; g.bias = a->b1; g.aux = a->pre;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  g = gemm_desc(a->act, a->W2, a->x3, B, D, Dff, dt);
-  g.epilogue = XP_EPI_BIAS_RESID; g.bias = a->b2; g.resid = a->x2;
-  if (sided) { g.resid_side = side_x2; g.out_side = a->side_out; g.side_S = 1; g.side_M = 1; }
-  return xp_gemm(&g, st);
+  // x2 = x[pooled] + attn_o Wo^T + bo, then the MLP
+  return out_proj_mlp_fwd(*a, B, S * D, side0, side_x2, a->side_out, s1, s1, st);
 }
 
 extern "C" size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* d) {
@@ -444,65 +487,29 @@ extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) 
   XP_REQUIRE(a->workspace && a->workspace_bytes >= p.total, "xp_encoder_layer_pooled_bwd: workspace too small (%zu < %zu)",
              a->workspace_bytes, p.total);
   Carver ws{(char*)a->workspace, 0, a->workspace_bytes};
-  void* dpre = ws.take(p.dpre); void* dh2 = ws.take(p.dhp); void* dx2 = ws.take(p.dhp); void* dattn = ws.take(p.dhp);
+  const TailBwdWs w = carve_tail_bwd(ws, p.t);
   char* dqkv = (char*)ws.take(p.dqkv); void* dh1 = ws.take(p.dh1);
   float* slabs = (float*)ws.take(p.slabs);
-  float* cs_pre = (float*)ws.take(p.cs_pre); float* ln2_part = (float*)ws.take(p.ln2); float* cs_q = (float*)ws.take(p.cs_q);
-  float* cs_kv = (float*)ws.take(p.cs_kv); float* ln1_part = (float*)ws.take(p.ln1); float* ln1p_part = (float*)ws.take(p.ln1p);
-  void* red_ws = ws.take(p.red); void* attn_ws = ws.take(p.attn);
-  const int64_t rows = d.rows, D = d.D, Dff = d.Dff, B = d.B, S = d.S;
+  float* cs_q = (float*)ws.take(p.cs_q); float* cs_kv = (float*)ws.take(p.cs_kv);
+  float* ln1_part = (float*)ws.take(p.ln1); float* ln1p_part = (float*)ws.take(p.ln1p);
+  void* attn_ws = ws.take(p.attn);
+  const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
   const int dt = d.dtype;
   const bool sided = a->side_in != nullptr;
   const int64_t sS = sided ? S : 0;
   const int32_t sM = sided ? (int32_t)d.M : 0, s1 = sided ? 1 : 0;
-  void* dkv = dqkv + (size_t)D * p.esz;      // dqkv[rows, 3D]: the k / v columns of every row, the q columns of the pooled rows only
+  void* dkv = dqkv + (size_t)D * p.t.esz;    // dqkv[rows, 3D]: the k / v columns of every row, the q columns of the pooled rows only
   Defer df;
-  WgradSide* wsd = rows >= 4096 ? wgrad_side() : nullptr;
-  hipStream_t mst = (hipStream_t)st;
-  void* wst = wsd ? (void*)wsd->side : st;
-  auto mark = [&](int i) -> int {           // side stream: everything the main stream has enqueued so far must finish first
-    if (!wsd) return XP_OK;
-    if (hipEventRecord(wsd->ev[i], mst) != hipSuccess || hipStreamWaitEvent(wsd->side, wsd->ev[i], 0) != hipSuccess) {
-      xp_set_error("xp_encoder_layer_pooled_bwd: event hand-off to the weight-gradient stream failed");
-      return XP_ERR_LAUNCH;
-    }
-    return XP_OK;
-  };
-  if ((rc = mark(0))) return rc;
-
-  // ---- MLP on the pooled rows
-  XpGemmDesc g = gemm_desc(a->dx3, a->W2, dpre, B, Dff, D, dt);               // dpre = (dx3 . W2) * quick_gelu'(pre)
-  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.resid = a->pre; g.ldr = Dff;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->db1) {
-    if ((rc = xp_colsum_partials(dpre, B, Dff, Dff, dt, cs_pre, p.cs_pre, st))) return rc;
-    df.add(cs_pre, a->db1, Dff, (int)p.cs_pre_rows, (int)Dff);
-  }
-  if (a->dw2 && (rc = run_wgrad(wgrad_desc(a->dx3, D, a->act, Dff, a->dw2, B, D, Dff, dt), slabs, p.slabs, wst, true))) return rc;
-  if ((rc = mark(1))) return rc;
-  g = gemm_desc(dpre, a->W1, dh2, B, D, Dff, dt);                             // dh2 = dpre . W1
-  g.b_kstrided = 1; g.ldb = D;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dw1 && (rc = run_wgrad(wgrad_desc(dpre, Dff, a->h2, D, a->dw1, B, Dff, D, dt), slabs, p.slabs, wst, true))) return rc;
-  // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)]
-  if ((rc = xp_layernorm_bwd_partials_side(dh2, D, a->x2, D, a->ln2_w, a->mean2, a->rstd2, a->dx3, D, dx2, D, 2, B, D, dt,
-                                           a->side_x2, s1, s1, s1, ln2_part, p.ln2, st))) return rc;
-  df.add(ln2_part, a->dln2_w, 4 * D, (int)p.lnp_rows, (int)D);
-  df.add(ln2_part + D, a->dln2_b, 4 * D, (int)p.lnp_rows, (int)D);
-  df.add(ln2_part + 2 * D, a->dbo, 4 * D, (int)p.lnp_rows, (int)D);
-  df.add(ln2_part + 3 * D, a->db2, 4 * D, (int)p.lnp_rows, (int)D);
-  if ((rc = mark(2))) return rc;
-  // ---- attention
-  g = gemm_desc(dx2, a->Wo, dattn, B, D, D, dt);                              // dattn = dx2 . Wo
-  g.b_kstrided = 1; g.ldb = D;
-  if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dwo && (rc = run_wgrad(wgrad_desc(dx2, D, a->attn_o, D, a->dwo, B, D, D, dt), slabs, p.slabs, wst, true))) return rc;
-  // dq lands in the q columns of the pooled rows of dqkv, dk / dv in the k / v columns of every row
-  if ((rc = xp_attn_pooled_bwd(a->q, a->kv, 2 * D, a->attn_o, dattn, a->stats, dqkv, S * 3 * D, dkv, 3 * D, d.q_scale, B, d.heads,
+  const WgradOrder wg{rows >= 4096 ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_pooled_bwd"};
+  if ((rc = wg.mark(0))) return rc;
+  // ---- MLP and dattn = dx2 . Wo on the pooled rows
+  if ((rc = mlp_out_proj_bwd(*a, B, p.t, w, slabs, p.slabs, s1, s1, df, wg, st))) return rc;
+  // ---- attention: dq lands in the q columns of the pooled rows of dqkv, dk / dv in the k / v columns of every row
+  if ((rc = xp_attn_pooled_bwd(a->q, a->kv, 2 * D, a->attn_o, w.dattn, a->stats, dqkv, S * 3 * D, dkv, 3 * D, d.q_scale, B, d.heads,
                                S, dt, attn_ws, p.attn, a->dbqkv ? cs_kv : nullptr, st))) return rc;
-  if ((rc = mark(3))) return rc;
+  if ((rc = wg.mark(3))) return rc;
   // dh1 = dkv . Wkv on every row, then the pooled rows again with their q columns: dqkv[b*S] . Wqkv
-  g = gemm_desc(dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * p.esz, dh1, rows, D, 2 * D, dt);
+  XpGemmDesc g = gemm_desc(dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * p.t.esz, dh1, rows, D, 2 * D, dt);
   g.lda = 3 * D; g.b_kstrided = 1; g.ldb = D;
   if ((rc = xp_gemm(&g, st))) return rc;
   g = gemm_desc(dqkv, a->Wqkv, dh1, B, D, 3 * D, dt);
@@ -511,8 +518,8 @@ extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) 
   if (a->dwqkv) {
     g = wgrad_desc(dqkv, 3 * D, a->h1p, D, a->dwqkv, B, D, D, dt);            // dWq = dq^T . h1p
     g.a_grp = 1; g.a_grp_stride = S;
-    if ((rc = run_wgrad(g, slabs, p.slabs, wst, true))) return rc;
-    if ((rc = run_wgrad(wgrad_desc(dkv, 3 * D, a->h1, D, a->dwqkv + D * D, rows, 2 * D, D, dt), slabs, p.slabs, wst, false))) return rc;
+    if ((rc = run_wgrad(g, slabs, p.slabs, wg.stream(), true))) return rc;
+    if ((rc = run_wgrad(wgrad_desc(dkv, 3 * D, a->h1, D, a->dwqkv + D * D, rows, 2 * D, D, dt), slabs, p.slabs, wg.stream(), false))) return rc;
   }
   if (a->dbqkv) {
     const int64_t kv_rows = xp_attn_pooled_colsum_rows(B, d.heads, S, dt);
@@ -527,17 +534,7 @@ extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) 
                                            a->side_in, sS, sM, sM, ln1_part, p.ln1, st))) return rc;
   df.add(ln1_part, a->dln1_w, 2 * D, (int)p.ln_rows, (int)D);
   df.add(ln1_part + D, a->dln1_b, 2 * D, (int)p.ln_rows, (int)D);
-  if ((rc = xp_layernorm_bwd_partials_side(dh1, S * D, a->x, S * D, a->ln1_w, a->mean1p, a->rstd1p, dx2, D, a->dx, S * D, 0, B, D, dt,
+  if ((rc = xp_layernorm_bwd_partials_side(dh1, S * D, a->x, S * D, a->ln1_w, a->mean1p, a->rstd1p, w.dx2, D, a->dx, S * D, 0, B, D, dt,
                                            a->side_in, s1, s1, sM, ln1p_part, p.ln1p, st))) return rc;
-  if (df.n) {
-    XP_REQUIRE(xp_reduce_rows_batch_workspace_bytes(df.segs, df.n) <= p.red, "xp_encoder_layer_pooled_bwd: reduce scratch too small");
-    if ((rc = xp_reduce_rows_batch(df.segs, df.n, red_ws, p.red, st))) return rc;
-  }
-  if (wsd) {      // join: the weight gradients (and every workspace the side stream read) belong to the main stream again
-    if (hipEventRecord(wsd->done, wsd->side) != hipSuccess || hipStreamWaitEvent(mst, wsd->done, 0) != hipSuccess) {
-      xp_set_error("xp_encoder_layer_pooled_bwd: joining the weight-gradient stream failed");
-      return XP_ERR_LAUNCH;
-    }
-  }
-  return XP_OK;
+  return finish_bwd(df, w.red, p.t.red, wg, st);
 }

@@ -145,26 +145,32 @@ WEIGHTS = WeightCache()
 _SPLITS = {}
 
 
-def _split_for(n_out: int, n_in: int, rows: int, dtype: torch.dtype, a_remap, slack: bool = False) -> int:
+def _split_for(n_out: int, n_in: int, rows: int, dtype: torch.dtype, a_remap, slack: bool = False, lddy: Optional[int] = None,
+               ldx: Optional[int] = None) -> int:
     """split-K factor for the weight-gradient GEMMs (kernel-family aware, decided by the library; memoised).  ``slack``: a launch
-    nothing waits for soon (the first three dW GEMMs of a layer's backward, as csrc/layer.hip issues them): fewer, longer slabs."""
-    key = (n_out, n_in, rows, dtype, a_remap, slack)          # (the CU budget is part of the plan: set_cu_budget clears the memo)
+    nothing waits for soon (the first three dW GEMMs of a layer's backward, as csrc/layer.hip issues them): fewer, longer slabs.
+    ``lddy`` / ``ldx``: row pitches of the two operands (default: dense, n_out / n_in)."""
+    lddy, ldx = lddy or n_out, ldx or n_in
+    key = (n_out, n_in, rows, dtype, a_remap, slack, lddy, ldx)   # (the CU budget is part of the plan: set_cu_budget clears the memo)
     s = _SPLITS.get(key)
     if s is None:
-        s = _SPLITS[key] = H.gemm_auto_split(n_out, n_in, rows, dtype, lda=n_out, ldb=n_in, a_remap=a_remap, slack=slack)
+        s = _SPLITS[key] = H.gemm_auto_split(n_out, n_in, rows, dtype, lda=lddy, ldb=ldx, a_remap=a_remap, slack=slack)
     return s
 
 
-def _wgrad(dy: torch.Tensor, x: torch.Tensor, rows: int, n_out: int, n_in: int, a_remap=(0, 0, 0), slack: bool = False) -> torch.Tensor:
-    """dW[n_out, n_in] = dY[rows, n_out]^T . X[rows, n_in] in fp32 (both operands read k-strided, split-K)."""
-    split = _split_for(n_out, n_in, rows, dy.dtype, tuple(a_remap), slack)
-    dw = torch.empty((n_out, n_in), dtype=torch.float32, device=dy.device)
-    if split == 1:
-        H.gemm(dy, x, n_out, n_in, rows, a_kstrided=True, b_kstrided=True, lda=n_out, ldb=n_in, out=dw,
+def _wgrad(dy: torch.Tensor, x: torch.Tensor, rows: int, n_out: int, n_in: int, a_remap=(0, 0, 0), slack: bool = False, *,
+           lddy: Optional[int] = None, ldx: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dW[n_out, n_in] = dY[rows, n_out]^T . X[rows, n_in] in fp32 (both operands read k-strided with row pitches ``lddy`` /
+    ``ldx``, split-K), into ``out`` when given."""
+    lddy, ldx = lddy or n_out, ldx or n_in
+    split = _split_for(n_out, n_in, rows, dy.dtype, tuple(a_remap), slack, lddy, ldx)
+    dw = torch.empty((n_out, n_in), dtype=torch.float32, device=dy.device) if out is None else out
+    if split <= 1:
+        H.gemm(dy, x, n_out, n_in, rows, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=dw,
                out_dtype=torch.float32, a_remap=a_remap)
     else:
         ws = H.workspace(split * n_out * n_in * 4, dy.device, "splitk")
-        H.gemm(dy, x, n_out, n_in, rows, a_kstrided=True, b_kstrided=True, lda=n_out, ldb=n_in, out=ws,
+        H.gemm(dy, x, n_out, n_in, rows, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=ws,
                split_k=split, a_remap=a_remap)
         H.splitk_reduce(ws, dw, splits=split)
     return dw
@@ -190,8 +196,13 @@ def set_cu_budget(cus: int) -> None:
     _PLANS.clear()
 
 
-def _a256(n: int) -> int:
-    return (n + 255) & ~255
+def _arena_layout(*pieces):
+    """``({name: offset}, total bytes)`` of (name, bytes) pieces laid out one after the other, each 256-byte aligned"""
+    off, o = {}, 0
+    for name, n in pieces:
+        off[name] = o
+        o += (n + 255) & ~255
+    return off, o
 
 
 class _LayerPlan:
@@ -206,14 +217,11 @@ class _LayerPlan:
         d.dtype, d.q_scale, d.ln_eps = _DT_CODE[dtype], (D // heads) ** -0.5, 1e-5
         self.dims = d
         es = _ES[dtype]
-        # arena: bf16/fp32 activations then fp32 statistics, 256-byte aligned pieces
-        self.off, o = {}, 0
-        for name, n in (("h1", rows * D * es), ("qkv", rows * 3 * D * es), ("attn_o", rows * D * es), ("x2", rows * D * es),
-                        ("h2", rows * D * es), ("pre", rows * Dff * es), ("act", rows * Dff * es), ("mean1", rows * 4),
-                        ("rstd1", rows * 4), ("mean2", rows * 4), ("rstd2", rows * 4), ("stats", B * heads * S * 2 * 4)):
-            self.off[name] = o
-            o += _a256(n)
-        self.arena_bytes = o
+        # arena: bf16/fp32 activations then fp32 statistics
+        self.off, self.arena_bytes = _arena_layout(
+            ("h1", rows * D * es), ("qkv", rows * 3 * D * es), ("attn_o", rows * D * es), ("x2", rows * D * es),
+            ("h2", rows * D * es), ("pre", rows * Dff * es), ("act", rows * Dff * es), ("mean1", rows * 4),
+            ("rstd1", rows * 4), ("mean2", rows * 4), ("rstd2", rows * 4), ("stats", B * heads * S * 2 * 4))
         lib = L.lib()
         self.fwd_ws = int(lib.xp_encoder_layer_fwd_workspace_bytes(C.byref(d)))
         self.bwd_ws = int(lib.xp_encoder_layer_bwd_workspace_bytes(C.byref(d)))
@@ -431,17 +439,49 @@ def layer_grad_groups(model):
     return groups
 
 
-def _layer_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, plan, side=None, side_x2=None):
-    dev = x.device
-    need = ctx.needs_input_grad
-    dx = torch.empty_like(x)
+def _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2):
+    """(data-parallel runs only) remember the layer's parameters, in the flat gradient order, for the backward's sink lookup"""
+    if GRAD_SINKS:
+        ctx.sink_params = (ln1_w, ln1_b, wq, wk, wv, bq, bk, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
+        ctx.sink_key = grad_sink_key(ctx.sink_params)
+    else:
+        ctx.sink_params, ctx.sink_key = (), None
+
+
+def _run_native_bwd(ctx, a, entry, plan, dx, ws_tag):
+    """The parameter-gradient plumbing of a native layer backward and the call itself.  ``a``: the argument struct of ``entry``
+    (xp_encoder_layer_bwd / xp_encoder_layer_pooled_bwd) with everything but dx, the parameter gradients and the workspace filled
+    in.  The gradients go to the layer's sink or a private flat buffer (plan.gnames order); a frozen parameter's pointer stays
+    NULL.  Returns the 17 leading outputs of the Function's backward: dx and the gradients in forward's argument order."""
+    dev, need = dx.device, ctx.needs_input_grad
     flat = None
     if GRAD_SINKS and ctx.sink_key is not None and all(need[1:17]):
         flat = _claim_sink(ctx.sink_key, GRAD_SINKS.get(ctx.sink_key), plan.gtotal, dev, ctx.sink_params)
     if flat is None:
         flat = torch.empty(plan.gtotal, dtype=torch.float32, device=dev)
-    parts = flat.split_with_sizes(plan.gsizes)
-    ws = H.workspace(plan.bwd_ws, dev, "layer_bwd")
+    # forward argument positions: 1,2 ln1 | 3..8 wq,bq,wk,bk,wv,bv | 9,10 wo,bo | 11,12 ln2 | 13,14 w1,b1 | 15,16 w2,b2
+    want = dict(dln1_w=need[1], dln1_b=need[2], dwqkv=need[3] or need[5] or need[7], dbqkv=need[4] or need[6] or need[8],
+                dwo=need[9], dbo=need[10], dln2_w=need[11], dln2_b=need[12], dw1=need[13], db1=need[14], dw2=need[15], db2=need[16])
+    g = {}
+    for name, t in zip(plan.gnames, flat.split_with_sizes(plan.gsizes)):
+        if want[name]:
+            g[name] = t
+            setattr(a, name, t.data_ptr())
+    ws = H.workspace(plan.bwd_ws, dev, ws_tag)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.dx = dx.data_ptr()
+    L.check(getattr(L.lib(), entry)(C.byref(a), H._stream()), entry)
+    D, Dff = plan.dims.D, plan.dims.Dff
+    gw = lambda n, shape: g[n].view(shape) if n in g else None
+    dwqkv, dbqkv = gw("dwqkv", (3 * D, D)), g.get("dbqkv")
+    pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
+    return (dx, g.get("dln1_w"), g.get("dln1_b"),
+            pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]), pick(dbqkv, 1, need[6]),
+            pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"), g.get("dln2_b"),
+            gw("dw1", (Dff, D)), g.get("db1"), gw("dw2", (D, Dff)), g.get("db2"))
+
+
+def _layer_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, plan, side=None, side_x2=None):
     a = L.XpLayerBwd()
     a.dims = plan.dims
     base, off = arena.data_ptr(), plan.off
@@ -452,31 +492,58 @@ def _layer_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_ma
     a.mean1, a.rstd1, a.mean2, a.rstd2 = base + off["mean1"], base + off["rstd1"], base + off["mean2"], base + off["rstd2"]
     a.stats = base + off["stats"]
     a.pad_mask = 0 if pad_mask is None else pad_mask.data_ptr()
-    a.dx3, a.dx = dx3.data_ptr(), dx.data_ptr()
-    # forward argument positions: 1,2 ln1 | 3..8 wq,bq,wk,bk,wv,bv | 9,10 wo,bo | 11,12 ln2 | 13,14 w1,b1 | 15,16 w2,b2
-    want = dict(dln1_w=need[1], dln1_b=need[2], dwqkv=need[3] or need[5] or need[7], dbqkv=need[4] or need[6] or need[8],
-                dwo=need[9], dbo=need[10], dln2_w=need[11], dln2_b=need[12], dw1=need[13], db1=need[14], dw2=need[15], db2=need[16])
-    g = {}
-    for name, t in zip(plan.gnames, parts):
-        if want[name]:
-            g[name] = t
-            setattr(a, name, t.data_ptr())
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    a.dx3 = dx3.data_ptr()
     if side is not None and side_x2 is not None:          # the forward's fp32 side rows of x and x2: read by the LayerNorm backward passes
         a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
         a.side_S, a.side_M = (plan.dims.S, plan.dims.M) if plan.dims.attn_mode == L.ATTN_PROXY else (1, 1)
-    L.check(L.lib().xp_encoder_layer_bwd(C.byref(a), H._stream()), "xp_encoder_layer_bwd")
-    D, Dff = plan.dims.D, plan.dims.Dff
-    gw = lambda n, shape: g[n].view(shape) if n in g else None
-    dwqkv, dbqkv = gw("dwqkv", (3 * D, D)), g.get("dbqkv")
-    pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
-    return (dx, g.get("dln1_w"), g.get("dln1_b"),
-            pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]), pick(dbqkv, 1, need[6]),
-            pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"), g.get("dln2_b"),
-            gw("dw1", (Dff, D)), g.get("db1"), gw("dw2", (D, Dff)), g.get("db2"), None, None, None, None, None, None, None, None)
+    return _run_native_bwd(ctx, a, "xp_encoder_layer_bwd", plan, torch.empty_like(x), "layer_bwd") + (None,) * 8
 
 
-# ------------------------------------------------------------------------------------------ encoder layer
+# ------------------------------------------------------------------------------------------ encoder layer, op by op
+# The same entry points in the same order with the same arguments as csrc/layer.hip issues them (XPRETRAIN_DEBUG=op_by_op, or
+# arguments the native calls do not take).  The stages the dense and the pooled layer share are written once, as in layer.hip
+# (out_proj_mlp_fwd, mlp_out_proj_bwd): out_proj onward over ``n`` rows -- all rows, or the B pooled ones.  Every operator is
+# looked up on ``H`` at call time (tools/determinism_hunt.py wraps those attributes).
+def _mlp_fwd_ops(x, ldr, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, n, training, side_x, side_x2, side_out, sd, out=None):
+    """x2 = x + attn_o Wo^T + bo (x read with row pitch ``ldr``), x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))), into ``out`` when given.
+    ``sd = (S, M)``: geometry of the fp32 side rows of the n rows (``side_x`` of x, ``side_x2`` / ``side_out`` written), or None."""
+    D, Dff = Wo.shape[0], W1.shape[0]
+    lns = None if sd is None else (sd[0], sd[1], sd[1])
+    x2 = H.gemm(attn_o, Wo, n, D, D, epilogue=L.EPI_BIAS_RESID, bias=bo.detach(), resid=x, ldr=ldr,
+                resid_side=side_x, out_side=side_x2, side=sd)
+    h2, mean2, rstd2 = H.layernorm_fwd(x2, ln2_w, ln2_b, n, D, x_side=side_x2, side=lns)
+    pre = torch.empty((n, Dff), dtype=x.dtype, device=x.device) if training else None
+    act = H.gemm(h2, W1, n, Dff, D, epilogue=L.EPI_BIAS_GELU, bias=b1.detach(), aux=pre)
+    x3 = H.gemm(act, W2, n, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2, out=out,
+                resid_side=side_x2, out_side=side_out, side=sd)
+    return x2, mean2, rstd2, h2, pre, act, x3
+
+
+def _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, n, need, defer, db1_fused, side_x2, lns):
+    """The backward of ``_mlp_fwd_ops`` down to ``dattn = dx2 . Wo``: returns ``(dx2, dattn, dwo, dbo, dln2_w, dln2_b, dw1, db1,
+    dw2, db2)``; the bias / LayerNorm gradients are final after ``defer.flush()``, frozen weights' gradients are None (``need``:
+    the Function's needs_input_grad).  ``db1_fused``: fc1's bias gradient out of the dpre GEMM's epilogue where the library offers
+    it (the dense layer), else always a column-sum pass over dpre (the pooled layer)."""
+    D, Dff = Wo.shape[0], W1.shape[0]
+    if need[14] and db1_fused:
+        dpre, db1 = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre, colsum_defer=defer,
+                           colsum_name="db1")
+    else:
+        dpre = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre)
+        db1 = H.colsum_deferred(dpre, n, Dff, defer, name="db1") if need[14] else None
+    dw2 = _wgrad(dx3, act, n, D, Dff, slack=True) if need[15] else None
+    dh2 = H.gemm(dpre, W1, n, D, Dff, b_kstrided=True)
+    dw1 = _wgrad(dpre, h2, n, Dff, D, slack=True) if need[13] else None
+    # out_proj's bias gradient = column sums of dx2, fc2's = column sums of dx3: both accumulated by the LayerNorm backward
+    # that reads dx3 and writes dx2
+    dx2, dln2_w, dln2_b, dbo, db2 = H.layernorm_bwd(dh2, x2, ln2_w, mean2, rstd2, n, D, dres=dx3, defer=defer,
+                                                    dx_colsum=True, dres_colsum=True, name="ln2", x_side=side_x2, side=lns)
+    dattn = H.gemm(dx2, Wo, n, D, D, b_kstrided=True)
+    dwo = _wgrad(dx2, attn_o, n, D, D, slack=True) if need[9] else None
+    keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter / bias sums ride on passes that run anyway)
+    return dx2, dattn, dwo, keep(10, dbo), keep(11, dln2_w), keep(12, dln2_b), dw1, db1, dw2, keep(16, db2)
+
+
 class EncoderLayerFn(torch.autograd.Function):
     """CLIPEncoderLayer.forward (modeling/CLIP_ViP.py:444-460) with CLIPAttention.forward2 (:332-381, video
     tower, ``size=(M,N,L)``) or CLIPAttention.forward (:266-330, text tower, causal + padding) and CLIPMLP
@@ -514,41 +581,26 @@ class EncoderLayerFn(torch.autograd.Function):
                 split.hold(x, arena, x3, side, side_out, side_x2)
             ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
             ctx.plan = plan
-            if GRAD_SINKS:          # (data-parallel runs only) the layer's parameters in the flat gradient order
-                ctx.sink_params = (ln1_w, ln1_b, wq, wk, wv, bq, bk, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
-                ctx.sink_key = grad_sink_key(ctx.sink_params)
-            else:
-                ctx.sink_params, ctx.sink_key = (), None
-            if side is not None:
-                ctx.mark_non_differentiable(side_out)
-                ctx.set_materialize_grads(False)       # no zero-filled "gradient" of the side rows in the backward
-                return x3, side_out
-            return x3
-        ctx.plan = None
-        sd = None if side is None else ((S, size[0]) if size is not None else (1, 1))
-        side_x2 = None if side is None else torch.empty_like(side)
-        side_out = None if side is None else torch.empty_like(side)
-
-        lns = None if side is None else ((S, size[0], size[0]) if size is not None else (1, 1, 1))
-        h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
-        qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
-        attn_o, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask)
-        x2 = H.gemm(attn_o, Wo, rows, D, D, epilogue=L.EPI_BIAS_RESID, bias=bo.detach(), resid=x,
-                    resid_side=side, out_side=side_x2, side=sd)
-        h2, mean2, rstd2 = H.layernorm_fwd(x2, ln2_w, ln2_b, rows, D, x_side=side_x2, side=lns)
-        pre = torch.empty((rows, Dff), dtype=dt, device=x.device) if training else None
-        act = H.gemm(h2, W1, rows, Dff, D, epilogue=L.EPI_BIAS_GELU, bias=b1.detach(), aux=pre)
-        x3 = H.gemm(act, W2, rows, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2,
-                    resid_side=side_x2, out_side=side_out, side=sd)
-
-        if training:
-            ctx.save_for_backward(x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
-                                  Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
-        ctx.meta = (B, S, heads, size, q_scale, D, Dff)
-        ctx.lns = lns
+            _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
+        else:
+            ctx.plan = None
+            sd = None if side is None else ((S, size[0]) if size is not None else (1, 1))
+            side_x2 = None if side is None else torch.empty_like(side)
+            side_out = None if side is None else torch.empty_like(side)
+            lns = None if side is None else (sd[0], sd[1], sd[1])
+            h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
+            qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
+            attn_o, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask)
+            x2, mean2, rstd2, h2, pre, act, x3 = _mlp_fwd_ops(x, None, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, rows, training,
+                                                              side, side_x2, side_out, sd)
+            if training:
+                ctx.save_for_backward(x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
+                                      Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
+            ctx.meta = (B, S, heads, size, q_scale, D, Dff)
+            ctx.lns = lns
         if side is not None:
             ctx.mark_non_differentiable(side_out)
-            ctx.set_materialize_grads(False)
+            ctx.set_materialize_grads(False)       # no zero-filled "gradient" of the side rows in the backward
             return x3, side_out
         return x3
 
@@ -568,26 +620,13 @@ class EncoderLayerFn(torch.autograd.Function):
         rows = x.shape[0]
         dx3 = dx3.contiguous()
         defer = H.DeferredReduce(x.device)       # the 4 bias + 4 LayerNorm-parameter reductions finish in 2 launches
-        # ---- MLP: x3 = x2 + fc2(quick_gelu(fc1(LN2(x2))))
-        # fc1's bias gradient = column sums of dpre: taken from the epilogue of the GEMM that produces dpre
         # parameter gradients are skipped for frozen parameters (freeze_text_encoder, VidCLIP.py:96-103): positions in
         # forward's argument list -- 1,2 ln1 | 3..8 q,k,v | 9,10 out_proj | 11,12 ln2 | 13,14 fc1 | 15,16 fc2
         need = ctx.needs_input_grad
-        if need[14]:
-            dpre, db1 = H.gemm(dx3, W2, rows, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre, colsum_defer=defer,
-                                  colsum_name="db1")
-        else:
-            dpre, db1 = H.gemm(dx3, W2, rows, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre), None
-        dw2 = _wgrad(dx3, act, rows, D, Dff, slack=True) if need[15] else None
-        dh2 = H.gemm(dpre, W1, rows, D, Dff, b_kstrided=True)
-        dw1 = _wgrad(dpre, h2, rows, Dff, D, slack=True) if need[13] else None
-        # out_proj's bias gradient = column sums of dx2, fc2's = column sums of dx3: both accumulated by the LayerNorm backward
-        # that reads dx3 and writes dx2
-        dx2, dln2_w, dln2_b, dbo, db2 = H.layernorm_bwd(dh2, x2, ln2_w, mean2, rstd2, rows, D, dres=dx3, defer=defer,
-                                                        dx_colsum=True, dres_colsum=True, name="ln2", x_side=side_x2, side=ctx.lns)
+        # ---- MLP: x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))), then dattn = dx2 . Wo
+        dx2, dattn, *tail = _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, rows, need, defer, True,
+                                         side_x2, ctx.lns)
         # ---- attention: x2 = x + out_proj(attn(qkv(LN1(x))))
-        dattn = H.gemm(dx2, Wo, rows, D, D, b_kstrided=True)
-        dwo = _wgrad(dx2, attn_o, rows, D, D, slack=True) if need[9] else None
         want_bqkv = need[4] or need[6] or need[8]
         if want_bqkv:       # the q/k/v bias gradients (column sums of dqkv) come out of the attention backward kernels
             dqkv, dbqkv = H.attn_bwd(qkv, attn_o, dattn, stats, B, S, heads, size=size, pad_mask=pad_mask, q_scale=q_scale,
@@ -607,9 +646,8 @@ class EncoderLayerFn(torch.autograd.Function):
         dx, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dres=dx2, defer=defer, name="ln1", x_side=side,
                                              side=ctx.lns)
         defer.flush()
-        keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter / out_proj bias sums ride on passes that run anyway)
-        return (dx, keep(1, dln1_w), keep(2, dln1_b), dwq, dbq, dwk, dbk, dwv, dbv, dwo, keep(10, dbo), keep(11, dln2_w),
-                keep(12, dln2_b), dw1, db1, dw2, keep(16, db2), None, None, None, None, None, None, None, None)
+        keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter sums ride on a pass that runs anyway)
+        return (dx, keep(1, dln1_w), keep(2, dln1_b), dwq, dbq, dwk, dbk, dwv, dbv, *tail) + (None,) * 8
 
 
 # ------------------------------------------------------------------------------------------ pooled last layer (video tower)
@@ -621,14 +659,11 @@ class _PooledLayerPlan:
         base = _layer_plan(rows, D, Dff, B, S, heads, size, dtype)
         self.dims, self.gsizes, self.gnames, self.gtotal = base.dims, base.gsizes, base.gnames, base.gtotal
         es = _ES[dtype]
-        self.off, o = {}, 0
-        for name, n in (("h1", rows * D * es), ("kv", rows * 2 * D * es), ("mean1", rows * 4), ("rstd1", rows * 4),
-                        ("h1p", B * D * es), ("q", B * D * es), ("attn_o", B * D * es), ("x2", B * D * es), ("h2", B * D * es),
-                        ("pre", B * Dff * es), ("act", B * Dff * es), ("mean1p", B * 4), ("rstd1p", B * 4), ("mean2", B * 4),
-                        ("rstd2", B * 4), ("stats", B * heads * 2 * 4)):
-            self.off[name] = o
-            o += _a256(n)
-        self.arena_bytes = o
+        self.off, self.arena_bytes = _arena_layout(
+            ("h1", rows * D * es), ("kv", rows * 2 * D * es), ("mean1", rows * 4), ("rstd1", rows * 4),
+            ("h1p", B * D * es), ("q", B * D * es), ("attn_o", B * D * es), ("x2", B * D * es), ("h2", B * D * es),
+            ("pre", B * Dff * es), ("act", B * Dff * es), ("mean1p", B * 4), ("rstd1p", B * 4), ("mean2", B * 4),
+            ("rstd2", B * 4), ("stats", B * heads * 2 * 4))
         lib = L.lib()
         self.fwd_ws = int(lib.xp_encoder_layer_pooled_fwd_workspace_bytes(C.byref(self.dims)))
         self.bwd_ws = int(lib.xp_encoder_layer_pooled_bwd_workspace_bytes(C.byref(self.dims)))
@@ -644,6 +679,41 @@ def _pooled_plan(rows, D, Dff, B, S, heads, size, dtype) -> _PooledLayerPlan:
 
 _POOLED_SAVED = ("h1", "kv", "h1p", "q", "attn_o", "x2", "h2", "pre", "act", "mean1", "rstd1", "mean1p", "rstd1p", "mean2", "rstd2",
                  "stats")
+
+
+def _pooled_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan, x3, keep_pre, side, side_out, side_x2):
+    arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=x.device)
+    ws = H.workspace(plan.fwd_ws, x.device, "layer_pooled_fwd")
+    a = L.XpLayerPooledFwd()
+    a.dims = plan.dims
+    a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
+    a.ln1_w, a.ln1_b, a.bqkv, a.bo = ln1_w.data_ptr(), ln1_b.data_ptr(), bqkv.data_ptr(), bo.data_ptr()
+    a.ln2_w, a.ln2_b, a.b1, a.b2 = ln2_w.data_ptr(), ln2_b.data_ptr(), b1.data_ptr(), b2.data_ptr()
+    base = arena.data_ptr()
+    for name in _POOLED_SAVED:
+        setattr(a, name, base + plan.off[name])
+    if not keep_pre:            # forward-only pass: the MLP pre-activation is not written
+        a.pre = 0
+    a.x3 = x3.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    if side is not None:
+        a.side_in, a.side_out, a.side_x2 = side.data_ptr(), side_out.data_ptr(), side_x2.data_ptr()
+    L.check(L.lib().xp_encoder_layer_pooled_fwd(C.byref(a), H._stream()), "xp_encoder_layer_pooled_fwd")
+    return arena
+
+
+def _pooled_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, plan, side=None, side_x2=None):
+    a = L.XpLayerPooledBwd()
+    a.dims = plan.dims
+    base = arena.data_ptr()
+    for name in _POOLED_SAVED:
+        setattr(a, name, base + plan.off[name])
+    a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
+    a.ln1_w, a.ln2_w = ln1_w.data_ptr(), ln2_w.data_ptr()
+    a.dx3 = dx3.data_ptr()
+    if side is not None:
+        a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
+    return _run_native_bwd(ctx, a, "xp_encoder_layer_pooled_bwd", plan, torch.empty_like(x), "layer_pooled_bwd") + (None,) * 6
 
 
 class PooledEncoderLayerFn(torch.autograd.Function):
@@ -681,48 +751,22 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             side_x2 = torch.empty((B, D), dtype=torch.float32, device=dev)
         if LAYER_CALLS and _native_ok(x, (ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2), (Wqkv, Wo, W1, W2), None):
             plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt)
-            arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
-            ws = H.workspace(plan.fwd_ws, dev, "layer_pooled_fwd")
-            a = L.XpLayerPooledFwd()
-            a.dims = plan.dims
-            a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
-            a.ln1_w, a.ln1_b, a.bqkv, a.bo = ln1_w.data_ptr(), ln1_b.data_ptr(), bqkv.data_ptr(), bo.data_ptr()
-            a.ln2_w, a.ln2_b, a.b1, a.b2 = ln2_w.data_ptr(), ln2_b.data_ptr(), b1.data_ptr(), b2.data_ptr()
-            base = arena.data_ptr()
-            for name in _POOLED_SAVED:
-                setattr(a, name, base + plan.off[name])
-            if not training:        # forward-only pass: the MLP pre-activation is not written
-                a.pre = 0
-            a.x3 = x3.data_ptr()
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            if side is not None:
-                a.side_in, a.side_out, a.side_x2 = side.data_ptr(), side_out.data_ptr(), side_x2.data_ptr()
-            L.check(L.lib().xp_encoder_layer_pooled_fwd(C.byref(a), H._stream()), "xp_encoder_layer_pooled_fwd")
+            arena = _pooled_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan, x3, training, side,
+                                       side_out, side_x2)
             ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2)
             ctx.plan = plan
-            if GRAD_SINKS:
-                ctx.sink_params = (ln1_w, ln1_b, wq, wk, wv, bq, bk, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
-                ctx.sink_key = grad_sink_key(ctx.sink_params)
-            else:
-                ctx.sink_params, ctx.sink_key = (), None
+            _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
         else:
-            # op by op: the same entry points in the same order with the same arguments as csrc/layer.hip issues them
             ctx.plan = None
-            lns, p1 = (None, None) if side is None else ((S, M, M), (1, 1, 1))
+            lns, p1, sd = (None, None, None) if side is None else ((S, M, M), (1, 1, 1), (1, 1))
             h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
             side0 = None if side is None else H.gather_rows(side, None, B, M, D)
             h1p, mean1p, rstd1p = H.layernorm_fwd(x, ln1_w, ln1_b, B, D, ldx=S * D, x_side=side0, side=p1)
             kv = H.gemm(h1, Wqkv[D:], rows, 2 * D, D, epilogue=L.EPI_BIAS, bias=bqkv[D:])
             q = H.gemm(h1p, Wqkv, B, D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
             attn_o, stats = H.attn_pooled_fwd(q, kv, B, S, heads)
-            sd = None if side is None else (1, 1)
-            x2 = H.gemm(attn_o, Wo, B, D, D, epilogue=L.EPI_BIAS_RESID, bias=bo.detach(), resid=x, ldr=S * D,
-                        resid_side=side0, out_side=side_x2, side=sd)
-            h2, mean2, rstd2 = H.layernorm_fwd(x2, ln2_w, ln2_b, B, D, x_side=side_x2, side=p1)
-            pre = torch.empty((B, Dff), dtype=dt, device=dev) if training else None
-            act = H.gemm(h2, W1, B, Dff, D, epilogue=L.EPI_BIAS_GELU, bias=b1.detach(), aux=pre)
-            H.gemm(act, W2, B, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2, out=x3,
-                   resid_side=side_x2, out_side=side_out, side=sd)
+            x2, mean2, rstd2, h2, pre, act, _ = _mlp_fwd_ops(x, S * D, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, B, training,
+                                                             side0, side_x2, side_out, sd, out=x3)
             if training:
                 ctx.save_for_backward(x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2,
                                       h2, pre, act, Wqkv, Wo, W1, W2, side, side_x2)
@@ -745,75 +789,20 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             raise TypeError(f"PooledEncoderLayerFn.backward: incoming gradient is {dx3.dtype} {tuple(dx3.shape)} on {dx3.device}, "
                             f"expected {x.dtype} {(B, D)} on {x.device}")
         dx3 = dx3.contiguous()
-        rows, dev = x.shape[0], x.device
-        dx = torch.empty_like(x)
-        pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
         if ctx.plan is not None:
             x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2 = saved
-            plan = ctx.plan
-            flat = None
-            if GRAD_SINKS and ctx.sink_key is not None and all(need[1:17]):
-                flat = _claim_sink(ctx.sink_key, GRAD_SINKS.get(ctx.sink_key), plan.gtotal, dev, ctx.sink_params)
-            if flat is None:
-                flat = torch.empty(plan.gtotal, dtype=torch.float32, device=dev)
-            parts = flat.split_with_sizes(plan.gsizes)
-            ws = H.workspace(plan.bwd_ws, dev, "layer_pooled_bwd")
-            a = L.XpLayerPooledBwd()
-            a.dims = plan.dims
-            base = arena.data_ptr()
-            for name in _POOLED_SAVED:
-                setattr(a, name, base + plan.off[name])
-            a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
-            a.ln1_w, a.ln2_w = ln1_w.data_ptr(), ln2_w.data_ptr()
-            a.dx3, a.dx = dx3.data_ptr(), dx.data_ptr()
-            want = dict(dln1_w=need[1], dln1_b=need[2], dwqkv=need[3] or need[5] or need[7], dbqkv=need[4] or need[6] or need[8],
-                        dwo=need[9], dbo=need[10], dln2_w=need[11], dln2_b=need[12], dw1=need[13], db1=need[14], dw2=need[15],
-                        db2=need[16])
-            g = {}
-            for name, t in zip(plan.gnames, parts):
-                if want[name]:
-                    g[name] = t
-                    setattr(a, name, t.data_ptr())
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            if side is not None:
-                a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
-            L.check(L.lib().xp_encoder_layer_pooled_bwd(C.byref(a), H._stream()), "xp_encoder_layer_pooled_bwd")
-            gw = lambda n, shape: g[n].view(shape) if n in g else None
-            dwqkv, dbqkv = gw("dwqkv", (3 * D, D)), g.get("dbqkv")
-            return (dx, g.get("dln1_w"), g.get("dln1_b"),
-                    pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]), pick(dbqkv, 1, need[6]),
-                    pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"),
-                    g.get("dln2_b"), gw("dw1", (Dff, D)), g.get("db1"), gw("dw2", (D, Dff)), g.get("db2"),
-                    None, None, None, None, None, None)
+            return _pooled_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, ctx.plan, side, side_x2)
         (x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
          Wqkv, Wo, W1, W2, side, side_x2) = saved
-        dt = x.dtype
-        lns, p1, pM = (None, None, None) if side is None else ((S, M, M), (1, 1, 1), (1, 1, M))
-
-        def wgrad(dy, lddy, xx, ldx, K, n_out, n_in, out, a_remap=(0, 0, 0), slack=True):
-            split = H.gemm_auto_split(n_out, n_in, K, dt, lda=lddy, ldb=ldx, a_remap=a_remap, slack=slack)
-            if split <= 1:
-                H.gemm(dy, xx, n_out, n_in, K, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=out,
-                       out_dtype=torch.float32, a_remap=a_remap)
-            else:
-                ws = H.workspace(split * n_out * n_in * 4, dev, "splitk")
-                H.gemm(dy, xx, n_out, n_in, K, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=ws, split_k=split,
-                       a_remap=a_remap)
-                H.splitk_reduce(ws, out, splits=split)
-            return out
-
+        rows, dev, dt = x.shape[0], x.device, x.dtype
+        dx = torch.empty_like(x)
+        lns, p1 = (None, None) if side is None else ((S, M, M), (1, 1, 1))
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
         defer = H.DeferredReduce(dev)
-        dpre = H.gemm(dx3, W2, B, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre)
-        db1 = H.colsum_deferred(dpre, B, Dff, defer, name="db1") if need[14] else None
-        dw2 = wgrad(dx3, D, act, Dff, B, D, Dff, f32(D, Dff)) if need[15] else None
-        dh2 = H.gemm(dpre, W1, B, D, Dff, b_kstrided=True)
-        dw1 = wgrad(dpre, Dff, h2, D, B, Dff, D, f32(Dff, D)) if need[13] else None
-        dx2, dln2_w, dln2_b, dbo, db2 = H.layernorm_bwd(dh2, x2, ln2_w, mean2, rstd2, B, D, dres=dx3, defer=defer, dx_colsum=True,
-                                                        dres_colsum=True, name="ln2", x_side=side_x2, side=p1)
-        dattn = H.gemm(dx2, Wo, B, D, D, b_kstrided=True)
-        dwo = wgrad(dx2, D, attn_o, D, B, D, D, f32(D, D)) if need[9] else None
-        # dqkv [rows, 3D]: dk / dv in the k / v columns of every row, dq in the q columns of the pooled rows only
+        # ---- MLP and dattn = dx2 . Wo on the pooled rows
+        dx2, dattn, *tail = _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, B, need, defer, False,
+                                         side_x2, p1)
+        # ---- attention.  dqkv [rows, 3D]: dk / dv in the k / v columns of every row, dq in the q columns of the pooled rows only
         dqkv = torch.empty((rows, 3 * D), dtype=dt, device=dev)
         dq_view, dkv = dqkv.view(B, S * 3 * D)[:, :D], dqkv[:, D:]
         want_b = need[4] or need[6] or need[8]
@@ -828,8 +817,8 @@ class PooledEncoderLayerFn(torch.autograd.Function):
         dwqkv = None
         if need[3] or need[5] or need[7]:
             dwqkv = f32(3 * D, D)
-            wgrad(dqkv, 3 * D, h1p, D, B, D, D, dwqkv[:D], a_remap=(1, S, 0))
-            wgrad(dkv, 3 * D, h1, D, rows, 2 * D, D, dwqkv[D:], slack=False)
+            _wgrad(dqkv, h1p, B, D, D, a_remap=(1, S, 0), slack=True, lddy=3 * D, out=dwqkv[:D])
+            _wgrad(dkv, h1, rows, 2 * D, D, lddy=3 * D, out=dwqkv[D:])
         if want_b:
             nq = L.lib().xp_colsum_partial_rows(B, D)
             part = defer.slot(nq * D * 4, "dbq")
@@ -845,9 +834,9 @@ class PooledEncoderLayerFn(torch.autograd.Function):
                                                        H._stream()), "xp_layernorm_bwd_partials_side")
         defer.flush()
         keep = lambda i, t: t if need[i] else None
+        pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
         return (dx, keep(1, dln1_w), keep(2, dln1_b), pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]),
-                pick(dbqkv, 1, need[6]), pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), dwo, keep(10, dbo), keep(11, dln2_w),
-                keep(12, dln2_b), dw1, db1, dw2, keep(16, db2), None, None, None, None, None, None)
+                pick(dbqkv, 1, need[6]), pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), *tail) + (None,) * 6
 
 
 def pooled_encoder_layer(x, layer, B, S, heads, size, side=None):
