@@ -219,11 +219,19 @@ int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, float* s
  * un-scaled projection output).  PROXY problems that fit one LDS group (M + L <= 208, M <= 16, no padding mask: 224^2 frames at patch
  * 16, any frame count) run as ONE persistent launch for dQ, dK and dV (attn_bwd5_kernel, round 6); its workgroups take problems from
  * a 4-byte device counter at the end of `workspace`, which this call resets with hipMemsetAsync on `stream` (the one operation of the
- * library besides kernel launches, event records and waits).  Everything else runs the dQ kernel, then the dK/dV kernel. */
+ * library besides kernel launches, event records and waits).  Everything else runs the dQ kernel, then the dK/dV kernel -- unless
+ * the wide one-launch backward is switched on (below). */
 int xp_attn_bwd(const void* qkv, int64_t ldqkv, const void* out, const void* dout, int64_t ldo,
                 const float* stats, const int64_t* pad_mask, void* dqkv, float q_scale,
                 int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
                 void* workspace, size_t workspace_bytes, void* stream);
+/* Opt-in, off by default, process-global planning state like the CU budget: PROXY problems with 208 < M + L <= 1152 (M <= 16, no
+ * padding mask, bf16: 448^2 frames at patch 16 have M + L = 788) run their backward as ONE persistent launch too (attn_bwd6_kernel:
+ * one workgroup does a whole problem, walking 192-row groups of the other dimension; same workspace, counter and column-sum rows as
+ * above) instead of the kernel pair.  The initial value is $XPRETRAIN_ATTN_BWD_WIDE (unset, empty or 0: off); the setter wins over
+ * the environment.  With the switch off every plan, launch and output bit is what it was without this kernel. */
+int xp_set_attn_bwd_wide(int32_t on);
+int32_t xp_get_attn_bwd_wide(void);
 /* The same with the bias gradients of q_proj / k_proj / v_proj on the way (autograd computes them as dqkv.sum(0),
  * CLIP_ViP.py:341-343): every backward workgroup also leaves the column sums of the dqkv rows it stores (as stored, i.e. rounded)
  * as one partial row: dqkv_colsum_partials[r * 3*H*64 + c], r < xp_attn_bwd_colsum_rows(...) -- finish with xp_reduce_rows_batch.
@@ -516,11 +524,13 @@ enum { XP_ATTN_KERNEL_FWD = 0,        /* attn_fwd_kernel: one 7-wave workgroup p
        XP_ATTN_KERNEL_BWD_PAIR = 3,   /* attn_bwd_dq_kernel, then attn_bwd_dkv_kernel */
        XP_ATTN_KERNEL_BWD5 = 4,       /* attn_bwd5_kernel: dQ, dK, dV in one persistent launch */
        XP_ATTN_KERNEL_F32 = 5 };      /* the fp32 compute mode's kernels (attention_f32.hip, which sizes their grids) */
+/* kernels only an opt-in switch plans (same number space as above; no default plan names them) */
+enum { XP_ATTN_OPTIN_BWD6 = 6 };      /* attn_bwd6_kernel: attn_bwd5's one launch for wider windows; xp_set_attn_bwd_wide */
 typedef struct XpAttnPlanInfo {
-  int32_t kernel;                       /* XP_ATTN_KERNEL_*                                                       */
+  int32_t kernel;                       /* XP_ATTN_KERNEL_* / XP_ATTN_OPTIN_*                                     */
   int32_t grid, lds_bytes;              /* main launch (each kernel of the pair): workgroups, dynamic LDS; f32: 0  */
   int32_t reduce_grid;                  /* proxy merge (forward) / proxy reduce (backward) workgroups; 0: none     */
-  int32_t uses_counter;                 /* the fused backward's problem counter is reset and used                 */
+  int32_t uses_counter;                 /* a fused backward's problem counter is reset and used                   */
   int32_t reserved;
   int64_t part[2], delta[2], dq[2], dkv[2], counter[2];  /* workspace regions (byte offset, bytes); 0 bytes: not used   */
   int64_t workspace_bytes;              /* this direction's regions (xp_attn_workspace_bytes: the larger direction) */

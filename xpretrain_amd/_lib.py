@@ -64,6 +64,8 @@ class XpAttnPlanInfo(C.Structure):
 
 # XP_ATTN_KERNEL_* by value, lower case
 ATTN_KERNELS = ("fwd", "fwd3", "fwd4", "bwd_pair", "bwd5", "f32")
+# XP_ATTN_OPTIN_* by value: kernels only an opt-in switch plans (xp_set_attn_bwd_wide)
+ATTN_OPTIN_KERNELS = {6: "bwd6"}
 
 
 class XpReduceSeg(C.Structure):
@@ -165,6 +167,8 @@ SIGNATURES = {
     "xp_attn_bwd": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, f32, i32, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp]),
     "xp_attn_bwd2": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, f32, i32, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp, vp]),
     "xp_attn_bwd_colsum_rows": (i64, [i32, i64, i64, i64, i64, i64, i64, i32]),
+    "xp_set_attn_bwd_wide": (i32, [i32]),
+    "xp_get_attn_bwd_wide": (i32, []),
     "xp_attn_pooled_workspace_bytes": (sz, [i64, i64, i64, i32]),
     "xp_attn_pooled_fwd": (i32, [vp, vp, i64, vp, vp, i64, i64, i64, i32, vp, sz, vp]),
     "xp_attn_pooled_colsum_rows": (i64, [i64, i64, i64, i32]),

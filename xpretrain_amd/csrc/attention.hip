@@ -24,6 +24,7 @@
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 namespace {
@@ -1180,9 +1181,10 @@ __device__ __forceinline__ void b5_stage_qdo(char* Y, const AP& p, const Prob& p
   }
 }
 
-// the wave's own query rows (tiles wave, wave + 8; rows >= R: zeros) straight from global memory: Q, dO, O fragments and (m, log l)
+// the wave's own query rows (tiles tile0 + wave, tile0 + wave + 8; rows >= R: zeros) straight from global memory: Q, dO, O fragments
+// and (m, log l)
 struct B5Own { bf16x8 q[2][2], d[2][2], o[2][2]; float m[2], lg[2]; };
-__device__ __forceinline__ void b5_load_own(B5Own& w, const AP& p, const Prob& pr, int wave, int lane) {
+__device__ __forceinline__ void b5_load_own(B5Own& w, const AP& p, const Prob& pr, int wave, int lane, int tile0 = 0) {
   const int i16 = lane & 15, g = lane >> 4;
   const bf16_t* qbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
   const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
@@ -1195,7 +1197,7 @@ __device__ __forceinline__ void b5_load_own(B5Own& w, const AP& p, const Prob& p
       p.stats + ((int64_t)pr.b * p.H + pr.h) * p.S * 2, 0, (unsigned)(p.S * 8), 0x00020000);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int rq_ = (wave + B5W * i) * 16 + i16;
+    const int rq_ = (tile0 + wave + B5W * i) * 16 + i16;
     const bool ok = rq_ < p.R;
     const unsigned tok = (unsigned)tok_of(p, pr.n, ok ? rq_ : 0);
     const unsigned oq = ok ? tok * (unsigned)(p.ldqkv * 2) + g * 16 : 0xFFFFFF00u;
@@ -1222,12 +1224,12 @@ __device__ __forceinline__ void b5_tfrag(B5TFrag& t, const char* tile, int lane)
 // query column i16 of each tile; rows 4g + r are keys).  tail: the step reaches past key R (those P are forced to zero: their K rows
 // are zero-filled, but P * 0 must not see an overflowed P).  corner: the wave's first tile holds the proxy query rows and this is a
 // frame n != 0 -- proxy x proxy scores are counted in frame 0 only.
-template <bool TAIL>
+template <bool TAIL, int IMG = B5_IMG>
 __device__ __forceinline__ void b5_dq_step(f32x4 (&dq)[2][4], const AP& p, const char* tK, const B5Own& w,
                                            const f32x4 (&c4)[2], const f32x4 (&nd4)[2], int t0, bool corner, int lane) {
-  // tK: the K image advanced to the step's first row (a multiple of 16 rows keeps the swizzle phase); V is B5_IMG further
+  // tK: the K image advanced to the step's first row (a multiple of 16 rows keeps the swizzle phase); V is IMG further
   const int g = lane >> 4, i16 = lane & 15;
-  const char* tV = tK + B5_IMG;
+  const char* tV = tK + IMG;
   f32x4 s[2][2], dp[2][2];
   {
     bf16x8 kf[2][2];
@@ -1290,12 +1292,13 @@ __device__ __forceinline__ void b5_dq_step(f32x4 (&dq)[2][4], const AP& p, const
 // phase B step: two sixteen-query sub-tiles at LDS row t0 * 16 against the wave's two key tiles (S orientation: the lane owns key
 // column i16 of each tile; rows 4g + r are queries, whose constants come from LDS as ready-made C operands).  Query rows >= R have
 // zero-filled Q / dO rows and zero constants (P = 1 times zeros); key lanes >= R only produce their own, discarded, columns.
+template <int IMG = B5_IMG, int CROWS = B5_ROWS>
 __device__ __forceinline__ void b5_dkv_step(f32x4 (&dk)[2][4], f32x4 (&dv)[2][4], const AP& p, const char* tQ, const float* tC,
                                             const bf16x8 (&kf)[2][2], const bf16x8 (&vf)[2][2], int t0, bool corner, int lane) {
-  // tQ: the Q image advanced to the step's first row (dO is B5_IMG further); tC: the row constants -(m + log l) advanced likewise
-  // (-delta is B5_ROWS floats further) -- every read of the step is one of a few per-lane bases plus an immediate
+  // tQ: the Q image advanced to the step's first row (dO is IMG further); tC: the row constants -(m + log l) advanced likewise
+  // (-delta is CROWS floats further) -- every read of the step is one of a few per-lane bases plus an immediate
   const int g = lane >> 4, i16 = lane & 15;
-  const char* tD = tQ + B5_IMG;
+  const char* tD = tQ + IMG;
   f32x4 s[2][2], dp[2][2];
   {
     bf16x8 qr[2][2];
@@ -1316,7 +1319,7 @@ __device__ __forceinline__ void b5_dkv_step(f32x4 (&dk)[2][4], f32x4 (&dv)[2][4]
     f32x4 n4[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      n4[t] = *reinterpret_cast<const f32x4*>(tC + B5_ROWS + t * 16 + 4 * g);
+      n4[t] = *reinterpret_cast<const f32x4*>(tC + CROWS + t * 16 + 4 * g);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) dr[t][kk] = frag_rows(tD, t, kk, lane);
     }
@@ -1363,7 +1366,7 @@ __device__ __forceinline__ void b5_dkv_step(f32x4 (&dk)[2][4], f32x4 (&dv)[2][4]
 // caller) and rows >= R are skipped.  cs[e]: the column sums of the rows stored (values as stored), columns 8 (lane & 7) + e,
 // summed over the lane's rows; b5_colsum_wave finishes them over the 8 row lanes.
 __device__ __forceinline__ void b5_store_tiles(const f32x4 (&acc)[2][4], float scale, char* stg, bf16_t* colbase, const AP& p, int n,
-                                               int wave, int lane, float (&cs)[8]) {
+                                               int wave, int lane, float (&cs)[8], int tile0 = 0) {
   const int i16 = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -1377,7 +1380,7 @@ __device__ __forceinline__ void b5_store_tiles(const f32x4 (&acc)[2][4], float s
   for (int e = 0; e < 8; ++e) cs[e] = 0.f;
 #pragma unroll
   for (int ps = 0; ps < 4; ++ps) {
-    const int rr = (wave + B5W * (ps >> 1)) * 16 + (ps & 1) * 8 + (lane >> 3);      // problem row of staging row 8 ps + (lane >> 3)
+    const int rr = (tile0 + wave + B5W * (ps >> 1)) * 16 + (ps & 1) * 8 + (lane >> 3);      // problem row of staging row 8 ps + (lane >> 3)
     const bf16x8 v = *reinterpret_cast<const bf16x8*>(stg + (ps * 8 + (lane >> 3)) * B5_STG_ROW + (lane & 7) * 16);
     if (rr >= p.M && rr < p.R) {
       *reinterpret_cast<bf16x8*>(colbase + (int64_t)tok_of(p, n, rr) * p.ldqkv + (lane & 7) * 8) = v;
@@ -1578,6 +1581,305 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
   }
 }
 
+// ============================================================================================ backward, fused, wide windows (opt-in)
+// attn_bwd6_kernel: attn_bwd5_kernel's one launch for the proxy problems whose window does NOT fit one LDS group (208 < R <= 1152,
+// M <= 16, no padding mask -- the shapes of attn_fwd4_kernel; 448^2 frames have R = 788).  Off unless XPRETRAIN_ATTN_BWD_WIDE=1 /
+// xp_set_attn_bwd_wide(1); the dQ / dKV kernel pair stays the default for these shapes.
+//   * one persistent 8-wave workgroup per CU, problems handed out by the device counter; ONE workgroup does a whole problem, so no
+//     dQ or dK / dV partial ever crosses a workgroup: an own-row accumulator simply stays in registers while the workgroup walks the
+//     other dimension group by group, as in the pair;
+//   * phase A, per block of 16 query tiles (two per wave): own Q / dO / O fragments and (m, log l) from global memory, delta and the
+//     row constants of the own rows into an LDS array that covers the whole problem; the {K, V} image comes by LDS-DMA one group of
+//     192 key rows at a time; dQ stays in registers over all groups and leaves through the per-wave staging as full 128-byte lines;
+//   * phase B, per block of 16 key tiles: own K / V fragments from global memory, the {Q, dO} image group by group, the row constants
+//     of a group straight out of the problem-wide array; dK / dV stay in registers over all groups;
+//   * the groups are double-buffered: the DMA of the NEXT stage (next group; next block's group 0; phase B's first group; the next
+//     problem's first group) is issued piece by piece inside the step loop of the current one.  One barrier per stage -- the point
+//     where the stage's DMA must have landed is also the point where the other buffer is free;
+//   * the step functions are attn_bwd5_kernel's (same arithmetic per score); the proxy x proxy corner lives in own block 0 / staged
+//     group 0; the one step that reaches past row R is peeled (phase A) or reads zero-filled rows with zero constants (phase B);
+//   * bias column sums: every wave adds the sums of the rows it stores to its own LDS row, block after block (fixed order); the
+//     workgroup's sum over the waves rides on a later stage's barrier.  Block 0 of the problem's nq partial rows gets the sums, the
+//     other rows of the two-kernel layout are zeroed (as attn_bwd5_kernel).
+// Groups of 192 rows, not 208: twelve tiles are six whole 32-row steps, so only a problem's LAST group has a step that reaches past R
+// (a 13th tile paired with a zero pad tile would give P = exp(-(m + log l)) on the pad rows of every group).  R = 788 is 5 groups
+// either way.  LDS: 2 buffers x {X, Y} x 192 rows x 128 B = 96 KiB; row constants 2 x 1152 x 4 B = 9 KiB; column-sum partials
+// 3 x 8 x 64 x 4 B = 6 KiB; output staging 8 waves x 32 rows x 144 B = 36 KiB; 16 B for the next problem's index: 150,544 B of the
+// 163,840 B of a CU.  The row-constant array sets R_max = 1152 (M = 16 with L = 1023 is R = 1039).
+// Deterministic: fixed summation order everywhere, the counter only decides WHICH workgroup computes a problem.
+constexpr int B6_G = 192;                                      // rows of a staged group
+constexpr int B6_IMG = B6_G * 128;                             // one operand image
+constexpr int B6_BUF = 2 * B6_IMG;                             // {K, V} or {Q, dO} of one group
+constexpr int B6_RMAX = 6 * B6_G;                              // rows the constant arrays hold
+constexpr int B6_BLK = 2 * B5W;                                // own tiles per block
+constexpr int B6_PIECES = B6_G / 64;                           // 64-row DMA pieces per group (a wave instruction per image each)
+constexpr int B6_OFF_STATS = 2 * B6_BUF;                       // c[B6_RMAX] = -(m + log l), nd[B6_RMAX] = -delta
+constexpr int B6_OFF_RED = B6_OFF_STATS + 2 * B6_RMAX * 4;     // column-sum partials [3][B5W][DH]
+constexpr int B6_OFF_NEXT = B6_OFF_RED + 3 * B5W * DH * 4;
+constexpr int B6_OFF_STG = B6_OFF_NEXT + 16;
+constexpr int B6_LDS = B6_OFF_STG + B5W * B5_STG_WAVE;
+static_assert(B6_LDS <= 160 * 1024, "attn_bwd6_kernel: LDS budget");
+
+// piece j (64 rows) of group grp of one row-major operand -> the group's swizzled LDS image (b5_stage_piece, with the group's first
+// row in the scalar offset; only the problem's first piece holds proxy rows)
+__device__ __forceinline__ void b6_stage_piece(char* img, __amdgpu_buffer_rsrc_t rs, unsigned ld_bytes, unsigned soff, unsigned vrow,
+                                               unsigned voff0, int R, unsigned frame_off, int lane, int wave, int grp, int j) {
+  typedef __attribute__((address_space(3))) char lds_c;
+  const int pass = j * B5W + wave;                              // < B6_G / 8
+  const int r0 = grp * B6_G + j * 64;
+  const int row = r0 + wave * 8 + (lane >> 3);
+  const unsigned v = row < R ? (r0 == 0 ? voff0 : vrow) : 0xFFFFFF00u;
+  const unsigned so = r0 == 0 ? soff : soff + frame_off + (unsigned)r0 * ld_bytes;
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_c*)(img + pass * 1024), 16, v, so, 0, 0);
+}
+// kind 0: piece j of the {K, V} image of group grp of problem pr; kind 1: of its {Q, dO} image
+__device__ __forceinline__ void b6_stage(char* buf, const AP& p, const Prob& pr, int kind, int grp, int lane, int wave, int j) {
+  B5Lane L; b5_lane_offsets(L, p, pr.n, lane, wave);
+  const unsigned ldq = (unsigned)(p.ldqkv * 2), ldo = (unsigned)(p.ldo * 2);
+  if (kind == 0) {
+    const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
+    const unsigned fo = (unsigned)(pr.n * p.L) * ldq;
+    b6_stage_piece(buf, rs, ldq, 0, L.vq, L.v0q, p.R, fo, lane, wave, grp, j);
+    b6_stage_piece(buf + B6_IMG, rs, ldq, (unsigned)(p.H * DH * 2), L.vq, L.v0q, p.R, fo, lane, wave, grp, j);
+  } else {
+    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16_t*>(p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH), 0, (unsigned)(((int64_t)p.S * p.ldqkv - pr.h * DH) * 2), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<bf16_t*>(p.dout + (int64_t)pr.b * p.S * p.ldo + pr.h * DH), 0, (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
+    b6_stage_piece(buf, rq, ldq, 0, L.vq, L.v0q, p.R, (unsigned)(pr.n * p.L) * ldq, lane, wave, grp, j);
+    b6_stage_piece(buf + B6_IMG, rdo, ldo, 0, L.vo, L.v0o, p.R, (unsigned)(pr.n * p.L) * ldo, lane, wave, grp, j);
+  }
+}
+// the wave's own key rows (tiles tile0 + wave, tile0 + wave + 8; rows >= R: zeros) straight from global memory: K and V fragments
+__device__ __forceinline__ void b6_load_own_kv(bf16x8 (&kf)[2][2], bf16x8 (&vf)[2][2], const AP& p, const Prob& pr, int wave, int lane,
+                                               int tile0) {
+  const int i16 = lane & 15, g = lane >> 4;
+  const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int rk = (tile0 + wave + B5W * i) * 16 + i16;
+    const unsigned o = rk < p.R ? (unsigned)tok_of(p, pr.n, rk) * (unsigned)(p.ldqkv * 2) + g * 16 : 0xFFFFFF00u;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      kf[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, o + kk * 64, 0, 0));
+      vf[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, o + kk * 64, p.H * DH * 2, 0));
+    }
+  }
+}
+// __shfl_xor with the caller's lane id: __shfl_xor derives its own, and hipcc hoists the permute addresses of every call site out of
+// the persistent loop, where they are registers the step loops spill
+__device__ __forceinline__ float b6_shfl_xor(float v, int o, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ o) << 2, __builtin_bit_cast(int, v)));
+}
+// b5_colsum_wave over the blocks of a problem: the wave's LDS row is set by its first block and added to by the later ones
+__device__ __forceinline__ void b6_colsum_wave(float (&cs)[8], float* red_row, int lane, bool first) {
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) cs[e] += b6_shfl_xor(cs[e], o, lane);
+  if (lane < 8) {
+    f32x4 a = {cs[0], cs[1], cs[2], cs[3]}, b = {cs[4], cs[5], cs[6], cs[7]};
+    if (!first) { a += *reinterpret_cast<const f32x4*>(red_row + lane * 8); b += *reinterpret_cast<const f32x4*>(red_row + lane * 8 + 4); }
+    store4(red_row + lane * 8, a);
+    store4(red_row + lane * 8 + 4, b);
+  }
+}
+
+__global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* sC = reinterpret_cast<float*>(smem + B6_OFF_STATS); float* sNd = sC + B6_RMAX;
+  float* red = reinterpret_cast<float*>(smem + B6_OFF_RED);
+  int* sNext = reinterpret_cast<int*>(smem + B6_OFF_NEXT);
+  char* stg = smem + B6_OFF_STG + (threadIdx.x >> 6) * B5_STG_WAVE;
+  // (the lane id from mbcnt wherever it is needed: threadIdx.x kept alive through the whole kernel is a register the step loops spill)
+#define B6_LANE0 ((int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)))
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  const int nt = (p.R + 15) / 16;                          // sixteen-row tiles of a problem
+  const int nblk = (nt + B6_BLK - 1) / B6_BLK;             // own blocks (either phase)
+  const int ngrp = (p.R + B6_G - 1) / B6_G;                // staged groups (either phase): >= 2
+  int prob = blockIdx.x, prev = -1;
+  if (prob >= p.nprob) return;
+  unsigned cur = 0;                                        // byte offset of the buffer the current stage reads; the next one lands in the other
+  {
+    const Prob pr(p, prob);
+    for (int j = 0; j < B6_PIECES; ++j) b6_stage(smem, p, pr, 0, 0, B6_LANE0, wave, j);
+  }
+  for (;;) {
+    const Prob pr(p, prob);
+    if (wave == 0 && B6_LANE0 == 0) *sNext = counter ? atomicAdd(counter, 1) + (int)gridDim.x : prob + (int)gridDim.x;
+    bf16_t* colbase = p.dqkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
+    // ---- phase A: dQ, one block of 16 query tiles after the other, each against every key group
+    for (int qb = 0; qb < nblk; ++qb) {
+      const bool active = qb * B6_BLK + wave < nt;         // owns at least one real tile (tiles qb*16 + wave, + 8)
+      const bool corner = wave == 0 && pr.n != 0 && qb == 0;
+      B5Own w;
+      float c1[2], nd1[2];                                 // the own rows' -(m + log l), -delta: splat into C operands per step (below)
+      f32x4 dq[2][4];
+      for (int kg = 0; kg < ngrp; ++kg) {
+        // (per-lane constants re-derived per stage from a lane id the compiler cannot see through: see attn_bwd5_kernel)
+        int lane = B6_LANE0;
+        asm volatile("" : "+v"(lane));
+        const int tid = wave * 64 + lane, i16 = lane & 15, g = lane >> 4;
+        __syncthreads();                                   // this stage's {K, V} group has landed; every wave is done with the other buffer
+        if (qb == 0 && kg == 0 && p.cs && prev >= 0 && tid < 2 * DH) {      // previous problem: dK / dV column sums
+          const Prob pv(p, prev);
+          float* row = b5_cs_row(p, pv);
+          if (tid < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid);
+          else          b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid - DH);
+        }
+        if (kg == 0) {
+          // the block's own rows; delta = sum_d dO * O from the fragments in registers; the row constants also go to the
+          // problem-wide LDS arrays for phase B (rows >= R: zeros)
+          b5_load_own(w, p, pr, wave, lane, qb * B6_BLK);
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            float dl = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+              for (int e = 0; e < 8; ++e) dl += (float)w.d[i][kk][e] * (float)w.o[i][kk][e];
+            dl += b6_shfl_xor(dl, 16, lane);
+            dl += b6_shfl_xor(dl, 32, lane);
+            const float c = -(w.m[i] + w.lg[i]);
+            c1[i] = c; nd1[i] = -dl;
+            const int rq = (qb * B6_BLK + wave + B5W * i) * 16 + i16;
+            if (g == 0 && rq < B6_RMAX) { sC[rq] = c; sNd[rq] = -dl; }
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) dq[i][dt] = f32x4{0, 0, 0, 0};
+          }
+        }
+        // the stage after this one: the next key group; the next block's first; phase B's first {Q, dO} group
+        const int nkind = kg + 1 < ngrp || qb + 1 < nblk ? 0 : 1, ngr = kg + 1 < ngrp ? kg + 1 : 0;
+        char* nbuf = smem + (cur ^ (unsigned)B6_BUF);
+        const int left = p.R - kg * B6_G;                   // key rows from this group's first one to R
+        const int nsteps = left >= B6_G ? B6_G / 32 : (left + 31) / 32, nfull = left >= B6_G ? B6_G / 32 : left / 32;
+        // (the four constants as four MFMA C operands held over the whole block are 16 registers the step loop does not have: 4, and
+        // re-splat in front of every step)
+#define B6_SPLAT_CONSTANTS                                                                                       \
+  f32x4 c4[2], nd4[2];                                                                                           \
+  _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                                \
+    float c = c1[i], n = nd1[i];                                                                                 \
+    asm volatile("" : "+v"(c), "+v"(n));                                                                         \
+    c4[i] = f32x4{c, c, c, c}; nd4[i] = f32x4{n, n, n, n};                                                       \
+  }
+        int st = 0;
+        for (; st < nfull; ++st) {
+          if (st < B6_PIECES) b6_stage(nbuf, p, pr, nkind, ngr, lane, wave, st);
+          if (active) {
+            unsigned xo = cur + (unsigned)st * (32 * 128);
+            asm volatile("" : "+s"(xo));
+            B6_SPLAT_CONSTANTS;
+            b5_dq_step<false, B6_IMG>(dq, p, smem + xo, w, c4, nd4, kg * (B6_G / 16) + 2 * st, corner, lane);
+          }
+        }
+        if (st < nsteps) {
+          if (st < B6_PIECES) b6_stage(nbuf, p, pr, nkind, ngr, lane, wave, st);
+          if (active) {
+            unsigned xo = cur + (unsigned)st * (32 * 128);
+            asm volatile("" : "+s"(xo));
+            B6_SPLAT_CONSTANTS;
+            b5_dq_step<true, B6_IMG>(dq, p, smem + xo, w, c4, nd4, kg * (B6_G / 16) + 2 * st, corner, lane);
+          }
+          ++st;
+        }
+#undef B6_SPLAT_CONSTANTS
+        for (; st < B6_PIECES; ++st) b6_stage(nbuf, p, pr, nkind, ngr, lane, wave, st);
+        cur ^= (unsigned)B6_BUF;
+      }
+      int lane = B6_LANE0;
+      asm volatile("" : "+v"(lane));
+      const int i16 = lane & 15, g = lane >> 4;
+      if (qb == 0 && wave == 0 && i16 < p.M) {             // proxy query rows: per-frame partials, reduced later
+        float* part = p.ws1 + ((int64_t)prob * p.M + i16) * DH;
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) store4(part + dt * 16 + 4 * g, dq[0][dt]);
+      }
+      float cs[8];
+      b5_store_tiles(dq, p.q_scale, stg, colbase, p, pr.n, wave, lane, cs, qb * B6_BLK);
+      if (p.cs) b6_colsum_wave(cs, red + wave * DH, lane, qb == 0);
+    }
+    // ---- phase B: dK, dV, one block of 16 key tiles after the other, each against every query group
+    int next = p.nprob;
+    for (int kb = 0; kb < nblk; ++kb) {
+      const bool active = kb * B6_BLK + wave < nt;
+      const bool corner = wave == 0 && pr.n != 0 && kb == 0;
+      bf16x8 kf[2][2], vf[2][2];
+      f32x4 dk[2][4], dv[2][4];
+      for (int qg = 0; qg < ngrp; ++qg) {
+        int lane = B6_LANE0;
+        asm volatile("" : "+v"(lane));
+        const int tid = wave * 64 + lane;
+        __syncthreads();                                   // this stage's {Q, dO} group has landed; the other buffer is free; (first
+        if (kb == 0 && qg == 0) {                          //  stage) every row constant and dQ column sum of the problem is in LDS
+          next = __builtin_amdgcn_readfirstlane(*sNext);
+          if (p.cs && tid < DH) {
+            float* row = b5_cs_row(p, pr);
+            b5_colsum_finish(red, row, tid);
+            for (int blk = 1; blk < p.nq; ++blk)           // rows of the two-kernel layout this launch does not use
+              for (int j = 0; j < 3; ++j) row[(int64_t)blk * 3 * p.H * DH + j * p.H * DH + tid] = 0.f;
+          }
+        }
+        if (qg == 0) {
+          b6_load_own_kv(kf, vf, p, pr, wave, lane, kb * B6_BLK);
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) { dk[i][dt] = f32x4{0, 0, 0, 0}; dv[i][dt] = f32x4{0, 0, 0, 0}; }
+        }
+        // the stage after this one: the next query group; the next block's first; the next problem's first {K, V} group
+        const bool last = qg + 1 == ngrp && kb + 1 == nblk;
+        const bool more = !last || next < p.nprob;
+        const Prob pn(p, last && more ? next : prob);
+        const int nkind = last ? 0 : 1, ngr = qg + 1 < ngrp ? qg + 1 : 0;
+        char* nbuf = smem + (cur ^ (unsigned)B6_BUF);
+        const int left = p.R - qg * B6_G;
+        const int nsteps = left >= B6_G ? B6_G / 32 : (left + 31) / 32;
+        for (int st = 0; st < nsteps || st < B6_PIECES; ++st) {
+          if (st < B6_PIECES && more) b6_stage(nbuf, p, pn, nkind, ngr, lane, wave, st);
+          if (active && st < nsteps) {
+            unsigned yo = cur + (unsigned)st * (32 * 128), co = (unsigned)B6_OFF_STATS + (unsigned)(qg * B6_G + st * 32) * 4;
+            asm volatile("" : "+s"(yo), "+s"(co));
+            b5_dkv_step<B6_IMG, B6_RMAX>(dk, dv, p, smem + yo, reinterpret_cast<const float*>(smem + co), kf, vf,
+                                         qg * (B6_G / 16) + 2 * st, corner, lane);
+          }
+        }
+        cur ^= (unsigned)B6_BUF;
+      }
+      int lane = B6_LANE0;
+      asm volatile("" : "+v"(lane));
+      const int i16 = lane & 15, g = lane >> 4;
+      if (kb == 0 && wave == 0 && i16 < p.M) {             // proxy keys: per-frame partials, reduced later
+        float* part = p.ws2 + ((int64_t)prob * p.M + i16) * (2 * DH);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) { store4(part + dt * 16 + 4 * g, dk[0][dt]); store4(part + DH + dt * 16 + 4 * g, dv[0][dt]); }
+      }
+      float cs[8];
+      b5_store_tiles(dk, 1.0f, stg, colbase + (int64_t)p.H * DH, p, pr.n, wave, lane, cs, kb * B6_BLK);
+      if (p.cs) b6_colsum_wave(cs, red + (B5W + wave) * DH, lane, kb == 0);
+      b5_store_tiles(dv, 1.0f, stg, colbase + (int64_t)2 * p.H * DH, p, pr.n, wave, lane, cs, kb * B6_BLK);
+      if (p.cs) b6_colsum_wave(cs, red + (2 * B5W + wave) * DH, lane, kb == 0);
+    }
+    prev = prob;
+    if (next >= p.nprob) break;
+    prob = next;
+  }
+  if (p.cs) {
+    __syncthreads();
+    const int tid0 = wave * 64 + B6_LANE0;
+    if (tid0 < 2 * DH) {
+      const Prob pv(p, prev);
+      float* row = b5_cs_row(p, pv);
+      if (tid0 < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid0);
+      else           b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid0 - DH);
+    }
+  }
+#undef B6_LANE0
+}
+
 int check_common(const char* name, int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L,
                  int64_t ldqkv, int64_t ldo, int32_t dtype) {
   XP_REQUIRE(dtype == XP_BF16 || dtype == XP_F32, "%s: bad dtype %d", name, dtype);
@@ -1604,6 +1906,12 @@ struct AttnPlan {
   int64_t ws_bytes, colsum_rows;     // colsum_rows: 0 in fp32 mode (callers run xp_colsum_partials)
 };
 
+// The opt-in one-launch backward for wide windows (attn_bwd6_kernel): XPRETRAIN_ATTN_BWD_WIDE=1, or xp_set_attn_bwd_wide(), which wins
+int g_attn_bwd_wide = [] {
+  const char* e = getenv("XPRETRAIN_ATTN_BWD_WIDE");
+  return e && *e && strcmp(e, "0") != 0 ? 1 : 0;
+}();
+
 // cus: the device's CUs (the persistent kernels' grids, attn_fwd4's admission).  CAUSAL is planned as M = 0, N = 1, L = S.
 AttnPlan plan_attn(AttnCall c, int cus) {
   AttnPlan p{};
@@ -1625,7 +1933,8 @@ AttnPlan plan_attn(AttnCall c, int cus) {
   if (c.dtype == XP_F32) { p.kernel = XP_ATTN_KERNEL_F32; return p; }
   // The persistent kernels: proxy problems, no padding mask, at most 16 proxy rows (their proxy x proxy mask lives in query tile 0 /
   // key sub-tile 0 only).  One LDS group (R <= 208): attn_fwd3 / attn_bwd5 (XPRETRAIN_DEBUG=attn_bwd_split keeps the two-kernel
-  // backward: A/B and the cross-check test); wider problems: attn_fwd4 where every XCD gets whole quads of workgroups.
+  // backward: A/B and the cross-check test); wider problems: attn_fwd4 where every XCD gets whole quads of workgroups, and, only
+  // with the XPRETRAIN_ATTN_BWD_WIDE switch on, attn_bwd6 up to the rows its LDS constant arrays hold (attn_bwd_split wins here too).
   const bool persistent = proxy && c.M <= 16 && !c.pad;
   const unsigned per_cu = (unsigned)(P < cus ? P : cus);
   if (!c.bwd && persistent && R <= FG) {
@@ -1634,6 +1943,9 @@ AttnPlan plan_attn(AttnCall c, int cus) {
     p.kernel = XP_ATTN_KERNEL_FWD4; p.grid = (unsigned)cus; p.lds = F3_LDS; p.lds_kernel = reinterpret_cast<const void*>(attn_fwd4_kernel);
   } else if (c.bwd && persistent && R <= FG && !xp_debug_flag("attn_bwd_split")) {
     p.kernel = XP_ATTN_KERNEL_BWD5; p.grid = per_cu; p.lds = B5_LDS; p.lds_kernel = reinterpret_cast<const void*>(attn_bwd5_kernel);
+    p.uses_counter = true;
+  } else if (c.bwd && persistent && R > FG && R <= B6_RMAX && g_attn_bwd_wide && !xp_debug_flag("attn_bwd_split")) {
+    p.kernel = XP_ATTN_OPTIN_BWD6; p.grid = per_cu; p.lds = B6_LDS; p.lds_kernel = reinterpret_cast<const void*>(attn_bwd6_kernel);
     p.uses_counter = true;
   } else {                           // the 7-wave kernels: the query blocks of one problem get workgroup ids 8 apart
     p.kernel = c.bwd ? XP_ATTN_KERNEL_BWD_PAIR : XP_ATTN_KERNEL_FWD; p.grid = (unsigned)(cdiv(P, 8) * 8 * nq);
@@ -1662,6 +1974,9 @@ int xp_attn_f32_bwd(const void* qkv, int64_t ldqkv, const void* out, const void*
 
 static void* g_attn_trace = nullptr;
 extern "C" int xp_debug_set_attn_trace(void* device_buffer) { g_attn_trace = device_buffer; return XP_OK; }
+
+extern "C" int xp_set_attn_bwd_wide(int32_t on) { g_attn_bwd_wide = on != 0; return XP_OK; }
+extern "C" int32_t xp_get_attn_bwd_wide(void) { return g_attn_bwd_wide; }
 
 extern "C" size_t xp_attn_workspace_bytes(int32_t mode, int64_t B, int64_t H, int64_t M, int64_t N, int64_t L) {
   // the larger direction, whatever the dtype (S is M + N*L for PROXY; for CAUSAL callers pass M=0, N=1, L=S)
@@ -1737,6 +2052,9 @@ extern "C" int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, con
   if (pl.kernel == XP_ATTN_KERNEL_BWD5) {
     attn_bwd5_kernel<<<pl.grid, B5THR, pl.lds, st>>>(p, counter);
     XP_CHECK_LAUNCH("xp_attn_bwd(fused)");
+  } else if (pl.kernel == XP_ATTN_OPTIN_BWD6) {
+    attn_bwd6_kernel<<<pl.grid, B5THR, pl.lds, st>>>(p, counter);
+    XP_CHECK_LAUNCH("xp_attn_bwd(fused, wide)");
   } else {
     attn_bwd_dq_kernel<<<pl.grid, FTHR, 0, st>>>(p);          // also computes delta = rowsum(dO * O) into ws0
     XP_CHECK_LAUNCH("xp_attn_bwd(dq)");

@@ -495,7 +495,8 @@ def attn_fwd(qkv: torch.Tensor, B: int, S: int, H: int, *, size=None, pad_mask=N
 
 def attn_plan(B: int, S: int, H: int, *, size=None, pad_mask=None, dtype=torch.bfloat16, backward=False, cus=0) -> dict:
     """The plan attn_fwd (``backward``: attn_bwd) launches for these arguments (xp_debug_attn_plan: host only, nothing launched) as
-    a dict of the XpAttnPlanInfo fields, ``kernel`` by name (_lib.ATTN_KERNELS); ``pad_mask`` counts as present or absent.  ``cus``
+    a dict of the XpAttnPlanInfo fields, ``kernel`` by name (_lib.ATTN_KERNELS, _lib.ATTN_OPTIN_KERNELS); ``pad_mask`` counts as
+    present or absent.  ``cus``
     > 0: a device of that many CUs that grants every dynamic-LDS opt-in (no GPU needed); <= 0: the current device."""
     mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
     M, N, Lp = size if size is not None else (0, 1, S)
@@ -503,8 +504,19 @@ def attn_plan(B: int, S: int, H: int, *, size=None, pad_mask=None, dtype=torch.b
     L.check(L.lib().xp_debug_attn_plan(mode, B, H, S, M, N, Lp, _DT[dtype], int(pad_mask is not None), int(backward), cus,
                                        C.byref(info)), "xp_debug_attn_plan")
     plan = {f: getattr(info, f) for f, _ in info._fields_ if f != "reserved"}
-    plan.update({f: tuple(plan[f]) for f in ("part", "delta", "dq", "dkv", "counter")}, kernel=L.ATTN_KERNELS[info.kernel])
+    plan.update({f: tuple(plan[f]) for f in ("part", "delta", "dq", "dkv", "counter")}, kernel=L.ATTN_OPTIN_KERNELS.get(info.kernel) or L.ATTN_KERNELS[info.kernel])
     return plan
+
+
+def set_attn_bwd_wide(on: bool) -> None:
+    """Opt-in (default off, or XPRETRAIN_ATTN_BWD_WIDE=1; this call wins over the environment): proxy attention backwards whose
+    window is wider than one LDS group (208 < M + L <= 1152, M <= 16, no padding mask, bf16) run as one persistent launch
+    (attn_bwd6_kernel, plan name ``bwd6``) instead of the dQ / dKV kernel pair.  Process-global planning state, like the CU budget."""
+    L.check(L.lib().xp_set_attn_bwd_wide(int(bool(on))), "xp_set_attn_bwd_wide")
+
+
+def get_attn_bwd_wide() -> bool:
+    return bool(L.lib().xp_get_attn_bwd_wide())
 
 
 def attn_bwd(qkv, out, dout, stats, B, S, H, *, size=None, pad_mask=None, q_scale=1.0, colsum_defer=None,
