@@ -42,7 +42,7 @@ struct AP {
   int nq, nprob;                        // forward: query blocks per problem, problems
   float q_scale;
   float* ws0; float* ws1; float* ws2;   // fwd: partials | bwd: delta, dq partials, dkv partials
-  unsigned long long* tr;               // xp_debug_set_attn_trace (fused backward): cycle stamps of one workgroup
+  unsigned long long* tr;               // xp_debug_set_attn_trace: cycle stamps of one workgroup
   float* cs; int cs_main;               // bwd, optional: column-sum partial rows of dqkv [cs_main + B*M][3*H*64] (see xp_attn_bwd2)
 };
 
@@ -94,6 +94,27 @@ __device__ __forceinline__ bf16x8 pack_p(f32x4 a, f32x4 b) {
 __device__ __forceinline__ float group_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); return fmaxf(v, __shfl_xor(v, 32, 64)); }
 __device__ __forceinline__ float group_sum(float v) { v += __shfl_xor(v, 16, 64); return v + __shfl_xor(v, 32, 64); }
 
+// Buffer resources of problem pr's head slice of one operand: base = the slice of the sample's first token, range = up to the end of
+// the sample's rows, so a loader's offset is token * pitch + byte inside the slice, and 0xFFFFFF00 is out of range (reads as zero)
+// for every one of them.  K's resource also reaches V, v_off(p) bytes further in the same row.
+constexpr unsigned OOB = 0xFFFFFF00u;
+__device__ __forceinline__ unsigned v_off(const AP& p) { return (unsigned)(p.H * DH * 2); }
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_q(const AP& p, const Prob& pr) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH), 0,
+                                           (unsigned)(((int64_t)p.S * p.ldqkv - pr.h * DH) * 2), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_kv(const AP& p, const Prob& pr) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH), 0,
+                                           (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_o(const AP& p, const Prob& pr, const bf16_t* o) {      // o: p.out or p.dout
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(o + (int64_t)pr.b * p.S * p.ldo + pr.h * DH), 0,
+                                           (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc_stats(const AP& p, const Prob& pr) {                  // 8 bytes per token
+  return __builtin_amdgcn_make_buffer_rsrc(p.stats + ((int64_t)pr.b * p.H + pr.h) * p.S * 2, 0, (unsigned)(p.S * 8), 0x00020000);
+}
+
 constexpr int PART = 2 + DH;   // forward proxy partial: m, l, O[64]
 
 // ============================================================================================ forward
@@ -119,17 +140,18 @@ __device__ __forceinline__ s16x4 frag_cols16(const char* tile, int dt, int sub, 
   return __builtin_bit_cast(s16x4, lds_read_tr16(tile + tile128_off(r0, dt * 2 + ((i & 3) >> 1)) + ((i & 1) << 3)));
 }
 
-// cooperative load of key rows [row0, row0 + nrows) of K AND V (same rows, V = K + voff_v bytes) into the linear swizzled
+// cooperative load of key rows [row0, row0 + nrows) of K AND V (same rows, V = K + v_off bytes) into the linear swizzled
 // images.  Branch-free: buffer loads relative to the sample's first token, rows >= R (or >= nrows) get an out-of-range
 // offset and read as zero.
-__device__ __forceinline__ void fwd_load_kv(char* gK, char* gV, __amdgpu_buffer_rsrc_t rs, unsigned ld_bytes, unsigned voff_v,
-                                            const AP& p, const Prob& pr, int row0, int nrows, int tid) {
+__device__ __forceinline__ void fwd_load_kv(char* gK, char* gV, const AP& p, const Prob& pr, int row0, int nrows, int tid) {
   constexpr int NJ = (FG * 8 + FTHR - 1) / FTHR;
+  const __amdgpu_buffer_rsrc_t rs = rsrc_kv(p, pr);
+  const unsigned ld_bytes = (unsigned)(p.ldqkv * 2), voff_v = v_off(p);
   u32x4 vk[NJ], vv[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int e = tid + j * FTHR, row = e >> 3, c = e & 7, r = row0 + row;
-    const unsigned off = (row < nrows && r < p.R) ? (unsigned)tok_of(p, pr.n, r) * ld_bytes + c * 16 : 0xFFFFFF00u;
+    const unsigned off = (row < nrows && r < p.R) ? (unsigned)tok_of(p, pr.n, r) * ld_bytes + c * 16 : OOB;
     vk[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0);
     vv[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, voff_v, 0);
   }
@@ -144,6 +166,59 @@ __device__ __forceinline__ void fwd_load_kv(char* gK, char* gV, __amdgpu_buffer_
 }
 
 struct FwdState { f32x4 o[4]; float m, l; };
+__device__ __forceinline__ void fwd_init(FwdState& st, float m0) {
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) st.o[dt] = f32x4{0, 0, 0, 0};
+  st.m = m0; st.l = 0.f;
+}
+// proxy rows of a PROXY problem see (or are seen by) every frame: a problem contributes a per-frame partial, reduced by a later kernel
+__device__ __forceinline__ bool proxy_row(const AP& p, int r) { return p.mode == XP_ATTN_PROXY && r < p.M; }
+// the proxy rows' partials of problem `prob`, the workspace layouts plan_attn sizes: forward (m, l, unnormalised O), backward dQ,
+// backward {dK, dV}.  The lane holds columns 16 dt + 4 g + r of row `row`.
+__device__ __forceinline__ void store_fwd_partial(const AP& p, int prob, int row, int g, const FwdState& st, float l) {
+  float* part = p.ws0 + ((int64_t)prob * p.M + row) * PART;
+  if (g == 0) { part[0] = st.m; part[1] = l; }
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) store4(part + 2 + dt * 16 + 4 * g, st.o[dt]);
+}
+__device__ __forceinline__ void store_dq_partial(const AP& p, int prob, int row, int g, const f32x4 (&dq)[4]) {
+  float* part = p.ws1 + ((int64_t)prob * p.M + row) * DH;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) store4(part + dt * 16 + 4 * g, dq[dt]);
+}
+__device__ __forceinline__ void store_dkv_partial(const AP& p, int prob, int row, int g, const f32x4 (&dk)[4], const f32x4 (&dv)[4]) {
+  float* part = p.ws2 + ((int64_t)prob * p.M + row) * (2 * DH);
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) { store4(part + dt * 16 + 4 * g, dk[dt]); store4(part + DH + dt * 16 + 4 * g, dv[dt]); }
+}
+// The forward epilogue of one query row (every lane of the row's group of four calls it): rows >= R leave nothing; a proxy row leaves
+// its partial; every other row is normalised and stored as bf16 with its (m, log l).
+__device__ __forceinline__ void fwd_finish_row(const FwdState& st, const AP& p, const Prob& pr, int prob, int rq, int g) {
+  const float l = group_sum(st.l);
+  if (rq >= p.R) return;
+  if (proxy_row(p, rq)) { store_fwd_partial(p, prob, rq, g, st, l); return; }
+  const int tok = tok_of(p, pr.n, rq);
+  const float inv = 1.0f / l;
+  bf16_t* orow = p.out + ((int64_t)pr.b * p.S + tok) * p.ldo + pr.h * DH;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) store4(orow + dt * 16 + 4 * g, st.o[dt] * inv);
+  if (g == 0) {
+    float* sp = p.stats + (((int64_t)pr.b * p.H + pr.h) * p.S + tok) * 2;
+    sp[0] = st.m; sp[1] = __logf(l);
+  }
+}
+
+// ---- shared lines of the 7-wave kernels whose own rows are queries (attn_fwd_kernel, attn_bwd_dq_kernel)
+// sixteen-key sub-tiles the query block at row qb visits: all of them, or (causal) those up to its last row
+__device__ __forceinline__ int own_query_nsub(const AP& p, int qb) {
+  int nsub = (p.R + 15) / 16;
+  if (p.mode == XP_ATTN_CAUSAL) { const int lim = (qb + FQ - 1) / 16 + 1; nsub = nsub < lim ? nsub : lim; }
+  return nsub;
+}
+// padding flags of the staged key rows [g0 * 16, + FG)
+__device__ __forceinline__ void fill_pad_flags(unsigned char* gPad, const AP& p, const Prob& pr, int g0, int tid) {
+  if (tid < FG) { const int r = g0 * 16 + tid; gPad[tid] = (p.pad && r < p.R) ? (p.pad[(int64_t)pr.b * p.S + r] == 0) : 0; }
+}
 
 // The masked score path as a real call: inlined into the step loops its sixteen (sub-tile, slot) predicates are hoisted
 // out of the key loop as loop invariants and spill; it runs on the tail step / causal band / proxy corner only.
@@ -233,8 +308,7 @@ __global__ __launch_bounds__(FTHR, 4) void attn_fwd_kernel(AP p) {
   if (prob >= p.nprob) return;
   const Prob pr(p, prob);
   const int qb = (slot % p.nq) * FQ;
-  unsigned long long* tr = (p.mode == XP_ATTN_PROXY && p.ws2 && prob == p.nprob / 2 && qb == 0 && tid == 0)
-                               ? reinterpret_cast<unsigned long long*>(p.ws2) : nullptr;      // xp_debug_set_attn_trace
+  unsigned long long* tr = (p.mode == XP_ATTN_PROXY && p.tr && prob == p.nprob / 2 && qb == 0 && tid == 0) ? p.tr : nullptr;
   if (tr) tr[0] = __builtin_amdgcn_s_memtime();
   const int rq = qb + wave * 16 + i16;            // this lane's query row (column of S^T)
   const bool qvalid = rq < p.R;
@@ -244,26 +318,15 @@ __global__ __launch_bounds__(FTHR, 4) void attn_fwd_kernel(AP p) {
   load_row_frag(qf, p.qkv + qtok * p.ldqkv + pr.h * DH, qvalid, g);
 
   FwdState st;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) st.o[dt] = f32x4{0, 0, 0, 0};
-  st.m = -INFINITY; st.l = 0.f;
-
-  int nsub = (p.R + 15) / 16;                     // sixteen-key sub-tiles this workgroup visits
-  if (p.mode == XP_ATTN_CAUSAL) { const int lim = (qb + FQ - 1) / 16 + 1; nsub = nsub < lim ? nsub : lim; }
-
-  // K slice of head h of this sample's first token; V is H*DH elements further
-  const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
-  const unsigned ld_bytes = (unsigned)(p.ldqkv * 2);
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
-  const unsigned voff_v = (unsigned)(p.H * DH * 2);
+  fwd_init(st, -INFINITY);
+  const int nsub = own_query_nsub(p, qb);
   const int wrow0 = qb + wave * 16;
   const bool wave_active = wrow0 < p.R;           // wave-uniform: waves past the last row only keep the barriers
   for (int g0 = 0; g0 < nsub; g0 += FG / 16) {
     const int ng = nsub - g0 < FG / 16 ? nsub - g0 : FG / 16;
     if (g0) __syncthreads();
-    fwd_load_kv(gK, gV, rs, ld_bytes, voff_v, p, pr, g0 * 16, ng * 16, tid);
-    if (tid < FG) { const int r = g0 * 16 + tid; gPad[tid] = (p.pad && r < p.R) ? (p.pad[(int64_t)pr.b * p.S + r] == 0) : 0; }
+    fwd_load_kv(gK, gV, p, pr, g0 * 16, ng * 16, tid);
+    fill_pad_flags(gPad, p, pr, g0, tid);
     if (tr && g0 == 0) tr[1] = __builtin_amdgcn_s_memtime();
     __syncthreads();
     if (tr && g0 == 0) tr[2] = __builtin_amdgcn_s_memtime();
@@ -277,25 +340,8 @@ __global__ __launch_bounds__(FTHR, 4) void attn_fwd_kernel(AP p) {
       else         fwd_step<4>(st, p, pr, gK, gV, gPad, qf, t0, kb, rq, qvalid, wrow0, lane);
     }
   }
-  const float m = st.m;
-  const float l = group_sum(st.l);
-  if (tr) tr[3] = __builtin_amdgcn_s_memtime();
-  if (!qvalid) return;
-  if (p.mode == XP_ATTN_PROXY && rq < p.M) {
-    float* part = p.ws0 + ((int64_t)prob * p.M + rq) * PART;
-    if (g == 0) { part[0] = m; part[1] = l; }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) store4(part + 2 + dt * 16 + 4 * g, st.o[dt]);
-    return;
-  }
-  const float inv = 1.0f / l;
-  bf16_t* orow = p.out + qtok * p.ldo + pr.h * DH;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt) store4(orow + dt * 16 + 4 * g, st.o[dt] * inv);
-  if (g == 0) {
-    float* sp = p.stats + (((int64_t)pr.b * p.H + pr.h) * p.S + tok_of(p, pr.n, rq)) * 2;
-    sp[0] = m; sp[1] = __logf(l);
-  }
+  if (tr) tr[3] = __builtin_amdgcn_s_memtime();      // (in front of the epilogue's two-shuffle sum of l)
+  fwd_finish_row(st, p, pr, prob, rq, g);
 }
 
 // ============================================================================================ forward, persistent + prefetch
@@ -322,12 +368,10 @@ constexpr int F3_LDS = 2 * F3_BUF;
 
 // K and V rows [0, R) of one problem -> linear swizzled LDS images by LDS-DMA: one wave instruction = 8 rows x 128 B; the
 // XOR swizzle of tile128_off is applied to the per-lane SOURCE chunk; rows >= R read as zero (out-of-range offset)
-__device__ __forceinline__ void fwd3_stage_kv(char* gK, char* gV, const AP& p, const Prob& pr, int lane, int wave, int row0 = 0) {
+__device__ __forceinline__ void fwd3_stage_kv(char* gK, char* gV, const AP& p, const Prob& pr, int lane, int wave, int row0) {
   typedef __attribute__((address_space(3))) char lds_c;
-  const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
-  const unsigned ld_bytes = (unsigned)(p.ldqkv * 2), voff_v = (unsigned)(p.H * DH * 2);
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
+  const unsigned ld_bytes = (unsigned)(p.ldqkv * 2), voff_v = v_off(p);
+  const __amdgpu_buffer_rsrc_t rs = rsrc_kv(p, pr);
   constexpr int NPASS = FG / 8;                               // 26 passes of 8 rows per operand
 #pragma unroll
   for (int j = 0; j < (NPASS + F3W - 1) / F3W; ++j) {
@@ -335,14 +379,14 @@ __device__ __forceinline__ void fwd3_stage_kv(char* gK, char* gV, const AP& p, c
     if (pass < NPASS) {
       const int row = pass * 8 + (lane >> 3);
       const int c = (lane & 7) ^ swz128(row);
-      const unsigned off = row0 + row < p.R ? (unsigned)tok_of(p, pr.n, row0 + row) * ld_bytes + c * 16 : 0xFFFFFF00u;
+      const unsigned off = row0 + row < p.R ? (unsigned)tok_of(p, pr.n, row0 + row) * ld_bytes + c * 16 : OOB;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_c*)(gK + pass * 1024), 16, off, 0, 0, 0);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_c*)(gV + pass * 1024), 16, off, voff_v, 0, 0);
     }
   }
 }
 // the wave's Q rows as B-operand fragments
-__device__ __forceinline__ void fwd3_load_q(bf16x8 (&qf)[F3T][2], const AP& p, const Prob& pr, int wave, int lane, int tile0 = 0) {
+__device__ __forceinline__ void fwd3_load_q(bf16x8 (&qf)[F3T][2], const AP& p, const Prob& pr, int wave, int lane, int tile0) {
   const bf16_t* qbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
 #pragma unroll
   for (int i = 0; i < F3T; ++i) {
@@ -378,7 +422,7 @@ constexpr float M_INIT = -1e30f;
 // query rows AND the group holds the proxy keys (query block 0, wave 0, key group 0)
 template <int NS, int NTL, bool TAIL>
 __device__ __forceinline__ void fwd3_step(FwdState (&st)[F3T], const AP& p, int frame, const char* gK, const char* gV,
-                                          const bf16x8 (&qf)[F3T][2], int t0, bool corner, int lane, int kb0 = 0) {
+                                          const bf16x8 (&qf)[F3T][2], int t0, bool corner, int lane, int kb0) {
   const int g = lane >> 4, i16 = lane & 15, kb = kb0 + t0 * 16;
   f32x4 s[NTL][NS];
   {
@@ -466,53 +510,39 @@ __device__ __forceinline__ void fwd3_step(FwdState (&st)[F3T], const AP& p, int 
   }
 }
 
-// all key steps of one problem for the wave's NTL tiles, then normalise and store
+// The key walk of one staged group for the wave's NTL query tiles: ng sub-tiles whose first one is global key row kb0.  Full
+// 4-sub-tile steps, then the rest: 1..4 sub-tiles, the last of which may reach past R.  A 2- or 3-sub-tile rest runs the 4-wide step
+// with its surplus keys masked (rows < FG of the images are always written -- zeros past R -- and t0 <= 8 there).
+template <int NTL>
+__device__ __forceinline__ void fwd3_walk(FwdState (&st)[F3T], const AP& p, int frame, const char* gK, const char* gV,
+                                          const bf16x8 (&qf)[F3T][2], int ng, int kb0, bool corner, int lane) {
+  int t0 = 0;
+  for (; t0 + 4 <= ng && kb0 + (t0 + 4) * 16 <= p.R; t0 += 4) fwd3_step<4, NTL, false>(st, p, frame, gK, gV, qf, t0, corner, lane, kb0);
+  if (t0 < ng) {
+    if (ng - t0 == 1) {
+      if (kb0 + ng * 16 > p.R) fwd3_step<1, NTL, true>(st, p, frame, gK, gV, qf, t0, corner, lane, kb0);
+      else                     fwd3_step<1, NTL, false>(st, p, frame, gK, gV, qf, t0, corner, lane, kb0);
+    } else {
+      fwd3_step<4, NTL, true>(st, p, frame, gK, gV, qf, t0, corner, lane, kb0);
+    }
+  }
+}
+// the epilogue of the wave's nt finished query tiles (tile0 + wave, + F3W)
+__device__ __forceinline__ void fwd3_finish(const FwdState (&st)[F3T], const AP& p, const Prob& pr, int prob, int tile0, int nt,
+                                            int wave, int lane) {
+#pragma unroll
+  for (int i = 0; i < F3T; ++i)
+    if (i < nt) fwd_finish_row(st[i], p, pr, prob, (tile0 + wave + F3W * i) * 16 + (lane & 15), lane >> 4);
+}
+// one single-group problem for the wave's NTL tiles: all key steps, then normalise and store
 template <int NTL>
 __device__ __forceinline__ void fwd3_problem(const AP& p, const Prob& pr, int prob, const char* gK, const char* gV,
                                              const bf16x8 (&qf)[F3T][2], int nsub, int wave, int lane) {
-  const int i16 = lane & 15, g = lane >> 4;
   FwdState st[F3T];
 #pragma unroll
-  for (int i = 0; i < F3T; ++i) {
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) st[i].o[dt] = f32x4{0, 0, 0, 0};
-    st[i].m = M_INIT; st[i].l = 0.f;
-  }
-  int t0 = 0;
-  for (; t0 + 4 <= nsub && (t0 + 4) * 16 <= p.R; t0 += 4) fwd3_step<4, NTL, false>(st, p, pr.n, gK, gV, qf, t0, wave == 0, lane);
-  // the rest: 1..4 sub-tiles, the last of which may reach past R.  A 2- or 3-sub-tile rest runs the 4-wide step with its
-  // surplus keys masked (rows < FG of the images are always written -- zeros past R -- and t0 <= 8 here)
-  if (t0 < nsub) {
-    if (nsub - t0 == 1) {
-      if (nsub * 16 > p.R) fwd3_step<1, NTL, true>(st, p, pr.n, gK, gV, qf, t0, wave == 0, lane);
-      else                 fwd3_step<1, NTL, false>(st, p, pr.n, gK, gV, qf, t0, wave == 0, lane);
-    } else {
-      fwd3_step<4, NTL, true>(st, p, pr.n, gK, gV, qf, t0, wave == 0, lane);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NTL; ++i) {
-    const int rq = (wave + F3W * i) * 16 + i16;
-    const float m = st[i].m;
-    const float l = group_sum(st[i].l);
-    if (rq >= p.R) continue;
-    if (rq < p.M) {
-      float* part = p.ws0 + ((int64_t)prob * p.M + rq) * PART;
-      if (g == 0) { part[0] = m; part[1] = l; }
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store4(part + 2 + dt * 16 + 4 * g, st[i].o[dt]);
-      continue;
-    }
-    const int tok = tok_of(p, pr.n, rq);
-    const float inv = 1.0f / l;
-    bf16_t* orow = p.out + ((int64_t)pr.b * p.S + tok) * p.ldo + pr.h * DH;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) store4(orow + dt * 16 + 4 * g, st[i].o[dt] * inv);
-    if (g == 0) {
-      float* sp = p.stats + (((int64_t)pr.b * p.H + pr.h) * p.S + tok) * 2;
-      sp[0] = m; sp[1] = __logf(l);
-    }
-  }
+  for (int i = 0; i < F3T; ++i) fwd_init(st[i], M_INIT);
+  fwd3_walk<NTL>(st, p, pr.n, gK, gV, qf, nsub, 0, wave == 0, lane);
+  fwd3_finish(st, p, pr, prob, 0, NTL, wave, lane);
 }
 
 __global__ __launch_bounds__(F3THR, 2) void attn_fwd3_kernel(AP p) {
@@ -527,11 +557,11 @@ __global__ __launch_bounds__(F3THR, 2) void attn_fwd3_kernel(AP p) {
   bf16x8 qf[F3T][2], qn[F3T][2];
   {
     const Prob pr(p, prob);
-    fwd3_stage_kv(smem, smem + FG * 128, p, pr, lane, wave);
-    fwd3_load_q(qf, p, pr, wave, lane);
+    fwd3_stage_kv(smem, smem + FG * 128, p, pr, lane, wave, 0);
+    fwd3_load_q(qf, p, pr, wave, lane, 0);
   }
-  unsigned long long* tr = (p.ws2 && (int)blockIdx.x == (int)gridDim.x / 2 && (wave == 0 || wave == 7) && lane == 0)
-                               ? reinterpret_cast<unsigned long long*>(p.ws2) + (wave ? 64 : 0) : nullptr;   // xp_debug_set_attn_trace
+  unsigned long long* tr = (p.tr && (int)blockIdx.x == (int)gridDim.x / 2 && (wave == 0 || wave == 7) && lane == 0)
+                               ? p.tr + (wave ? 64 : 0) : nullptr;
   int it = 0;
   for (;;) {
     if (tr && it < 8) tr[it * 4 + 0] = __builtin_amdgcn_s_memtime();
@@ -543,8 +573,8 @@ __global__ __launch_bounds__(F3THR, 2) void attn_fwd3_kernel(AP p) {
     if (next < p.nprob) {
       const Prob pn(p, next);
       char* nK = smem + (cur ^ 1) * F3_BUF;
-      fwd3_stage_kv(nK, nK + FG * 128, p, pn, lane, wave);
-      fwd3_load_q(qn, p, pn, wave, lane);
+      fwd3_stage_kv(nK, nK + FG * 128, p, pn, lane, wave, 0);
+      fwd3_load_q(qn, p, pn, wave, lane, 0);
     }
     if (tr && it < 8) tr[it * 4 + 2] = __builtin_amdgcn_s_memtime();
     if (nt == 2)      fwd3_problem<2>(p, pr, prob, gK, gK + FG * 128, qf, nsub, wave, lane);
@@ -587,7 +617,7 @@ __device__ __forceinline__ F4Stage f4_stage(const AP& p, int s, int nqb, int ngr
 
 __global__ __launch_bounds__(F3THR, 2) void attn_fwd4_kernel(AP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, i16 = lane & 15, g = lane >> 4;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ntiles = (p.R + 15) / 16;                     // sixteen-row tiles of a problem
   const int nqb = (ntiles + 2 * F3W - 1) / (2 * F3W);     // query blocks of 16 tiles
@@ -617,57 +647,19 @@ __global__ __launch_bounds__(F3THR, 2) void attn_fwd4_kernel(AP p) {
     const int nt = tile0 + wave >= ntiles ? 0 : (tile0 + wave + F3W >= ntiles ? 1 : 2);       // this wave's query tiles in the item
     if (sg.kg == 0) {
 #pragma unroll
-      for (int i = 0; i < F3T; ++i) {
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) st[i].o[dt] = f32x4{0, 0, 0, 0};
-        st[i].m = M_INIT; st[i].l = 0.f;
-      }
+      for (int i = 0; i < F3T; ++i) fwd_init(st[i], M_INIT);
     }
     // the key steps of this group: ng sub-tiles starting at global key row kb0
     const int kb0 = sg.kg * FG;
     const int ng = ntiles - sg.kg * (FG / 16) < FG / 16 ? ntiles - sg.kg * (FG / 16) : FG / 16;
     const bool corner = sg.qb == 0 && wave == 0 && sg.kg == 0;
-    auto run = [&](auto ntl_c) {
-      constexpr int NTL = decltype(ntl_c)::value;
-      int t0 = 0;
-      for (; t0 + 4 <= ng && kb0 + (t0 + 4) * 16 <= p.R; t0 += 4) fwd3_step<4, NTL, false>(st, p, pr.n, gK, gK + FG * 128, qf, t0, corner, lane, kb0);
-      if (t0 < ng) {
-        if (ng - t0 == 1) {
-          if (kb0 + ng * 16 > p.R) fwd3_step<1, NTL, true>(st, p, pr.n, gK, gK + FG * 128, qf, t0, corner, lane, kb0);
-          else                     fwd3_step<1, NTL, false>(st, p, pr.n, gK, gK + FG * 128, qf, t0, corner, lane, kb0);
-        } else {
-          fwd3_step<4, NTL, true>(st, p, pr.n, gK, gK + FG * 128, qf, t0, corner, lane, kb0);
-        }
-      }
-    };
-    if (nt == 2)      run(std::integral_constant<int, 2>{});
-    else if (nt == 1) run(std::integral_constant<int, 1>{});
-    if (sg.kg == ngrp - 1) {                               // last key group of the item: normalise and store
-#pragma unroll
-      for (int i = 0; i < F3T; ++i) {
-        if (i >= nt) continue;
-        const int rq = (tile0 + wave + F3W * i) * 16 + i16;
-        const float m = st[i].m;
-        const float l = group_sum(st[i].l);
-        if (rq >= p.R) continue;
-        if (rq < p.M) {
-          float* part = p.ws0 + ((int64_t)sg.prob * p.M + rq) * PART;
-          if (g == 0) { part[0] = m; part[1] = l; }
-#pragma unroll
-          for (int dt = 0; dt < 4; ++dt) store4(part + 2 + dt * 16 + 4 * g, st[i].o[dt]);
-          continue;
-        }
-        const int tok = tok_of(p, pr.n, rq);
-        const float inv = 1.0f / l;
-        bf16_t* orow = p.out + ((int64_t)pr.b * p.S + tok) * p.ldo + pr.h * DH;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) store4(orow + dt * 16 + 4 * g, st[i].o[dt] * inv);
-        if (g == 0) {
-          float* sp = p.stats + (((int64_t)pr.b * p.H + pr.h) * p.S + tok) * 2;
-          sp[0] = m; sp[1] = __logf(l);
-        }
-      }
-    }
+    // (dispatched through a generic lambda: with the two instantiations called directly hipcc allocates this kernel 6 more VGPRs,
+    // 231 against the 225 it has had.  That is an accident of this compiler's allocation, not a property of the code: re-check the
+    // kernel's .vgpr_count after a compiler update, and call fwd3_walk<NTL> directly if the difference is gone)
+    auto walk = [&](auto ntl) { fwd3_walk<decltype(ntl)::value>(st, p, pr.n, gK, gK + FG * 128, qf, ng, kb0, corner, lane); };
+    if (nt == 2)      walk(std::integral_constant<int, 2>{});
+    else if (nt == 1) walk(std::integral_constant<int, 1>{});
+    if (sg.kg == ngrp - 1) fwd3_finish(st, p, pr, sg.prob, tile0, nt, wave, lane);      // last key group of the item
     if (!nx.valid) break;
     if (nx.kg == 0) {
 #pragma unroll
@@ -713,27 +705,27 @@ __global__ __launch_bounds__(256) void attn_fwd_merge_kernel(AP p) {
 // in LDS in groups of up to 208 rows by branch-free buffer loads, 64-row steps with a 16-row tail (16x16x16 MFMA), query
 // blocks of one problem 8 workgroup ids apart.  LDS 53-56 KiB: two workgroups per CU.
 
-// cooperative load of rows [row0, row0 + nrows) of TWO row-major operands (own resource / pitch each) into linear swizzled
-// images; rows >= R or >= nrows read as zero.
-__device__ __forceinline__ void stage_rows2(char* gA, char* gB, __amdgpu_buffer_rsrc_t ra, unsigned lda_bytes,
-                                            __amdgpu_buffer_rsrc_t rb, unsigned ldb_bytes, const AP& p, const Prob& pr,
-                                            int row0, int nrows, int tid) {
+// cooperative load of rows [row0, row0 + nrows) of Q and dO (own resource / pitch each) into linear swizzled images; rows >= R or
+// >= nrows read as zero.
+__device__ __forceinline__ void load_qdo(char* gQ, char* gDO, const AP& p, const Prob& pr, int row0, int nrows, int tid) {
   constexpr int NJ = (FG * 8 + FTHR - 1) / FTHR;
-  u32x4 va[NJ], vb[NJ];
+  const __amdgpu_buffer_rsrc_t rq = rsrc_q(p, pr), rdo = rsrc_o(p, pr, p.dout);
+  const unsigned ldq_bytes = (unsigned)(p.ldqkv * 2), ldo_bytes = (unsigned)(p.ldo * 2);
+  u32x4 vq[NJ], vd[NJ];
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int e = tid + j * FTHR, row = e >> 3, c = e & 7, r = row0 + row;
     const bool ok = row < nrows && r < p.R;
     const unsigned tok = ok ? (unsigned)tok_of(p, pr.n, r) : 0u;
-    va[j] = __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? tok * lda_bytes + c * 16 : 0xFFFFFF00u, 0, 0);
-    vb[j] = __builtin_amdgcn_raw_buffer_load_b128(rb, ok ? tok * ldb_bytes + c * 16 : 0xFFFFFF00u, 0, 0);
+    vq[j] = __builtin_amdgcn_raw_buffer_load_b128(rq, ok ? tok * ldq_bytes + c * 16 : OOB, 0, 0);
+    vd[j] = __builtin_amdgcn_raw_buffer_load_b128(rdo, ok ? tok * ldo_bytes + c * 16 : OOB, 0, 0);
   }
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const int e = tid + j * FTHR, row = e >> 3, c = e & 7;
     if (row < FG) {
-      *reinterpret_cast<u32x4*>(gA + tile128_off(row, c)) = va[j];
-      *reinterpret_cast<u32x4*>(gB + tile128_off(row, c)) = vb[j];
+      *reinterpret_cast<u32x4*>(gQ + tile128_off(row, c)) = vq[j];
+      *reinterpret_cast<u32x4*>(gDO + tile128_off(row, c)) = vd[j];
     }
   }
 }
@@ -768,6 +760,10 @@ __device__ __forceinline__ void wg_colsum64(f32x4 (&v)[4], float* red, float* ds
     for (int w = 0; w < FW; ++w) a += red[w * DH + tid];
     dst[tid] = a;
   }
+}
+// the three bias column-sum partial rows (q | k | v, H * DH floats each) of own-row block blk of problem pr: columns of head pr.h
+__device__ __forceinline__ float* cs_row(const AP& p, const Prob& pr, int blk) {
+  return p.cs + ((int64_t)(pr.b * p.N + pr.n) * p.nq + blk) * (3 * p.H * DH) + pr.h * DH;
 }
 __device__ __forceinline__ f32x4 round_bf16(f32x4 x) {
   return f32x4{(float)(bf16_t)x[0], (float)(bf16_t)x[1], (float)(bf16_t)x[2], (float)(bf16_t)x[3]};
@@ -883,18 +879,12 @@ __global__ __launch_bounds__(FTHR, 4) void attn_bwd_dkv_kernel(AP p) {
 
   const int nsub = (p.R + 15) / 16;
   const int s0 = p.mode == XP_ATTN_CAUSAL ? (kb / 64) * 4 : 0;     // queries before the first key never see it
-  const bf16_t* qbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
-  const bf16_t* dobase = p.dout + (int64_t)pr.b * p.S * p.ldo + pr.h * DH;
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(qbase), 0, (unsigned)(((int64_t)p.S * p.ldqkv - pr.h * DH) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(dobase), 0, (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
   const int wkey0 = kb + wave * 16;
   const bool wave_active = wkey0 < p.R;
   for (int g0 = s0; g0 < nsub; g0 += FG / 16) {
     const int ng = nsub - g0 < FG / 16 ? nsub - g0 : FG / 16;
     if (g0 != s0) __syncthreads();
-    stage_rows2(gQ, gDO, rq, (unsigned)(p.ldqkv * 2), rdo, (unsigned)(p.ldo * 2), p, pr, g0 * 16, ng * 16, tid);
+    load_qdo(gQ, gDO, p, pr, g0 * 16, ng * 16, tid);
     if (tid < FG) {
       const int r = g0 * 16 + tid;
       float mm = 0.f, lg = 0.f, dl = 0.f;
@@ -912,13 +902,8 @@ __global__ __launch_bounds__(FTHR, 4) void attn_bwd_dkv_kernel(AP p) {
       else              dkv_step<2>(st, p, pr, gQ, gDO, gM, gLg, gDl, kf, vf, t0, qb, rk, kvalid, kpad, wkey0, lane);
     }
   }
-  const bool partial_row = kvalid && p.mode == XP_ATTN_PROXY && rk < p.M;      // proxy keys: per-frame partials, reduced later
-  const bool final_row = kvalid && !partial_row;
-  if (partial_row) {
-    float* part = p.ws2 + ((int64_t)prob * p.M + rk) * (2 * DH);
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) { store4(part + dt * 16 + 4 * g, st.dk[dt]); store4(part + DH + dt * 16 + 4 * g, st.dv[dt]); }
-  }
+  const bool partial_row = kvalid && proxy_row(p, rk), final_row = kvalid && !partial_row;
+  if (partial_row) store_dkv_partial(p, prob, rk, g, st.dk, st.dv);
   if (final_row) {
     bf16_t* base = p.dqkv + ktok * p.ldqkv + pr.h * DH;
 #pragma unroll
@@ -928,7 +913,7 @@ __global__ __launch_bounds__(FTHR, 4) void attn_bwd_dkv_kernel(AP p) {
     }
   }
   if (p.cs) {          // bias gradients of k_proj / v_proj: column sums of the rows just stored (as stored: rounded)
-    float* row = p.cs + ((int64_t)(pr.b * p.N + pr.n) * p.nq + blk) * (3 * p.H * DH) + pr.h * DH;
+    float* row = cs_row(p, pr, blk);
     f32x4 v[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) v[dt] = final_row ? round_bf16(st.dk[dt]) : f32x4{0, 0, 0, 0};
@@ -1020,20 +1005,14 @@ __global__ __launch_bounds__(FTHR, 4) void attn_bwd_dq_kernel(AP p) {
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0, 0, 0, 0};
 
-  int nsub = (p.R + 15) / 16;
-  if (p.mode == XP_ATTN_CAUSAL) { const int lim = (qb + FQ - 1) / 16 + 1; nsub = nsub < lim ? nsub : lim; }
-  const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
-  const unsigned ld_bytes = (unsigned)(p.ldqkv * 2);
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
-  const unsigned voff_v = (unsigned)(p.H * DH * 2);
+  const int nsub = own_query_nsub(p, qb);
   const int wrow0 = qb + wave * 16;
   const bool wave_active = wrow0 < p.R;
   for (int g0 = 0; g0 < nsub; g0 += FG / 16) {
     const int ng = nsub - g0 < FG / 16 ? nsub - g0 : FG / 16;
     if (g0) __syncthreads();
-    fwd_load_kv(gK, gV, rs, ld_bytes, voff_v, p, pr, g0 * 16, ng * 16, tid);
-    if (tid < FG) { const int r = g0 * 16 + tid; gPad[tid] = (p.pad && r < p.R) ? (p.pad[(int64_t)pr.b * p.S + r] == 0) : 0; }
+    fwd_load_kv(gK, gV, p, pr, g0 * 16, ng * 16, tid);
+    fill_pad_flags(gPad, p, pr, g0, tid);
     __syncthreads();
     if (!wave_active) continue;
     for (int t0 = 0; t0 < ng; t0 += 4) {
@@ -1043,20 +1022,15 @@ __global__ __launch_bounds__(FTHR, 4) void attn_bwd_dq_kernel(AP p) {
       else         dq_step<4>(dq, p, pr, gK, gV, gPad, qf, dof, mq, lgq, dlq, t0, kb, rq, qvalid, wrow0, lane);
     }
   }
-  const bool partial_row = qvalid && p.mode == XP_ATTN_PROXY && rq < p.M;
-  const bool final_row = qvalid && !partial_row;
-  if (partial_row) {
-    float* part = p.ws1 + ((int64_t)prob * p.M + rq) * DH;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) store4(part + dt * 16 + 4 * g, dq[dt]);
-  }
+  const bool partial_row = qvalid && proxy_row(p, rq), final_row = qvalid && !partial_row;      // proxy rows: per-frame partials, reduced later
+  if (partial_row) store_dq_partial(p, prob, rq, g, dq);
   if (final_row) {
     bf16_t* base = p.dqkv + qtok * p.ldqkv + pr.h * DH;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store4(base + dt * 16 + 4 * g, dq[dt] * p.q_scale);
   }
   if (p.cs) {          // bias gradient of q_proj
-    float* row = p.cs + ((int64_t)(pr.b * p.N + pr.n) * p.nq + blk) * (3 * p.H * DH) + pr.h * DH;
+    float* row = cs_row(p, pr, blk);
     f32x4 v[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) v[dt] = final_row ? round_bf16(dq[dt] * p.q_scale) : f32x4{0, 0, 0, 0};
@@ -1125,23 +1099,24 @@ constexpr int B5_STG_WAVE = 32 * B5_STG_ROW;                   // one wave's two
 constexpr int B5_OFF_STG = B5_OFF_NEXT + 16;
 constexpr int B5_LDS = B5_OFF_STG + B5W * B5_STG_WAVE;
 
-// rows [0, FG) of one row-major operand (the 64 elements of a (token, head) slice; rows >= R read as zero) -> linear swizzled LDS
-// image by LDS-DMA, one wave instruction = 8 rows x 128 B.  The per-lane part of the source offset does not depend on the problem
+// rows of one row-major operand (the 64 elements of a (token, head) slice; rows >= R read as zero) -> linear swizzled LDS image of a
+// group of ROWS rows by LDS-DMA, one wave instruction = 8 rows x 128 B.  The per-lane part of the source offset does not depend on the problem
 // (vrow: byte offset of the lane's row inside a 64-row block + its swizzled 16-byte chunk); the frame and the 64-row block ride in
 // the scalar offset, so a problem costs the loader no vector registers beyond the proxy rows of block 0 (voff0).
-// `j`: ONE of the four 64-row blocks (a wave instruction each): the caller spreads the pieces over its step loop -- issued in one
-// burst, the 8 instructions of a wave cost it ~3k cycles of queueing in front of the first MFMA (tools/attn_bwd_trace.py).
+// `j`: ONE 64-row block (a wave instruction) of the ROWS-row group whose first problem row is row0 (0, or a multiple of 64 in
+// attn_bwd6_kernel: only the problem's first block holds proxy rows): the caller spreads the pieces over its step loop -- issued in
+// one burst, the 8 instructions of a wave cost it ~3k cycles of queueing in front of the first MFMA (tools/attn_bwd_trace.py).
+template <int ROWS>
 __device__ __forceinline__ void b5_stage_piece(char* img, __amdgpu_buffer_rsrc_t rs, unsigned ld_bytes, unsigned soff, unsigned vrow,
-                                               unsigned voff0, int R, unsigned frame_off, int lane, int wave, int j) {
+                                               unsigned voff0, int R, unsigned frame_off, int lane, int wave, int row0, int j) {
   typedef __attribute__((address_space(3))) char lds_c;
-  constexpr int NPASS = FG / 8;
   const int pass = j * B5W + wave;
-  if (pass < NPASS) {
-    const int row = pass * 8 + (lane >> 3);
-    const unsigned v = row < R ? (j == 0 ? voff0 : vrow) : 0xFFFFFF00u;
-    const unsigned so = j == 0 ? soff : soff + frame_off + (unsigned)(j * 64) * ld_bytes;
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_c*)(img + pass * 1024), 16, v, so, 0, 0);
-  }
+  if (ROWS % (8 * B5W) != 0 && pass >= ROWS / 8) return;        // (a last block of fewer than 64 rows)
+  const int r0 = row0 + j * 64;
+  const int row = r0 + wave * 8 + (lane >> 3);
+  const unsigned v = row < R ? (r0 == 0 ? voff0 : vrow) : OOB;
+  const unsigned so = r0 == 0 ? soff : soff + frame_off + (unsigned)r0 * ld_bytes;
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_c*)(img + pass * 1024), 16, v, so, 0, 0);
 }
 constexpr int B5_PIECES = (FG / 8 + B5W - 1) / B5W;            // 4
 struct B5Lane { unsigned vq, vo, v0q, v0o; };                 // per-lane source offsets for pitch ldqkv / ldo (block >= 1 / block 0)
@@ -1154,61 +1129,44 @@ __device__ __forceinline__ void b5_lane_offsets(B5Lane& L, const AP& p, int n, i
   L.v0q = tok0 * (unsigned)(p.ldqkv * 2) + c16;
   L.v0o = tok0 * (unsigned)(p.ldo * 2) + c16;
 }
-// pieces [j0, j1) of the {K, V} image of problem pr / of its {Q, dO} image
-__device__ __forceinline__ void b5_stage_kv(char* X, const AP& p, const Prob& pr, int lane, int wave, int j0 = 0, int j1 = B5_PIECES) {
-  const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
+// piece j of the {K, V} images (X, X + IMG) of problem pr's ROWS-row group at problem row row0 / of its {Q, dO} images
+template <int ROWS, int IMG>
+__device__ __forceinline__ void b5_stage_kv(char* X, const AP& p, const Prob& pr, int row0, int j, int lane, int wave) {
+  const __amdgpu_buffer_rsrc_t rs = rsrc_kv(p, pr);
   B5Lane L; b5_lane_offsets(L, p, pr.n, lane, wave);
   const unsigned ld = (unsigned)(p.ldqkv * 2), fo = (unsigned)(pr.n * p.L) * ld;
-  for (int j = j0; j < j1; ++j) {
-    b5_stage_piece(X, rs, ld, 0, L.vq, L.v0q, p.R, fo, lane, wave, j);
-    b5_stage_piece(X + B5_IMG, rs, ld, (unsigned)(p.H * DH * 2), L.vq, L.v0q, p.R, fo, lane, wave, j);
-  }
+  b5_stage_piece<ROWS>(X, rs, ld, 0, L.vq, L.v0q, p.R, fo, lane, wave, row0, j);
+  b5_stage_piece<ROWS>(X + IMG, rs, ld, v_off(p), L.vq, L.v0q, p.R, fo, lane, wave, row0, j);
 }
-__device__ __forceinline__ void b5_stage_qdo(char* Y, const AP& p, const Prob& pr, int lane, int wave, int j0 = 0, int j1 = B5_PIECES) {
-  const bf16_t* qbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
-  const bf16_t* dobase = p.dout + (int64_t)pr.b * p.S * p.ldo + pr.h * DH;
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(qbase), 0, (unsigned)(((int64_t)p.S * p.ldqkv - pr.h * DH) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(dobase), 0, (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
+template <int ROWS, int IMG>
+__device__ __forceinline__ void b5_stage_qdo(char* Y, const AP& p, const Prob& pr, int row0, int j, int lane, int wave) {
+  const __amdgpu_buffer_rsrc_t rq = rsrc_q(p, pr), rdo = rsrc_o(p, pr, p.dout);
   B5Lane L; b5_lane_offsets(L, p, pr.n, lane, wave);
   const unsigned ldq = (unsigned)(p.ldqkv * 2), ldo = (unsigned)(p.ldo * 2);
-  for (int j = j0; j < j1; ++j) {
-    b5_stage_piece(Y, rq, ldq, 0, L.vq, L.v0q, p.R, (unsigned)(pr.n * p.L) * ldq, lane, wave, j);
-    b5_stage_piece(Y + B5_IMG, rdo, ldo, 0, L.vo, L.v0o, p.R, (unsigned)(pr.n * p.L) * ldo, lane, wave, j);
-  }
+  b5_stage_piece<ROWS>(Y, rq, ldq, 0, L.vq, L.v0q, p.R, (unsigned)(pr.n * p.L) * ldq, lane, wave, row0, j);
+  b5_stage_piece<ROWS>(Y + IMG, rdo, ldo, 0, L.vo, L.v0o, p.R, (unsigned)(pr.n * p.L) * ldo, lane, wave, row0, j);
 }
 
 // the wave's own query rows (tiles tile0 + wave, tile0 + wave + 8; rows >= R: zeros) straight from global memory: Q, dO, O fragments
 // and (m, log l)
 struct B5Own { bf16x8 q[2][2], d[2][2], o[2][2]; float m[2], lg[2]; };
-__device__ __forceinline__ void b5_load_own(B5Own& w, const AP& p, const Prob& pr, int wave, int lane, int tile0 = 0) {
+__device__ __forceinline__ void b5_load_own(B5Own& w, const AP& p, const Prob& pr, int wave, int lane, int tile0) {
   const int i16 = lane & 15, g = lane >> 4;
-  const bf16_t* qbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(qbase), 0, (unsigned)(((int64_t)p.S * p.ldqkv - pr.h * DH) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(p.dout + (int64_t)pr.b * p.S * p.ldo + pr.h * DH), 0, (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(p.out + (int64_t)pr.b * p.S * p.ldo + pr.h * DH), 0, (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rst = __builtin_amdgcn_make_buffer_rsrc(
-      p.stats + ((int64_t)pr.b * p.H + pr.h) * p.S * 2, 0, (unsigned)(p.S * 8), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rq = rsrc_q(p, pr), rdo = rsrc_o(p, pr, p.dout), ro = rsrc_o(p, pr, p.out), rst = rsrc_stats(p, pr);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int rq_ = (tile0 + wave + B5W * i) * 16 + i16;
     const bool ok = rq_ < p.R;
     const unsigned tok = (unsigned)tok_of(p, pr.n, ok ? rq_ : 0);
-    const unsigned oq = ok ? tok * (unsigned)(p.ldqkv * 2) + g * 16 : 0xFFFFFF00u;
-    const unsigned oo = ok ? tok * (unsigned)(p.ldo * 2) + g * 16 : 0xFFFFFF00u;
+    const unsigned oq = ok ? tok * (unsigned)(p.ldqkv * 2) + g * 16 : OOB;
+    const unsigned oo = ok ? tok * (unsigned)(p.ldo * 2) + g * 16 : OOB;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       w.q[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rq, oq + kk * 64, 0, 0));
       w.d[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rdo, oo + kk * 64, 0, 0));
       w.o[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ro, oo + kk * 64, 0, 0));
     }
-    const unsigned os = ok ? tok * 8u : 0xFFFFFF00u;          // rows >= R: (0, 0).  (two dword loads: hipcc lowers the b64 builtin
+    const unsigned os = ok ? tok * 8u : OOB;          // rows >= R: (0, 0).  (two dword loads: hipcc lowers the b64 builtin
     w.m[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rst, os, 0, 0));          //  to ONE dword, splat)
     w.lg[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rst, os + 4, 0, 0));
   }
@@ -1366,7 +1324,7 @@ __device__ __forceinline__ void b5_dkv_step(f32x4 (&dk)[2][4], f32x4 (&dv)[2][4]
 // caller) and rows >= R are skipped.  cs[e]: the column sums of the rows stored (values as stored), columns 8 (lane & 7) + e,
 // summed over the lane's rows; b5_colsum_wave finishes them over the 8 row lanes.
 __device__ __forceinline__ void b5_store_tiles(const f32x4 (&acc)[2][4], float scale, char* stg, bf16_t* colbase, const AP& p, int n,
-                                               int wave, int lane, float (&cs)[8], int tile0 = 0) {
+                                               int wave, int lane, float (&cs)[8], int tile0) {
   const int i16 = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -1389,16 +1347,24 @@ __device__ __forceinline__ void b5_store_tiles(const f32x4 (&acc)[2][4], float s
     }
   }
 }
-// column sums of one wave: over the 8 row lanes (lane >> 3), then one LDS row per wave; the workgroup's fixed-order sum over the
-// waves happens after the next barrier (b5_colsum_finish)
-__device__ __forceinline__ void b5_colsum_wave(float (&cs)[8], float* red_row, int lane) {
+// __shfl_xor with the caller's lane id: __shfl_xor derives its own, and hipcc hoists the permute addresses of every call site out of
+// the persistent loop, where they are registers the step loops spill
+__device__ __forceinline__ float shfl_xor_lane(float v, int o, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ o) << 2, __builtin_bit_cast(int, v)));
+}
+// column sums of one wave: over the 8 row lanes (lane >> 3), then one LDS row per wave, set by the wave's first block of a problem and
+// added to by the later ones (attn_bwd6_kernel); the workgroup's fixed-order sum over the waves happens after the next barrier
+// (b5_colsum_finish_dq / _dkv)
+__device__ __forceinline__ void b5_colsum_wave(float (&cs)[8], float* red_row, int lane, bool first) {
 #pragma unroll
   for (int o = 8; o < 64; o <<= 1)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) cs[e] += __shfl_xor(cs[e], o, 64);
+    for (int e = 0; e < 8; ++e) cs[e] += shfl_xor_lane(cs[e], o, lane);
   if (lane < 8) {
-    store4(red_row + lane * 8, f32x4{cs[0], cs[1], cs[2], cs[3]});
-    store4(red_row + lane * 8 + 4, f32x4{cs[4], cs[5], cs[6], cs[7]});
+    f32x4 a = {cs[0], cs[1], cs[2], cs[3]}, b = {cs[4], cs[5], cs[6], cs[7]};
+    if (!first) { a += *reinterpret_cast<const f32x4*>(red_row + lane * 8); b += *reinterpret_cast<const f32x4*>(red_row + lane * 8 + 4); }
+    store4(red_row + lane * 8, a);
+    store4(red_row + lane * 8 + 4, b);
   }
 }
 __device__ __forceinline__ void b5_colsum_finish(const float* red, float* dst, int d) {
@@ -1407,16 +1373,48 @@ __device__ __forceinline__ void b5_colsum_finish(const float* red, float* dst, i
   for (int w = 0; w < B5W; ++w) a += red[w * DH + d];
   dst[d] = a;
 }
+// The three bias column-sum rows of a problem go to block 0 of its p.nq rows.  Threads [0, DH): problem pr's dQ sums, and zeros to the
+// other blocks' rows of the two-kernel layout, which this launch does not use
+__device__ __forceinline__ void b5_colsum_finish_dq(const AP& p, const Prob& pr, const float* red, int tid) {
+  if (!(p.cs && tid < DH)) return;
+  float* row = cs_row(p, pr, 0);
+  b5_colsum_finish(red, row, tid);
+  for (int blk = 1; blk < p.nq; ++blk)
+    for (int j = 0; j < 3; ++j) row[(int64_t)blk * 3 * p.H * DH + j * p.H * DH + tid] = 0.f;
+}
+// threads [0, 2 DH): the dK / dV sums of problem prev (< 0: none yet)
+__device__ __forceinline__ void b5_colsum_finish_dkv(const AP& p, int prev, const float* red, int tid) {
+  if (!(p.cs && prev >= 0 && tid < 2 * DH)) return;
+  const Prob pv(p, prev);
+  float* row = cs_row(p, pv, 0);
+  if (tid < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid);
+  else          b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid - DH);
+}
 
-// the three bias column-sum rows of one problem (block 0 of its p.nq rows; the other blocks of the two-kernel layout are zero)
-__device__ __forceinline__ float* b5_cs_row(const AP& p, const Prob& pr) {
-  return p.cs + ((int64_t)(pr.b * p.N + pr.n) * p.nq) * (3 * p.H * DH) + pr.h * DH;
+// The row constants of the wave's own query tiles (tile0 + wave, + 8): c = -(m + log l) and nd = -delta, delta = sum_d dO * O from the
+// fragments in registers (each of the 4 lanes of a row holds 16 of the 64 d).  They also go to the LDS array sC = c[CROWS] | nd[CROWS]
+// for phase B (rows >= R: zeros).
+template <int CROWS>
+__device__ __forceinline__ void b5_own_constants(float (&c)[2], float (&nd)[2], const B5Own& w, float* sC, int tile0, int wave, int lane) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    float dl = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dl += (float)w.d[i][kk][e] * (float)w.o[i][kk][e];
+    dl += shfl_xor_lane(dl, 16, lane);
+    dl += shfl_xor_lane(dl, 32, lane);
+    c[i] = -(w.m[i] + w.lg[i]); nd[i] = -dl;
+    const int rq = (tile0 + wave + B5W * i) * 16 + (lane & 15);
+    if ((lane >> 4) == 0 && rq < CROWS) { sC[rq] = c[i]; sC[CROWS + rq] = nd[i]; }
+  }
 }
 
 __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* X = smem; char* Y = smem + 2 * B5_IMG;
-  float* sC = reinterpret_cast<float*>(smem + B5_OFF_STATS); float* sNd = sC + B5_ROWS;
+  float* sC = reinterpret_cast<float*>(smem + B5_OFF_STATS);   // c[B5_ROWS] | nd[B5_ROWS]
   float* red = reinterpret_cast<float*>(smem + B5_OFF_RED);
   int* sNext = reinterpret_cast<int*>(smem + B5_OFF_NEXT);
   char* stg = smem + B5_OFF_STG + (threadIdx.x >> 6) * B5_STG_WAVE;
@@ -1432,8 +1430,8 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
   B5Own w;
   {
     const Prob pr(p, prob);
-    b5_stage_kv(X, p, pr, lane0, wave);
-    b5_load_own(w, p, pr, wave, lane0);
+    for (int j = 0; j < B5_PIECES; ++j) b5_stage_kv<FG, B5_IMG>(X, p, pr, 0, j, lane0, wave);
+    b5_load_own(w, p, pr, wave, lane0, 0);
   }
   unsigned long long* tr = (p.tr && (int)blockIdx.x == (int)gridDim.x / 2 && (wave == 0 || wave == 7) && lane0 == 0)
                                ? p.tr + (wave ? 64 : 0) : nullptr;
@@ -1451,31 +1449,16 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
     __syncthreads();                                       // X (K, V of prob) has landed; every wave is done with Y and `red`
     B5_STAMP(1);
     const Prob pr(p, prob);
-    if (p.cs && prev >= 0 && tid < 2 * DH) {               // previous problem: dK / dV column sums
-      const Prob pv(p, prev);
-      float* row = b5_cs_row(p, pv);
-      if (tid < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid);
-      else          b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid - DH);
-    }
+    b5_colsum_finish_dkv(p, prev, red, tid);               // previous problem
     const bool corner = wave == 0 && pr.n != 0;
     bf16x8 kf[2][2], vf[2][2];
     {
-      // ---- phase A: dQ of the wave's query tiles; delta = sum_d dO * O from the fragments in registers (each of the 4 lanes of a
-      // row holds 16 of the 64 d); the row constants also go to LDS for phase B (rows >= R: zeros)
+      // ---- phase A: dQ of the wave's query tiles
+      float c1[2], nd1[2];
+      b5_own_constants<B5_ROWS>(c1, nd1, w, sC, 0, wave, lane);
       f32x4 c4[2], nd4[2];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        float dl = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) dl += (float)w.d[i][kk][e] * (float)w.o[i][kk][e];
-        dl = group_sum(dl);
-        const float c = -(w.m[i] + w.lg[i]);
-        c4[i] = f32x4{c, c, c, c}; nd4[i] = f32x4{-dl, -dl, -dl, -dl};
-        const int rq = (wave + B5W * i) * 16 + i16;
-        if (g == 0 && rq < B5_ROWS) { sC[rq] = c; sNd[rq] = -dl; }
-      }
+      for (int i = 0; i < 2; ++i) { c4[i] = f32x4{c1[i], c1[i], c1[i], c1[i]}; nd4[i] = f32x4{nd1[i], nd1[i], nd1[i], nd1[i]}; }
       f32x4 dq[2][4];
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -1487,24 +1470,20 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
       const int nfull = p.R / 32 < nsteps ? p.R / 32 : nsteps;
       int st = 0;
       for (; st < nfull; ++st) {
-        if (st < B5_PIECES) b5_stage_qdo(Y, p, pr, lane, wave, st, st + 1);
+        if (st < B5_PIECES) b5_stage_qdo<FG, B5_IMG>(Y, p, pr, 0, st, lane, wave);
         if (active) b5_dq_step<false>(dq, p, X + st * (32 * 128), w, c4, nd4, 2 * st, corner, lane);
       }
       if (st < nsteps) {
-        if (st < B5_PIECES) b5_stage_qdo(Y, p, pr, lane, wave, st, st + 1);
+        if (st < B5_PIECES) b5_stage_qdo<FG, B5_IMG>(Y, p, pr, 0, st, lane, wave);
         if (active) b5_dq_step<true>(dq, p, X + st * (32 * 128), w, c4, nd4, 2 * st, corner, lane);
         ++st;
       }
-      if (st < B5_PIECES) b5_stage_qdo(Y, p, pr, lane, wave, st, B5_PIECES);
+      for (; st < B5_PIECES; ++st) b5_stage_qdo<FG, B5_IMG>(Y, p, pr, 0, st, lane, wave);
       B5_STAMP(3);
-      if (wave == 0 && i16 < p.M && i16 < p.R) {              // proxy query rows: per-frame partials, reduced later
-        float* part = p.ws1 + ((int64_t)prob * p.M + i16) * DH;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) store4(part + dt * 16 + 4 * g, dq[0][dt]);
-      }
+      if (wave == 0 && i16 < p.M && i16 < p.R) store_dq_partial(p, prob, i16, g, dq[0]);      // proxy query rows
       float cs[8];
-      b5_store_tiles(dq, p.q_scale, stg, p.dqkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH, p, pr.n, wave, lane, cs);
-      if (p.cs) b5_colsum_wave(cs, red + wave * DH, lane);
+      b5_store_tiles(dq, p.q_scale, stg, p.dqkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH, p, pr.n, wave, lane, cs, 0);
+      if (p.cs) b5_colsum_wave(cs, red + wave * DH, lane, true);
       // the wave's own key rows for phase B, out of the image (X is overwritten after the barrier)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -1522,12 +1501,7 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
     asm volatile("" : "+v"(lane));
     tid = wave * 64 + lane; i16 = lane & 15; g = lane >> 4;
     const int next = *sNext;
-    if (p.cs && tid < DH) {
-      float* row = b5_cs_row(p, pr);
-      b5_colsum_finish(red, row, tid);
-      for (int blk = 1; blk < p.nq; ++blk)                 // rows of the two-kernel layout this launch does not use
-        for (int j = 0; j < 3; ++j) row[(int64_t)blk * 3 * p.H * DH + j * p.H * DH + tid] = 0.f;
-    }
+    b5_colsum_finish_dq(p, pr, red, tid);
     {
       // ---- phase B: dK, dV of the wave's key tiles
       f32x4 dk[2][4], dv[2][4];
@@ -1539,7 +1513,7 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
       // scalar: the Y images and the row constants live above the 64 KiB an LDS instruction's immediate reaches, and hipcc otherwise
       // re-associates every read into (lane part + step) + image constant -- one v_add per read, 25 per step.
       for (int st = 0; st < nsteps || st < B5_PIECES; ++st) {
-        if (st < B5_PIECES && next < p.nprob) { const Prob pn(p, next); b5_stage_kv(X, p, pn, lane, wave, st, st + 1); }
+        if (st < B5_PIECES && next < p.nprob) { const Prob pn(p, next); b5_stage_kv<FG, B5_IMG>(X, p, pn, 0, st, lane, wave); }
         if (active && st < nsteps) {
           unsigned yo = 2u * B5_IMG + (unsigned)st * (32 * 128), co = (unsigned)B5_OFF_STATS + (unsigned)st * (32 * 4);
           asm volatile("" : "+s"(yo), "+s"(co));
@@ -1549,18 +1523,14 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
       B5_STAMP(6);
       // the next problem's own query rows: issued here, behind the step loop (48 registers the loop does not have), in front of the
       // stores and the column sums that cover most of their latency
-      if (next < p.nprob) { const Prob pn(p, next); b5_load_own(w, p, pn, wave, lane); }
-      if (wave == 0 && i16 < p.M && i16 < p.R) {              // proxy keys: per-frame partials, reduced later
-        float* part = p.ws2 + ((int64_t)prob * p.M + i16) * (2 * DH);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) { store4(part + dt * 16 + 4 * g, dk[0][dt]); store4(part + DH + dt * 16 + 4 * g, dv[0][dt]); }
-      }
+      if (next < p.nprob) { const Prob pn(p, next); b5_load_own(w, p, pn, wave, lane, 0); }
+      if (wave == 0 && i16 < p.M && i16 < p.R) store_dkv_partial(p, prob, i16, g, dk[0], dv[0]);      // proxy keys
       bf16_t* colbase = p.dqkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH;
       float cs[8];
-      b5_store_tiles(dk, 1.0f, stg, colbase + (int64_t)p.H * DH, p, pr.n, wave, lane, cs);
-      if (p.cs) b5_colsum_wave(cs, red + (B5W + wave) * DH, lane);
-      b5_store_tiles(dv, 1.0f, stg, colbase + (int64_t)2 * p.H * DH, p, pr.n, wave, lane, cs);
-      if (p.cs) b5_colsum_wave(cs, red + (2 * B5W + wave) * DH, lane);
+      b5_store_tiles(dk, 1.0f, stg, colbase + (int64_t)p.H * DH, p, pr.n, wave, lane, cs, 0);
+      if (p.cs) b5_colsum_wave(cs, red + (B5W + wave) * DH, lane, true);
+      b5_store_tiles(dv, 1.0f, stg, colbase + (int64_t)2 * p.H * DH, p, pr.n, wave, lane, cs, 0);
+      if (p.cs) b5_colsum_wave(cs, red + (2 * B5W + wave) * DH, lane, true);
     }
     B5_STAMP(7);
     ++it;
@@ -1571,13 +1541,7 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd5_kernel(AP p, int* counter)
 #undef B5_STAMP
   if (p.cs) {
     __syncthreads();
-    const int tid = tid0;
-    if (tid < 2 * DH) {
-      const Prob pv(p, prev);
-      float* row = b5_cs_row(p, pv);
-      if (tid < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid);
-      else          b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid - DH);
-    }
+    b5_colsum_finish_dkv(p, prev, red, tid0);
   }
 }
 
@@ -1620,78 +1584,31 @@ constexpr int B6_OFF_STG = B6_OFF_NEXT + 16;
 constexpr int B6_LDS = B6_OFF_STG + B5W * B5_STG_WAVE;
 static_assert(B6_LDS <= 160 * 1024, "attn_bwd6_kernel: LDS budget");
 
-// piece j (64 rows) of group grp of one row-major operand -> the group's swizzled LDS image (b5_stage_piece, with the group's first
-// row in the scalar offset; only the problem's first piece holds proxy rows)
-__device__ __forceinline__ void b6_stage_piece(char* img, __amdgpu_buffer_rsrc_t rs, unsigned ld_bytes, unsigned soff, unsigned vrow,
-                                               unsigned voff0, int R, unsigned frame_off, int lane, int wave, int grp, int j) {
-  typedef __attribute__((address_space(3))) char lds_c;
-  const int pass = j * B5W + wave;                              // < B6_G / 8
-  const int r0 = grp * B6_G + j * 64;
-  const int row = r0 + wave * 8 + (lane >> 3);
-  const unsigned v = row < R ? (r0 == 0 ? voff0 : vrow) : 0xFFFFFF00u;
-  const unsigned so = r0 == 0 ? soff : soff + frame_off + (unsigned)r0 * ld_bytes;
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_c*)(img + pass * 1024), 16, v, so, 0, 0);
-}
-// kind 0: piece j of the {K, V} image of group grp of problem pr; kind 1: of its {Q, dO} image
+// piece j of group grp of problem pr into buf.  kind 0: the {K, V} images; kind 1: the {Q, dO} images
 __device__ __forceinline__ void b6_stage(char* buf, const AP& p, const Prob& pr, int kind, int grp, int lane, int wave, int j) {
-  B5Lane L; b5_lane_offsets(L, p, pr.n, lane, wave);
-  const unsigned ldq = (unsigned)(p.ldqkv * 2), ldo = (unsigned)(p.ldo * 2);
-  if (kind == 0) {
-    const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
-    const unsigned fo = (unsigned)(pr.n * p.L) * ldq;
-    b6_stage_piece(buf, rs, ldq, 0, L.vq, L.v0q, p.R, fo, lane, wave, grp, j);
-    b6_stage_piece(buf + B6_IMG, rs, ldq, (unsigned)(p.H * DH * 2), L.vq, L.v0q, p.R, fo, lane, wave, grp, j);
-  } else {
-    const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(p.qkv + (int64_t)pr.b * p.S * p.ldqkv + pr.h * DH), 0, (unsigned)(((int64_t)p.S * p.ldqkv - pr.h * DH) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rdo = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<bf16_t*>(p.dout + (int64_t)pr.b * p.S * p.ldo + pr.h * DH), 0, (unsigned)(((int64_t)p.S * p.ldo - pr.h * DH) * 2), 0x00020000);
-    b6_stage_piece(buf, rq, ldq, 0, L.vq, L.v0q, p.R, (unsigned)(pr.n * p.L) * ldq, lane, wave, grp, j);
-    b6_stage_piece(buf + B6_IMG, rdo, ldo, 0, L.vo, L.v0o, p.R, (unsigned)(pr.n * p.L) * ldo, lane, wave, grp, j);
-  }
+  if (kind == 0) b5_stage_kv<B6_G, B6_IMG>(buf, p, pr, grp * B6_G, j, lane, wave);
+  else           b5_stage_qdo<B6_G, B6_IMG>(buf, p, pr, grp * B6_G, j, lane, wave);
 }
 // the wave's own key rows (tiles tile0 + wave, tile0 + wave + 8; rows >= R: zeros) straight from global memory: K and V fragments
 __device__ __forceinline__ void b6_load_own_kv(bf16x8 (&kf)[2][2], bf16x8 (&vf)[2][2], const AP& p, const Prob& pr, int wave, int lane,
                                                int tile0) {
   const int i16 = lane & 15, g = lane >> 4;
-  const bf16_t* kbase = p.qkv + (int64_t)pr.b * p.S * p.ldqkv + (int64_t)p.H * DH + pr.h * DH;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(kbase), 0, (unsigned)((int64_t)p.S * p.ldqkv * 2 - ((int64_t)p.H * DH + pr.h * DH) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = rsrc_kv(p, pr);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int rk = (tile0 + wave + B5W * i) * 16 + i16;
-    const unsigned o = rk < p.R ? (unsigned)tok_of(p, pr.n, rk) * (unsigned)(p.ldqkv * 2) + g * 16 : 0xFFFFFF00u;
+    const unsigned o = rk < p.R ? (unsigned)tok_of(p, pr.n, rk) * (unsigned)(p.ldqkv * 2) + g * 16 : OOB;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       kf[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, o + kk * 64, 0, 0));
-      vf[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, o + kk * 64, p.H * DH * 2, 0));
+      vf[i][kk] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, o + kk * 64, v_off(p), 0));
     }
-  }
-}
-// __shfl_xor with the caller's lane id: __shfl_xor derives its own, and hipcc hoists the permute addresses of every call site out of
-// the persistent loop, where they are registers the step loops spill
-__device__ __forceinline__ float b6_shfl_xor(float v, int o, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((lane ^ o) << 2, __builtin_bit_cast(int, v)));
-}
-// b5_colsum_wave over the blocks of a problem: the wave's LDS row is set by its first block and added to by the later ones
-__device__ __forceinline__ void b6_colsum_wave(float (&cs)[8], float* red_row, int lane, bool first) {
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) cs[e] += b6_shfl_xor(cs[e], o, lane);
-  if (lane < 8) {
-    f32x4 a = {cs[0], cs[1], cs[2], cs[3]}, b = {cs[4], cs[5], cs[6], cs[7]};
-    if (!first) { a += *reinterpret_cast<const f32x4*>(red_row + lane * 8); b += *reinterpret_cast<const f32x4*>(red_row + lane * 8 + 4); }
-    store4(red_row + lane * 8, a);
-    store4(red_row + lane * 8 + 4, b);
   }
 }
 
 __global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* sC = reinterpret_cast<float*>(smem + B6_OFF_STATS); float* sNd = sC + B6_RMAX;
+  float* sC = reinterpret_cast<float*>(smem + B6_OFF_STATS);   // c[B6_RMAX] | nd[B6_RMAX]
   float* red = reinterpret_cast<float*>(smem + B6_OFF_RED);
   int* sNext = reinterpret_cast<int*>(smem + B6_OFF_NEXT);
   char* stg = smem + B6_OFF_STG + (threadIdx.x >> 6) * B5_STG_WAVE;
@@ -1723,34 +1640,17 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter)
         // (per-lane constants re-derived per stage from a lane id the compiler cannot see through: see attn_bwd5_kernel)
         int lane = B6_LANE0;
         asm volatile("" : "+v"(lane));
-        const int tid = wave * 64 + lane, i16 = lane & 15, g = lane >> 4;
+        const int tid = wave * 64 + lane;
         __syncthreads();                                   // this stage's {K, V} group has landed; every wave is done with the other buffer
-        if (qb == 0 && kg == 0 && p.cs && prev >= 0 && tid < 2 * DH) {      // previous problem: dK / dV column sums
-          const Prob pv(p, prev);
-          float* row = b5_cs_row(p, pv);
-          if (tid < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid);
-          else          b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid - DH);
-        }
+        if (qb == 0 && kg == 0) b5_colsum_finish_dkv(p, prev, red, tid);      // previous problem
         if (kg == 0) {
-          // the block's own rows; delta = sum_d dO * O from the fragments in registers; the row constants also go to the
-          // problem-wide LDS arrays for phase B (rows >= R: zeros)
+          // the block's own rows, and their constants into the problem-wide LDS arrays
           b5_load_own(w, p, pr, wave, lane, qb * B6_BLK);
+          b5_own_constants<B6_RMAX>(c1, nd1, w, sC, qb * B6_BLK, wave, lane);
 #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            float dl = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-              for (int e = 0; e < 8; ++e) dl += (float)w.d[i][kk][e] * (float)w.o[i][kk][e];
-            dl += b6_shfl_xor(dl, 16, lane);
-            dl += b6_shfl_xor(dl, 32, lane);
-            const float c = -(w.m[i] + w.lg[i]);
-            c1[i] = c; nd1[i] = -dl;
-            const int rq = (qb * B6_BLK + wave + B5W * i) * 16 + i16;
-            if (g == 0 && rq < B6_RMAX) { sC[rq] = c; sNd[rq] = -dl; }
+          for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) dq[i][dt] = f32x4{0, 0, 0, 0};
-          }
         }
         // the stage after this one: the next key group; the next block's first; phase B's first {Q, dO} group
         const int nkind = kg + 1 < ngrp || qb + 1 < nblk ? 0 : 1, ngr = kg + 1 < ngrp ? kg + 1 : 0;
@@ -1793,14 +1693,10 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter)
       int lane = B6_LANE0;
       asm volatile("" : "+v"(lane));
       const int i16 = lane & 15, g = lane >> 4;
-      if (qb == 0 && wave == 0 && i16 < p.M) {             // proxy query rows: per-frame partials, reduced later
-        float* part = p.ws1 + ((int64_t)prob * p.M + i16) * DH;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) store4(part + dt * 16 + 4 * g, dq[0][dt]);
-      }
+      if (qb == 0 && wave == 0 && i16 < p.M) store_dq_partial(p, prob, i16, g, dq[0]);      // proxy query rows
       float cs[8];
       b5_store_tiles(dq, p.q_scale, stg, colbase, p, pr.n, wave, lane, cs, qb * B6_BLK);
-      if (p.cs) b6_colsum_wave(cs, red + wave * DH, lane, qb == 0);
+      if (p.cs) b5_colsum_wave(cs, red + wave * DH, lane, qb == 0);
     }
     // ---- phase B: dK, dV, one block of 16 key tiles after the other, each against every query group
     int next = p.nprob;
@@ -1816,12 +1712,7 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter)
         __syncthreads();                                   // this stage's {Q, dO} group has landed; the other buffer is free; (first
         if (kb == 0 && qg == 0) {                          //  stage) every row constant and dQ column sum of the problem is in LDS
           next = __builtin_amdgcn_readfirstlane(*sNext);
-          if (p.cs && tid < DH) {
-            float* row = b5_cs_row(p, pr);
-            b5_colsum_finish(red, row, tid);
-            for (int blk = 1; blk < p.nq; ++blk)           // rows of the two-kernel layout this launch does not use
-              for (int j = 0; j < 3; ++j) row[(int64_t)blk * 3 * p.H * DH + j * p.H * DH + tid] = 0.f;
-          }
+          b5_colsum_finish_dq(p, pr, red, tid);
         }
         if (qg == 0) {
           b6_load_own_kv(kf, vf, p, pr, wave, lane, kb * B6_BLK);
@@ -1852,16 +1743,12 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter)
       int lane = B6_LANE0;
       asm volatile("" : "+v"(lane));
       const int i16 = lane & 15, g = lane >> 4;
-      if (kb == 0 && wave == 0 && i16 < p.M) {             // proxy keys: per-frame partials, reduced later
-        float* part = p.ws2 + ((int64_t)prob * p.M + i16) * (2 * DH);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) { store4(part + dt * 16 + 4 * g, dk[0][dt]); store4(part + DH + dt * 16 + 4 * g, dv[0][dt]); }
-      }
+      if (kb == 0 && wave == 0 && i16 < p.M) store_dkv_partial(p, prob, i16, g, dk[0], dv[0]);      // proxy keys
       float cs[8];
       b5_store_tiles(dk, 1.0f, stg, colbase + (int64_t)p.H * DH, p, pr.n, wave, lane, cs, kb * B6_BLK);
-      if (p.cs) b6_colsum_wave(cs, red + (B5W + wave) * DH, lane, kb == 0);
+      if (p.cs) b5_colsum_wave(cs, red + (B5W + wave) * DH, lane, kb == 0);
       b5_store_tiles(dv, 1.0f, stg, colbase + (int64_t)2 * p.H * DH, p, pr.n, wave, lane, cs, kb * B6_BLK);
-      if (p.cs) b6_colsum_wave(cs, red + (2 * B5W + wave) * DH, lane, kb == 0);
+      if (p.cs) b5_colsum_wave(cs, red + (2 * B5W + wave) * DH, lane, kb == 0);
     }
     prev = prob;
     if (next >= p.nprob) break;
@@ -1869,13 +1756,7 @@ __global__ __launch_bounds__(B5THR, 2) void attn_bwd6_kernel(AP p, int* counter)
   }
   if (p.cs) {
     __syncthreads();
-    const int tid0 = wave * 64 + B6_LANE0;
-    if (tid0 < 2 * DH) {
-      const Prob pv(p, prev);
-      float* row = b5_cs_row(p, pv);
-      if (tid0 < DH) b5_colsum_finish(red + B5W * DH, row + p.H * DH, tid0);
-      else           b5_colsum_finish(red + 2 * B5W * DH, row + 2 * p.H * DH, tid0 - DH);
-    }
+    b5_colsum_finish_dkv(p, prev, red, wave * 64 + B6_LANE0);
   }
 #undef B6_LANE0
 }
@@ -2000,7 +1881,7 @@ extern "C" int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ld
   if ((rc = plan_attn_for(AttnCall{mode, B, H, S, M, N, L, dtype, pad_mask != nullptr, false}, 0, pl))) return rc;
   AP p = pl.geo;
   p.qkv = (const bf16_t*)qkv; p.ldqkv = ldqkv; p.out = (bf16_t*)out; p.ldo = ldo; p.stats = stats; p.pad = pad_mask;
-  p.ws0 = pl.part.in(workspace); p.ws2 = (float*)g_attn_trace;
+  p.ws0 = pl.part.in(workspace); p.tr = reinterpret_cast<unsigned long long*>(g_attn_trace);
   hipStream_t st = (hipStream_t)stream;
   if (pl.kernel == XP_ATTN_KERNEL_FWD3)      attn_fwd3_kernel<<<pl.grid, F3THR, pl.lds, st>>>(p);
   else if (pl.kernel == XP_ATTN_KERNEL_FWD4) attn_fwd4_kernel<<<pl.grid, F3THR, pl.lds, st>>>(p);
