@@ -57,7 +57,12 @@ enum {
   XP_EPI_BIAS_RESID = 4, /* C = acc + bias[n] + resid[m,n]                       (:455,:460)       */
   XP_EPI_GELU_BWD = 5,   /* C = acc * d/dx quick_gelu(resid[m,n])                                 */
   XP_EPI_PATCH = 6,      /* C = acc + tab1[t,n] + tab2[l,n], t=(m%c_grp)/tab_L, l=m%tab_L (:182-185) */
-  XP_EPI_SCALE = 7       /* C = acc * scale                                                      */
+  XP_EPI_SCALE = 7,      /* C = acc * scale                                                      */
+  /* hidden_act "gelu" (transformers' GELUActivation, the erf form; LAION / OpenCLIP conversions): kinds 3 and 5 with the other
+   * activation -- same operands, same planning (family, epilogue implementation, tile height, split, column sums, workspace), a
+   * kernel instantiation of their own.  Phi / phi: the standard normal CDF / density; all math fp32. */
+  XP_EPI_BIAS_GELU_ERF = 8, /* aux = acc + bias[n];  C = 0.5 aux (1 + erf(aux / sqrt 2)) = aux Phi(aux); aux == NULL as for kind 3 */
+  XP_EPI_GELU_ERF_BWD = 9   /* C = acc * (Phi(r) + r phi(r)), r = resid[m,n]:  d/dx of the above                                  */
 };
 
 typedef struct XpGemmDesc {
@@ -79,7 +84,7 @@ typedef struct XpGemmDesc {
   /* optional: column sums of the FINISHED outputs (fp32, before rounding), one partial row per half tile height of rows:
    * colsum_partials[r*N + n], r < xp_gemm_colsum_rows(desc).  This is the bias gradient of the Linear whose output
    * gradient this GEMM produces (autograd computes it as grad.sum(0), CLIP_ViP.py:383-396) without re-reading it.
-   * Only where xp_gemm_colsum_rows() > 0 (large bf16 problems, EPI_NONE / EPI_GELU_BWD); finish with
+   * Only where xp_gemm_colsum_rows() > 0 (large bf16 problems, EPI_NONE / EPI_GELU_BWD / EPI_GELU_ERF_BWD); finish with
    * xp_reduce_rows_batch. */
   float* colsum_partials;
   /* reserved (round 3 selected a second kernel set of the 256-wide family here; since round 4 there is one): ignored */
@@ -384,7 +389,11 @@ typedef struct XpLayerDims {
   int64_t M, N, L;                      /* XP_ATTN_PROXY: S == M + N*L; XP_ATTN_CAUSAL: pass 0, 1, S                 */
   int32_t attn_mode, dtype;
   float q_scale, ln_eps;                /* head_dim^-0.5 (:341), 1e-5                                                */
+  int32_t act;                          /* the MLP's activation (config.hidden_act, :388): XP_ACT_QUICK_GELU (0, what a zero-
+                                         * initialised struct means) or XP_ACT_GELU (erf GELU: the fc1 / dpre GEMMs take
+                                         * XP_EPI_BIAS_GELU_ERF / XP_EPI_GELU_ERF_BWD); any other value is an error         */
 } XpLayerDims;
+enum { XP_ACT_QUICK_GELU = 0, XP_ACT_GELU = 1 };
 
 typedef struct XpLayerFwd {
   XpLayerDims dims;

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Micro-benchmarks of the individual HIP kernels at BASELINE cfg #2 shapes (B=8, T=12, 224^2, ViT-B/16).
-Run on the GPU box:  python tools/bench_kernels.py [gemm|gemmfwd|ln|attn|all]  -> prints one line per kernel."""
+Run on the GPU box:  python tools/bench_kernels.py [gemm|gemmfwd|ln|attn|all]  -> prints one line per kernel.
+`python tools/bench_kernels.py act [rounds]`: the two GEMMs that carry the MLP activation (fc1 forward with both outputs, dpre with
+fused column sums), quick_gelu (epilogue kinds 3 / 5) against erf GELU (kinds 8 / 9), interleaved."""
 import sys
 
 import torch
@@ -56,6 +58,33 @@ def bench_gemm(fwd_only=False):
         print(f"colsum   {name:4s}: {us:8.1f} us  {M*N*2/us/1e3:7.1f} GB/s")
 
 
+def bench_act(rounds=3):
+    """fc1 forward [18848 x 3072 x 768] (+bias, activation, pre-activation kept) and dpre = (dx3 . W2) * act'(pre) with fc1's bias
+    gradient fused, per activation; `rounds` interleaved rounds (one GPU drifts by more than the difference between two launches)"""
+    M, N, K = 8 * 2356, 3072, 768
+    bf = torch.bfloat16
+    h2 = torch.randn(M, K, device="cuda").to(bf)
+    W1 = (torch.randn(N, K, device="cuda") * 0.02).to(bf)
+    b1 = torch.randn(N, device="cuda") * 0.02
+    act, pre = (torch.empty(M, N, dtype=bf, device="cuda") for _ in range(2))
+    dx3 = torch.randn(M, K, device="cuda").to(bf)
+    W2 = (torch.randn(K, N, device="cuda") * 0.02).to(bf)          # fc2's weight [D, Dff], read k-strided
+    dpre = torch.empty(M, N, dtype=bf, device="cuda")
+    defer = H.DeferredReduce(h2.device)
+
+    def bwd(epi):           # (a fresh DeferredReduce per launch: the launch under test is the GEMM, the second-level reduce is not run)
+        H.gemm(dx3, W2, M, N, K, b_kstrided=True, epilogue=epi, resid=pre, out=dpre, colsum_defer=H.DeferredReduce(h2.device))
+    H.gemm(h2, W1, M, N, K, out=act, bias=b1, epilogue=L.EPI_BIAS_GELU, aux=pre)
+    for r in range(rounds):
+        for name, fwd_epi, bwd_epi in (("quick_gelu", L.EPI_BIAS_GELU, L.EPI_GELU_BWD), ("gelu", L.EPI_BIAS_GELU_ERF, L.EPI_GELU_ERF_BWD)):
+            plan = H.gemm(dx3, W2, M, N, K, b_kstrided=True, epilogue=bwd_epi, resid=pre, out=dpre, colsum_defer=defer, plan_only=True)
+            assert plan["colsum_rows"] > 0, plan
+            uf = timeit(lambda: H.gemm(h2, W1, M, N, K, out=act, bias=b1, epilogue=fwd_epi, aux=pre))
+            ub = timeit(lambda: bwd(bwd_epi))
+            print(f"round {r} {name:10s} fc1 fwd (kind {fwd_epi}): {uf:7.1f} us {2*M*N*K/uf/1e6:6.1f} TFLOP/s | "
+                  f"dpre + column sums (kind {bwd_epi}): {ub:7.1f} us {2*M*N*K/ub/1e6:6.1f} TFLOP/s")
+
+
 def bench_ln():
     M, D = 8 * 2356, 768
     x = torch.randn(M, D, device="cuda").to(torch.bfloat16)
@@ -91,6 +120,8 @@ if __name__ == "__main__":
         bench_gemm()
     if what == "gemmfwd":
         bench_gemm(fwd_only=True)
+    if what == "act":
+        bench_act(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
     if what in ("ln", "all"):
         bench_ln()
     if what in ("attn", "all"):

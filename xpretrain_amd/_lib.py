@@ -17,7 +17,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpretrain_hip.so")
 
 XP_BF16, XP_F32 = 0, 1
-(EPI_NONE, EPI_BIAS, EPI_BIAS_QSCALE, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_GELU_BWD, EPI_PATCH, EPI_SCALE) = range(8)
+(EPI_NONE, EPI_BIAS, EPI_BIAS_QSCALE, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_GELU_BWD, EPI_PATCH, EPI_SCALE,
+ EPI_BIAS_GELU_ERF, EPI_GELU_ERF_BWD) = range(10)
+# XpLayerDims.act (XP_ACT_*) by config.hidden_act, and the fc1 / dpre epilogue kinds of each
+ACT_QUICK_GELU, ACT_GELU = 0, 1
+ACTS = {"quick_gelu": ACT_QUICK_GELU, "gelu": ACT_GELU}
+EPI_ACT_FWD = (EPI_BIAS_GELU, EPI_BIAS_GELU_ERF)
+EPI_ACT_BWD = (EPI_GELU_BWD, EPI_GELU_ERF_BWD)
 ATTN_PROXY, ATTN_CAUSAL = 0, 1
 
 i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
@@ -78,7 +84,7 @@ XP_REDUCE_MAX_SEGS = 16
 
 class XpLayerDims(C.Structure):
     _fields_ = [("rows", i64), ("D", i64), ("Dff", i64), ("B", i64), ("S", i64), ("heads", i64),
-                ("M", i64), ("N", i64), ("L", i64), ("attn_mode", i32), ("dtype", i32), ("q_scale", f32), ("ln_eps", f32)]
+                ("M", i64), ("N", i64), ("L", i64), ("attn_mode", i32), ("dtype", i32), ("q_scale", f32), ("ln_eps", f32), ("act", i32)]
 
 
 class XpLayerFwd(C.Structure):

@@ -83,6 +83,34 @@ __device__ __forceinline__ float quick_gelu_grad_f(float x) {
   return s * (1.0f + 1.702f * x * (1.0f - s));
 }
 
+// erf GELU (hidden_act "gelu": x * Phi(x), Phi the standard normal CDF) and its derivative Phi(x) + x * phi(x).
+// Phi(-|x|) = erfc(|x| / sqrt 2) / 2 by Abramowitz & Stegun 7.1.26: erfc(z) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2),
+// t = 1 / (1 + p z), |error| <= 1.5e-7 ABSOLUTE for every z >= 0 -- the rounding of an fp32 value near 1, which is what Phi is where
+// the error matters (x * Phi(-|x|) has its extremum 0.17 at |x| = 0.75; the tail's relative error is irrelevant: its absolute size
+// is).  Branch-free, one v_rcp_f32 and one v_exp_f32 as the quick_gelu pair above -- the device library's erff branches per lane
+// on |x| < 1 -- and exp(-z^2) = exp(-x^2 / 2) = sqrt(2 pi) phi(x) is the very factor the derivative needs.
+struct NormalCdfPdf { float cdf, pdf; };
+__device__ __forceinline__ NormalCdfPdf normal_cdf_pdf(float x) {
+  const float z = fabsf(x) * 0.70710678118654752f;
+  const float t = fast_rcp(1.0f + 0.3275911f * z);
+  const float e = __expf(-z * z);
+  float q = 1.061405429f;
+  q = q * t - 1.453152027f;
+  q = q * t + 1.421413741f;
+  q = q * t - 0.284496736f;
+  q = q * t + 0.254829592f;
+  const float h = 0.5f * q * t * e;                    // Phi(-|x|)
+  return NormalCdfPdf{x < 0.0f ? h : 1.0f - h, 0.39894228040143268f * e};
+}
+__device__ __forceinline__ float gelu_erf_f(float x) { return x * normal_cdf_pdf(x).cdf; }
+__device__ __forceinline__ float gelu_erf_grad_f(float x) {
+  const NormalCdfPdf n = normal_cdf_pdf(x);
+  return n.cdf + x * n.pdf;
+}
+// the MLP activation of a GEMM kernel instantiation (gemm_common.h: ACT template parameters): XP_ACT_QUICK_GELU / XP_ACT_GELU
+template <int ACT> __device__ __forceinline__ float act_f(float x) { return ACT == 0 ? quick_gelu_f(x) : gelu_erf_f(x); }
+template <int ACT> __device__ __forceinline__ float act_grad_f(float x) { return ACT == 0 ? quick_gelu_grad_f(x) : gelu_erf_grad_f(x); }
+
 // ------------------------------------------------------------------------------------------ gfx950 packed-fp32 hazard
 // Measured on MI355X (tools/race_repro.py, csrc/probe.hip::probe_pk_kernel): a `v_pk_add_f32` whose LOW
 // result half takes the HIGH dword of a source pair (`op_sel:[0,1]`, the form hipcc emits for `x - m[1]` when it keeps two

@@ -232,8 +232,11 @@ __device__ __forceinline__ typename Frag<T>::type lfrag(const char* tile, int ot
 
 // ---- the kernel -----------------------------------------------------------------------------------
 // AIM: 0 = A is a matrix; 1 / 2 = A is gathered from fp32 / uint8 frames (register-staged bf16 NT kernel only)
-template <typename T, bool AKS, bool BKS, bool GLDS, int AIM = 0>
+// Act: the activation of the two GELU epilogue kinds as a trailing tag pack (gemm_common.h::ActOf) -- empty: quick_gelu, every kind;
+// GeluErfTag: launched for the GELU kinds only.  A new activation adds kernels instead of branches to the ones the default step runs.
+template <typename T, bool AKS, bool BKS, bool GLDS, int AIM = 0, typename... Act>
 __global__ __launch_bounds__(GLDS ? 2 * NT : NT) void gemm_kernel(KParams p) {
+  constexpr int ACT = ActOf<Act...>::value;
   static_assert(AIM == 0 || (!AKS && !GLDS && sizeof(T) == 2), "on-the-fly patch gather: bf16, k-contiguous A, register staging");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   auto sA = [&](int s) -> char* { return smem + (2 * s) * TILE_BYTES; };
@@ -359,12 +362,12 @@ __global__ __launch_bounds__(GLDS ? 2 * NT : NT) void gemm_kernel(KParams p) {
   float* Cf = reinterpret_cast<float*>(p.C);
   T* Ct = reinterpret_cast<T*>(p.C);
   if (gridDim.z > 1) Cf += (int64_t)blockIdx.z * p.M * p.N;
-  const bool fast = fast_epi_dispatch(p, [&](auto epi_c, auto f32_c, auto) {      // (no fused column sums in this family)
+  const bool fast = fast_epi_dispatch<ACT>(p, [&](auto epi_c, auto f32_c, auto) {      // (no fused column sums in this family)
     constexpr int EPI = decltype(epi_c)::value;
     constexpr bool F32 = decltype(f32_c)::value;
     constexpr int RPP = NWV * 4, NP = 128 / RPP;    // 16 lanes per row, RPP rows per pass
     const int c8 = tid & 15, r16 = tid >> 4;
-    const FastEpi<T, EPI, F32> fe(p, F32 ? (void*)Cf : (void*)Ct, n0 + c8 * 8);
+    const FastEpi<T, EPI, F32, ACT> fe(p, F32 ? (void*)Cf : (void*)Ct, n0 + c8 * 8);
     const unsigned mrow = (unsigned)m0 + r16;
     Raw8<T> pre[NP];
     if constexpr (EpiTraits<EPI>::pre) {
@@ -398,7 +401,7 @@ __global__ __launch_bounds__(GLDS ? 2 * NT : NT) void gemm_kernel(KParams p) {
         const char* rp = smem + row * 512;
         const f32x8 v = {*reinterpret_cast<const f32x4*>(rp + (((2 * c8) ^ (row & 7)) << 4)),
                          *reinterpret_cast<const f32x4*>(rp + (((2 * c8 + 1) ^ (row & 7)) << 4))};
-        epi_row8<T>(p, el8, v, m, n8, Cf, Ct);
+        epi_row8<T, ACT>(p, el8, v, m, n8, Cf, Ct);
       }
     }
     if (trace && lane == 0) tr[3] = __builtin_amdgcn_s_memtime();
@@ -415,18 +418,26 @@ __global__ __launch_bounds__(GLDS ? 2 * NT : NT) void gemm_kernel(KParams p) {
     const int64_t m = m0 + row;
     if (m >= p.M) break;
     const f32x4 v = *reinterpret_cast<const f32x4*>(smem + row * 512 + ((c ^ (row & 7)) << 4));
-    epi_row<T>(p, el, v, m, n, Cf, Ct);
+    epi_row<T, ACT>(p, el, v, m, n, Cf, Ct);
   }
   if (trace && lane == 0) tr[3] = __builtin_amdgcn_s_memtime();
 }
 
+// the kernel of one operand layout / loader for activation `act` (XP_ACT_*)
+template <typename T, bool AKS, bool BKS, bool GLDS, int AIM = 0>
+void launch1(int act, const KParams& kp, dim3 grid, hipStream_t st) {
+  const size_t lds = 4 * TILE_BYTES;
+  if (act == XP_ACT_GELU) gemm_kernel<T, AKS, BKS, GLDS, AIM, GeluErfTag><<<grid, GLDS ? 2 * NT : NT, lds, st>>>(kp);
+  else                    gemm_kernel<T, AKS, BKS, GLDS, AIM><<<grid, GLDS ? 2 * NT : NT, lds, st>>>(kp);
+}
+
 template <typename T, bool GLDS>
 void launch2(const XpGemmDesc* d, const KParams& kp, dim3 grid, hipStream_t st) {
-  const size_t lds = 4 * TILE_BYTES;
-  if (!d->a_kstrided && !d->b_kstrided)      gemm_kernel<T, false, false, GLDS><<<grid, GLDS ? 2 * NT : NT, lds, st>>>(kp);
-  else if (!d->a_kstrided && d->b_kstrided)  gemm_kernel<T, false, true, GLDS><<<grid, GLDS ? 2 * NT : NT, lds, st>>>(kp);
-  else if (d->a_kstrided && d->b_kstrided)   gemm_kernel<T, true, true, GLDS><<<grid, GLDS ? 2 * NT : NT, lds, st>>>(kp);
-  else                                       gemm_kernel<T, true, false, GLDS><<<grid, GLDS ? 2 * NT : NT, lds, st>>>(kp);
+  const int act = epi_act(d->epilogue);
+  if (!d->a_kstrided && !d->b_kstrided)      launch1<T, false, false, GLDS>(act, kp, grid, st);
+  else if (!d->a_kstrided && d->b_kstrided)  launch1<T, false, true, GLDS>(act, kp, grid, st);
+  else if (d->a_kstrided && d->b_kstrided)   launch1<T, true, true, GLDS>(act, kp, grid, st);
+  else                                       launch1<T, true, false, GLDS>(act, kp, grid, st);
 }
 
 // The direct-to-LDS path needs dense, un-remapped operands whose tails the buffer bounds check can zero-fill.
@@ -451,9 +462,8 @@ template <typename T>
 void launch(Family f, const XpGemmDesc* d, const KParams& kp, dim3 grid, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
     if (f == Family::FRAMES) {          // A gathered from the frame tensor by the loader
-      const size_t lds = 4 * TILE_BYTES;
-      if (d->a_frames_u8) gemm_kernel<T, false, false, false, 2><<<grid, NT, lds, st>>>(kp);
-      else                gemm_kernel<T, false, false, false, 1><<<grid, NT, lds, st>>>(kp);
+      if (d->a_frames_u8) launch1<T, false, false, false, 2>(epi_act(d->epilogue), kp, grid, st);
+      else                launch1<T, false, false, false, 1>(epi_act(d->epilogue), kp, grid, st);
       return;
     }
   }
@@ -737,7 +747,7 @@ static GemmPlan plan_gemm(const XpGemmDesc* d, int split) {
                (!d->resid || rows * d->ldr * esz < lim) && (!d->aux || rows * d->ldaux * osz < lim);
   // the 256 family has only the fast epilogue, for the (epilogue, output type, column sums) combinations fast_epi_dispatch
   // specialises (gemm_common.h::fast_epi_specialised)
-  const int ep = d->epilogue;
+  const int ep = epi_base(d->epilogue);      // (the erf-GELU kinds plan as kinds 3 / 5: gemm_common.h)
   const bool f32 = d->out_dtype == XP_F32, cs_epi = ep == XP_EPI_NONE || ep == XP_EPI_GELU_BWD;
   p.epi_impl = epi_impl(p.fast_epi, p.wide, ep, f32, d->colsum_partials != nullptr);
   const bool epi256 = p.epi_impl == XP_GEMM_EPI_FAST;
@@ -791,8 +801,8 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
                "xp_gemm: a_frames must be 16-byte (fp32) / 8-byte (uint8) aligned with a row pitch that keeps 8-pixel strips aligned");
     if (d->a_frames_u8) for (int c = 0; c < 3; ++c) XP_REQUIRE(d->fr_std[c] > 0.f, "xp_gemm: fr_std[%d] must be positive", c);
   }
-  const int ep = d->epilogue;
-  XP_REQUIRE(ep >= XP_EPI_NONE && ep <= XP_EPI_SCALE, "xp_gemm: bad epilogue %d", ep);
+  XP_REQUIRE(d->epilogue >= XP_EPI_NONE && d->epilogue <= XP_EPI_GELU_ERF_BWD, "xp_gemm: bad epilogue %d", d->epilogue);
+  const int ep = epi_base(d->epilogue);      // the erf-GELU kinds: the operands of kinds 3 / 5, another kernel instantiation
   if (ep == XP_EPI_BIAS || ep == XP_EPI_BIAS_QSCALE || ep == XP_EPI_BIAS_GELU || ep == XP_EPI_BIAS_RESID)
     XP_REQUIRE(d->bias, "xp_gemm: epilogue %d needs bias", ep);
   if (ep == XP_EPI_BIAS_RESID || ep == XP_EPI_GELU_BWD) XP_REQUIRE(d->resid && d->ldr % 4 == 0, "xp_gemm: epilogue %d needs resid", ep);

@@ -115,8 +115,11 @@ __device__ __forceinline__ bf16x8 frag(const char* tile, int ot, int ks, int lan
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-template <bool AKS, bool BKS>
+// Act: the activation of the two GELU epilogue kinds as a trailing tag pack (gemm_common.h::ActOf): empty = quick_gelu, every kind
+// (`gemm256_kernel<false, false>` stays the kernel the step runs, name and code); GeluErfTag: launched for the GELU kinds only
+template <bool AKS, bool BKS, typename... Act>
 __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
+  constexpr int ACT = ActOf<Act...>::value;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -252,13 +255,13 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
-  const bool fast = fast_epi_dispatch(p, [&](auto epi_c, auto f32_c, auto cs_c) {
+  const bool fast = fast_epi_dispatch<ACT>(p, [&](auto epi_c, auto f32_c, auto cs_c) {
     constexpr int EPI = decltype(epi_c)::value;
     constexpr bool F32 = decltype(f32_c)::value;
     constexpr bool COLSUM = decltype(cs_c)::value;
     f32x8 cs = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     const int c = lane & 7, r8 = lane >> 3;           // 8 columns per lane: 8 lanes per row, 8 rows per pass
-    const FastEpi<T, EPI, F32> fe(p, F32 ? (void*)Cf : (void*)Ct, n0 + wn * CW + c * 8);
+    const FastEpi<T, EPI, F32, ACT> fe(p, F32 ? (void*)Cf : (void*)Ct, n0 + wn * CW + c * 8);
     const unsigned mrow = (unsigned)(m0 + wm * (MT * 16)) + r8;
     Raw8<T> pre[2][4];
     if constexpr (EpiTraits<EPI>::pre) {
@@ -310,8 +313,8 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
 }
 
 template <bool AKS, bool BKS>
-bool launch_one(const KParams& kp, dim3 grid, hipStream_t st) {
-  auto kern = gemm256_kernel<AKS, BKS>;
+bool launch_one(int act, const KParams& kp, dim3 grid, hipStream_t st) {
+  auto kern = act == XP_ACT_GELU ? gemm256_kernel<AKS, BKS, GeluErfTag> : gemm256_kernel<AKS, BKS>;
   if (!xp_device_cus(reinterpret_cast<const void*>(kern), LDS_BYTES)) return false;      // the 128 KiB opt-in (xp_gemm reports a refusal)
   kern<<<grid, NTH, LDS_BYTES, st>>>(kp);
   return true;
@@ -322,6 +325,10 @@ template __global__ void gemm256_kernel<false, false>(KParams);
 template __global__ void gemm256_kernel<false, true>(KParams);
 template __global__ void gemm256_kernel<true, true>(KParams);
 template __global__ void gemm256_kernel<true, false>(KParams);
+template __global__ void gemm256_kernel<false, false, GeluErfTag>(KParams);
+template __global__ void gemm256_kernel<false, true, GeluErfTag>(KParams);
+template __global__ void gemm256_kernel<true, true, GeluErfTag>(KParams);
+template __global__ void gemm256_kernel<true, false, GeluErfTag>(KParams);
 
 }  // namespace
 
@@ -355,8 +362,9 @@ int xp_gemm256_group_n(const XpGemmDesc* d, int tiles_n) {
 
 // Launches a problem gemm.hip::plan_gemm gave to this family (kp and grid as planned).  false: the dynamic-LDS opt-in was refused.
 bool xp_gemm256_launch(const XpGemmDesc* d, const xpgemm::KParams& kp, dim3 grid, hipStream_t st) {
-  if (!d->a_kstrided && !d->b_kstrided)      return launch_one<false, false>(kp, grid, st);
-  else if (!d->a_kstrided && d->b_kstrided)  return launch_one<false, true>(kp, grid, st);
-  else if (d->a_kstrided && d->b_kstrided)   return launch_one<true, true>(kp, grid, st);
-  return launch_one<true, false>(kp, grid, st);
+  const int act = xpgemm::epi_act(d->epilogue);
+  if (!d->a_kstrided && !d->b_kstrided)      return launch_one<false, false>(act, kp, grid, st);
+  else if (!d->a_kstrided && d->b_kstrided)  return launch_one<false, true>(act, kp, grid, st);
+  else if (d->a_kstrided && d->b_kstrided)   return launch_one<true, true>(act, kp, grid, st);
+  return launch_one<true, false>(act, kp, grid, st);
 }

@@ -12,11 +12,28 @@ struct Remap {
   }
 };
 
+// The erf-GELU kinds are kinds 3 / 5 with another activation: planner and kernels work on the BASE kind (epi_base) and the
+// activation (epi_act), which selects a kernel instantiation (template parameter ACT) instead of a run-time branch -- the
+// kernels of the quick_gelu kinds keep their generated code, instruction for instruction.
+__host__ __device__ constexpr int epi_base(int epilogue) {
+  return epilogue == XP_EPI_BIAS_GELU_ERF ? XP_EPI_BIAS_GELU : epilogue == XP_EPI_GELU_ERF_BWD ? XP_EPI_GELU_BWD : epilogue;
+}
+__host__ __device__ constexpr int epi_act(int epilogue) {
+  return epilogue == XP_EPI_BIAS_GELU_ERF || epilogue == XP_EPI_GELU_ERF_BWD ? XP_ACT_GELU : XP_ACT_QUICK_GELU;
+}
+
+// Kernel templates take the activation as a trailing, normally EMPTY pack of tag types: the quick_gelu instantiations keep their
+// names as profilers print them (`gemm256_kernel<false, false>`: tools and records match on those) and the pack adds nothing to
+// their code.
+struct GeluErfTag {};
+template <typename... Tag> struct ActOf { static constexpr int value = XP_ACT_QUICK_GELU; };
+template <> struct ActOf<GeluErfTag> { static constexpr int value = XP_ACT_GELU; };
+
 struct KParams {
   const void* A; const void* B; void* C;
   int64_t M, N, K, lda, ldb, ldc;
   Remap amap, cmap;
-  int epilogue, out_f32;
+  int epilogue, out_f32;     // epilogue: the BASE kind (epi_base; <= XP_EPI_SCALE) -- the activation is the kernel's ACT parameter
   int64_t k_per_split;
   const float* bias; float scale; int64_t scale_cols;
   const void* resid; int64_t ldr;
@@ -76,7 +93,7 @@ struct EpiLane {
 };
 
 // Finish and store 4 consecutive outputs of row m (all math fp32; coalesced across the lanes of a row).
-template <typename T>
+template <typename T, int ACT = XP_ACT_QUICK_GELU>
 __device__ __forceinline__ void epi_row(const KParams& p, const EpiLane& el, f32x4 v, int64_t m, int64_t n, float* Cf, T* Ct) {
   const int ep = p.epilogue;
   v = (v + el.bias) * el.colscale;
@@ -86,7 +103,7 @@ __device__ __forceinline__ void epi_row(const KParams& p, const EpiLane& el, f32
     else if (p.out_f32) store4(reinterpret_cast<float*>(p.aux) + crow * p.ldaux + n, v);
     else                store4(reinterpret_cast<T*>(p.aux) + crow * p.ldaux + n, v);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = quick_gelu_f(v[e]);
+    for (int e = 0; e < 4; ++e) v[e] = act_f<ACT>(v[e]);
   } else if (ep == XP_EPI_BIAS_RESID) {
     const SideRows sr(p);
     int64_t sb;
@@ -95,7 +112,7 @@ __device__ __forceinline__ void epi_row(const KParams& p, const EpiLane& el, f32
   } else if (ep == XP_EPI_GELU_BWD) {
     const f32x4 pre = load4(reinterpret_cast<const T*>(p.resid) + crow * p.ldr + n);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] *= quick_gelu_grad_f(pre[e]);
+    for (int e = 0; e < 4; ++e) v[e] *= act_grad_f<ACT>(pre[e]);
   } else if (ep == XP_EPI_PATCH) {
     const int64_t w = p.cmap.grp ? (m % p.cmap.grp) : m;
     v += load4(p.tab1 + (w / p.tab_L) * p.N + n);
@@ -113,7 +130,7 @@ struct EpiLane8 {
     bias = f32x8{a.bias, b.bias}; cs = f32x8{a.colscale, b.colscale};
   }
 };
-template <typename T>
+template <typename T, int ACT = XP_ACT_QUICK_GELU>
 __device__ __forceinline__ void epi_row8(const KParams& p, const EpiLane8& el, f32x8 v, int64_t m, int64_t n, float* Cf, T* Ct) {
   const int ep = p.epilogue;
   v.lo = (v.lo + el.bias.lo) * el.cs.lo; v.hi = (v.hi + el.bias.hi) * el.cs.hi;
@@ -123,7 +140,7 @@ __device__ __forceinline__ void epi_row8(const KParams& p, const EpiLane8& el, f
     else if (p.out_f32) store8(reinterpret_cast<float*>(p.aux) + crow * p.ldaux + n, v);
     else                store8(reinterpret_cast<T*>(p.aux) + crow * p.ldaux + n, v);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { v.lo[e] = quick_gelu_f(v.lo[e]); v.hi[e] = quick_gelu_f(v.hi[e]); }
+    for (int e = 0; e < 4; ++e) { v.lo[e] = act_f<ACT>(v.lo[e]); v.hi[e] = act_f<ACT>(v.hi[e]); }
   } else if (ep == XP_EPI_BIAS_RESID) {
     const SideRows sr(p);
     int64_t sb;
@@ -138,7 +155,7 @@ __device__ __forceinline__ void epi_row8(const KParams& p, const EpiLane8& el, f
   } else if (ep == XP_EPI_GELU_BWD) {
     const f32x8 pre = load8(reinterpret_cast<const T*>(p.resid) + crow * p.ldr + n);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { v.lo[e] *= quick_gelu_grad_f(pre.lo[e]); v.hi[e] *= quick_gelu_grad_f(pre.hi[e]); }
+    for (int e = 0; e < 4; ++e) { v.lo[e] *= act_grad_f<ACT>(pre.lo[e]); v.hi[e] *= act_grad_f<ACT>(pre.hi[e]); }
   } else if (ep == XP_EPI_PATCH) {
     const int64_t w = p.cmap.grp ? (m % p.cmap.grp) : m;
     const f32x8 a = load8(p.tab1 + (w / p.tab_L) * p.N + n), b = load8(p.tab2 + (w % p.tab_L) * p.N + n);
@@ -159,6 +176,7 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 constexpr unsigned EPI_OOB = 0xFFFFFF00u;     // + 16 (second half of a 32-byte access) must not wrap
 
 template <int EPI> struct EpiTraits {
+  static_assert(EPI >= XP_EPI_NONE && EPI <= XP_EPI_SCALE, "EpiTraits takes the base kind (epi_base)");
   static constexpr bool bias = EPI == XP_EPI_BIAS || EPI == XP_EPI_BIAS_QSCALE || EPI == XP_EPI_BIAS_GELU || EPI == XP_EPI_BIAS_RESID;
   static constexpr bool scale = EPI == XP_EPI_BIAS_QSCALE || EPI == XP_EPI_SCALE;
   static constexpr bool pre = EPI == XP_EPI_BIAS_RESID || EPI == XP_EPI_GELU_BWD;     // needs an [M, N] side input
@@ -193,8 +211,8 @@ __device__ __forceinline__ f32x8 raw8_f32(const Raw8<T>& x) {
   }
 }
 
-// Per-wave state of the fast epilogue; the lane owns columns n .. n+7.
-template <typename T, int EPI, bool F32>
+// Per-wave state of the fast epilogue; the lane owns columns n .. n+7.  ACT: the activation of the two GELU kinds.
+template <typename T, int EPI, bool F32, int ACT = XP_ACT_QUICK_GELU>
 struct FastEpi {
   using Tr = EpiTraits<EPI>;
   static constexpr unsigned OSZ = F32 ? 4 : sizeof(T);
@@ -230,7 +248,7 @@ struct FastEpi {
     if constexpr (EPI == XP_EPI_BIAS_GELU) {
       if (keep_aux) bstore8<T, F32>(rx, off_x(m), v);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { v.lo[e] = quick_gelu_f(v.lo[e]); v.hi[e] = quick_gelu_f(v.hi[e]); }
+      for (int e = 0; e < 4; ++e) { v.lo[e] = act_f<ACT>(v.lo[e]); v.hi[e] = act_f<ACT>(v.hi[e]); }
     } else if constexpr (EPI == XP_EPI_BIAS_RESID) {
       int64_t sb;
       if (side.on() && ok && side.hit(m, sb)) {       // fp32 side row: residual operand and result in fp32 (rare, divergent)
@@ -244,7 +262,7 @@ struct FastEpi {
     } else if constexpr (EPI == XP_EPI_GELU_BWD) {
       const f32x8 r = raw8_f32<T>(pre);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { v.lo[e] *= quick_gelu_grad_f(r.lo[e]); v.hi[e] *= quick_gelu_grad_f(r.hi[e]); }
+      for (int e = 0; e < 4; ++e) { v.lo[e] *= act_grad_f<ACT>(r.lo[e]); v.hi[e] *= act_grad_f<ACT>(r.hi[e]); }
     }
     bstore8<T, F32>(rc, off_c(m), v);
     return v;
@@ -253,7 +271,8 @@ struct FastEpi {
 
 // The (epilogue, output type, column sums) combinations the fast epilogue specialises: column sums with bf16 out after NONE /
 // GELU_BWD, fp32 out after NONE, bf16 out after every kind but PATCH / SCALE.  The one predicate of both sides: the planner
-// (gemm.hip::plan_gemm, which gives the 256 family only these) and fast_epi_dispatch below.
+// (gemm.hip::plan_gemm, which gives the 256 family only these) and fast_epi_dispatch below.  `epilogue`: the base kind (epi_base)
+// here and in epi_impl -- the erf-GELU kinds are specialised exactly where kinds 3 / 5 are.
 __host__ __device__ inline bool fast_epi_specialised(int epilogue, bool out_f32, bool colsum) {
   if (colsum) return !out_f32 && (epilogue == XP_EPI_NONE || epilogue == XP_EPI_GELU_BWD);
   return out_f32 ? epilogue == XP_EPI_NONE : epilogue >= XP_EPI_NONE && epilogue <= XP_EPI_GELU_BWD;
@@ -269,11 +288,18 @@ __host__ __device__ inline int epi_impl(int fast_epi, int wide, int epilogue, bo
 // Calls f(integral_constant<int, EPI>, bool_constant<F32>, bool_constant<COLSUM>) for the (epilogue, output type) pairs the
 // fast path specialises; returns false for any other pair (the caller then runs the generic epilogue).  COLSUM (column
 // sums of the finished outputs, i.e. the bias gradient of the layer that produced this GEMM's input gradient) exists for
-// the two epilogues the backward uses it with; the host rejects every other combination.
-template <typename F>
+// the two epilogues the backward uses it with; the host rejects every other combination.  A kernel instantiated for another
+// activation (ACT != XP_ACT_QUICK_GELU) is launched for the two GELU kinds only and specialises nothing else.
+template <int ACT = XP_ACT_QUICK_GELU, typename F>
 __device__ __forceinline__ bool fast_epi_dispatch(const KParams& p, F&& f) {
   using std::integral_constant; using std::bool_constant;
   if (epi_impl(p.fast_epi, p.wide, p.epilogue, p.out_f32, p.colsum != nullptr) != XP_GEMM_EPI_FAST) return false;
+  if constexpr (ACT != XP_ACT_QUICK_GELU) {
+    if (p.colsum)                               f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<true>{});
+    else if (p.epilogue == XP_EPI_BIAS_GELU)    f(integral_constant<int, XP_EPI_BIAS_GELU>{}, bool_constant<false>{}, bool_constant<false>{});
+    else                                        f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<false>{});
+    return true;
+  } else {
   if (p.colsum) {
     if (p.epilogue == XP_EPI_GELU_BWD) f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<true>{});
     else                               f(integral_constant<int, XP_EPI_NONE>{}, bool_constant<false>{}, bool_constant<true>{});
@@ -290,6 +316,7 @@ __device__ __forceinline__ bool fast_epi_dispatch(const KParams& p, F&& f) {
     case XP_EPI_BIAS_GELU:   f(integral_constant<int, XP_EPI_BIAS_GELU>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
     case XP_EPI_BIAS_RESID:  f(integral_constant<int, XP_EPI_BIAS_RESID>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
     default:                 f(integral_constant<int, XP_EPI_GELU_BWD>{}, bool_constant<false>{}, bool_constant<false>{}); return true;
+  }
   }
 }
 

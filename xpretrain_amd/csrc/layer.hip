@@ -138,7 +138,11 @@ struct WgradOrder {
 // `Args`: XpLayerFwd / XpLayerPooledFwd (XpLayerBwd / XpLayerPooledBwd): only the fields the two have in common are read.
 // Side rows: (sS, sM) is the geometry of the n rows' fp32 side rows, stored with stride sM (dense: side_S, side_M; pooled: 1, 1).
 
-// x2 = resid + attn_o Wo^T + bo (resid: x with row pitch ldr, its side rows in side_x) ; x3 = x2 + fc2(quick_gelu(fc1(LN2(x2))))
+// the fc1 / dpre epilogue kinds of the layer's activation (XpLayerDims::act, validated by check_dims)
+inline int epi_act_fwd(const XpLayerDims& d) { return d.act == XP_ACT_GELU ? XP_EPI_BIAS_GELU_ERF : XP_EPI_BIAS_GELU; }
+inline int epi_act_bwd(const XpLayerDims& d) { return d.act == XP_ACT_GELU ? XP_EPI_GELU_ERF_BWD : XP_EPI_GELU_BWD; }
+
+// x2 = resid + attn_o Wo^T + bo (resid: x with row pitch ldr, its side rows in side_x) ; x3 = x2 + fc2(act(fc1(LN2(x2))))
 template <class Args>
 int out_proj_mlp_fwd(const Args& a, int64_t n, int64_t ldr, const float* side_x, float* side_x2, float* side_out, int64_t sS,
                      int32_t sM, void* st) {
@@ -152,9 +156,9 @@ int out_proj_mlp_fwd(const Args& a, int64_t n, int64_t ldr, const float* side_x,
   if ((rc = xp_gemm(&g, st))) return rc;
   if ((rc = xp_layernorm_fwd_side(a.x2, D, a.ln2_w, a.ln2_b, a.h2, D, a.mean2, a.rstd2, n, D, d.ln_eps, dt,
                                   side_x2, nullptr, sS, sM, sM, st))) return rc;
-  // pre = h2 W1^T + b1 ; act = quick_gelu(pre)
+  // pre = h2 W1^T + b1 ; act = quick_gelu(pre) or gelu(pre)
   g = gemm_desc(a.h2, a.W1, a.act, n, Dff, D, dt);
-  g.epilogue = XP_EPI_BIAS_GELU; g.bias = a.b1; g.aux = a.pre;
+  g.epilogue = epi_act_fwd(d); g.bias = a.b1; g.aux = a.pre;
   if (xp_debug_flag("fc1_no_pre")) g.aux = nullptr;      // measurement only (tools/fc1_one_output.py): the backward then reads garbage
   if ((rc = xp_gemm(&g, st))) return rc;
   // x3 = x2 + act W2^T + b2
@@ -196,7 +200,7 @@ TailBwdWs carve_tail_bwd(Carver& ws, const TailBwdPlan& p) {
   return w;
 }
 
-// x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))) and x2 = resid + out_proj(attn_o), backwards: leaves dx2 and dattn in the workspace,
+// x3 = x2 + fc2(act(fc1(LN2(x2)))) and x2 = resid + out_proj(attn_o), backwards: leaves dx2 and dattn in the workspace,
 // issues dW2, dW1, dWo and defers db1, dln2_w, dln2_b, dbo, db2.  Marks 1 and 2 of the weight-gradient stream.
 template <class Args>
 int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwdPlan& p, const TailBwdWs& w, float* slabs, size_t slab_bytes, int64_t sS,
@@ -204,8 +208,8 @@ int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwdPlan& p, const TailB
   const int64_t D = a.dims.D, Dff = a.dims.Dff;
   const int dt = a.dims.dtype;
   int rc;
-  XpGemmDesc g = gemm_desc(a.dx3, a.W2, w.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * quick_gelu'(pre)
-  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.resid = a.pre; g.ldr = Dff;
+  XpGemmDesc g = gemm_desc(a.dx3, a.W2, w.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * act'(pre)
+  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(a.dims); g.resid = a.pre; g.ldr = Dff;
   if (a.db1 && p.db1_fused_rows > 0) g.colsum_partials = w.cs_pre;
   if ((rc = xp_gemm(&g, st))) return rc;
   if (a.db1) {
@@ -247,6 +251,8 @@ int check_dims(const char* name, const XpLayerDims& d) {
   XP_REQUIRE(d.rows > 0 && d.D > 0 && d.Dff > 0 && d.B > 0 && d.S > 0 && d.heads > 0, "%s: empty dimension", name);
   XP_REQUIRE(d.rows == d.B * d.S && d.D == d.heads * 64, "%s: rows != B*S or D != heads*64", name);
   XP_REQUIRE(d.dtype == XP_BF16 || d.dtype == XP_F32, "%s: bad dtype %d", name, d.dtype);
+  XP_REQUIRE(d.act == XP_ACT_QUICK_GELU || d.act == XP_ACT_GELU, "%s: bad XpLayerDims::act %d (XP_ACT_QUICK_GELU = 0, XP_ACT_GELU = 1)",
+             name, d.act);
   return XP_OK;
 }
 
@@ -312,7 +318,7 @@ BwdPlan plan_bwd(const XpLayerDims& d) {
   const int64_t rows = d.rows, D = d.D, Dff = d.Dff;
   // fc1's bias gradient: fused into the dX GEMM epilogue where the library offers it, else a column-sum pass over dpre
   XpGemmDesc g = gemm_desc(nullptr, nullptr, nullptr, rows, Dff, D, d.dtype);
-  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = XP_EPI_GELU_BWD; g.ldr = Dff;
+  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(d); g.ldr = Dff;
   g.resid = &g;                          // (only tested for non-NULL by the planning queries)
   p.t = plan_tail_bwd(rows, D, Dff, d.dtype, xp_gemm_colsum_rows(&g));
   // (fc2's bias gradient = column sums of dx3: taken by the second LayerNorm's backward)
@@ -361,7 +367,7 @@ extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
   // dW GEMMs beside the dX chain (video tower only: the text tower is 256 rows on a side stream of its own already)
   const WgradOrder wg{(d.attn_mode == XP_ATTN_PROXY && rows >= 4096) ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_bwd"};
   if ((rc = wg.mark(0))) return rc;
-  // ---- MLP: x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))), then dattn = dx2 . Wo of x2 = x + out_proj(attn(qkv(LN1(x))))
+  // ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo of x2 = x + out_proj(attn(qkv(LN1(x))))
   if ((rc = mlp_out_proj_bwd(*a, rows, p.t, w, slabs, p.slabs, a->side_S, a->side_M, df, wg, st))) return rc;
   // ---- attention
   if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, w.dattn, D, a->stats, a->pad_mask, dqkv, d.q_scale, d.attn_mode, d.B, d.heads,

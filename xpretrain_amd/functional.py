@@ -2,7 +2,7 @@
 
 The unit of fusion is the transformer layer (``EncoderLayerFn``), not the op: the forward chains
 LN -> fused-QKV GEMM (+bias, q-scale) -> fused attention -> out-proj GEMM (+bias +residual) -> LN ->
-fc1 GEMM (+bias +quick_gelu) -> fc2 GEMM (+bias +residual); the backward chains the matching dX / dW
+fc1 GEMM (+bias +quick_gelu or erf gelu) -> fc2 GEMM (+bias +residual); the backward chains the matching dX / dW
 GEMMs with the activation-derivative and residual-gradient adds folded into GEMM / LayerNorm epilogues.
 All arithmetic happens in ``libxpretrain_hip.so`` (``hip_ops``); torch only owns the buffers and the graph.
 
@@ -209,12 +209,13 @@ class _LayerPlan:
     """Sizes / offsets of one (shape, dtype) of encoder layer: the saved-activation arena of the forward, the flat
     parameter-gradient buffer of the backward, the workspace sizes."""
 
-    def __init__(self, rows, D, Dff, B, S, heads, size, dtype):
+    def __init__(self, rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU):
         d = L.XpLayerDims()
         d.rows, d.D, d.Dff, d.B, d.S, d.heads = rows, D, Dff, B, S, heads
         d.M, d.N, d.L = size if size is not None else (0, 1, S)
         d.attn_mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
         d.dtype, d.q_scale, d.ln_eps = _DT_CODE[dtype], (D // heads) ** -0.5, 1e-5
+        d.act = act                 # the MLP's activation (L.ACTS): the fc1 / dpre epilogue kinds the native stages pick
         self.dims = d
         es = _ES[dtype]
         # arena: bf16/fp32 activations then fp32 statistics
@@ -231,8 +232,8 @@ class _LayerPlan:
         self.gtotal = sum(self.gsizes)
 
 
-def _layer_plan(rows, D, Dff, B, S, heads, size, dtype) -> _LayerPlan:
-    key = (rows, D, Dff, B, S, heads, size, dtype)
+def _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU) -> _LayerPlan:
+    key = (rows, D, Dff, B, S, heads, size, dtype, act)
     p = _PLANS.get(key)
     if p is None:
         p = _PLANS[key] = _LayerPlan(*key)
@@ -360,7 +361,7 @@ def _layer_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1,
     if split is None:
         parts = [(plan, 0, 0, None)]
     else:                       # two half-batch chains: (plan of half the batch, first row, first sample, stream)
-        hp = _layer_plan(d.rows // 2, D, Dff, d.B // 2, d.S, d.heads, (d.M, d.N, d.L), x.dtype)
+        hp = _layer_plan(d.rows // 2, D, Dff, d.B // 2, d.S, d.heads, (d.M, d.N, d.L), x.dtype, d.act)
         if (d.rows // 2) % 4:   # the second chain's statistics / stream pointers are offset by rows/2 elements: keep them 16-byte aligned
             raise RuntimeError(f"ForwardSplit: (B/2)*S = {d.rows // 2} rows per chain must be a multiple of 4")
         parts = [(hp, 0, 0, None), (hp, d.rows // 2, d.B // 2, split.stream)]
@@ -496,7 +497,7 @@ def _layer_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_ma
     if side is not None and side_x2 is not None:          # the forward's fp32 side rows of x and x2: read by the LayerNorm backward passes
         a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
         a.side_S, a.side_M = (plan.dims.S, plan.dims.M) if plan.dims.attn_mode == L.ATTN_PROXY else (1, 1)
-    return _run_native_bwd(ctx, a, "xp_encoder_layer_bwd", plan, torch.empty_like(x), "layer_bwd") + (None,) * 8
+    return _run_native_bwd(ctx, a, "xp_encoder_layer_bwd", plan, torch.empty_like(x), "layer_bwd") + (None,) * 9
 
 
 # ------------------------------------------------------------------------------------------ encoder layer, op by op
@@ -504,32 +505,37 @@ def _layer_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_ma
 # arguments the native calls do not take).  The stages the dense and the pooled layer share are written once, as in layer.hip
 # (out_proj_mlp_fwd, mlp_out_proj_bwd): out_proj onward over ``n`` rows -- all rows, or the B pooled ones.  Every operator is
 # looked up on ``H`` at call time (tools/determinism_hunt.py wraps those attributes).
-def _mlp_fwd_ops(x, ldr, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, n, training, side_x, side_x2, side_out, sd, out=None):
-    """x2 = x + attn_o Wo^T + bo (x read with row pitch ``ldr``), x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))), into ``out`` when given.
-    ``sd = (S, M)``: geometry of the fp32 side rows of the n rows (``side_x`` of x, ``side_x2`` / ``side_out`` written), or None."""
+def _mlp_fwd_ops(x, ldr, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, n, training, side_x, side_x2, side_out, sd, out=None,
+                 act=L.ACT_QUICK_GELU):
+    """x2 = x + attn_o Wo^T + bo (x read with row pitch ``ldr``), x3 = x2 + fc2(act(fc1(LN2(x2)))), into ``out`` when given.
+    ``sd = (S, M)``: geometry of the fp32 side rows of the n rows (``side_x`` of x, ``side_x2`` / ``side_out`` written), or None.
+    ``act``: the activation (L.ACT_*), i.e. which of the two fc1 epilogue kinds runs."""
     D, Dff = Wo.shape[0], W1.shape[0]
     lns = None if sd is None else (sd[0], sd[1], sd[1])
     x2 = H.gemm(attn_o, Wo, n, D, D, epilogue=L.EPI_BIAS_RESID, bias=bo.detach(), resid=x, ldr=ldr,
                 resid_side=side_x, out_side=side_x2, side=sd)
     h2, mean2, rstd2 = H.layernorm_fwd(x2, ln2_w, ln2_b, n, D, x_side=side_x2, side=lns)
     pre = torch.empty((n, Dff), dtype=x.dtype, device=x.device) if training else None
-    act = H.gemm(h2, W1, n, Dff, D, epilogue=L.EPI_BIAS_GELU, bias=b1.detach(), aux=pre)
-    x3 = H.gemm(act, W2, n, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2, out=out,
+    a = H.gemm(h2, W1, n, Dff, D, epilogue=L.EPI_ACT_FWD[act], bias=b1.detach(), aux=pre)
+    x3 = H.gemm(a, W2, n, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2, out=out,
                 resid_side=side_x2, out_side=side_out, side=sd)
-    return x2, mean2, rstd2, h2, pre, act, x3
+    return x2, mean2, rstd2, h2, pre, a, x3
 
 
-def _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, n, need, defer, db1_fused, side_x2, lns):
+def _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, n, need, defer, db1_fused, side_x2, lns,
+                 act_kind=L.ACT_QUICK_GELU):
     """The backward of ``_mlp_fwd_ops`` down to ``dattn = dx2 . Wo``: returns ``(dx2, dattn, dwo, dbo, dln2_w, dln2_b, dw1, db1,
     dw2, db2)``; the bias / LayerNorm gradients are final after ``defer.flush()``, frozen weights' gradients are None (``need``:
     the Function's needs_input_grad).  ``db1_fused``: fc1's bias gradient out of the dpre GEMM's epilogue where the library offers
-    it (the dense layer), else always a column-sum pass over dpre (the pooled layer)."""
+    it (the dense layer), else always a column-sum pass over dpre (the pooled layer).  ``act_kind``: the activation (L.ACT_*) whose
+    derivative the dpre epilogue applies."""
     D, Dff = Wo.shape[0], W1.shape[0]
+    epi = L.EPI_ACT_BWD[act_kind]
     if need[14] and db1_fused:
-        dpre, db1 = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre, colsum_defer=defer,
+        dpre, db1 = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=epi, resid=pre, colsum_defer=defer,
                            colsum_name="db1")
     else:
-        dpre = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=L.EPI_GELU_BWD, resid=pre)
+        dpre = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=epi, resid=pre)
         db1 = H.colsum_deferred(dpre, n, Dff, defer, name="db1") if need[14] else None
     dw2 = _wgrad(dx3, act, n, D, Dff, slack=True) if need[15] else None
     dh2 = H.gemm(dpre, W1, n, D, Dff, b_kstrided=True)
@@ -552,10 +558,14 @@ class EncoderLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2,
                 B: int, S: int, heads: int, size: Optional[Tuple[int, int, int]], pad_mask: Optional[torch.Tensor],
-                training: bool = True, side: Optional[torch.Tensor] = None, split: Optional["ForwardSplit"] = None):
-        """``side`` (fp32, bf16 compute only): the fp32 side rows of ``x`` (SideRows, csrc/gemm_common.h) -- [B*M, D], the proxy rows of
+                training: bool = True, side: Optional[torch.Tensor] = None, split: Optional["ForwardSplit"] = None,
+                act: int = L.ACT_QUICK_GELU):
+        """``act``: the MLP's activation (L.ACTS[config.hidden_act]).
+        ``side`` (fp32, bf16 compute only): the fp32 side rows of ``x`` (SideRows, csrc/gemm_common.h) -- [B*M, D], the proxy rows of
         every sample, in the video tower; [B*S, D], the whole stream, in the text tower.  The call then returns ``(x3, side_out)``."""
         dt = x.dtype
+        if act not in (L.ACT_QUICK_GELU, L.ACT_GELU):
+            raise ValueError(f"EncoderLayerFn: act={act!r} is not one of {L.ACTS}")
         if side is not None and (dt != torch.bfloat16 or side.dtype != torch.float32 or not side.is_contiguous() or side.device != x.device
                                  or tuple(side.shape) != ((B * size[0] if size is not None else B * S), x.shape[1])):
             raise TypeError("EncoderLayerFn: side rows must be a contiguous fp32 [B*M, D] (video) / [B*S, D] (text) tensor beside a bf16 stream")
@@ -570,7 +580,7 @@ class EncoderLayerFn(torch.autograd.Function):
         bqkv = WEIGHTS.fused((bq, bk, bv), torch.float32)
         Wo, W1, W2 = WEIGHTS.get(wo, dt), WEIGHTS.get(w1, dt), WEIGHTS.get(w2, dt)
         if LAYER_CALLS and _native_ok(x, (ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2), (Wqkv, Wo, W1, W2), pad_mask):
-            plan = _layer_plan(rows, D, Dff, B, S, heads, size, dt)
+            plan = _layer_plan(rows, D, Dff, B, S, heads, size, dt, act)
             if split is not None and (size is None or B % 2 or pad_mask is not None):
                 split = None
             if split is not None and WEIGHTS.casts != casts0:       # a weight copy was (re)made on this stream just now: the second
@@ -591,12 +601,12 @@ class EncoderLayerFn(torch.autograd.Function):
             h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
             qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
             attn_o, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask)
-            x2, mean2, rstd2, h2, pre, act, x3 = _mlp_fwd_ops(x, None, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, rows, training,
-                                                              side, side_x2, side_out, sd)
+            x2, mean2, rstd2, h2, pre, a, x3 = _mlp_fwd_ops(x, None, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, rows, training,
+                                                            side, side_x2, side_out, sd, act=act)
             if training:
-                ctx.save_for_backward(x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
+                ctx.save_for_backward(x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, a,
                                       Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
-            ctx.meta = (B, S, heads, size, q_scale, D, Dff)
+            ctx.meta = (B, S, heads, size, q_scale, D, Dff, act)
             ctx.lns = lns
         if side is not None:
             ctx.mark_non_differentiable(side_out)
@@ -607,7 +617,7 @@ class EncoderLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx3, _dside=None):
         if dx3 is None:             # (set_materialize_grads(False): the layer output did not reach the loss)
-            return (None,) * 25
+            return (None,) * 26
         if ctx.plan is not None:
             x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, side, side_x2 = ctx.saved_tensors
             if dx3.dtype != x.dtype or dx3.device != x.device or dx3.shape != x.shape:
@@ -616,16 +626,16 @@ class EncoderLayerFn(torch.autograd.Function):
             return _layer_bwd_native(ctx, dx3.contiguous(), x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, ctx.plan, side, side_x2)
         (x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
          Wqkv, Wo, W1, W2, pad_mask, side, side_x2) = ctx.saved_tensors
-        B, S, heads, size, q_scale, D, Dff = ctx.meta
+        B, S, heads, size, q_scale, D, Dff, act_kind = ctx.meta
         rows = x.shape[0]
         dx3 = dx3.contiguous()
         defer = H.DeferredReduce(x.device)       # the 4 bias + 4 LayerNorm-parameter reductions finish in 2 launches
         # parameter gradients are skipped for frozen parameters (freeze_text_encoder, VidCLIP.py:96-103): positions in
         # forward's argument list -- 1,2 ln1 | 3..8 q,k,v | 9,10 out_proj | 11,12 ln2 | 13,14 fc1 | 15,16 fc2
         need = ctx.needs_input_grad
-        # ---- MLP: x3 = x2 + fc2(quick_gelu(fc1(LN2(x2)))), then dattn = dx2 . Wo
+        # ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo
         dx2, dattn, *tail = _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, rows, need, defer, True,
-                                         side_x2, ctx.lns)
+                                         side_x2, ctx.lns, act_kind)
         # ---- attention: x2 = x + out_proj(attn(qkv(LN1(x))))
         want_bqkv = need[4] or need[6] or need[8]
         if want_bqkv:       # the q/k/v bias gradients (column sums of dqkv) come out of the attention backward kernels
@@ -647,7 +657,7 @@ class EncoderLayerFn(torch.autograd.Function):
                                              side=ctx.lns)
         defer.flush()
         keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter sums ride on a pass that runs anyway)
-        return (dx, keep(1, dln1_w), keep(2, dln1_b), dwq, dbq, dwk, dbk, dwv, dbv, *tail) + (None,) * 8
+        return (dx, keep(1, dln1_w), keep(2, dln1_b), dwq, dbq, dwk, dbk, dwv, dbv, *tail) + (None,) * 9
 
 
 # ------------------------------------------------------------------------------------------ pooled last layer (video tower)
@@ -655,8 +665,8 @@ class _PooledLayerPlan:
     """Sizes / offsets of one (shape, dtype) of the pooled last layer (xp_encoder_layer_pooled_fwd / _bwd): every-row pieces
     (h1, kv, LayerNorm-1 statistics) and the pooled rows' pieces ([B, .])."""
 
-    def __init__(self, rows, D, Dff, B, S, heads, size, dtype):
-        base = _layer_plan(rows, D, Dff, B, S, heads, size, dtype)
+    def __init__(self, rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU):
+        base = _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act)
         self.dims, self.gsizes, self.gnames, self.gtotal = base.dims, base.gsizes, base.gnames, base.gtotal
         es = _ES[dtype]
         self.off, self.arena_bytes = _arena_layout(
@@ -669,11 +679,11 @@ class _PooledLayerPlan:
         self.bwd_ws = int(lib.xp_encoder_layer_pooled_bwd_workspace_bytes(C.byref(self.dims)))
 
 
-def _pooled_plan(rows, D, Dff, B, S, heads, size, dtype) -> _PooledLayerPlan:
-    key = ("pooled", rows, D, Dff, B, S, heads, size, dtype)
+def _pooled_plan(rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU) -> _PooledLayerPlan:
+    key = ("pooled", rows, D, Dff, B, S, heads, size, dtype, act)
     p = _PLANS.get(key)
     if p is None:
-        p = _PLANS[key] = _PooledLayerPlan(rows, D, Dff, B, S, heads, size, dtype)
+        p = _PLANS[key] = _PooledLayerPlan(rows, D, Dff, B, S, heads, size, dtype, act)
     return p
 
 
@@ -713,7 +723,7 @@ def _pooled_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, plan,
     a.dx3 = dx3.data_ptr()
     if side is not None:
         a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
-    return _run_native_bwd(ctx, a, "xp_encoder_layer_pooled_bwd", plan, torch.empty_like(x), "layer_pooled_bwd") + (None,) * 6
+    return _run_native_bwd(ctx, a, "xp_encoder_layer_pooled_bwd", plan, torch.empty_like(x), "layer_pooled_bwd") + (None,) * 7
 
 
 class PooledEncoderLayerFn(torch.autograd.Function):
@@ -727,8 +737,11 @@ class PooledEncoderLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2,
-                B: int, S: int, heads: int, size: Tuple[int, int, int], training: bool = True, side: Optional[torch.Tensor] = None):
+                B: int, S: int, heads: int, size: Tuple[int, int, int], training: bool = True, side: Optional[torch.Tensor] = None,
+                act: int = L.ACT_QUICK_GELU):
         dt = x.dtype
+        if act not in (L.ACT_QUICK_GELU, L.ACT_GELU):
+            raise ValueError(f"PooledEncoderLayerFn: act={act!r} is not one of {L.ACTS}")
         rows, D = x.shape
         M = size[0]
         if side is not None and (dt != torch.bfloat16 or side.dtype != torch.float32 or not side.is_contiguous() or side.device != x.device
@@ -750,7 +763,7 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             side_out = torch.empty((B, D), dtype=torch.float32, device=dev)
             side_x2 = torch.empty((B, D), dtype=torch.float32, device=dev)
         if LAYER_CALLS and _native_ok(x, (ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2), (Wqkv, Wo, W1, W2), None):
-            plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt)
+            plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt, act)
             arena = _pooled_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan, x3, training, side,
                                        side_out, side_x2)
             ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2)
@@ -765,12 +778,12 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             kv = H.gemm(h1, Wqkv[D:], rows, 2 * D, D, epilogue=L.EPI_BIAS, bias=bqkv[D:])
             q = H.gemm(h1p, Wqkv, B, D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
             attn_o, stats = H.attn_pooled_fwd(q, kv, B, S, heads)
-            x2, mean2, rstd2, h2, pre, act, _ = _mlp_fwd_ops(x, S * D, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, B, training,
-                                                             side0, side_x2, side_out, sd, out=x3)
+            x2, mean2, rstd2, h2, pre, a, _ = _mlp_fwd_ops(x, S * D, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, B, training,
+                                                           side0, side_x2, side_out, sd, out=x3, act=act)
             if training:
                 ctx.save_for_backward(x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2,
-                                      h2, pre, act, Wqkv, Wo, W1, W2, side, side_x2)
-        ctx.meta = (B, S, heads, M, q_scale, D, Dff)
+                                      h2, pre, a, Wqkv, Wo, W1, W2, side, side_x2)
+        ctx.meta = (B, S, heads, M, q_scale, D, Dff, act)
         if side is not None:
             ctx.mark_non_differentiable(side_out)
             ctx.set_materialize_grads(False)
@@ -780,8 +793,8 @@ class PooledEncoderLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx3, _dside=None):
         if dx3 is None:
-            return (None,) * 23
-        B, S, heads, M, q_scale, D, Dff = ctx.meta
+            return (None,) * 24
+        B, S, heads, M, q_scale, D, Dff, act_kind = ctx.meta
         need = ctx.needs_input_grad
         saved = ctx.saved_tensors          # (read once: a checkpointed layer's tensors unpack once)
         x = saved[0]
@@ -801,7 +814,7 @@ class PooledEncoderLayerFn(torch.autograd.Function):
         defer = H.DeferredReduce(dev)
         # ---- MLP and dattn = dx2 . Wo on the pooled rows
         dx2, dattn, *tail = _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, B, need, defer, False,
-                                         side_x2, p1)
+                                         side_x2, p1, act_kind)
         # ---- attention.  dqkv [rows, 3D]: dk / dv in the k / v columns of every row, dq in the q columns of the pooled rows only
         dqkv = torch.empty((rows, 3 * D), dtype=dt, device=dev)
         dq_view, dkv = dqkv.view(B, S * 3 * D)[:, :D], dqkv[:, D:]
@@ -836,13 +849,13 @@ class PooledEncoderLayerFn(torch.autograd.Function):
         keep = lambda i, t: t if need[i] else None
         pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
         return (dx, keep(1, dln1_w), keep(2, dln1_b), pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]),
-                pick(dbqkv, 1, need[6]), pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), *tail) + (None,) * 6
+                pick(dbqkv, 1, need[6]), pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), *tail) + (None,) * 7
 
 
 def pooled_encoder_layer(x, layer, B, S, heads, size, side=None):
     """Apply ``PooledEncoderLayerFn`` with the parameters of a ``CLIPEncoderLayer`` module: ``[B, D]`` (with ``side``: also the fp32
     rows)."""
-    return PooledEncoderLayerFn.apply(x, *_layer_params(layer), B, S, heads, tuple(size), torch.is_grad_enabled(), side)
+    return PooledEncoderLayerFn.apply(x, *_layer_params(layer), B, S, heads, tuple(size), torch.is_grad_enabled(), side, _layer_act(layer))
 
 
 # ------------------------------------------------------------------------------------------ fp32 side rows (proxy tokens)
@@ -1123,8 +1136,14 @@ def _layer_params(layer):
     return tuple(d[k] for d in tabs for k in ("weight", "bias"))
 
 
+def _layer_act(layer) -> int:
+    """the activation of a CLIPEncoderLayer's MLP (CLIPMLP.act_kind, from its tower's config.hidden_act) as L.ACT_*"""
+    return layer._modules["mlp"].__dict__.get("act_kind", L.ACT_QUICK_GELU)
+
+
 def encoder_layer(x, layer, B, S, heads, size, pad_mask, side=None, split=None):
     """Apply ``EncoderLayerFn`` with the parameters of a ``CLIPEncoderLayer`` module.  With ``side`` (the proxy rows of x in fp32)
     returns ``(x3, side_out)``.  ``split``: a ``ForwardSplit`` (the tower runs as two half-batch chains)."""
     # `training` argument: forward-only passes (torch.no_grad: retrieval / inference) skip the MLP pre-activation
-    return EncoderLayerFn.apply(x, *_layer_params(layer), B, S, heads, size, pad_mask, torch.is_grad_enabled(), side, split)
+    return EncoderLayerFn.apply(x, *_layer_params(layer), B, S, heads, size, pad_mask, torch.is_grad_enabled(), side, split,
+                                _layer_act(layer))

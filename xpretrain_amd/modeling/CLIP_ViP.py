@@ -199,9 +199,11 @@ class CLIPMLP(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
-        if config.hidden_act != "quick_gelu":
-            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the fused MLP epilogue implements quick_gelu "
-                                      "(every openai/clip-* config)")
+        if config.hidden_act not in XF.L.ACTS:
+            raise NotImplementedError(f"hidden_act={config.hidden_act!r}: the fused MLP epilogues implement 'quick_gelu' (every "
+                                      "openai/clip-* config) and 'gelu' (erf GELU: the LAION / OpenCLIP conversions)")
+        # per tower, as the reference's ACT2FN[config.hidden_act] (:388): which fc1 / dpre epilogue kinds the layer calls pick
+        self.act_kind = XF.L.ACTS[config.hidden_act]
         self.fc1 = nn.Linear(config.hidden_size, config.intermediate_size)
         self.fc2 = nn.Linear(config.intermediate_size, config.hidden_size)
 

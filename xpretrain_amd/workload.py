@@ -9,21 +9,23 @@ import torch
 
 
 def hf_config_dict(vision_hidden, vision_heads, vision_layers, vision_inter, patch, image,
-                   text_hidden, text_heads, text_layers, text_inter, vocab, max_pos, proj) -> dict:
-    """A CLIPConfig-compatible dict (the shape of openai/clip-vit-base-patch{16,32}'s config.json)."""
+                   text_hidden, text_heads, text_layers, text_inter, vocab, max_pos, proj, hidden_act="quick_gelu") -> dict:
+    """A CLIPConfig-compatible dict (the shape of openai/clip-vit-base-patch{16,32}'s config.json).  ``hidden_act``: "quick_gelu"
+    (OpenAI's checkpoints) or "gelu" (the LAION / OpenCLIP conversions), one name for both towers or a ``(vision, text)`` pair."""
+    act_v, act_t = (hidden_act, hidden_act) if isinstance(hidden_act, str) else hidden_act
     text = {"model_type": "clip_text_model", "hidden_size": text_hidden, "intermediate_size": text_inter, "num_attention_heads": text_heads,
-            "num_hidden_layers": text_layers, "max_position_embeddings": max_pos, "vocab_size": vocab, "hidden_act": "quick_gelu",
+            "num_hidden_layers": text_layers, "max_position_embeddings": max_pos, "vocab_size": vocab, "hidden_act": act_t,
             "layer_norm_eps": 1e-5, "attention_dropout": 0.0, "projection_dim": proj, "bos_token_id": 0, "eos_token_id": 2, "pad_token_id": 1}
     vision = {"model_type": "clip_vision_model", "hidden_size": vision_hidden, "intermediate_size": vision_inter,
               "num_attention_heads": vision_heads, "num_hidden_layers": vision_layers, "image_size": image, "patch_size": patch,
-              "hidden_act": "quick_gelu", "layer_norm_eps": 1e-5, "attention_dropout": 0.0, "projection_dim": proj, "num_channels": 3}
+              "hidden_act": act_v, "layer_norm_eps": 1e-5, "attention_dropout": 0.0, "projection_dim": proj, "num_channels": 3}
     return {"model_type": "clip", "projection_dim": proj, "logit_scale_init_value": 2.6592, "initializer_factor": 1.0,
             "text_config": text, "vision_config": vision}
 
 
-def vit_b_config(patch: int = 16, image: int = 224) -> dict:
+def vit_b_config(patch: int = 16, image: int = 224, hidden_act="quick_gelu") -> dict:
     """ViT-B/{patch} video tower + the 12-layer / 512-wide CLIP text tower"""
-    return hf_config_dict(768, 12, 12, 3072, patch, image, 512, 8, 12, 2048, 49408, 77, 512)
+    return hf_config_dict(768, 12, 12, 3072, patch, image, 512, 8, 12, 2048, 49408, 77, 512, hidden_act=hidden_act)
 
 
 def synthetic_inputs(B, T, R, Lt, vocab=49408, seed=4321, dtype=torch.float32):
