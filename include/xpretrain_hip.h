@@ -363,6 +363,37 @@ int xp_vsc_fc_loss(const float* vis, const float* txt, const float* img, const f
                    float* loss, float* d_vis, float* d_txt, float* d_img, float* d_cap, float* d_log_scale,
                    int64_t n, int64_t d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The whole family of learnable-temperature contrastive losses of optimization/loss.py behind one entry: loss and every
+ * gradient in one call, fp32, fixed reduction order (bit-reproducible), all launches on `stream`.
+ * vis, txt [n,d]; img, cap [m,d]: gathered unit-norm features.  With s = exp(*log_scale), S1 = s V T^T, S2 = s V C^T,
+ * S3 = s I C^T, "rows(S)" = mean over i of (lse_j S_ij - S_ii) and "cols(S)" the same over columns:
+ *   XP_LOSS_NCE            rows(S1) + cols(S1)                                         NCELearnableTempLoss          :134-141
+ *   XP_LOSS_VS_VC          rows + cols of S1 and of S2                                 NCELearnableTempLoss_vs_vc    :212-225
+ *   XP_LOSS_VS_VC_FC       VS_VC + rows(S3) + cols(S3)                                 NCELearnableTempLoss_vs_vc_fc :235-254
+ *   XP_LOSS_VSC            cols(S1) + cols(S2) + mean_i(ra_i - S1_ii) + mean_i(rb_i - S2_ii) with merged negatives:
+ *                          ra_i = lse(S1[i,:] U S2[i,j!=i]), rb_i = lse(S1[i,j!=i] U S2[i,:])    NCELearnableTempLoss_vsc :264-286
+ *   XP_LOSS_VSC_FC         VSC + rows(S3) + cols(S3)                                   NCELearnableTempLoss_vsc_fc   :296-324
+ *   XP_LOSS_VIDIMG         rows + cols of the [n+m, n+m] logits of [V;I] against [T;C]  VidImgNCELearnableTempLoss    :151-160
+ *   XP_LOSS_VIDIMG_DIVIDE  rows + cols of S1 (mean over n) + rows + cols of S3 [m,m] (mean over m)
+ *                                                                                      VidImgDivideNCELearnableTempLoss :170-183
+ *   XP_LOSS_DSL            dual softmax, the prior NOT detached                        NCELearnableTempDSLLoss       :193-202
+ *       A = S1, Pc = softmax over i of A (per column), Pr = softmax over j of A (per row), B1 = A o Pc, B2 = A o Pr
+ *       loss = mean_i[lse_j B1_ij - B1_ii] + mean_j[lse_i B2_ij - B2_jj]
+ *       G1 = (softmax_rows(B1) - I)/n, G2 = (softmax_cols(B2) - I)/n, u_j = sum_k G1_kj B1_kj, w_i = sum_k G2_ik B2_ik
+ *       dloss/dA = Pc o (G1 o (1 + A) - u_j) + Pr o (G2 o (1 + A) - w_i);  dV = s G T, dT = s G^T V, d ls = sum(G o A)
+ * Every gradient follows the same way: d loss / d S* from the softmaxes, then two GEMMs per logit matrix and
+ * d log_scale = sum over the matrices of sum(G o S).
+ * A kind that does not read an operand takes NULL for it and for its gradient (they are ignored): NCE and DSL read neither
+ * img nor cap; VS_VC and VSC do not read img.  Only VIDIMG and VIDIMG_DIVIDE accept m != n.  n, m (n + m for VIDIMG) <= 16384.
+ * xp_nce_loss and xp_vsc_fc_loss are this entry with their kind: same kernels, same bits. */
+enum XpLossKind { XP_LOSS_NCE, XP_LOSS_VSC_FC, XP_LOSS_DSL, XP_LOSS_VS_VC, XP_LOSS_VS_VC_FC,
+                  XP_LOSS_VSC, XP_LOSS_VIDIMG, XP_LOSS_VIDIMG_DIVIDE };
+size_t xp_contrastive_loss_workspace_bytes(int32_t kind, int64_t n, int64_t m, int64_t d);
+int xp_contrastive_loss(int32_t kind, const float* vis, const float* txt, const float* img, const float* cap,
+                        const float* log_scale, float* loss, float* d_vis, float* d_txt, float* d_img, float* d_cap,
+                        float* d_log_scale, int64_t n, int64_t m, int64_t d,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------- Retrieval evaluation
  * validate() of tasks/run_video_retrieval.py:123-203 on gathered unit-norm features (fp32):
  *   sim = text . vis^T                     cal_cossim, utils/metrics.py:3-5

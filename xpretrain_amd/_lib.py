@@ -25,6 +25,9 @@ ACTS = {"quick_gelu": ACT_QUICK_GELU, "gelu": ACT_GELU}
 EPI_ACT_FWD = (EPI_BIAS_GELU, EPI_BIAS_GELU_ERF)
 EPI_ACT_BWD = (EPI_GELU_BWD, EPI_GELU_ERF_BWD)
 ATTN_PROXY, ATTN_CAUSAL = 0, 1
+# XpLossKind, in the header's order
+(XP_LOSS_NCE, XP_LOSS_VSC_FC, XP_LOSS_DSL, XP_LOSS_VS_VC, XP_LOSS_VS_VC_FC, XP_LOSS_VSC, XP_LOSS_VIDIMG,
+ XP_LOSS_VIDIMG_DIVIDE) = range(8)
 
 i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -201,6 +204,8 @@ SIGNATURES = {
     "xp_retrieval_ranks": (i32, [vp, vp, i64, i64, i32, vp, vp, vp]),
     "xp_vsc_fc_loss_workspace_bytes": (sz, [i64, i64]),
     "xp_vsc_fc_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, sz, vp]),
+    "xp_contrastive_loss_workspace_bytes": (sz, [i32, i64, i64, i64]),
+    "xp_contrastive_loss": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, sz, vp]),
     "xp_encoder_layer_fwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),
     "xp_encoder_layer_fwd": (i32, [C.POINTER(XpLayerFwd), vp]),
     "xp_encoder_layer_bwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),

@@ -1112,6 +1112,26 @@ class VscFcLossFn(torch.autograd.Function):
         return tuple(t * g for t in ctx.saved_tensors)
 
 
+class ContrastiveLossFn(torch.autograd.Function):
+    """Any loss of the learnable-temperature family (optimization/loss.py:126-324) by its ``XP_LOSS_*`` kind; loss and
+    gradients in one kernel pass.  An operand the kind does not read gets no gradient (``None``): with ``vs_vc`` / ``vsc`` the
+    frame pass of the video tower has no backward at all, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, kind, vis, txt, img, cap, log_scale):
+        def f(t):
+            return None if t is None else t.contiguous().float()
+        loss, *grads = H.contrastive_loss(kind, f(vis), f(txt), f(img), f(cap), log_scale=log_scale.detach().float().reshape(()))
+        ctx.has = [g is not None for g in grads]
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        saved = iter(ctx.saved_tensors)
+        return (None, *[next(saved) * g if h else None for h in ctx.has])
+
+
 def _layer_params(layer):
     """the 16 parameters of a CLIPEncoderLayer in EncoderLayerFn's argument order.  The sub-module handles are cached on the layer
     (nn.Module.__getattr__ chains cost ~10 us per call otherwise); the Parameter objects are read from the modules' own tables

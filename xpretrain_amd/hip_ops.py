@@ -471,6 +471,44 @@ def vsc_fc_loss(vis, txt, img, cap, log_scale):
     return (loss, *grads, dls)
 
 
+# XpLossKind -> (reads img, reads cap); an operand the kind does not read goes to the library as NULL
+_LOSS_OPERANDS = {L.XP_LOSS_NCE: (False, False), L.XP_LOSS_VSC_FC: (True, True), L.XP_LOSS_DSL: (False, False),
+                  L.XP_LOSS_VS_VC: (False, True), L.XP_LOSS_VS_VC_FC: (True, True), L.XP_LOSS_VSC: (False, True),
+                  L.XP_LOSS_VIDIMG: (True, True), L.XP_LOSS_VIDIMG_DIVIDE: (True, True)}
+
+
+def contrastive_loss(kind: int, vis, txt, img=None, cap=None, *, log_scale):
+    """xp_contrastive_loss: any loss of the learnable-temperature family (``L.XP_LOSS_*``) and all its gradients in one call.
+    vis/txt [n,d], img/cap [m,d].  Returns (loss, d_vis, d_txt, d_img, d_cap, d_log_scale) -- fp32 device tensors, ``None``
+    where the kind has no such operand (an ``img`` / ``cap`` it does not read is ignored).  What the kind itself rules out
+    (m != n, a missing operand, an unknown kind) is refused by the library before anything is launched."""
+    kind = int(kind)
+    use_img, use_cap = _LOSS_OPERANDS.get(kind, (img is not None, cap is not None))
+    img, cap = img if use_img else None, cap if use_cap else None
+    ops = [(vis, "vis"), (txt, "txt"), (img, "img"), (cap, "cap")]
+    for t, name in ops + [(log_scale, "log_scale")]:
+        if t is not None:
+            _chk(t, name, torch.float32)
+    for t, name in ops:
+        if t is not None and (t.dim() != 2 or t.shape[1] != vis.shape[-1] or not t.is_contiguous()):
+            raise ValueError(f"contrastive_loss: {name} must be a contiguous [rows, {vis.shape[-1]}] matrix, got {tuple(t.shape)}")
+    if txt.shape != vis.shape or (img is not None and cap is not None and img.shape != cap.shape):
+        raise ValueError(f"contrastive_loss: feature shapes differ: {[None if t is None else tuple(t.shape) for t, _ in ops]}")
+    n, d = vis.shape
+    side = cap if cap is not None else img
+    m = n if side is None else side.shape[0]
+    dev = vis.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dls = torch.empty((), dtype=torch.float32, device=dev)
+    grads = [None if t is None else torch.empty_like(t) for t, _ in ops]
+    nb = L.lib().xp_contrastive_loss_workspace_bytes(kind, n, m, d)
+    ws = workspace(nb, dev, "loss")
+    L.check(L.lib().xp_contrastive_loss(kind, _p(vis), _p(txt), _p(img), _p(cap), _p(log_scale), _p(loss), _p(grads[0]),
+                                        _p(grads[1]), _p(grads[2]), _p(grads[3]), _p(dls), n, m, d, _p(ws), ws.numel(),
+                                        _stream()), "xp_contrastive_loss")
+    return (loss, *grads, dls)
+
+
 # --------------------------------------------------------------------------------------- attention
 def _attn_ws(mode, B, H, M, N, Lp, device):
     nb = L.lib().xp_attn_workspace_bytes(mode, B, H, M, N, Lp)

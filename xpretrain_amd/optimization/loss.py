@@ -2,12 +2,15 @@
 
 ``NCELearnableTempLoss`` (loss.py:126-141) is the hot-path loss: fused HIP kernel computing
 exp(temp) * vis @ text^T, both cross-entropies and all gradients in one call
-(csrc/loss.hip).  ``build_loss_func(cfg)`` keeps the reference's factory signature (loss.py:326-328).
+(csrc/loss.hip).  The other learnable-temperature losses the reference drivers name (run_pretrain.py:355-363,
+run_video_retrieval.py:333) run through the same library path, one ``XP_LOSS_*`` kind each (xp_contrastive_loss).
+``build_loss_func(cfg)`` keeps the reference's factory signature (loss.py:326-328).
 """
 from __future__ import annotations
 
 from torch import nn
 
+from .. import _lib as L
 from .. import functional as XF
 
 
@@ -33,7 +36,60 @@ class NCELearnableTempLoss_vsc_fc(nn.Module):
         return XF.VscFcLossFn.apply(vis_feat, text_feat, img_feat, cap_feat, temp)
 
 
-_LOSSES = {"NCELearnableTempLoss": NCELearnableTempLoss, "NCELearnableTempLoss_vsc_fc": NCELearnableTempLoss_vsc_fc}
+class _FamilyLoss(nn.Module):
+    """a loss of the family by its kind; `temp` is the LOG-scale parameter"""
+    kind = None
+
+    def __init__(self, cfg=None):
+        super().__init__()
+
+    def forward(self, vis_feat, text_feat, img_feat, cap_feat, temp):
+        return XF.ContrastiveLossFn.apply(self.kind, vis_feat, text_feat, img_feat, cap_feat, temp)
+
+
+class VidImgNCELearnableTempLoss(_FamilyLoss):
+    """loss.py:143-160: NCELearnableTempLoss over the concatenations [vis; img] and [text; cap] (img/cap may have another
+    row count than vis/text)."""
+    kind = L.XP_LOSS_VIDIMG
+
+
+class VidImgDivideNCELearnableTempLoss(_FamilyLoss):
+    """loss.py:162-183: NCELearnableTempLoss(vis, text) + NCELearnableTempLoss(img, cap), each with its own mean."""
+    kind = L.XP_LOSS_VIDIMG_DIVIDE
+
+
+class NCELearnableTempDSLLoss(_FamilyLoss):
+    """loss.py:185-202, the retrieval finetuning loss with the dual-softmax prior: each direction's logits are multiplied by
+    their softmax over the OTHER axis before the cross-entropy; the prior is not detached (its Jacobian is in the gradient)."""
+    kind = L.XP_LOSS_DSL
+
+    def forward(self, vis_feat, text_feat, temp):
+        return XF.ContrastiveLossFn.apply(self.kind, vis_feat, text_feat, None, None, temp)
+
+
+class NCELearnableTempLoss_vs_vc(_FamilyLoss):
+    """loss.py:204-225: video-subtitle + video-caption, four cross-entropy terms.  `img_feat` is accepted and not read."""
+    kind = L.XP_LOSS_VS_VC
+
+
+class NCELearnableTempLoss_vs_vc_fc(_FamilyLoss):
+    """loss.py:227-254: vs_vc + frame-caption, six cross-entropy terms."""
+    kind = L.XP_LOSS_VS_VC_FC
+
+
+class NCELearnableTempLoss_vsc(_FamilyLoss):
+    """loss.py:256-286: video-(subtitle, caption) with the off-diagonal negatives of both merged behind either positive.
+    `img_feat` is accepted and not read."""
+    kind = L.XP_LOSS_VSC
+
+    def forward(self, vis_feat, text_feat, img_feat, cap_feat, temp):
+        assert text_feat.shape[0] == cap_feat.shape[0]                       # loss.py:265
+        return super().forward(vis_feat, text_feat, img_feat, cap_feat, temp)
+
+
+_LOSSES = {c.__name__: c for c in (
+    NCELearnableTempLoss, VidImgNCELearnableTempLoss, VidImgDivideNCELearnableTempLoss, NCELearnableTempDSLLoss,
+    NCELearnableTempLoss_vs_vc, NCELearnableTempLoss_vs_vc_fc, NCELearnableTempLoss_vsc, NCELearnableTempLoss_vsc_fc)}
 
 
 def build_loss_func(cfg):
