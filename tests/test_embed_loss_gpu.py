@@ -90,6 +90,41 @@ def test_l2norm_and_cast(dtype):
     assert torch.equal(H.cast_back(H.cast(w, dtype)), w.to(dtype).float())
 
 
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_text_embed_bwd_many_rows_mostly_padding(dtype):
+    """640 token rows (B 20, Lt 32), the padding id filling more than half of every row: the first occurrence of that id walks
+    three 256-row ballot chunks that each hold repeats (the other test has 48 rows: one chunk), other ids repeat across chunks too"""
+    from xpretrain_amd import hip_ops as H
+    B, Lt, D, V = 20, 32, 512, 40
+    g = torch.Generator().manual_seed(20)
+    ids = torch.randint(0, V - 1, (B, Lt), generator=g)
+    for b in range(B):
+        ids[b, 5 + b % 11:] = V - 1                     # 17 .. 27 of the 32 positions
+    assert bool(((ids == V - 1).sum(1) > Lt // 2).all())
+    ids = ids.cuda()
+    dx = torch.randn(B, Lt, D, generator=g).cuda().to(dtype)
+    d_tok, d_pos = H.text_embed_bwd(ids, dx, V, Lt)
+    rt = torch.zeros(V, D, dtype=torch.float64, device="cuda").index_add_(0, ids.view(-1), dx.double().view(-1, D))
+    assert report(f"d_tok 640 rows {dtype}", d_tok, rt, 1e-5) <= 1e-5
+    pad_row = report(f"d_tok 640 rows, the padding id's row {dtype}", d_tok[V - 1], rt[V - 1], 1e-5)
+    assert pad_row <= 1e-5
+    assert report(f"d_pos_text 640 rows {dtype}", d_pos, dx.double().sum(0), 1e-5) <= 1e-5
+    again, _ = H.text_embed_bwd(ids, dx, V, Lt)
+    assert torch.equal(again, d_tok)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_cast_beyond_the_grid_cap(dtype):
+    """9 Mi elements: more 4-element vectors than the 8192-block grid has threads, so the grid-stride loop runs a second time
+    (the token-embedding table's cast in production)"""
+    from xpretrain_amd import hip_ops as H
+    n = 9 << 20
+    w = torch.randn(n, device="cuda")
+    got = H.cast(w, dtype)
+    assert torch.equal(got, w.to(dtype))
+    assert torch.equal(H.cast_back(got), w.to(dtype).float())
+
+
 def test_nce_loss_against_reference_fixtures(golden):
     """fp32 kernel vs outputs of the reference's NCELearnableTempLoss (tests/golden/loss.pt)."""
     from xpretrain_amd import hip_ops as H

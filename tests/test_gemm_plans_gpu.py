@@ -16,37 +16,14 @@ import torch
 
 from tests import gemm_cases as G
 from tests.gpu_util import OUT, report
+from tests.guarded import _SENT, Guarded, _guarded_defer      # noqa: F401  (the guard helpers, shared with the workspace tests)
 from tests.test_planning_cpu import case_budget, case_desc, check_plan, resolve_split, set_case_env
 
 pytestmark = pytest.mark.gpu
 
 DT = {"bf16": torch.bfloat16, "f32": torch.float32}
 TOL = {"bf16": 6e-3, "f32": 2e-5}           # tests/test_gemm_gpu.py: output rounding (bf16) / accumulation (fp32 output)
-_SENT = {torch.bfloat16: (torch.int16, 0x7FA5), torch.float32: (torch.int32, 0x7FA5A5A5)}      # NaN bit patterns
 PAD_VALUE = 1000.0                          # input elements outside the operands' extents
-
-
-class Guarded:
-    """a [rows, cols] matrix inside a flat buffer that holds a sentinel bit pattern in front of it, after it and in every
-    element the kernel must not write"""
-
-    def __init__(self, rows, cols, dtype, lead=64, tail_rows=2):
-        self.itype, self.sent = _SENT[dtype]
-        self.lead, self.rows, self.cols = lead, rows, cols
-        self.flat = torch.empty(lead + (rows + tail_rows) * cols + lead, dtype=dtype, device="cuda")
-        self.flat.view(self.itype).fill_(self.sent)
-        self.mat = self.flat[lead:lead + rows * cols].view(rows, cols)
-
-    def check(self, tag, rows, ncols):
-        """nothing outside columns [0, ncols) of `rows` (a row-index tensor, or an int: the first rows) was written"""
-        written = torch.zeros(self.flat.numel(), dtype=torch.bool, device="cuda")
-        w = written[self.lead:self.lead + self.rows * self.cols].view(self.rows, self.cols)
-        if isinstance(rows, int):
-            w[:rows, :ncols] = True
-        else:
-            w[rows, :ncols] = True
-        bad = (self.flat.view(self.itype)[~written] != self.sent).sum().item()
-        assert bad == 0, f"{tag}: {bad} elements written outside the output window"
 
 
 def _remap(grp, stride, off, r):
@@ -104,18 +81,6 @@ def _edges_ok(tag, C, ref, plan, tol):
     print(f"{tag}: last tile row {e_row:.2e} last tile column {e_col:.2e}")
     assert e_row <= tol and e_col <= tol, (tag, e_row, e_col)
     return max(e_row, e_col)
-
-
-def _guarded_defer(nrows, N):
-    """a DeferredReduce whose partial-row slot sits in a Guarded buffer"""
-    from xpretrain_amd import hip_ops as H
-
-    class Defer(H.DeferredReduce):
-        def slot(self, nbytes, name):
-            assert nbytes == nrows * N * 4
-            self.guard = Guarded(nrows, N, torch.float32)
-            return self.guard.mat
-    return Defer(torch.device("cuda"))
 
 
 def _log(line):

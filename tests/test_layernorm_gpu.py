@@ -11,6 +11,16 @@ TOL = {torch.bfloat16: 6e-3, torch.float32: 1e-5}
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("rows,cols", [(204, 768), (7, 512), (1030, 128), (33, 1024), (5, 192)])
 def test_layernorm_fwd_bwd(dtype, rows, cols):
+    _fwd_bwd(dtype, rows, cols)
+
+
+def test_layernorm_bf16_width_not_a_multiple_of_8():
+    """cols = 132: the only way into ln_fwd_kernel<bf16_t> (8-byte accesses) -- every other tested width is a multiple of 8 and
+    takes the 16-byte kernel; two 256-column slabs would not reach its tail either (132 = 33 lanes of 4)"""
+    _fwd_bwd(torch.bfloat16, 37, 132)
+
+
+def _fwd_bwd(dtype, rows, cols):
     from xpretrain_amd import hip_ops as H
     torch.manual_seed(rows + cols)
     x = (torch.randn(rows, cols, device="cuda") * 2 + 0.5).to(dtype)
@@ -23,6 +33,11 @@ def test_layernorm_fwd_bwd(dtype, rows, cols):
     tol = TOL[dtype]
     assert report(f"ln_fwd {dtype} {rows}x{cols}", y, yref, tol) <= tol
     assert report("ln_mean", mean, xd.mean(-1), 1e-5) <= 1e-5
+    rstd_ref = 1.0 / (xd.detach().var(-1, unbiased=False) + 1e-5).sqrt()
+    tol_r = 1e-5 if dtype == torch.float32 else 1e-4          # relative, per row
+    e_rstd = ((rstd.double() - rstd_ref).abs() / rstd_ref).max().item()
+    print(f"ln_rstd {dtype} {rows}x{cols}: max relative error {e_rstd:.3e} tol {tol_r:.0e}")
+    assert report("ln_rstd", rstd, rstd_ref, tol_r) <= tol_r and e_rstd <= tol_r
     dy = torch.randn(rows, cols, device="cuda").to(dtype)
     dres = torch.randn(rows, cols, device="cuda").to(dtype)
     yref.backward(dy.double())
