@@ -18,7 +18,7 @@ by reading every kernel's use of its workspace (before this file first ran on a 
     accumulation into scratch.  attention_f32.hip: ``delta`` only, written by its first backward kernel.
   * csrc/attention_pooled.hip: per-chunk (m, l), O and dq partials, each written by its chunk's workgroup and combined in chunk
     order by a second launch; no counter, no atomics.
-  * xp_reduce_rows_batch / xp_colsum (gemm.hip), xp_layernorm_bwd* (layernorm.hip), xp_vip_embed_bwd (embed.hip): partial rows
+  * xp_reduce_rows_batch / xp_colsum (reduce.hip), xp_layernorm_bwd* (layernorm.hip), xp_vip_embed_bwd (embed.hip): partial rows
     written by level 1, read by level 2; segments of <= 64 rows skip level 1 and do not touch the workspace.  No such word.
   * loss.hip: logits, statistics, G matrices and part[] are each written by one launch and read by the following ones.
   * layer.hip: a bump allocator over the caller's workspace that checks every take against ``workspace_bytes``; the regions are

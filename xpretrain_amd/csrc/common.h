@@ -37,6 +37,10 @@ int xp_device_cus(const void* kernel = nullptr, int lds_bytes = 0);     // CUs o
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// reduce.hip, rows_reduce_kernel: out[y][c] (+)= the sum of rows [y * nsum, min((y + 1) * nsum, nrows)) of the dense fp32 matrix
+// in[nrows][width], for every y < ceil(nrows / nsum), in that file's fixed order (tree A).  The caller checks the launch.
+void xp_launch_rows_reduce(const float* in, float* out, int nrows, int nsum, int width, int accumulate, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------ scalars
 template <typename T> struct DT;
 template <> struct DT<bf16_t> { static constexpr int id = XP_BF16; };

@@ -13,6 +13,10 @@
 // k-strided operands (dX: W[n][k] with contraction over n; dW: dY[m][n], X[m][k] with contraction over m)
 // are NOT transposed in memory: they are staged as [k][row] tiles and read with ds_read_b64_tr_b16
 // (bf16) / ds_read_b32 (f32), which deliver exactly the MFMA fragment.
+//
+// This file: the 128x128 kernel, its debug trace and in-step timer, the planner (plan_gemm: family, tiling, split-K, epilogue) with
+// xp_gemm, and the split-K planning (xp_gemm_auto_split*, the CU budget).  The 256x256 family is gemm256.hip; the split-K slab sum
+// and the column sums of the bias gradients are reduce.hip.
 #include "common.h"
 #include "gemm_common.h"
 #include <stdlib.h>
@@ -471,184 +475,6 @@ void launch(Family f, const XpGemmDesc* d, const KParams& kp, dim3 grid, hipStre
   else                     launch2<T, false>(d, kp, grid, st);
 }
 
-// ---- split-K slab reduce, column sums ---------------------------------------------------------------
-__global__ void splitk_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ out, int64_t n4,
-                                     int splits, int accumulate) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const f32x4* sl = reinterpret_cast<const f32x4*>(slabs);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 s = accumulate ? reinterpret_cast<const f32x4*>(out)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-    int z = 0;
-    for (; z + 4 <= splits; z += 4) {         // 4 independent 16-byte loads in flight per lane
-      const f32x4 a = sl[(int64_t)z * n4 + i], b = sl[(int64_t)(z + 1) * n4 + i];
-      const f32x4 c = sl[(int64_t)(z + 2) * n4 + i], d = sl[(int64_t)(z + 3) * n4 + i];
-      s += (a + b) + (c + d);
-    }
-    for (; z < splits; ++z) s += sl[(int64_t)z * n4 + i];
-    reinterpret_cast<f32x4*>(out)[i] = s;
-  }
-}
-
-// Column sums (bias gradients): block = 4 waves; wave w sums rows r0+w, r0+w+4, ... of a CS_ROWS-row chunk for 256
-// columns (4 per lane, 8/16-byte loads, 512 B contiguous per wave instruction), 4-deep independent accumulators;
-// LDS combine of the 4 waves; one partial row per chunk -> splitk_reduce.  Grid: (cols/256, rows/CS_ROWS).
-// rows per chunk: narrow matrices need many chunks to fill the chip, wide ones can take longer chunks (fewer partial rows
-// for the second level): aim at >= ~2048 workgroups, 32..128 rows each
-static inline int cs_rows(int64_t rows, int64_t cols) {
-  const int64_t per = rows * cdiv(cols, 256) / 2048;
-  return per >= 128 ? 128 : (per >= 64 ? 64 : 32);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict__ X, int64_t rows, int64_t cols, int64_t ldx,
-                                                             float* __restrict__ part, int CS_ROWS) {
-  __shared__ float red[4][256];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t c = ((int64_t)blockIdx.x * 64 + lane) * 4;
-  const int64_t r0 = (int64_t)blockIdx.y * CS_ROWS;
-  const int64_t r1 = r0 + CS_ROWS < rows ? r0 + CS_ROWS : rows;
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-  if (c < cols) {
-    int64_t r = r0 + w;
-    for (; r + 4 < r1; r += 8) { s0 += load4(X + r * ldx + c); s1 += load4(X + (r + 4) * ldx + c); }
-    if (r < r1) s0 += load4(X + r * ldx + c);
-  }
-  store4(&red[w][lane * 4], s0 + s1);
-  __syncthreads();
-  if (w == 0 && c < cols) {
-    const f32x4 t = load4(&red[0][lane * 4]) + load4(&red[1][lane * 4]) + load4(&red[2][lane * 4]) + load4(&red[3][lane * 4]);
-    store4(part + (int64_t)blockIdx.y * cols + c, t);
-  }
-}
-
-// out[y][c] (+)= sum of `nsum` consecutive rows of in[.][width] starting at y*nsum; 64 columns per block, 4 waves
-// take every 4th row, LDS combine (deterministic order).
-__global__ __launch_bounds__(256) void rows_reduce_kernel(const float* __restrict__ in, float* __restrict__ out, int nrows,
-                                                          int nsum, int width, int accumulate) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  const int r0 = blockIdx.y * nsum, r1 = r0 + nsum < nrows ? r0 + nsum : nrows;
-  float s0 = 0.f, s1 = 0.f;
-  if (c < width) {
-    int r = r0 + w;
-    for (; r + 4 < r1; r += 8) { s0 += in[(int64_t)r * width + c]; s1 += in[(int64_t)(r + 4) * width + c]; }
-    if (r < r1) s0 += in[(int64_t)r * width + c];
-  }
-  red[w][lane] = s0 + s1;
-  __syncthreads();
-  if (w == 0 && c < width) {
-    const float t = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-    float* o = out + (int64_t)blockIdx.y * width + c;
-    *o = accumulate ? *o + t : t;
-  }
-}
-
-// ---- batched two-level row reduction (bias / LayerNorm-parameter gradients of one encoder layer in two launches) ----
-struct BatchArgs {
-  XpReduceSeg seg[XP_REDUCE_MAX_SEGS];
-  float* part2[XP_REDUCE_MAX_SEGS];        // level-1 output [<=32][width] per segment
-  int cb0[XP_REDUCE_MAX_SEGS + 1];         // prefix sum of 64-column blocks
-  int n;
-};
-constexpr int RB_DIRECT = 64;              // segments with <= this many rows skip level 1
-
-__device__ __forceinline__ int batch_find(const BatchArgs& a, int bx) {
-  int s = 0;
-  while (s + 1 < a.n && bx >= a.cb0[s + 1]) ++s;
-  return s;
-}
-
-// sum rows [r0, r1) of `in` (pitch `stride`) for column c; 4 waves take every 4th row, LDS combine (fixed order)
-__device__ __forceinline__ float batch_colsum(const float* __restrict__ in, int64_t stride, int r0, int r1, int c, bool ok,
-                                              float (*red)[64]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  float s0 = 0.f, s1 = 0.f;
-  if (ok) {
-    int r = r0 + w;
-    for (; r + 4 < r1; r += 8) { s0 += in[(int64_t)r * stride + c]; s1 += in[(int64_t)(r + 4) * stride + c]; }
-    if (r < r1) s0 += in[(int64_t)r * stride + c];
-  }
-  red[w][lane] = s0 + s1;
-  __syncthreads();
-  return red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-}
-
-__global__ __launch_bounds__(256) void reduce_batch_l1_kernel(BatchArgs a) {
-  __shared__ float red[4][64];
-  const int s = batch_find(a, blockIdx.x);
-  const XpReduceSeg sg = a.seg[s];
-  if (sg.nrows <= RB_DIRECT) return;
-  const int nsum = (sg.nrows + 31) / 32;
-  const int r0 = blockIdx.y * nsum;
-  if (r0 >= sg.nrows) return;
-  const int r1 = r0 + nsum < sg.nrows ? r0 + nsum : sg.nrows;
-  const int c = (blockIdx.x - a.cb0[s]) * 64 + (threadIdx.x & 63);
-  const float t = batch_colsum(sg.in, sg.stride, r0, r1, c, c < sg.width, red);
-  if (threadIdx.x < 64 && c < sg.width) a.part2[s][(int64_t)blockIdx.y * sg.width + c] = t;
-}
-
-__global__ __launch_bounds__(256) void reduce_batch_l2_kernel(BatchArgs a) {
-  __shared__ float red[4][64];
-  const int s = batch_find(a, blockIdx.x);
-  const XpReduceSeg sg = a.seg[s];
-  const bool direct = sg.nrows <= RB_DIRECT;
-  const int nsum = (sg.nrows + 31) / 32;
-  const int n2 = direct ? sg.nrows : (sg.nrows + nsum - 1) / nsum;
-  const int c = (blockIdx.x - a.cb0[s]) * 64 + (threadIdx.x & 63);
-  const float t = batch_colsum(direct ? sg.in : a.part2[s], direct ? sg.stride : (int64_t)sg.width, 0, n2, c, c < sg.width, red);
-  if (threadIdx.x < 64 && c < sg.width) sg.out[c] = sg.accumulate ? sg.out[c] + t : t;
-}
-
-// The same two levels with FOUR adjacent columns per lane (16-byte loads, 256 columns per workgroup): a quarter of the workgroups --
-// the scalar level 1 of a ViT-B layer is 4992 workgroups of ~4 KB each, 20 us of workgroup dispatch on the backward's critical
-// stream for 14 MB.  Per column the rows are summed in exactly the order of batch_colsum (wave w takes rows r0 + w, + 8, ... into s0 and
-// r0 + w + 4, ... into s1; four wave sums combined in order): results are bit-identical to the scalar kernels.
-__device__ __forceinline__ f32x4 batch_colsum4(const float* __restrict__ in, int64_t stride, int r0, int r1, int c, bool ok,
-                                               f32x4 (*red)[64]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-  if (ok) {
-    int r = r0 + w;
-    for (; r + 4 < r1; r += 8) {
-      s0 += *reinterpret_cast<const f32x4*>(in + (int64_t)r * stride + c);
-      s1 += *reinterpret_cast<const f32x4*>(in + (int64_t)(r + 4) * stride + c);
-    }
-    if (r < r1) s0 += *reinterpret_cast<const f32x4*>(in + (int64_t)r * stride + c);
-  }
-  red[w][lane] = s0 + s1;
-  __syncthreads();
-  return ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-}
-
-__global__ __launch_bounds__(256) void reduce_batch4_l1_kernel(BatchArgs a) {
-  __shared__ f32x4 red[4][64];
-  const int s = batch_find(a, blockIdx.x);
-  const XpReduceSeg sg = a.seg[s];
-  if (sg.nrows <= RB_DIRECT) return;
-  const int nsum = (sg.nrows + 31) / 32;
-  const int r0 = blockIdx.y * nsum;
-  if (r0 >= sg.nrows) return;
-  const int r1 = r0 + nsum < sg.nrows ? r0 + nsum : sg.nrows;
-  const int c = (blockIdx.x - a.cb0[s]) * 256 + (threadIdx.x & 63) * 4;
-  const f32x4 t = batch_colsum4(sg.in, sg.stride, r0, r1, c, c < sg.width, red);
-  if (threadIdx.x < 64 && c < sg.width) *reinterpret_cast<f32x4*>(a.part2[s] + (int64_t)blockIdx.y * sg.width + c) = t;
-}
-
-__global__ __launch_bounds__(256) void reduce_batch4_l2_kernel(BatchArgs a) {
-  __shared__ f32x4 red[4][64];
-  const int s = batch_find(a, blockIdx.x);
-  const XpReduceSeg sg = a.seg[s];
-  const bool direct = sg.nrows <= RB_DIRECT;
-  const int nsum = (sg.nrows + 31) / 32;
-  const int n2 = direct ? sg.nrows : (sg.nrows + nsum - 1) / nsum;
-  const int c = (blockIdx.x - a.cb0[s]) * 256 + (threadIdx.x & 63) * 4;
-  const f32x4 t = batch_colsum4(direct ? sg.in : a.part2[s], direct ? sg.stride : (int64_t)sg.width, 0, n2, c, c < sg.width, red);
-  if (threadIdx.x < 64 && c < sg.width) {
-    f32x4* o = reinterpret_cast<f32x4*>(sg.out + c);
-    *o = sg.accumulate ? *o + t : t;
-  }
-}
-
 }  // namespace
 
 // occupancy query for the default bf16 NT direct-to-LDS kernel: resident workgroups per CU at `lds_bytes` dynamic LDS
@@ -951,99 +777,4 @@ static int32_t auto_split_fill(const XpGemmDesc* d, int64_t fill) {
   if (t128 >= 256) return 1;
   s0 = 512 / t128 < d->K / 512 ? 512 / t128 : d->K / 512;
   return valid_split(d->K, s0, ke);
-}
-
-extern "C" int xp_splitk_reduce(const float* slabs, float* out, int64_t n, int32_t splits, int32_t accumulate,
-                                void* stream) {
-  XP_REQUIRE(slabs && out && n > 0 && n % 4 == 0 && splits >= 1, "xp_splitk_reduce: bad arguments");
-  const int64_t n4 = n / 4;
-  int blocks = (int)(cdiv(n4, 256) < 8192 ? cdiv(n4, 256) : 8192);
-  splitk_reduce_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(slabs, out, n4, splits, accumulate);
-  XP_CHECK_LAUNCH("xp_splitk_reduce");
-  return XP_OK;
-}
-
-extern "C" int64_t xp_colsum_partial_rows(int64_t rows, int64_t cols) { return cdiv(rows, cs_rows(rows, cols)); }
-
-extern "C" int xp_colsum_partials(const void* X, int64_t rows, int64_t cols, int64_t ldx, int32_t dtype, float* partials,
-                                  size_t partials_bytes, void* stream) {
-  XP_REQUIRE(X && partials && rows > 0 && cols > 0 && cols % 4 == 0 && ldx % 4 == 0, "xp_colsum_partials: bad arguments");
-  const int csr = cs_rows(rows, cols), chunks = (int)cdiv(rows, csr);
-  XP_REQUIRE(partials_bytes >= (size_t)chunks * cols * sizeof(float), "xp_colsum_partials: partials buffer too small");
-  dim3 grid((unsigned)cdiv(cols, 256), chunks);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == XP_BF16) colsum_partial_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)X, rows, cols, ldx, partials, csr);
-  else if (dtype == XP_F32) colsum_partial_kernel<float><<<grid, 256, 0, st>>>((const float*)X, rows, cols, ldx, partials, csr);
-  else XP_REQUIRE(false, "xp_colsum_partials: bad dtype %d", dtype);
-  XP_CHECK_LAUNCH("xp_colsum_partials");
-  return XP_OK;
-}
-
-extern "C" size_t xp_reduce_rows_batch_workspace_bytes(const XpReduceSeg* segs_host, int32_t n) {
-  size_t b = 0;
-  for (int i = 0; segs_host && i < n; ++i) b += (size_t)32 * (size_t)(segs_host[i].width > 0 ? segs_host[i].width : 0) * sizeof(float);
-  return b + 16;
-}
-
-extern "C" int xp_reduce_rows_batch(const XpReduceSeg* segs_host, int32_t n, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-  XP_REQUIRE(segs_host && n > 0 && n <= XP_REDUCE_MAX_SEGS, "xp_reduce_rows_batch: n=%d not in 1..%d", n, XP_REDUCE_MAX_SEGS);
-  XP_REQUIRE(workspace && workspace_bytes >= xp_reduce_rows_batch_workspace_bytes(segs_host, n), "xp_reduce_rows_batch: workspace too small");
-  BatchArgs a;
-  a.n = n;
-  float* ws = (float*)workspace;
-  // four columns per lane when every segment allows 16-byte accesses (widths, pitches and addresses multiples of 4 floats: every
-  // segment the encoder layers pass); XPRETRAIN_DEBUG=rows_reduce_scalar keeps the one-column kernels (bit-identity test)
-  bool vec = ((uintptr_t)workspace & 15) == 0 && !xp_debug_flag("rows_reduce_scalar");
-  for (int i = 0; i < n && vec; ++i) {
-    const XpReduceSeg& sg = segs_host[i];
-    vec = sg.width % 4 == 0 && sg.stride % 4 == 0 && ((uintptr_t)sg.in & 15) == 0 && ((uintptr_t)sg.out & 15) == 0;
-  }
-  const int cw = vec ? 256 : 64;
-  int cb = 0;
-  bool any_l1 = false;
-  for (int i = 0; i < n; ++i) {
-    const XpReduceSeg& sg = segs_host[i];
-    XP_REQUIRE(sg.in && sg.out && sg.nrows > 0 && sg.width > 0 && sg.stride >= sg.width, "xp_reduce_rows_batch: bad segment %d", i);
-    a.seg[i] = sg; a.part2[i] = ws; a.cb0[i] = cb;
-    ws += (size_t)32 * sg.width;
-    cb += (int)cdiv(sg.width, cw);
-    any_l1 = any_l1 || sg.nrows > RB_DIRECT;
-  }
-  for (int i = n; i <= XP_REDUCE_MAX_SEGS; ++i) a.cb0[i] = cb;
-  hipStream_t st = (hipStream_t)stream;
-  if (any_l1) {
-    if (vec) reduce_batch4_l1_kernel<<<dim3((unsigned)cb, 32), 256, 0, st>>>(a);
-    else     reduce_batch_l1_kernel<<<dim3((unsigned)cb, 32), 256, 0, st>>>(a);
-    XP_CHECK_LAUNCH("xp_reduce_rows_batch(level 1)");
-  }
-  if (vec) reduce_batch4_l2_kernel<<<(unsigned)cb, 256, 0, st>>>(a);
-  else     reduce_batch_l2_kernel<<<(unsigned)cb, 256, 0, st>>>(a);
-  XP_CHECK_LAUNCH("xp_reduce_rows_batch(level 2)");
-  return XP_OK;
-}
-
-extern "C" size_t xp_colsum_workspace_bytes(int64_t rows, int64_t cols) {
-  return (size_t)((cdiv(rows, 32) + 32) * cols * sizeof(float));
-}
-
-extern "C" int xp_colsum(const void* X, int64_t rows, int64_t cols, int64_t ldx, int32_t dtype, float* out,
-                         int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-  XP_REQUIRE(X && out && rows > 0 && cols > 0 && cols % 4 == 0 && ldx % 4 == 0, "xp_colsum: bad arguments");
-  XP_REQUIRE(workspace && workspace_bytes >= xp_colsum_workspace_bytes(rows, cols), "xp_colsum: workspace too small");
-  const int csr = cs_rows(rows, cols), chunks = (int)cdiv(rows, csr);
-  dim3 grid((unsigned)cdiv(cols, 256), chunks);
-  hipStream_t st = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  if (dtype == XP_BF16) colsum_partial_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)X, rows, cols, ldx, part, csr);
-  else                  colsum_partial_kernel<float><<<grid, 256, 0, st>>>((const float*)X, rows, cols, ldx, part, csr);
-  XP_CHECK_LAUNCH("xp_colsum(partial)");
-  // two-level deterministic reduce of the chunk partials (chunks -> <=32 -> 1): no thread walks hundreds of rows
-  const int lvl = (int)cdiv(chunks, 32), n2 = (int)cdiv(chunks, lvl);
-  float* part2 = part + (int64_t)chunks * cols;
-  rows_reduce_kernel<<<dim3((unsigned)cdiv(cols, 64), (unsigned)n2), 256, 0, st>>>(part, part2, chunks, lvl, (int)cols, 0);
-  XP_CHECK_LAUNCH("xp_colsum(reduce1)");
-  rows_reduce_kernel<<<dim3((unsigned)cdiv(cols, 64), 1), 256, 0, st>>>(part2, out, n2, n2, (int)cols, accumulate);
-  XP_CHECK_LAUNCH("xp_colsum(reduce2)");
-  return XP_OK;
 }

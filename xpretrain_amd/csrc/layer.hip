@@ -1,7 +1,7 @@
 // One CLIPEncoderLayer pass per C-ABI call (modeling/CLIP_ViP.py:444-460 with CLIPAttention.forward2 :332-381 or
 // .forward :266-330 and CLIPMLP :392-396): the 8 forward / ~21 backward kernel launches of a layer are issued from native
 // code.  Pure host-side sequencing over the public entry points of this library (xp_layernorm_*, xp_gemm, xp_attn_*,
-// xp_colsum_partials, xp_splitk_reduce, xp_reduce_rows_batch) -- no kernel of its own -- so the arithmetic is identical,
+// and reduce.hip's xp_colsum_partials, xp_splitk_reduce, xp_reduce_rows_batch) -- no kernel of its own -- so the arithmetic is identical,
 // launch for launch, to driving those entry points one by one (the Python op-by-op path, functional.EncoderLayerFn with
 // XPRETRAIN_DEBUG=op_by_op; tests compare the two bit for bit).  Why: ~810 launches per training step cost 13.6 ms of
 // Python / ctypes time against 16.7 ms of GPU time (BENCH_r01); from C++ a launch costs 3-4 us.

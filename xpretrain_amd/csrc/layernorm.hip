@@ -4,7 +4,8 @@
 // loads, 512 B contiguous per wave instruction), statistics by DPP/shuffle wave reductions in fp32,
 // two-pass variance.  Backward fuses the residual-gradient add (dx = dres + LN'(dy)) and accumulates
 // the per-column dgamma/dbeta in registers across the rows a wave owns; one partial row per block is
-// reduced by xp_splitk_reduce's kernel.
+// left for the row reductions of reduce.hip (xp_reduce_rows_batch; xp_layernorm_bwd: rows_reduce_kernel,
+// then ln_param_reduce2_kernel below).
 #include "common.h"
 #include <stdlib.h>
 
@@ -266,30 +267,10 @@ __global__ __launch_bounds__(256) XP_NO_PK_F32 void ln_bwd_kernel(const T* __res
   }
 }
 
-// Sum `nsum` consecutive partial rows (each 2*cols wide: dgamma | dbeta) per blockIdx.y; 64 columns per block,
-// 4 waves take every 4th row (coalesced 256-byte reads, 4 loads in flight), LDS combine.  Called twice
-// (1024 -> 32 -> 1 rows) so no thread walks more than 8 rows and the sum order is fixed (deterministic).
-__global__ __launch_bounds__(256) void ln_param_reduce_kernel(const float* __restrict__ in, float* __restrict__ out, int nrows,
-                                                              int nsum, int width, int accumulate) {
-  __shared__ float red[4][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  const int r0 = blockIdx.y * nsum, r1 = r0 + nsum < nrows ? r0 + nsum : nrows;
-  float s0 = 0.f, s1 = 0.f;
-  if (c < width) {
-    int r = r0 + w;
-    for (; r + 4 < r1; r += 8) { s0 += in[(int64_t)r * width + c]; s1 += in[(int64_t)(r + 4) * width + c]; }
-    if (r < r1) s0 += in[(int64_t)r * width + c];
-  }
-  red[w][lane] = s0 + s1;
-  __syncthreads();
-  if (w == 0 && c < width) {
-    const float t = red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane];
-    float* o = out + (int64_t)blockIdx.y * width + c;
-    *o = accumulate ? *o + t : t;
-  }
-}
-
+// Last level of xp_layernorm_bwd's parameter-gradient reduction: sums the <= 32 rows (each 2*cols wide: dgamma | dbeta) the first
+// level left (reduce.hip::rows_reduce_kernel) and splits the result into the two outputs, which may be separate buffers.
+// Its order is NOT reduce.hip's tree A but "tree B": ONE accumulator per wave over rows w, w+4, ..., then the same four-wave combine
+// ((W0 + W1) + W2) + W3 -- different bits from tree A from 9 rows on (tests/reduce_emulation.py::tree_b).
 __global__ __launch_bounds__(256) void ln_param_reduce2_kernel(const float* __restrict__ in, float* dgamma, float* dbeta,
                                                                int nrows, int cols, int accumulate) {
   __shared__ float red[4][64];
@@ -413,7 +394,7 @@ extern "C" int xp_layernorm_bwd_side(const void* dy, int64_t lddy, const void* x
   float* part = (float*)workspace;
   const int width = 2 * (int)cols, lvl = (int)cdiv(blocks, 32);
   float* part2 = part + (int64_t)blocks * width;
-  ln_param_reduce_kernel<<<dim3((unsigned)cdiv(width, 64), (unsigned)cdiv(blocks, lvl)), 256, 0, st>>>(part, part2, blocks, lvl, width, 0);
+  xp_launch_rows_reduce(part, part2, blocks, lvl, width, 0, st);
   XP_CHECK_LAUNCH("xp_layernorm_bwd(reduce1)");
   const int n2 = (int)cdiv(blocks, lvl);
   // level 2 on the gamma half and the beta half (row stride = width)

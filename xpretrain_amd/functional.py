@@ -833,11 +833,7 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             _wgrad(dqkv, h1p, B, D, D, a_remap=(1, S, 0), slack=True, lddy=3 * D, out=dwqkv[:D])
             _wgrad(dkv, h1, rows, 2 * D, D, lddy=3 * D, out=dwqkv[D:])
         if want_b:
-            nq = L.lib().xp_colsum_partial_rows(B, D)
-            part = defer.slot(nq * D * 4, "dbq")
-            L.check(L.lib().xp_colsum_partials(H._p(dqkv), B, D, S * 3 * D, H._dt(dqkv), H._p(part), part.numel(), H._stream()),
-                    "xp_colsum_partials")
-            defer.add(part, 0, dbqkv, nq, D, D)
+            H.colsum_deferred(dqkv, B, D, defer, ldx=S * 3 * D, name="dbq", out=dbqkv)
         _, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dx=dx, defer=defer, name="ln1", x_side=side, side=lns)
         # the pooled rows once more, with their residual gradient (the parameter-gradient partial rows of this pass are dropped)
         ws = H.workspace(L.lib().xp_layernorm_bwd_workspace_bytes(B, D), dev, "ln1_pooled")

@@ -220,15 +220,17 @@ class DeferredReduce:
         self.segs, self._keep, self._names = [], [], set()
 
 
-def colsum_deferred(X: torch.Tensor, rows: int, cols: int, defer: DeferredReduce, ldx=None, name="colsum") -> torch.Tensor:
-    """Bias gradient whose final reduction is finished by ``defer.flush()``."""
+def colsum_deferred(X: torch.Tensor, rows: int, cols: int, defer: DeferredReduce, ldx=None, name="colsum", out=None,
+                    accumulate=False) -> torch.Tensor:
+    """Bias gradient whose final reduction is finished by ``defer.flush()``; written (``accumulate``: added) to the first ``cols``
+    elements of ``out`` if given."""
     _chk(X, "X")
-    out = torch.empty(cols, dtype=torch.float32, device=X.device)
+    out = torch.empty(cols, dtype=torch.float32, device=X.device) if out is None else out
     chunks = L.lib().xp_colsum_partial_rows(rows, cols)
     part = defer.slot(chunks * cols * 4, name)
     L.check(L.lib().xp_colsum_partials(_p(X), rows, cols, ldx or cols, _dt(X), _p(part), part.numel(), _stream()),
             "xp_colsum_partials")
-    defer.add(part, 0, out, chunks, cols, cols)
+    defer.add(part, 0, out, chunks, cols, cols, accumulate)
     return out
 
 
