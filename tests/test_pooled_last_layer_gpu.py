@@ -192,6 +192,48 @@ def test_native_pooled_calls_equal_the_op_by_op_composition(dtype):
                 assert g1[n] is not None and torch.equal(g1[n], g0[n]), n
 
 
+def test_pooled_op_by_op_backward_makes_every_layernorm_call_through_hip_ops(monkeypatch):
+    """the op-by-op backward of one pooled layer (B 2, S 9 = 1 + 2*4, D 128, bf16 with side rows) reaches the library's LayerNorm
+    backward through ``H.layernorm_bwd`` only -- LN2, LN1 over all rows, LN1 over the pooled rows (the pass whose parameter-gradient
+    partial rows are dropped) -- where tools/determinism_hunt.py can wrap it; dx and all sixteen gradients equal the native call's
+    bit for bit"""
+    import xpretrain_amd.functional as XF
+    from xpretrain_amd import hip_ops as H
+    B, S, size, D, heads, Dff = 2, 9, (1, 2, 4), 128, 2, 512
+    torch.manual_seed(3)
+    g = lambda *shape, s=0.05: (torch.randn(*shape, device="cuda") * s).requires_grad_()
+    params = [1 + g(D), g(D), g(D, D), g(D), g(D, D), g(D), g(D, D), g(D), g(D, D), g(D), 1 + g(D), g(D), g(Dff, D), g(Dff), g(D, Dff), g(D)]
+    params = [p.detach().requires_grad_() for p in params]
+    side = torch.randn(B * size[0], D, device="cuda")
+    x = torch.randn(B * S, D, device="cuda").bfloat16()
+    x.view(B, S, D)[:, :size[0]] = side.view(B, size[0], D).bfloat16()
+    x.requires_grad_()
+    w = torch.randn(B, D, device="cuda")
+    calls = []
+    real = H.layernorm_bwd
+
+    def counted(*a, **k):
+        calls.append((a[5], k.get("name")))
+        return real(*a, **k)
+
+    def run(native):
+        monkeypatch.setattr(XF, "LAYER_CALLS", native)
+        for t in [x] + params:
+            t.grad = None
+        x3, side_out = XF.PooledEncoderLayerFn.apply(x, *params, B, S, heads, size, True, side)
+        assert side_out.shape == (B, D) and not side_out.requires_grad
+        (x3.float() * w).sum().backward()
+        torch.cuda.synchronize()
+        return [t.grad.clone() for t in [x] + params]
+    native = run(True)
+    monkeypatch.setattr(H, "layernorm_bwd", counted)
+    ops = run(False)
+    assert calls == [(B, "ln2"), (B * S, "ln1"), (B, "ln1_pooled")]
+    assert len(native) == len(ops) == 17
+    for i, (a, b) in enumerate(zip(native, ops)):
+        assert torch.equal(a, b), f"gradient {i} differs between the native call and the op-by-op path"
+
+
 # ------------------------------------------------------------------------------------------------ where the switch applies
 def test_switch_falls_back_to_dense_where_the_stream_is_read(monkeypatch):
     """output_hidden_states=True, the vision tower called directly, a forward hook on the last layer: torch.equal to the

@@ -19,10 +19,26 @@ namespace {
 
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-struct Carver {            // bump allocator over the caller's workspace
-  char* base; size_t off, cap;
-  void* take(size_t n) { void* p = base ? base + off : nullptr; off += align256(n); return p; }
+// Bump allocator over a layer call's workspace.  Every call has ONE carve_* function below: the *_workspace_bytes query runs it
+// with a null base (nothing is checked, bytes() is the answer), the call runs it over the caller's buffer, where every take is
+// checked against `cap` -- so the reported size and the pointers a call uses cannot drift apart.
+struct Carver {
+  char* base; size_t cap, off = 0;
+  bool fits = true;          // false: a take went past cap (the pointers are then not to be used)
+  template <class T = void>
+  T* take(size_t n, size_t* aligned = nullptr) {       // aligned: the piece's size as the callee is told it
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    n = align256(n);
+    off += n;
+    if (aligned) *aligned = n;
+    if (base && off + 256 > cap) fits = false;
+    return p;
+  }
+  size_t bytes() const { return off + 256; }           // the pieces and the 256 bytes of slack the ABI-1 sizes have always had
 };
+// the refusal of a short workspace, before anything is launched (`w`: what carve_* returned, its Carver in `ws`)
+#define XP_REQUIRE_WORKSPACE(name, a, w)                                                                    \
+  XP_REQUIRE((a)->workspace && (w).ws.fits, "%s: workspace too small (%zu < %zu)", name, (a)->workspace_bytes, (w).ws.bytes())
 
 XpGemmDesc gemm_desc(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int dtype) {
   XpGemmDesc d;
@@ -170,70 +186,62 @@ int out_proj_mlp_fwd(const Args& a, int64_t n, int64_t ldr, const float* side_x,
 
 // The part of a backward workspace the shared stages use, for n rows: [dpre | dh2 | dx2 | dattn] activation-gradient temporaries,
 // fc1's bias-gradient partial rows, the second LayerNorm's partial rows, the batched-reduce scratch.
-struct TailBwdPlan {
-  size_t esz, dpre, dh, cs_pre, ln2, red, bytes, slabs;     // slabs: what the stage's three dW GEMMs need (not part of bytes)
+struct TailBwd {
+  void *dpre, *dh2, *dx2, *dattn, *red; float *cs_pre, *ln2_part;
+  size_t esz, cs_pre_bytes, ln2_bytes, red_bytes, slabs;    // slabs: what the stage's three dW GEMMs need (the caller carves them)
   int64_t db1_fused_rows, cs_pre_rows, ln_rows;
 };
-struct TailBwdWs { void *dpre, *dh2, *dx2, *dattn, *red; float *cs_pre, *ln2_part; };
 // db1_fused_rows: partial rows of fc1's bias gradient out of the dpre GEMM's epilogue (xp_gemm_colsum_rows), 0 = a separate
 // column-sum pass over dpre
-TailBwdPlan plan_tail_bwd(int64_t n, int64_t D, int64_t Dff, int dt, int64_t db1_fused_rows) {
-  TailBwdPlan p;
-  memset(&p, 0, sizeof(p));
-  p.esz = dt == XP_BF16 ? 2 : 4;
-  p.dpre = align256(n * Dff * p.esz); p.dh = align256(n * D * p.esz);
-  p.db1_fused_rows = db1_fused_rows;
-  p.cs_pre_rows = db1_fused_rows > 0 ? db1_fused_rows : xp_colsum_partial_rows(n, Dff);
-  p.cs_pre = align256(p.cs_pre_rows * Dff * sizeof(float));
-  p.ln_rows = xp_layernorm_bwd_partial_rows(n);
-  p.ln2 = align256(xp_layernorm_bwd_workspace_bytes(n, D));
-  p.red = align256((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16);
-  p.bytes = p.dpre + 3 * p.dh + p.cs_pre + p.ln2 + p.red;
-  p.slabs = max_slab_bytes(0, {wgrad_desc(nullptr, nullptr, nullptr, n, D, Dff, dt), wgrad_desc(nullptr, nullptr, nullptr, n, Dff, D, dt),
+TailBwd carve_tail_bwd(Carver& ws, int64_t n, int64_t D, int64_t Dff, int dt, int64_t db1_fused_rows) {
+  TailBwd t;
+  t.esz = dt == XP_BF16 ? 2 : 4;
+  t.dpre = ws.take(n * Dff * t.esz); t.dh2 = ws.take(n * D * t.esz); t.dx2 = ws.take(n * D * t.esz); t.dattn = ws.take(n * D * t.esz);
+  t.db1_fused_rows = db1_fused_rows;
+  t.cs_pre_rows = db1_fused_rows > 0 ? db1_fused_rows : xp_colsum_partial_rows(n, Dff);
+  t.cs_pre = ws.take<float>(t.cs_pre_rows * Dff * sizeof(float), &t.cs_pre_bytes);
+  t.ln_rows = xp_layernorm_bwd_partial_rows(n);
+  t.ln2_part = ws.take<float>(xp_layernorm_bwd_workspace_bytes(n, D), &t.ln2_bytes);
+  t.red = ws.take((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16, &t.red_bytes);
+  t.slabs = max_slab_bytes(0, {wgrad_desc(nullptr, nullptr, nullptr, n, D, Dff, dt), wgrad_desc(nullptr, nullptr, nullptr, n, Dff, D, dt),
                                wgrad_desc(nullptr, nullptr, nullptr, n, D, D, dt)});
-  return p;
-}
-TailBwdWs carve_tail_bwd(Carver& ws, const TailBwdPlan& p) {
-  TailBwdWs w;
-  w.dpre = ws.take(p.dpre); w.dh2 = ws.take(p.dh); w.dx2 = ws.take(p.dh); w.dattn = ws.take(p.dh);
-  w.cs_pre = (float*)ws.take(p.cs_pre); w.ln2_part = (float*)ws.take(p.ln2); w.red = ws.take(p.red);
-  return w;
+  return t;
 }
 
 // x3 = x2 + fc2(act(fc1(LN2(x2)))) and x2 = resid + out_proj(attn_o), backwards: leaves dx2 and dattn in the workspace,
 // issues dW2, dW1, dWo and defers db1, dln2_w, dln2_b, dbo, db2.  Marks 1 and 2 of the weight-gradient stream.
 template <class Args>
-int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwdPlan& p, const TailBwdWs& w, float* slabs, size_t slab_bytes, int64_t sS,
+int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwd& t, float* slabs, size_t slab_bytes, int64_t sS,
                      int32_t sM, Defer& df, const WgradOrder& wg, void* st) {
   const int64_t D = a.dims.D, Dff = a.dims.Dff;
   const int dt = a.dims.dtype;
   int rc;
-  XpGemmDesc g = gemm_desc(a.dx3, a.W2, w.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * act'(pre)
+  XpGemmDesc g = gemm_desc(a.dx3, a.W2, t.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * act'(pre)
   g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(a.dims); g.resid = a.pre; g.ldr = Dff;
-  if (a.db1 && p.db1_fused_rows > 0) g.colsum_partials = w.cs_pre;
+  if (a.db1 && t.db1_fused_rows > 0) g.colsum_partials = t.cs_pre;
   if ((rc = xp_gemm(&g, st))) return rc;
   if (a.db1) {
-    if (p.db1_fused_rows == 0 && (rc = xp_colsum_partials(w.dpre, n, Dff, Dff, dt, w.cs_pre, p.cs_pre, st))) return rc;
-    df.add(w.cs_pre, a.db1, Dff, (int)p.cs_pre_rows, (int)Dff);
+    if (t.db1_fused_rows == 0 && (rc = xp_colsum_partials(t.dpre, n, Dff, Dff, dt, t.cs_pre, t.cs_pre_bytes, st))) return rc;
+    df.add(t.cs_pre, a.db1, Dff, (int)t.cs_pre_rows, (int)Dff);
   }
   if (a.dw2 && (rc = run_wgrad(wgrad_desc(a.dx3, a.act, a.dw2, n, D, Dff, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
   if ((rc = wg.mark(1))) return rc;                                           // dpre is ready for dW1
-  g = gemm_desc(w.dpre, a.W1, w.dh2, n, D, Dff, dt);                          // dh2 = dpre . W1
+  g = gemm_desc(t.dpre, a.W1, t.dh2, n, D, Dff, dt);                          // dh2 = dpre . W1
   g.b_kstrided = 1; g.ldb = D;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a.dw1 && (rc = run_wgrad(wgrad_desc(w.dpre, a.h2, a.dw1, n, Dff, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  if (a.dw1 && (rc = run_wgrad(wgrad_desc(t.dpre, a.h2, a.dw1, n, Dff, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
   // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)] -- out_proj's and fc2's bias gradients
-  if ((rc = xp_layernorm_bwd_partials_side(w.dh2, D, a.x2, D, a.ln2_w, a.mean2, a.rstd2, a.dx3, D, w.dx2, D, 2, n, D, dt,
-                                           a.side_x2, sS, sM, sM, w.ln2_part, p.ln2, st))) return rc;
-  df.add(w.ln2_part, a.dln2_w, 4 * D, (int)p.ln_rows, (int)D);
-  df.add(w.ln2_part + D, a.dln2_b, 4 * D, (int)p.ln_rows, (int)D);
-  df.add(w.ln2_part + 2 * D, a.dbo, 4 * D, (int)p.ln_rows, (int)D);
-  df.add(w.ln2_part + 3 * D, a.db2, 4 * D, (int)p.ln_rows, (int)D);
+  if ((rc = xp_layernorm_bwd_partials_side(t.dh2, D, a.x2, D, a.ln2_w, a.mean2, a.rstd2, a.dx3, D, t.dx2, D, 2, n, D, dt,
+                                           a.side_x2, sS, sM, sM, t.ln2_part, t.ln2_bytes, st))) return rc;
+  df.add(t.ln2_part, a.dln2_w, 4 * D, (int)t.ln_rows, (int)D);
+  df.add(t.ln2_part + D, a.dln2_b, 4 * D, (int)t.ln_rows, (int)D);
+  df.add(t.ln2_part + 2 * D, a.dbo, 4 * D, (int)t.ln_rows, (int)D);
+  df.add(t.ln2_part + 3 * D, a.db2, 4 * D, (int)t.ln_rows, (int)D);
   if ((rc = wg.mark(2))) return rc;                                           // dx2 is ready for dWo
-  g = gemm_desc(w.dx2, a.Wo, w.dattn, n, D, D, dt);                           // dattn = dx2 . Wo
+  g = gemm_desc(t.dx2, a.Wo, t.dattn, n, D, D, dt);                           // dattn = dx2 . Wo
   g.b_kstrided = 1; g.ldb = D;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a.dwo && (rc = run_wgrad(wgrad_desc(w.dx2, a.attn_o, a.dwo, n, D, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  if (a.dwo && (rc = run_wgrad(wgrad_desc(t.dx2, a.attn_o, a.dwo, n, D, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
   return XP_OK;
 }
 
@@ -263,11 +271,22 @@ extern "C" void* xp_side_stream(void) {
   return w ? (void*)w->side : nullptr;
 }
 
+// workspace of the forward: the attention workspace, then `side_rows` fp32 side rows of x2 (where XpLayerFwd::side_x2 is not given)
+namespace {
+struct FwdWs { Carver ws; void* attn; float* side_x2; size_t attn_bytes; };
+FwdWs carve_fwd(const XpLayerDims& d, int64_t side_rows, void* base, size_t cap) {
+  FwdWs w;
+  Carver& ws = w.ws = Carver{(char*)base, cap};
+  w.attn = ws.take(xp_attn_workspace_bytes(d.attn_mode, d.B, d.heads, d.M, d.N, d.L), &w.attn_bytes);
+  w.side_x2 = ws.take<float>((size_t)side_rows * d.D * sizeof(float));
+  return w;
+}
+}  // namespace
+
 extern "C" size_t xp_encoder_layer_fwd_workspace_bytes(const XpLayerDims* d) {
   if (!d) return 0;
-  // + the fp32 side rows of x2 (video: the proxy tokens; text: every row), used when XpLayerFwd::side_in is given
-  const size_t side_rows = d->attn_mode == XP_ATTN_PROXY ? (size_t)d->B * d->M : (size_t)d->rows;
-  return align256(xp_attn_workspace_bytes(d->attn_mode, d->B, d->heads, d->M, d->N, d->L)) + align256(side_rows * d->D * sizeof(float)) + 256;
+  // the side rows a caller may pass: the proxy tokens of every sample (video), every row (text)
+  return carve_fwd(*d, d->attn_mode == XP_ATTN_PROXY ? d->B * d->M : d->rows, nullptr, 0).ws.bytes();
 }
 
 extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
@@ -285,12 +304,11 @@ extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
   const bool sided = a->side_in != nullptr;
   XP_REQUIRE(!sided || (a->side_out && dt == XP_BF16 && a->side_S > 0 && a->side_M > 0 && a->side_M <= a->side_S),
              "xp_encoder_layer_fwd: side rows need side_in and side_out, bf16 and 0 < side_M <= side_S");
-  const size_t attn_ws = align256(xp_attn_workspace_bytes(d.attn_mode, d.B, d.heads, d.M, d.N, d.L));
   const int64_t sS = a->side_S;
   const int32_t sM = a->side_M;
-  XP_REQUIRE(!sided || a->workspace_bytes >= attn_ws + align256((size_t)(cdiv(rows, sS) * sM) * D * sizeof(float)),
-             "xp_encoder_layer_fwd: workspace too small for the side rows");
-  float* side_x2 = !sided ? nullptr : a->side_x2 ? a->side_x2 : reinterpret_cast<float*>(static_cast<char*>(a->workspace) + attn_ws);
+  const FwdWs w = carve_fwd(d, sided ? cdiv(rows, sS) * sM : 0, a->workspace, a->workspace_bytes);
+  XP_REQUIRE_WORKSPACE("xp_encoder_layer_fwd", a, w);
+  float* side_x2 = !sided ? nullptr : a->side_x2 ? a->side_x2 : w.side_x2;
   // h1 = LN1(x)
   if ((rc = xp_layernorm_fwd_side(a->x, D, a->ln1_w, a->ln1_b, a->h1, D, a->mean1, a->rstd1, rows, D, d.ln_eps, dt,
                                   a->side_in, nullptr, sS, sM, sM, st))) return rc;
@@ -299,46 +317,46 @@ extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
   g.epilogue = XP_EPI_BIAS_QSCALE; g.bias = a->bqkv; g.scale = d.q_scale; g.scale_cols = D;
   if ((rc = xp_gemm(&g, st))) return rc;
   if ((rc = xp_attn_fwd(a->qkv, 3 * D, a->attn_o, D, a->stats, a->pad_mask, d.attn_mode, d.B, d.heads, d.S, d.M, d.N, d.L, dt,
-                        a->workspace, a->workspace_bytes, st))) return rc;
+                        w.attn, w.attn_bytes, st))) return rc;
   return out_proj_mlp_fwd(*a, rows, D, a->side_in, side_x2, a->side_out, sS, sM, st);
 }
 
-// workspace of the backward: the shared stages' part (TailBwdPlan), [dqkv | dh1], split-K slabs, the q/k/v bias-gradient and first
+// workspace of the backward: the shared stages' part (TailBwd), [dqkv | dh1], split-K slabs, the q/k/v bias-gradient and first
 // LayerNorm's partial rows, the attention workspace
 namespace {
-struct BwdPlan {
-  TailBwdPlan t;
-  size_t dqkv, slabs, cs_qkv, ln1, attn, total;
+struct BwdWs {
+  Carver ws; TailBwd t;
+  void *dqkv, *dh1, *attn; float *slabs, *cs_qkv, *ln1_part;
+  size_t slab_bytes, cs_qkv_bytes, ln1_bytes, attn_bytes;
   int64_t cs_qkv_rows;
   bool cs_qkv_fused;
 };
-BwdPlan plan_bwd(const XpLayerDims& d) {
-  BwdPlan p;
-  memset(&p, 0, sizeof(p));
+BwdWs carve_bwd(const XpLayerDims& d, void* base, size_t cap) {
+  BwdWs w;
+  Carver& ws = w.ws = Carver{(char*)base, cap};
   const int64_t rows = d.rows, D = d.D, Dff = d.Dff;
   // fc1's bias gradient: fused into the dX GEMM epilogue where the library offers it, else a column-sum pass over dpre
   XpGemmDesc g = gemm_desc(nullptr, nullptr, nullptr, rows, Dff, D, d.dtype);
   g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(d); g.ldr = Dff;
   g.resid = &g;                          // (only tested for non-NULL by the planning queries)
-  p.t = plan_tail_bwd(rows, D, Dff, d.dtype, xp_gemm_colsum_rows(&g));
+  w.t = carve_tail_bwd(ws, rows, D, Dff, d.dtype, xp_gemm_colsum_rows(&g));
   // (fc2's bias gradient = column sums of dx3: taken by the second LayerNorm's backward)
-  p.dqkv = align256(rows * 3 * D * p.t.esz);
-  p.slabs = align256(max_slab_bytes(p.t.slabs, {wgrad_desc(nullptr, nullptr, nullptr, rows, 3 * D, D, d.dtype)}));
+  w.dqkv = ws.take(rows * 3 * D * w.t.esz); w.dh1 = ws.take(rows * D * w.t.esz);
+  w.slabs = ws.take<float>(max_slab_bytes(w.t.slabs, {wgrad_desc(nullptr, nullptr, nullptr, rows, 3 * D, D, d.dtype)}), &w.slab_bytes);
   // the q/k/v bias gradients: out of the attention backward kernels where they offer it, else a column-sum pass over dqkv
-  p.cs_qkv_rows = xp_attn_bwd_colsum_rows(d.attn_mode, d.B, d.heads, d.S, d.M, d.N, d.L, d.dtype);
-  p.cs_qkv_fused = p.cs_qkv_rows > 0;
-  if (!p.cs_qkv_fused) p.cs_qkv_rows = xp_colsum_partial_rows(rows, 3 * D);
-  p.cs_qkv = align256(p.cs_qkv_rows * 3 * D * sizeof(float));
-  p.ln1 = p.t.ln2;                       // (both LayerNorms run over the same [rows, D])
-  p.attn = align256(xp_attn_workspace_bytes(d.attn_mode, d.B, d.heads, d.M, d.N, d.L));
-  p.total = p.t.bytes + p.dqkv + p.t.dh + p.slabs + p.cs_qkv + p.ln1 + p.attn + 256;
-  return p;
+  w.cs_qkv_rows = xp_attn_bwd_colsum_rows(d.attn_mode, d.B, d.heads, d.S, d.M, d.N, d.L, d.dtype);
+  w.cs_qkv_fused = w.cs_qkv_rows > 0;
+  if (!w.cs_qkv_fused) w.cs_qkv_rows = xp_colsum_partial_rows(rows, 3 * D);
+  w.cs_qkv = ws.take<float>(w.cs_qkv_rows * 3 * D * sizeof(float), &w.cs_qkv_bytes);
+  w.ln1_part = ws.take<float>(w.t.ln2_bytes, &w.ln1_bytes);      // (both LayerNorms run over the same [rows, D])
+  w.attn = ws.take(xp_attn_workspace_bytes(d.attn_mode, d.B, d.heads, d.M, d.N, d.L), &w.attn_bytes);
+  return w;
 }
 }  // namespace
 
 extern "C" size_t xp_encoder_layer_bwd_workspace_bytes(const XpLayerDims* d) {
   if (!d || d->rows <= 0) return 0;
-  return plan_bwd(*d).total;
+  return carve_bwd(*d, nullptr, 0).ws.bytes();
 }
 
 extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
@@ -352,15 +370,8 @@ extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
   XP_REQUIRE((!a->side_in && !a->side_x2) || (a->side_in && a->side_x2 && d.dtype == XP_BF16 && a->side_S > 0 && a->side_M > 0 &&
                                                a->side_M <= a->side_S),
              "xp_encoder_layer_bwd: side rows need side_in and side_x2, bf16 and 0 < side_M <= side_S");
-  const BwdPlan p = plan_bwd(d);
-  XP_REQUIRE(a->workspace && a->workspace_bytes >= p.total, "xp_encoder_layer_bwd: workspace too small (%zu < %zu)",
-             a->workspace_bytes, p.total);
-  Carver ws{(char*)a->workspace, 0, a->workspace_bytes};
-  const TailBwdWs w = carve_tail_bwd(ws, p.t);
-  void* dqkv = ws.take(p.dqkv); void* dh1 = ws.take(p.t.dh);
-  float* slabs = (float*)ws.take(p.slabs);
-  float* cs_qkv = (float*)ws.take(p.cs_qkv); float* ln1_part = (float*)ws.take(p.ln1);
-  void* attn_ws = ws.take(p.attn);
+  const BwdWs w = carve_bwd(d, a->workspace, a->workspace_bytes);
+  XP_REQUIRE_WORKSPACE("xp_encoder_layer_bwd", a, w);
   const int64_t rows = d.rows, D = d.D;
   const int dt = d.dtype;
   Defer df;
@@ -368,24 +379,24 @@ extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
   const WgradOrder wg{(d.attn_mode == XP_ATTN_PROXY && rows >= 4096) ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_bwd"};
   if ((rc = wg.mark(0))) return rc;
   // ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo of x2 = x + out_proj(attn(qkv(LN1(x))))
-  if ((rc = mlp_out_proj_bwd(*a, rows, p.t, w, slabs, p.slabs, a->side_S, a->side_M, df, wg, st))) return rc;
+  if ((rc = mlp_out_proj_bwd(*a, rows, w.t, w.slabs, w.slab_bytes, a->side_S, a->side_M, df, wg, st))) return rc;
   // ---- attention
-  if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, w.dattn, D, a->stats, a->pad_mask, dqkv, d.q_scale, d.attn_mode, d.B, d.heads,
-                         d.S, d.M, d.N, d.L, dt, attn_ws, p.attn, (a->dbqkv && p.cs_qkv_fused) ? cs_qkv : nullptr, st))) return rc;
+  if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, w.t.dattn, D, a->stats, a->pad_mask, w.dqkv, d.q_scale, d.attn_mode, d.B, d.heads,
+                         d.S, d.M, d.N, d.L, dt, w.attn, w.attn_bytes, (a->dbqkv && w.cs_qkv_fused) ? w.cs_qkv : nullptr, st))) return rc;
   if ((rc = wg.mark(3))) return rc;                                           // dqkv is ready for dWqkv
-  XpGemmDesc g = gemm_desc(dqkv, a->Wqkv, dh1, rows, D, 3 * D, dt);           // dh1 = dqkv . Wqkv
+  XpGemmDesc g = gemm_desc(w.dqkv, a->Wqkv, w.dh1, rows, D, 3 * D, dt);       // dh1 = dqkv . Wqkv
   g.b_kstrided = 1; g.ldb = D;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dwqkv && (rc = run_wgrad(wgrad_desc(dqkv, a->h1, a->dwqkv, rows, 3 * D, D, dt), slabs, p.slabs, wg.stream(), false))) return rc;
+  if (a->dwqkv && (rc = run_wgrad(wgrad_desc(w.dqkv, a->h1, a->dwqkv, rows, 3 * D, D, dt), w.slabs, w.slab_bytes, wg.stream(), false))) return rc;
   if (a->dbqkv) {
-    if (!p.cs_qkv_fused && (rc = xp_colsum_partials(dqkv, rows, 3 * D, 3 * D, dt, cs_qkv, p.cs_qkv, st))) return rc;
-    df.add(cs_qkv, a->dbqkv, 3 * D, (int)p.cs_qkv_rows, (int)(3 * D));
+    if (!w.cs_qkv_fused && (rc = xp_colsum_partials(w.dqkv, rows, 3 * D, 3 * D, dt, w.cs_qkv, w.cs_qkv_bytes, st))) return rc;
+    df.add(w.cs_qkv, a->dbqkv, 3 * D, (int)w.cs_qkv_rows, (int)(3 * D));
   }
-  if ((rc = xp_layernorm_bwd_partials_side(dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, w.dx2, D, a->dx, D, 0, rows, D, dt,
-                                           a->side_in, a->side_S, a->side_M, a->side_M, ln1_part, p.ln1, st))) return rc;
-  df.add(ln1_part, a->dln1_w, 2 * D, (int)p.t.ln_rows, (int)D);
-  df.add(ln1_part + D, a->dln1_b, 2 * D, (int)p.t.ln_rows, (int)D);
-  return finish_bwd(df, w.red, p.t.red, wg, st);
+  if ((rc = xp_layernorm_bwd_partials_side(w.dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, w.t.dx2, D, a->dx, D, 0, rows, D, dt,
+                                           a->side_in, a->side_S, a->side_M, a->side_M, w.ln1_part, w.ln1_bytes, st))) return rc;
+  df.add(w.ln1_part, a->dln1_w, 2 * D, (int)w.t.ln_rows, (int)D);
+  df.add(w.ln1_part + D, a->dln1_b, 2 * D, (int)w.t.ln_rows, (int)D);
+  return finish_bwd(df, w.t.red, w.t.red_bytes, wg, st);
 }
 
 // ================================================================================== pooled last layer (video tower)
@@ -403,38 +414,50 @@ int check_pooled_dims(const char* name, const XpLayerDims& d) {
   return XP_OK;
 }
 
-struct PooledBwdPlan {
-  TailBwdPlan t;             // the shared stages over the B pooled rows
-  size_t dqkv, dh1, slabs, cs_q, cs_kv, ln1, ln1p, attn, total;
+// workspace of the pooled forward: the attention partials, then two [B, D] fp32 side buffers (the pooled rows of side_in; side_x2
+// of a forward-only pass)
+struct PooledFwdWs { Carver ws; void* attn; float *side0, *side_x2; size_t attn_bytes; };
+PooledFwdWs carve_pooled_fwd(const XpLayerDims& d, void* base, size_t cap) {
+  PooledFwdWs w;
+  Carver& ws = w.ws = Carver{(char*)base, cap};
+  w.attn = ws.take(xp_attn_pooled_workspace_bytes(d.B, d.heads, d.S, d.dtype), &w.attn_bytes);
+  w.side0 = ws.take<float>((size_t)d.B * d.D * sizeof(float)); w.side_x2 = ws.take<float>((size_t)d.B * d.D * sizeof(float));
+  return w;
+}
+
+// workspace of the pooled backward: the shared stages over the B pooled rows (TailBwd), [dqkv | dh1] over every row, split-K slabs,
+// the q and k/v bias-gradient partial rows, LayerNorm 1's partial rows of both passes, the attention partials
+struct PooledBwdWs {
+  Carver ws; TailBwd t;
+  char* dqkv; void *dh1, *attn; float *slabs, *cs_q, *cs_kv, *ln1_part, *ln1p_part;
+  size_t slab_bytes, cs_q_bytes, ln1_bytes, ln1p_bytes, attn_bytes;
   int64_t cs_q_rows, ln_rows;
 };
-PooledBwdPlan plan_pooled_bwd(const XpLayerDims& d) {
-  PooledBwdPlan p;
-  memset(&p, 0, sizeof(p));
+PooledBwdWs carve_pooled_bwd(const XpLayerDims& d, void* base, size_t cap) {
+  PooledBwdWs w;
+  Carver& ws = w.ws = Carver{(char*)base, cap};
   const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
   const int dt = d.dtype;
-  p.t = plan_tail_bwd(B, D, d.Dff, dt, 0);      // fc1's bias gradient: always a column-sum pass over dpre
-  p.dqkv = align256(rows * 3 * D * p.t.esz); p.dh1 = align256(rows * D * p.t.esz);
+  w.t = carve_tail_bwd(ws, B, D, d.Dff, dt, 0);      // fc1's bias gradient: always a column-sum pass over dpre
+  w.dqkv = ws.take<char>(rows * 3 * D * w.t.esz); w.dh1 = ws.take(rows * D * w.t.esz);
   XpGemmDesc gq = wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, B, D, D, dt);       // dWq: dq of the pooled rows of dqkv
   gq.a_grp = 1; gq.a_grp_stride = S;
-  p.slabs = align256(max_slab_bytes(p.t.slabs, {gq, wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, rows, 2 * D, D, dt)}));
-  p.cs_q_rows = xp_colsum_partial_rows(B, D);
-  p.cs_q = align256(p.cs_q_rows * D * sizeof(float));
-  p.cs_kv = align256(xp_attn_pooled_colsum_rows_max(B, S) * 2 * D * sizeof(float));
-  p.ln_rows = xp_layernorm_bwd_partial_rows(rows);
-  p.ln1 = align256(xp_layernorm_bwd_workspace_bytes(rows, D));
-  p.ln1p = p.t.ln2;                             // (LayerNorm 1 once more over the [B, D] pooled rows)
-  p.attn = align256(xp_attn_pooled_workspace_bytes(B, d.heads, S, dt));
-  p.total = p.t.bytes + p.dqkv + p.dh1 + p.slabs + p.cs_q + p.cs_kv + p.ln1 + p.ln1p + p.attn + 256;
-  return p;
+  w.slabs = ws.take<float>(max_slab_bytes(w.t.slabs, {gq, wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, rows, 2 * D, D, dt)}), &w.slab_bytes);
+  w.cs_q_rows = xp_colsum_partial_rows(B, D);
+  w.cs_q = ws.take<float>(w.cs_q_rows * D * sizeof(float), &w.cs_q_bytes);
+  w.cs_kv = ws.take<float>(xp_attn_pooled_colsum_rows_max(B, S) * 2 * D * sizeof(float));
+  w.ln_rows = xp_layernorm_bwd_partial_rows(rows);
+  w.ln1_part = ws.take<float>(xp_layernorm_bwd_workspace_bytes(rows, D), &w.ln1_bytes);
+  w.ln1p_part = ws.take<float>(w.t.ln2_bytes, &w.ln1p_bytes);      // (LayerNorm 1 once more over the [B, D] pooled rows)
+  w.attn = ws.take(xp_attn_pooled_workspace_bytes(B, d.heads, S, dt), &w.attn_bytes);
+  return w;
 }
 
 }  // namespace
 
 extern "C" size_t xp_encoder_layer_pooled_fwd_workspace_bytes(const XpLayerDims* d) {
   if (!d || d->B <= 0 || d->D <= 0 || d->S <= 0 || d->heads <= 0) return 0;
-  // the attention partials + two [B, D] fp32 side buffers (the pooled rows of side_in; side_x2 of a forward-only pass)
-  return align256(xp_attn_pooled_workspace_bytes(d->B, d->heads, d->S, d->dtype)) + 2 * align256((size_t)d->B * d->D * sizeof(float)) + 256;
+  return carve_pooled_fwd(*d, nullptr, 0).ws.bytes();
 }
 
 extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) {
@@ -449,10 +472,10 @@ extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) 
   const int dt = d.dtype;
   const bool sided = a->side_in != nullptr;
   XP_REQUIRE(!sided || (a->side_out && dt == XP_BF16), "xp_encoder_layer_pooled_fwd: side rows need side_in and side_out, and bf16");
-  const size_t attn_ws = align256(xp_attn_pooled_workspace_bytes(B, d.heads, S, dt)), side_b = align256((size_t)B * D * sizeof(float));
-  XP_REQUIRE(a->workspace && a->workspace_bytes >= attn_ws + 2 * side_b, "xp_encoder_layer_pooled_fwd: workspace too small");
-  float* side0 = !sided ? nullptr : reinterpret_cast<float*>(static_cast<char*>(a->workspace) + attn_ws);
-  float* side_x2 = !sided ? nullptr : a->side_x2 ? a->side_x2 : reinterpret_cast<float*>(static_cast<char*>(a->workspace) + attn_ws + side_b);
+  const PooledFwdWs w = carve_pooled_fwd(d, a->workspace, a->workspace_bytes);
+  XP_REQUIRE_WORKSPACE("xp_encoder_layer_pooled_fwd", a, w);
+  float* side0 = sided ? w.side0 : nullptr;
+  float* side_x2 = !sided ? nullptr : a->side_x2 ? a->side_x2 : w.side_x2;
   const int64_t sS = sided ? S : 0;
   const int32_t sM = sided ? (int32_t)d.M : 0, s1 = sided ? 1 : 0;
   const size_t esz = dt == XP_BF16 ? 2 : 4;
@@ -469,14 +492,14 @@ extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) 
   g = gemm_desc(a->h1p, a->Wqkv, a->q, B, D, D, dt);
   g.epilogue = XP_EPI_BIAS_QSCALE; g.bias = a->bqkv; g.scale = d.q_scale; g.scale_cols = D;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if ((rc = xp_attn_pooled_fwd(a->q, a->kv, 2 * D, a->attn_o, a->stats, B, d.heads, S, dt, a->workspace, attn_ws, st))) return rc;
+  if ((rc = xp_attn_pooled_fwd(a->q, a->kv, 2 * D, a->attn_o, a->stats, B, d.heads, S, dt, w.attn, w.attn_bytes, st))) return rc;
   // x2 = x[pooled] + attn_o Wo^T + bo, then the MLP
   return out_proj_mlp_fwd(*a, B, S * D, side0, side_x2, a->side_out, s1, s1, st);
 }
 
 extern "C" size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* d) {
   if (!d || d->rows <= 0 || d->B <= 0 || d->D <= 0 || d->Dff <= 0 || d->S <= 0 || d->heads <= 0) return 0;
-  return plan_pooled_bwd(*d).total;
+  return carve_pooled_bwd(*d, nullptr, 0).ws.bytes();
 }
 
 extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) {
@@ -489,58 +512,51 @@ extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) 
              a->stats && a->dx3 && a->dx, "xp_encoder_layer_pooled_bwd: null pointer");
   XP_REQUIRE((!a->side_in && !a->side_x2) || (a->side_in && a->side_x2 && d.dtype == XP_BF16),
              "xp_encoder_layer_pooled_bwd: side rows need side_in and side_x2, and bf16");
-  const PooledBwdPlan p = plan_pooled_bwd(d);
-  XP_REQUIRE(a->workspace && a->workspace_bytes >= p.total, "xp_encoder_layer_pooled_bwd: workspace too small (%zu < %zu)",
-             a->workspace_bytes, p.total);
-  Carver ws{(char*)a->workspace, 0, a->workspace_bytes};
-  const TailBwdWs w = carve_tail_bwd(ws, p.t);
-  char* dqkv = (char*)ws.take(p.dqkv); void* dh1 = ws.take(p.dh1);
-  float* slabs = (float*)ws.take(p.slabs);
-  float* cs_q = (float*)ws.take(p.cs_q); float* cs_kv = (float*)ws.take(p.cs_kv);
-  float* ln1_part = (float*)ws.take(p.ln1); float* ln1p_part = (float*)ws.take(p.ln1p);
-  void* attn_ws = ws.take(p.attn);
+  const PooledBwdWs w = carve_pooled_bwd(d, a->workspace, a->workspace_bytes);
+  XP_REQUIRE_WORKSPACE("xp_encoder_layer_pooled_bwd", a, w);
+  char* const dqkv = w.dqkv;
   const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
   const int dt = d.dtype;
   const bool sided = a->side_in != nullptr;
   const int64_t sS = sided ? S : 0;
   const int32_t sM = sided ? (int32_t)d.M : 0, s1 = sided ? 1 : 0;
-  void* dkv = dqkv + (size_t)D * p.t.esz;    // dqkv[rows, 3D]: the k / v columns of every row, the q columns of the pooled rows only
+  void* dkv = dqkv + (size_t)D * w.t.esz;    // dqkv[rows, 3D]: the k / v columns of every row, the q columns of the pooled rows only
   Defer df;
   const WgradOrder wg{rows >= 4096 ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_pooled_bwd"};
   if ((rc = wg.mark(0))) return rc;
   // ---- MLP and dattn = dx2 . Wo on the pooled rows
-  if ((rc = mlp_out_proj_bwd(*a, B, p.t, w, slabs, p.slabs, s1, s1, df, wg, st))) return rc;
+  if ((rc = mlp_out_proj_bwd(*a, B, w.t, w.slabs, w.slab_bytes, s1, s1, df, wg, st))) return rc;
   // ---- attention: dq lands in the q columns of the pooled rows of dqkv, dk / dv in the k / v columns of every row
-  if ((rc = xp_attn_pooled_bwd(a->q, a->kv, 2 * D, a->attn_o, w.dattn, a->stats, dqkv, S * 3 * D, dkv, 3 * D, d.q_scale, B, d.heads,
-                               S, dt, attn_ws, p.attn, a->dbqkv ? cs_kv : nullptr, st))) return rc;
+  if ((rc = xp_attn_pooled_bwd(a->q, a->kv, 2 * D, a->attn_o, w.t.dattn, a->stats, dqkv, S * 3 * D, dkv, 3 * D, d.q_scale, B, d.heads,
+                               S, dt, w.attn, w.attn_bytes, a->dbqkv ? w.cs_kv : nullptr, st))) return rc;
   if ((rc = wg.mark(3))) return rc;
   // dh1 = dkv . Wkv on every row, then the pooled rows again with their q columns: dqkv[b*S] . Wqkv
-  XpGemmDesc g = gemm_desc(dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * p.t.esz, dh1, rows, D, 2 * D, dt);
+  XpGemmDesc g = gemm_desc(dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * w.t.esz, w.dh1, rows, D, 2 * D, dt);
   g.lda = 3 * D; g.b_kstrided = 1; g.ldb = D;
   if ((rc = xp_gemm(&g, st))) return rc;
-  g = gemm_desc(dqkv, a->Wqkv, dh1, B, D, 3 * D, dt);
+  g = gemm_desc(dqkv, a->Wqkv, w.dh1, B, D, 3 * D, dt);
   g.a_grp = 1; g.a_grp_stride = S; g.b_kstrided = 1; g.ldb = D; g.c_grp = 1; g.c_grp_stride = S;
   if ((rc = xp_gemm(&g, st))) return rc;
   if (a->dwqkv) {
     g = wgrad_desc(dqkv, 3 * D, a->h1p, D, a->dwqkv, B, D, D, dt);            // dWq = dq^T . h1p
     g.a_grp = 1; g.a_grp_stride = S;
-    if ((rc = run_wgrad(g, slabs, p.slabs, wg.stream(), true))) return rc;
-    if ((rc = run_wgrad(wgrad_desc(dkv, 3 * D, a->h1, D, a->dwqkv + D * D, rows, 2 * D, D, dt), slabs, p.slabs, wg.stream(), false))) return rc;
+    if ((rc = run_wgrad(g, w.slabs, w.slab_bytes, wg.stream(), true))) return rc;
+    if ((rc = run_wgrad(wgrad_desc(dkv, 3 * D, a->h1, D, a->dwqkv + D * D, rows, 2 * D, D, dt), w.slabs, w.slab_bytes, wg.stream(), false))) return rc;
   }
   if (a->dbqkv) {
     const int64_t kv_rows = xp_attn_pooled_colsum_rows(B, d.heads, S, dt);
     XP_REQUIRE(kv_rows > 0, "xp_encoder_layer_pooled_bwd: no current device");
-    if ((rc = xp_colsum_partials(dqkv, B, D, S * 3 * D, dt, cs_q, p.cs_q, st))) return rc;
-    df.add(cs_q, a->dbqkv, D, (int)p.cs_q_rows, (int)D);
-    df.add(cs_kv, a->dbqkv + D, 2 * D, (int)kv_rows, (int)(2 * D));
+    if ((rc = xp_colsum_partials(dqkv, B, D, S * 3 * D, dt, w.cs_q, w.cs_q_bytes, st))) return rc;
+    df.add(w.cs_q, a->dbqkv, D, (int)w.cs_q_rows, (int)D);
+    df.add(w.cs_kv, a->dbqkv + D, 2 * D, (int)kv_rows, (int)(2 * D));
   }
   // dx = LN1'(dh1) on every row; the pooled rows once more with their residual gradient dx2 (the parameter-gradient partial
   // rows of that second pass are dropped: the first pass has counted those rows)
-  if ((rc = xp_layernorm_bwd_partials_side(dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, nullptr, D, a->dx, D, 0, rows, D, dt,
-                                           a->side_in, sS, sM, sM, ln1_part, p.ln1, st))) return rc;
-  df.add(ln1_part, a->dln1_w, 2 * D, (int)p.ln_rows, (int)D);
-  df.add(ln1_part + D, a->dln1_b, 2 * D, (int)p.ln_rows, (int)D);
-  if ((rc = xp_layernorm_bwd_partials_side(dh1, S * D, a->x, S * D, a->ln1_w, a->mean1p, a->rstd1p, w.dx2, D, a->dx, S * D, 0, B, D, dt,
-                                           a->side_in, s1, s1, sM, ln1p_part, p.ln1p, st))) return rc;
-  return finish_bwd(df, w.red, p.t.red, wg, st);
+  if ((rc = xp_layernorm_bwd_partials_side(w.dh1, D, a->x, D, a->ln1_w, a->mean1, a->rstd1, nullptr, D, a->dx, D, 0, rows, D, dt,
+                                           a->side_in, sS, sM, sM, w.ln1_part, w.ln1_bytes, st))) return rc;
+  df.add(w.ln1_part, a->dln1_w, 2 * D, (int)w.ln_rows, (int)D);
+  df.add(w.ln1_part + D, a->dln1_b, 2 * D, (int)w.ln_rows, (int)D);
+  if ((rc = xp_layernorm_bwd_partials_side(w.dh1, S * D, a->x, S * D, a->ln1_w, a->mean1p, a->rstd1p, w.t.dx2, D, a->dx, S * D, 0, B, D, dt,
+                                           a->side_in, s1, s1, sM, w.ln1p_part, w.ln1p_bytes, st))) return rc;
+  return finish_bwd(df, w.t.red, w.t.red_bytes, wg, st);
 }

@@ -196,18 +196,36 @@ def set_cu_budget(cus: int) -> None:
     _PLANS.clear()
 
 
-def _arena_layout(*pieces):
-    """``({name: offset}, total bytes)`` of (name, bytes) pieces laid out one after the other, each 256-byte aligned"""
-    off, o = {}, 0
-    for name, n in pieces:
-        off[name] = o
-        o += (n + 255) & ~255
-    return off, o
+def _arena_layout(pieces):
+    """``(((name, offset, bytes per row), ...), total bytes)`` of (name, row count, bytes per row) pieces laid out one after the
+    other, each 256-byte aligned"""
+    fill, o = [], 0
+    for name, n, bpr in pieces:
+        fill.append((name, o, bpr))
+        o += (n * bpr + 255) & ~255
+    return tuple(fill), o
+
+
+def _finish_plan(plan, dims, rD, pieces, queries):
+    """what _LayerPlan and _PooledLayerPlan derive from their table of saved pieces and their two workspace queries"""
+    plan.dims, plan.pieces, plan.rD, plan.side_row = dims, pieces, rD, dims.D * 4      # rD: bytes of a [., D] compute-dtype row
+    plan.side_S, plan.side_M = (dims.S, dims.M) if dims.attn_mode == L.ATTN_PROXY else (1, 1)      # fp32 side rows: [B*M, D] / [rows, D]
+    plan.fill, plan.arena_bytes = _arena_layout(pieces)
+    plan.fwd_ws, plan.bwd_ws = (int(getattr(L.lib(), q)(C.byref(dims))) for q in queries)
+    # flat fp32 parameter gradients, in the order of EncoderLayerFn.forward's parameter arguments
+    D, Dff = dims.D, dims.Dff
+    plan.gsizes = [D, D, 3 * D * D, 3 * D, D * D, D, D, D, Dff * D, Dff, D * Dff, D]
+    plan.gnames = ["dln1_w", "dln1_b", "dwqkv", "dbqkv", "dwo", "dbo", "dln2_w", "dln2_b", "dw1", "db1", "dw2", "db2"]
+    plan.gtotal = sum(plan.gsizes)
 
 
 class _LayerPlan:
     """Sizes / offsets of one (shape, dtype) of encoder layer: the saved-activation arena of the forward, the flat
-    parameter-gradient buffer of the backward, the workspace sizes."""
+    parameter-gradient buffer of the backward, the workspace sizes.  ``pieces`` is THE table of what the forward saves for the
+    backward: (field name in XpLayerFwd and XpLayerBwd, row count, bytes per row), in arena order -- compute-dtype activations, then
+    fp32 statistics.  The arena layout (``fill``, ``arena_bytes``), the pointer fill of both argument structs (_layer_args) and the
+    second forward chain's offsets (first row * bytes per row: every piece is row-proportional, ``stats`` holds heads * 2 floats
+    per token row) all come from it: a new saved piece is one row here."""
 
     def __init__(self, rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU):
         d = L.XpLayerDims()
@@ -216,20 +234,11 @@ class _LayerPlan:
         d.attn_mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
         d.dtype, d.q_scale, d.ln_eps = _DT_CODE[dtype], (D // heads) ** -0.5, 1e-5
         d.act = act                 # the MLP's activation (L.ACTS): the fc1 / dpre epilogue kinds the native stages pick
-        self.dims = d
-        es = _ES[dtype]
-        # arena: bf16/fp32 activations then fp32 statistics
-        self.off, self.arena_bytes = _arena_layout(
-            ("h1", rows * D * es), ("qkv", rows * 3 * D * es), ("attn_o", rows * D * es), ("x2", rows * D * es),
-            ("h2", rows * D * es), ("pre", rows * Dff * es), ("act", rows * Dff * es), ("mean1", rows * 4),
-            ("rstd1", rows * 4), ("mean2", rows * 4), ("rstd2", rows * 4), ("stats", B * heads * S * 2 * 4))
-        lib = L.lib()
-        self.fwd_ws = int(lib.xp_encoder_layer_fwd_workspace_bytes(C.byref(d)))
-        self.bwd_ws = int(lib.xp_encoder_layer_bwd_workspace_bytes(C.byref(d)))
-        # flat fp32 parameter gradients, in the order of EncoderLayerFn.forward's parameter arguments
-        self.gsizes = [D, D, 3 * D * D, 3 * D, D * D, D, D, D, Dff * D, Dff, D * Dff, D]
-        self.gnames = ["dln1_w", "dln1_b", "dwqkv", "dbqkv", "dwo", "dbo", "dln2_w", "dln2_b", "dw1", "db1", "dw2", "db2"]
-        self.gtotal = sum(self.gsizes)
+        rD, rF = D * _ES[dtype], Dff * _ES[dtype]      # bytes of a [., D] / [., Dff] row
+        _finish_plan(self, d, rD, (("h1", rows, rD), ("qkv", rows, 3 * rD), ("attn_o", rows, rD), ("x2", rows, rD), ("h2", rows, rD),
+                                   ("pre", rows, rF), ("act", rows, rF), ("mean1", rows, 4), ("rstd1", rows, 4), ("mean2", rows, 4),
+                                   ("rstd2", rows, 4), ("stats", rows, heads * 2 * 4)),
+                     ("xp_encoder_layer_fwd_workspace_bytes", "xp_encoder_layer_bwd_workspace_bytes"))
 
 
 def _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU) -> _LayerPlan:
@@ -240,19 +249,17 @@ def _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU) ->
     return p
 
 
-def _native_ok(x, vecs, mats, pad_mask) -> bool:
+def _native_ok(x, params, pad_mask) -> bool:
     """The native layer calls hand raw device pointers to C: everything the op-by-op path validates per call (hip_ops._chk)
-    is validated here in one place -- 1-D parameters contiguous fp32 on x's device, weight copies contiguous in the compute
-    dtype, an int64 contiguous padding mask.  False -> the caller takes the op-by-op path, whose checks raise a TypeError
-    that names the offending argument (a model cast with .bfloat16(), a bool mask, a strided parameter ...)."""
-    dev, dt = x.device, x.dtype
+    is validated here in one place -- of ``params`` (in _FWD_PARAMS order) the 1-D parameters contiguous fp32 on x's device, the
+    weight copies ("W..") contiguous in the compute dtype; an int64 contiguous padding mask.  False -> the caller takes the
+    op-by-op path, whose checks raise a TypeError that names the offending argument (a model cast with .bfloat16(), a bool mask,
+    a strided parameter ...)."""
+    dev = x.device
     if not x.is_cuda or not x.is_contiguous():
         return False
-    for v in vecs:
-        if v.dtype != torch.float32 or v.device != dev or not v.is_contiguous():
-            return False
-    for m in mats:
-        if m.dtype != dt or m.device != dev or not m.is_contiguous():
+    for n, t in zip(_FWD_PARAMS, params):
+        if t.dtype != (x.dtype if n[0] == "W" else torch.float32) or t.device != dev or not t.is_contiguous():
             return False
     if pad_mask is not None and (pad_mask.dtype != torch.int64 or pad_mask.device != dev or not pad_mask.is_contiguous()):
         return False
@@ -344,51 +351,76 @@ class ForwardSplit:
         self.held.clear()       # (freed on the main stream, behind the join)
 
 
-def _layer_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan, pad_mask, keep_pre=True, side=None,
-                      split=None):
+# ---- the argument structs of the four native layer calls ----------------------------------------------------------------------------
+# Parameter pointer fields of the forward / backward structs, in the order their tensors are handed around
+_FWD_PARAMS = ("ln1_w", "ln1_b", "Wqkv", "bqkv", "Wo", "bo", "ln2_w", "ln2_b", "W1", "b1", "W2", "b2")
+_BWD_PARAMS = ("ln1_w", "ln2_w", "Wqkv", "Wo", "W1", "W2")
+
+
+def _layer_args(struct, plan, dims, names, params, arena, r0=0, keep_pre=True, **tensors):
+    """An argument struct of a native layer call: ``dims``, the parameter pointers (``names``: _FWD_PARAMS / _BWD_PARAMS, of the
+    tensors ``params``), the saved pieces (plan.fill over ``arena``) and ``tensors`` by field name (x, x3, dx3, dx, the parameter
+    gradients, the pooled layer's side rows; None: the field stays NULL) -- the pieces and the [., D] streams from token row ``r0``
+    on (the second forward chain).  ``keep_pre`` False: a forward-only pass, the MLP pre-activation is not written (pre = NULL).
+    Nothing is launched and no workspace is taken (_call_native does that), so a CPU test can build the structs."""
+    a = struct()
+    a.dims = dims
+    for n, t in zip(names, params):
+        setattr(a, n, t.data_ptr())
+    base = arena.data_ptr()
+    for n, o, bpr in plan.fill:
+        setattr(a, n, base + o + r0 * bpr)
+    if not keep_pre:
+        a.pre = 0
+    first = r0 * plan.rD
+    for n, t in tensors.items():
+        if t is not None:
+            setattr(a, n, t.data_ptr() + first)
+    return a
+
+
+def _side_args(a, plan, r0, **sides):
+    """the dense layer's fp32 side rows from token row ``r0`` on, and their geometry"""
+    a.side_S, a.side_M = plan.side_S, plan.side_M
+    first = r0 // plan.side_S * plan.side_M * plan.side_row
+    for n, t in sides.items():
+        if t is not None:
+            setattr(a, n, t.data_ptr() + first)
+
+
+def _call_native(entry, a, ws_bytes, device, ws_tag):
+    ws = H.workspace(ws_bytes, device, ws_tag)          # (per stream)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    L.check(getattr(L.lib(), entry)(C.byref(a), H._stream()), entry)
+
+
+def _layer_fwd_args(plan, dims, x, params, pad_mask, arena, x3, keep_pre, side, side_out, side_x2, r0=0):
+    """``dims``: the full batch's (plan.dims) or one chain's; the buffers are always the full batch's"""
+    a = _layer_args(L.XpLayerFwd, plan, dims, _FWD_PARAMS, params, arena, r0, keep_pre, x=x, x3=x3)
+    a.pad_mask = 0 if pad_mask is None else pad_mask.data_ptr()
+    if side is not None:
+        _side_args(a, plan, r0, side_in=side, side_out=side_out, side_x2=side_x2)
+    return a
+
+
+def _layer_fwd_native(x, params, plan, pad_mask, keep_pre=True, side=None, split=None):
     dev = x.device
     arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
     x3 = torch.empty_like(x)
-    side_out = side_x2 = None
-    if side is not None:
-        side_out = torch.empty_like(side)
-        if keep_pre:            # training pass: the x2 side rows are kept for the backward's second LayerNorm
-            side_x2 = torch.empty_like(side)
+    side_out = None if side is None else torch.empty_like(side)
+    side_x2 = torch.empty_like(side) if side is not None and keep_pre else None      # training: kept for the backward's second LayerNorm
     d = plan.dims
-    es, D, Dff = _ES[x.dtype], d.D, d.Dff
-    base, off = arena.data_ptr(), plan.off
-    video = d.attn_mode == L.ATTN_PROXY
     if split is None:
-        parts = [(plan, 0, 0, None)]
-    else:                       # two half-batch chains: (plan of half the batch, first row, first sample, stream)
-        hp = _layer_plan(d.rows // 2, D, Dff, d.B // 2, d.S, d.heads, (d.M, d.N, d.L), x.dtype, d.act)
+        parts = [(plan, 0, None)]
+    else:                       # two half-batch chains: (plan of half the batch, first row, stream)
+        hp = _layer_plan(d.rows // 2, d.D, d.Dff, d.B // 2, d.S, d.heads, (d.M, d.N, d.L), x.dtype, d.act)
         if (d.rows // 2) % 4:   # the second chain's statistics / stream pointers are offset by rows/2 elements: keep them 16-byte aligned
             raise RuntimeError(f"ForwardSplit: (B/2)*S = {d.rows // 2} rows per chain must be a multiple of 4")
-        parts = [(hp, 0, 0, None), (hp, d.rows // 2, d.B // 2, split.stream)]
-    for pl, r0, b0, stream in parts:
+        parts = [(hp, 0, None), (hp, d.rows // 2, split.stream)]
+    for pl, r0, stream in parts:
         with (torch.cuda.stream(stream) if stream is not None else _NULLCTX):
-            ws = H.workspace(pl.fwd_ws, dev, "layer_fwd")          # (per stream)
-            a = L.XpLayerFwd()
-            a.dims = pl.dims
-            a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr() + r0 * D * es, Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
-            a.ln1_w, a.ln1_b, a.bqkv, a.bo = ln1_w.data_ptr(), ln1_b.data_ptr(), bqkv.data_ptr(), bo.data_ptr()
-            a.ln2_w, a.ln2_b, a.b1, a.b2 = ln2_w.data_ptr(), ln2_b.data_ptr(), b1.data_ptr(), b2.data_ptr()
-            a.pad_mask = 0 if pad_mask is None else pad_mask.data_ptr()
-            rD, rF = r0 * D * es, r0 * Dff * es
-            a.h1, a.qkv, a.attn_o = base + off["h1"] + rD, base + off["qkv"] + 3 * rD, base + off["attn_o"] + rD
-            a.x2, a.h2 = base + off["x2"] + rD, base + off["h2"] + rD
-            a.pre, a.act, a.x3 = (base + off["pre"] + rF) if keep_pre else 0, base + off["act"] + rF, x3.data_ptr() + rD
-            a.mean1, a.rstd1 = base + off["mean1"] + r0 * 4, base + off["rstd1"] + r0 * 4
-            a.mean2, a.rstd2 = base + off["mean2"] + r0 * 4, base + off["rstd2"] + r0 * 4
-            a.stats = base + off["stats"] + b0 * d.heads * d.S * 2 * 4
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-            if side is not None:
-                so = (b0 * d.M if video else r0) * D * 4          # side rows: [B*M, D] (video) / [rows, D] (text), fp32
-                a.side_in, a.side_out = side.data_ptr() + so, side_out.data_ptr() + so
-                a.side_S, a.side_M = (d.S, d.M) if video else (1, 1)
-                if side_x2 is not None:
-                    a.side_x2 = side_x2.data_ptr() + so
-            L.check(L.lib().xp_encoder_layer_fwd(C.byref(a), H._stream()), "xp_encoder_layer_fwd")
+            a = _layer_fwd_args(plan, pl.dims, x, params, pad_mask, arena, x3, keep_pre, side, side_out, side_x2, r0)
+            _call_native("xp_encoder_layer_fwd", a, pl.fwd_ws, dev, "layer_fwd")
     return x3, arena, side_out, side_x2
 
 
@@ -449,12 +481,20 @@ def _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b
         ctx.sink_params, ctx.sink_key = (), None
 
 
-def _run_native_bwd(ctx, a, entry, plan, dx, ws_tag):
-    """The parameter-gradient plumbing of a native layer backward and the call itself.  ``a``: the argument struct of ``entry``
-    (xp_encoder_layer_bwd / xp_encoder_layer_pooled_bwd) with everything but dx, the parameter gradients and the workspace filled
-    in.  The gradients go to the layer's sink or a private flat buffer (plan.gnames order); a frozen parameter's pointer stays
-    NULL.  Returns the 17 leading outputs of the Function's backward: dx and the gradients in forward's argument order."""
-    dev, need = dx.device, ctx.needs_input_grad
+def _qkv_grads(dwqkv, dbqkv, need, D):
+    """the gradients of wq, bq, wk, bk, wv, bv (forward argument positions 3..8): row slices of the fused dwqkv [3D, D] / dbqkv
+    [3D], None for a frozen parameter"""
+    pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
+    return (pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]), pick(dbqkv, 1, need[6]),
+            pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]))
+
+
+def _run_native_bwd(ctx, build, entry, ws_tag, plan, x, *rest):
+    """The parameter-gradient plumbing of a native layer backward and the call itself.  ``build(plan, x, *rest, dx, grads)``: the
+    argument struct of ``entry`` (_layer_bwd_args for xp_encoder_layer_bwd, _pooled_bwd_args for xp_encoder_layer_pooled_bwd).  The
+    gradients go to the layer's sink or a private flat buffer (plan.gnames order); a frozen parameter's pointer stays NULL.
+    Returns the 17 leading outputs of the Function's backward: dx and the gradients in forward's argument order."""
+    dev, need = x.device, ctx.needs_input_grad
     flat = None
     if GRAD_SINKS and ctx.sink_key is not None and all(need[1:17]):
         flat = _claim_sink(ctx.sink_key, GRAD_SINKS.get(ctx.sink_key), plan.gtotal, dev, ctx.sink_params)
@@ -463,41 +503,22 @@ def _run_native_bwd(ctx, a, entry, plan, dx, ws_tag):
     # forward argument positions: 1,2 ln1 | 3..8 wq,bq,wk,bk,wv,bv | 9,10 wo,bo | 11,12 ln2 | 13,14 w1,b1 | 15,16 w2,b2
     want = dict(dln1_w=need[1], dln1_b=need[2], dwqkv=need[3] or need[5] or need[7], dbqkv=need[4] or need[6] or need[8],
                 dwo=need[9], dbo=need[10], dln2_w=need[11], dln2_b=need[12], dw1=need[13], db1=need[14], dw2=need[15], db2=need[16])
-    g = {}
-    for name, t in zip(plan.gnames, flat.split_with_sizes(plan.gsizes)):
-        if want[name]:
-            g[name] = t
-            setattr(a, name, t.data_ptr())
-    ws = H.workspace(plan.bwd_ws, dev, ws_tag)
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    a.dx = dx.data_ptr()
-    L.check(getattr(L.lib(), entry)(C.byref(a), H._stream()), entry)
+    g = {name: t for name, t in zip(plan.gnames, flat.split_with_sizes(plan.gsizes)) if want[name]}
+    dx = torch.empty_like(x)
+    _call_native(entry, build(plan, x, *rest, dx, g), plan.bwd_ws, dev, ws_tag)
     D, Dff = plan.dims.D, plan.dims.Dff
     gw = lambda n, shape: g[n].view(shape) if n in g else None
-    dwqkv, dbqkv = gw("dwqkv", (3 * D, D)), g.get("dbqkv")
-    pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
-    return (dx, g.get("dln1_w"), g.get("dln1_b"),
-            pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]), pick(dbqkv, 1, need[6]),
-            pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"), g.get("dln2_b"),
+    return (dx, g.get("dln1_w"), g.get("dln1_b"), *_qkv_grads(gw("dwqkv", (3 * D, D)), g.get("dbqkv"), need, D),
+            gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"), g.get("dln2_b"),
             gw("dw1", (Dff, D)), g.get("db1"), gw("dw2", (D, Dff)), g.get("db2"))
 
 
-def _layer_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, plan, side=None, side_x2=None):
-    a = L.XpLayerBwd()
-    a.dims = plan.dims
-    base, off = arena.data_ptr(), plan.off
-    a.x, a.h1, a.qkv, a.attn_o, a.x2 = x.data_ptr(), base + off["h1"], base + off["qkv"], base + off["attn_o"], base + off["x2"]
-    a.h2, a.pre, a.act = base + off["h2"], base + off["pre"], base + off["act"]
-    a.Wqkv, a.Wo, a.W1, a.W2 = Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
-    a.ln1_w, a.ln2_w = ln1_w.data_ptr(), ln2_w.data_ptr()
-    a.mean1, a.rstd1, a.mean2, a.rstd2 = base + off["mean1"], base + off["rstd1"], base + off["mean2"], base + off["rstd2"]
-    a.stats = base + off["stats"]
+def _layer_bwd_args(plan, x, params, arena, dx3, pad_mask, side, side_x2, dx, grads):
+    a = _layer_args(L.XpLayerBwd, plan, plan.dims, _BWD_PARAMS, params, arena, x=x, dx3=dx3, dx=dx, **grads)
     a.pad_mask = 0 if pad_mask is None else pad_mask.data_ptr()
-    a.dx3 = dx3.data_ptr()
     if side is not None and side_x2 is not None:          # the forward's fp32 side rows of x and x2: read by the LayerNorm backward passes
-        a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
-        a.side_S, a.side_M = (plan.dims.S, plan.dims.M) if plan.dims.attn_mode == L.ATTN_PROXY else (1, 1)
-    return _run_native_bwd(ctx, a, "xp_encoder_layer_bwd", plan, torch.empty_like(x), "layer_bwd") + (None,) * 9
+        _side_args(a, plan, 0, side_in=side, side_x2=side_x2)
+    return a
 
 
 # ------------------------------------------------------------------------------------------ encoder layer, op by op
@@ -550,6 +571,38 @@ def _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo,
     return dx2, dattn, dwo, keep(10, dbo), keep(11, dln2_w), keep(12, dln2_b), dw1, db1, dw2, keep(16, db2)
 
 
+# ---- what EncoderLayerFn and PooledEncoderLayerFn share ---------------------------------------------------------------------------
+def _check_layer_args(name, x, heads, act, side, side_rows, side_what):
+    if act not in (L.ACT_QUICK_GELU, L.ACT_GELU):
+        raise ValueError(f"{name}: act={act!r} is not one of {L.ACTS}")
+    if side is not None and (x.dtype != torch.bfloat16 or side.dtype != torch.float32 or not side.is_contiguous() or side.device != x.device
+                             or tuple(side.shape) != (side_rows, x.shape[1])):
+        raise TypeError(f"{name}: side rows must be a contiguous fp32 {side_what} tensor beside a bf16 stream")
+    if x.shape[1] // heads != 64:
+        raise RuntimeError(f"xpretrain_amd attention kernels are built for head_dim 64, got {x.shape[1] // heads}")
+
+
+def _compute_weights(dt, wq, bq, wk, bk, wv, bv, wo, w1, w2):
+    """``(Wqkv, bqkv, Wo, W1, W2)``: the fused q/k/v operand and the other weights in the compute dtype (WeightCache)"""
+    get = WEIGHTS.get
+    return WEIGHTS.fused((wq, wk, wv), dt), WEIGHTS.fused((bq, bk, bv), torch.float32), get(wo, dt), get(w1, dt), get(w2, dt)
+
+
+def _layer_outputs(ctx, x3, side_out):
+    if side_out is None:
+        return x3
+    ctx.mark_non_differentiable(side_out)
+    ctx.set_materialize_grads(False)       # no zero-filled "gradient" of the side rows in the backward
+    return x3, side_out
+
+
+def _check_dx3(name, dx3, x, shape):
+    if dx3.dtype != x.dtype or dx3.device != x.device or tuple(dx3.shape) != tuple(shape):
+        raise TypeError(f"{name}.backward: incoming gradient is {dx3.dtype} {tuple(dx3.shape)} on {dx3.device}, "
+                        f"expected {x.dtype} {tuple(shape)} on {x.device}")
+    return dx3.contiguous()
+
+
 class EncoderLayerFn(torch.autograd.Function):
     """CLIPEncoderLayer.forward (modeling/CLIP_ViP.py:444-460) with CLIPAttention.forward2 (:332-381, video
     tower, ``size=(M,N,L)``) or CLIPAttention.forward (:266-330, text tower, causal + padding) and CLIPMLP
@@ -564,29 +617,21 @@ class EncoderLayerFn(torch.autograd.Function):
         ``side`` (fp32, bf16 compute only): the fp32 side rows of ``x`` (SideRows, csrc/gemm_common.h) -- [B*M, D], the proxy rows of
         every sample, in the video tower; [B*S, D], the whole stream, in the text tower.  The call then returns ``(x3, side_out)``."""
         dt = x.dtype
-        if act not in (L.ACT_QUICK_GELU, L.ACT_GELU):
-            raise ValueError(f"EncoderLayerFn: act={act!r} is not one of {L.ACTS}")
-        if side is not None and (dt != torch.bfloat16 or side.dtype != torch.float32 or not side.is_contiguous() or side.device != x.device
-                                 or tuple(side.shape) != ((B * size[0] if size is not None else B * S), x.shape[1])):
-            raise TypeError("EncoderLayerFn: side rows must be a contiguous fp32 [B*M, D] (video) / [B*S, D] (text) tensor beside a bf16 stream")
+        _check_layer_args("EncoderLayerFn", x, heads, act, side, B * size[0] if size is not None else B * S,
+                          "[B*M, D] (video) / [B*S, D] (text)")
         rows, D = x.shape
         Dff = w1.shape[0]
-        dh = D // heads
-        if dh != 64:
-            raise RuntimeError(f"xpretrain_amd attention kernels are built for head_dim 64, got {dh}")
-        q_scale = dh ** -0.5
+        q_scale = 64 ** -0.5
         casts0 = WEIGHTS.casts
-        Wqkv = WEIGHTS.fused((wq, wk, wv), dt)
-        bqkv = WEIGHTS.fused((bq, bk, bv), torch.float32)
-        Wo, W1, W2 = WEIGHTS.get(wo, dt), WEIGHTS.get(w1, dt), WEIGHTS.get(w2, dt)
-        if LAYER_CALLS and _native_ok(x, (ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2), (Wqkv, Wo, W1, W2), pad_mask):
+        Wqkv, bqkv, Wo, W1, W2 = _compute_weights(dt, wq, bq, wk, bk, wv, bv, wo, w1, w2)
+        params = (ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2)          # (_FWD_PARAMS)
+        if LAYER_CALLS and _native_ok(x, params, pad_mask):
             plan = _layer_plan(rows, D, Dff, B, S, heads, size, dt, act)
             if split is not None and (size is None or B % 2 or pad_mask is not None):
                 split = None
             if split is not None and WEIGHTS.casts != casts0:       # a weight copy was (re)made on this stream just now: the second
                 split.stream.wait_stream(torch.cuda.current_stream())   # chain must not read it before the cast has run
-            x3, arena, side_out, side_x2 = _layer_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan,
-                                                             pad_mask, keep_pre=training, side=side, split=split)
+            x3, arena, side_out, side_x2 = _layer_fwd_native(x, params, plan, pad_mask, keep_pre=training, side=side, split=split)
             if split is not None:
                 split.hold(x, arena, x3, side, side_out, side_x2)
             ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
@@ -608,22 +653,17 @@ class EncoderLayerFn(torch.autograd.Function):
                                       Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
             ctx.meta = (B, S, heads, size, q_scale, D, Dff, act)
             ctx.lns = lns
-        if side is not None:
-            ctx.mark_non_differentiable(side_out)
-            ctx.set_materialize_grads(False)       # no zero-filled "gradient" of the side rows in the backward
-            return x3, side_out
-        return x3
+        return _layer_outputs(ctx, x3, side_out)
 
     @staticmethod
     def backward(ctx, dx3, _dside=None):
         if dx3 is None:             # (set_materialize_grads(False): the layer output did not reach the loss)
             return (None,) * 26
         if ctx.plan is not None:
-            x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, side, side_x2 = ctx.saved_tensors
-            if dx3.dtype != x.dtype or dx3.device != x.device or dx3.shape != x.shape:
-                raise TypeError(f"EncoderLayerFn.backward: incoming gradient is {dx3.dtype} {tuple(dx3.shape)} on {dx3.device}, "
-                                f"expected {x.dtype} {tuple(x.shape)} on {x.device}")
-            return _layer_bwd_native(ctx, dx3.contiguous(), x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, ctx.plan, side, side_x2)
+            x, arena, *params, pad_mask, side, side_x2 = ctx.saved_tensors          # (params: _BWD_PARAMS)
+            dx3 = _check_dx3("EncoderLayerFn", dx3, x, x.shape)
+            return _run_native_bwd(ctx, _layer_bwd_args, "xp_encoder_layer_bwd", "layer_bwd", ctx.plan, x, params, arena, dx3, pad_mask,
+                                   side, side_x2) + (None,) * 9
         (x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
          Wqkv, Wo, W1, W2, pad_mask, side, side_x2) = ctx.saved_tensors
         B, S, heads, size, q_scale, D, Dff, act_kind = ctx.meta
@@ -642,41 +682,28 @@ class EncoderLayerFn(torch.autograd.Function):
             dqkv, dbqkv = H.attn_bwd(qkv, attn_o, dattn, stats, B, S, heads, size=size, pad_mask=pad_mask, q_scale=q_scale,
                                      colsum_defer=defer, colsum_name="dbqkv")
         else:
-            dqkv = H.attn_bwd(qkv, attn_o, dattn, stats, B, S, heads, size=size, pad_mask=pad_mask, q_scale=q_scale)
+            dqkv, dbqkv = H.attn_bwd(qkv, attn_o, dattn, stats, B, S, heads, size=size, pad_mask=pad_mask, q_scale=q_scale), None
         dh1 = H.gemm(dqkv, Wqkv, rows, D, 3 * D, b_kstrided=True)
-        if need[3] or need[5] or need[7]:
-            dwqkv = _wgrad(dqkv, h1, rows, 3 * D, D)
-            dwq, dwk, dwv = dwqkv[:D], dwqkv[D:2 * D], dwqkv[2 * D:]
-        else:
-            dwq = dwk = dwv = None
-        if want_bqkv:
-            dbq, dbk, dbv = dbqkv[:D], dbqkv[D:2 * D], dbqkv[2 * D:]
-        else:
-            dbq = dbk = dbv = None
+        dwqkv = _wgrad(dqkv, h1, rows, 3 * D, D) if need[3] or need[5] or need[7] else None
         dx, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dres=dx2, defer=defer, name="ln1", x_side=side,
                                              side=ctx.lns)
         defer.flush()
         keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter sums ride on a pass that runs anyway)
-        return (dx, keep(1, dln1_w), keep(2, dln1_b), dwq, dbq, dwk, dbk, dwv, dbv, *tail) + (None,) * 9
+        return (dx, keep(1, dln1_w), keep(2, dln1_b), *_qkv_grads(dwqkv, dbqkv, need, D), *tail) + (None,) * 9
 
 
 # ------------------------------------------------------------------------------------------ pooled last layer (video tower)
 class _PooledLayerPlan:
-    """Sizes / offsets of one (shape, dtype) of the pooled last layer (xp_encoder_layer_pooled_fwd / _bwd): every-row pieces
-    (h1, kv, LayerNorm-1 statistics) and the pooled rows' pieces ([B, .])."""
+    """Sizes / offsets of one (shape, dtype) of the pooled last layer (xp_encoder_layer_pooled_fwd / _bwd), as _LayerPlan: the table
+    holds the every-row pieces (h1, kv, LayerNorm-1 statistics), then the pooled rows' pieces ([B, .])."""
 
     def __init__(self, rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU):
-        base = _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act)
-        self.dims, self.gsizes, self.gnames, self.gtotal = base.dims, base.gsizes, base.gnames, base.gtotal
-        es = _ES[dtype]
-        self.off, self.arena_bytes = _arena_layout(
-            ("h1", rows * D * es), ("kv", rows * 2 * D * es), ("mean1", rows * 4), ("rstd1", rows * 4),
-            ("h1p", B * D * es), ("q", B * D * es), ("attn_o", B * D * es), ("x2", B * D * es), ("h2", B * D * es),
-            ("pre", B * Dff * es), ("act", B * Dff * es), ("mean1p", B * 4), ("rstd1p", B * 4), ("mean2", B * 4),
-            ("rstd2", B * 4), ("stats", B * heads * 2 * 4))
-        lib = L.lib()
-        self.fwd_ws = int(lib.xp_encoder_layer_pooled_fwd_workspace_bytes(C.byref(self.dims)))
-        self.bwd_ws = int(lib.xp_encoder_layer_pooled_bwd_workspace_bytes(C.byref(self.dims)))
+        rD, rF = D * _ES[dtype], Dff * _ES[dtype]
+        _finish_plan(self, _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act).dims, rD,
+                     (("h1", rows, rD), ("kv", rows, 2 * rD), ("mean1", rows, 4), ("rstd1", rows, 4), ("h1p", B, rD), ("q", B, rD),
+                      ("attn_o", B, rD), ("x2", B, rD), ("h2", B, rD), ("pre", B, rF), ("act", B, rF), ("mean1p", B, 4),
+                      ("rstd1p", B, 4), ("mean2", B, 4), ("rstd2", B, 4), ("stats", B, heads * 2 * 4)),
+                     ("xp_encoder_layer_pooled_fwd_workspace_bytes", "xp_encoder_layer_pooled_bwd_workspace_bytes"))
 
 
 def _pooled_plan(rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU) -> _PooledLayerPlan:
@@ -687,43 +714,14 @@ def _pooled_plan(rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU) -
     return p
 
 
-_POOLED_SAVED = ("h1", "kv", "h1p", "q", "attn_o", "x2", "h2", "pre", "act", "mean1", "rstd1", "mean1p", "rstd1p", "mean2", "rstd2",
-                 "stats")
+def _pooled_fwd_args(plan, x, params, arena, x3, keep_pre, side, side_out, side_x2):
+    return _layer_args(L.XpLayerPooledFwd, plan, plan.dims, _FWD_PARAMS, params, arena, keep_pre=keep_pre, x=x, x3=x3,
+                       side_in=side, side_out=side_out, side_x2=side_x2)
 
 
-def _pooled_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan, x3, keep_pre, side, side_out, side_x2):
-    arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=x.device)
-    ws = H.workspace(plan.fwd_ws, x.device, "layer_pooled_fwd")
-    a = L.XpLayerPooledFwd()
-    a.dims = plan.dims
-    a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
-    a.ln1_w, a.ln1_b, a.bqkv, a.bo = ln1_w.data_ptr(), ln1_b.data_ptr(), bqkv.data_ptr(), bo.data_ptr()
-    a.ln2_w, a.ln2_b, a.b1, a.b2 = ln2_w.data_ptr(), ln2_b.data_ptr(), b1.data_ptr(), b2.data_ptr()
-    base = arena.data_ptr()
-    for name in _POOLED_SAVED:
-        setattr(a, name, base + plan.off[name])
-    if not keep_pre:            # forward-only pass: the MLP pre-activation is not written
-        a.pre = 0
-    a.x3 = x3.data_ptr()
-    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    if side is not None:
-        a.side_in, a.side_out, a.side_x2 = side.data_ptr(), side_out.data_ptr(), side_x2.data_ptr()
-    L.check(L.lib().xp_encoder_layer_pooled_fwd(C.byref(a), H._stream()), "xp_encoder_layer_pooled_fwd")
-    return arena
-
-
-def _pooled_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, plan, side=None, side_x2=None):
-    a = L.XpLayerPooledBwd()
-    a.dims = plan.dims
-    base = arena.data_ptr()
-    for name in _POOLED_SAVED:
-        setattr(a, name, base + plan.off[name])
-    a.x, a.Wqkv, a.Wo, a.W1, a.W2 = x.data_ptr(), Wqkv.data_ptr(), Wo.data_ptr(), W1.data_ptr(), W2.data_ptr()
-    a.ln1_w, a.ln2_w = ln1_w.data_ptr(), ln2_w.data_ptr()
-    a.dx3 = dx3.data_ptr()
-    if side is not None:
-        a.side_in, a.side_x2 = side.data_ptr(), side_x2.data_ptr()
-    return _run_native_bwd(ctx, a, "xp_encoder_layer_pooled_bwd", plan, torch.empty_like(x), "layer_pooled_bwd") + (None,) * 7
+def _pooled_bwd_args(plan, x, params, arena, dx3, side, side_x2, dx, grads):
+    return _layer_args(L.XpLayerPooledBwd, plan, plan.dims, _BWD_PARAMS, params, arena, x=x, dx3=dx3, dx=dx, side_in=side,
+                       side_x2=side_x2, **grads)
 
 
 class PooledEncoderLayerFn(torch.autograd.Function):
@@ -740,32 +738,26 @@ class PooledEncoderLayerFn(torch.autograd.Function):
                 B: int, S: int, heads: int, size: Tuple[int, int, int], training: bool = True, side: Optional[torch.Tensor] = None,
                 act: int = L.ACT_QUICK_GELU):
         dt = x.dtype
-        if act not in (L.ACT_QUICK_GELU, L.ACT_GELU):
-            raise ValueError(f"PooledEncoderLayerFn: act={act!r} is not one of {L.ACTS}")
         rows, D = x.shape
         M = size[0]
-        if side is not None and (dt != torch.bfloat16 or side.dtype != torch.float32 or not side.is_contiguous() or side.device != x.device
-                                 or tuple(side.shape) != (B * M, D)):
-            raise TypeError("PooledEncoderLayerFn: side rows must be a contiguous fp32 [B*M, D] tensor beside a bf16 stream")
+        _check_layer_args("PooledEncoderLayerFn", x, heads, act, side, B * M, "[B*M, D]")
         Dff = w1.shape[0]
-        if D // heads != 64:
-            raise RuntimeError(f"xpretrain_amd attention kernels are built for head_dim 64, got {D // heads}")
         if M < 1 or S != M + size[1] * size[2] or rows != B * S:
             raise RuntimeError(f"PooledEncoderLayerFn: token 0 must be a proxy row of a [B*S, D] stream (size={size}, S={S}, rows={rows})")
         q_scale = 64 ** -0.5
-        Wqkv = WEIGHTS.fused((wq, wk, wv), dt)
-        bqkv = WEIGHTS.fused((bq, bk, bv), torch.float32)
-        Wo, W1, W2 = WEIGHTS.get(wo, dt), WEIGHTS.get(w1, dt), WEIGHTS.get(w2, dt)
+        Wqkv, bqkv, Wo, W1, W2 = _compute_weights(dt, wq, bq, wk, bk, wv, bv, wo, w1, w2)
         dev = x.device
         x3 = torch.empty((B, D), dtype=dt, device=dev)
         side_out = side_x2 = None
         if side is not None:
             side_out = torch.empty((B, D), dtype=torch.float32, device=dev)
             side_x2 = torch.empty((B, D), dtype=torch.float32, device=dev)
-        if LAYER_CALLS and _native_ok(x, (ln1_w, ln1_b, bqkv, bo, ln2_w, ln2_b, b1, b2), (Wqkv, Wo, W1, W2), None):
+        params = (ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2)          # (_FWD_PARAMS)
+        if LAYER_CALLS and _native_ok(x, params, None):
             plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt, act)
-            arena = _pooled_fwd_native(x, ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, plan, x3, training, side,
-                                       side_out, side_x2)
+            arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
+            a = _pooled_fwd_args(plan, x, params, arena, x3, training, side, side_out, side_x2)
+            _call_native("xp_encoder_layer_pooled_fwd", a, plan.fwd_ws, dev, "layer_pooled_fwd")
             ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2)
             ctx.plan = plan
             _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
@@ -784,11 +776,7 @@ class PooledEncoderLayerFn(torch.autograd.Function):
                 ctx.save_for_backward(x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2,
                                       h2, pre, a, Wqkv, Wo, W1, W2, side, side_x2)
         ctx.meta = (B, S, heads, M, q_scale, D, Dff, act)
-        if side is not None:
-            ctx.mark_non_differentiable(side_out)
-            ctx.set_materialize_grads(False)
-            return x3, side_out
-        return x3
+        return _layer_outputs(ctx, x3, side_out)
 
     @staticmethod
     def backward(ctx, dx3, _dside=None):
@@ -797,14 +785,11 @@ class PooledEncoderLayerFn(torch.autograd.Function):
         B, S, heads, M, q_scale, D, Dff, act_kind = ctx.meta
         need = ctx.needs_input_grad
         saved = ctx.saved_tensors          # (read once: a checkpointed layer's tensors unpack once)
-        x = saved[0]
-        if dx3.dtype != x.dtype or dx3.device != x.device or tuple(dx3.shape) != (B, D):
-            raise TypeError(f"PooledEncoderLayerFn.backward: incoming gradient is {dx3.dtype} {tuple(dx3.shape)} on {dx3.device}, "
-                            f"expected {x.dtype} {(B, D)} on {x.device}")
-        dx3 = dx3.contiguous()
+        dx3 = _check_dx3("PooledEncoderLayerFn", dx3, saved[0], (B, D))
         if ctx.plan is not None:
-            x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2 = saved
-            return _pooled_bwd_native(ctx, dx3, x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, ctx.plan, side, side_x2)
+            x, arena, *params, side, side_x2 = saved          # (params: _BWD_PARAMS)
+            return _run_native_bwd(ctx, _pooled_bwd_args, "xp_encoder_layer_pooled_bwd", "layer_pooled_bwd", ctx.plan, x, params, arena,
+                                   dx3, side, side_x2) + (None,) * 7
         (x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
          Wqkv, Wo, W1, W2, side, side_x2) = saved
         rows, dev, dt = x.shape[0], x.device, x.dtype
@@ -836,16 +821,11 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             H.colsum_deferred(dqkv, B, D, defer, ldx=S * 3 * D, name="dbq", out=dbqkv)
         _, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dx=dx, defer=defer, name="ln1", x_side=side, side=lns)
         # the pooled rows once more, with their residual gradient (the parameter-gradient partial rows of this pass are dropped)
-        ws = H.workspace(L.lib().xp_layernorm_bwd_workspace_bytes(B, D), dev, "ln1_pooled")
-        L.check(L.lib().xp_layernorm_bwd_partials_side(H._p(dh1), S * D, H._p(x), S * D, H._p(ln1_w), H._p(mean1p), H._p(rstd1p),
-                                                       H._p(dx2), D, H._p(dx), S * D, 0, B, D, H._dt(x), H._p(side),
-                                                       *((1, 1, M) if side is not None else (0, 0, 0)), H._p(ws), ws.numel(),
-                                                       H._stream()), "xp_layernorm_bwd_partials_side")
+        H.layernorm_bwd(dh1, x, ln1_w, mean1p, rstd1p, B, D, ldx=S * D, lddy=S * D, dres=dx2, dx=dx, lddx=S * D, defer=defer,
+                        param_grads=False, name="ln1_pooled", x_side=side, side=(1, 1, M))
         defer.flush()
         keep = lambda i, t: t if need[i] else None
-        pick = lambda t, i, ok: t[i * D:(i + 1) * D] if (t is not None and ok) else None
-        return (dx, keep(1, dln1_w), keep(2, dln1_b), pick(dwqkv, 0, need[3]), pick(dbqkv, 0, need[4]), pick(dwqkv, 1, need[5]),
-                pick(dbqkv, 1, need[6]), pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]), *tail) + (None,) * 7
+        return (dx, keep(1, dln1_w), keep(2, dln1_b), *_qkv_grads(dwqkv, dbqkv, need, D), *tail) + (None,) * 7
 
 
 def pooled_encoder_layer(x, layer, B, S, heads, size, side=None):

@@ -261,18 +261,23 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, dres=None, dx=None, lddx=None,
                   dgamma=None, dbeta=None, accumulate=False, defer: "DeferredReduce" = None, dx_colsum=False, dres_colsum=False,
-                  name="ln", x_side=None, side=None):
+                  name="ln", x_side=None, side=None, param_grads=True):
     """Returns (dx, dgamma, dbeta) -- plus colsum(dx) when ``dx_colsum``, plus colsum(dres) when ``dres_colsum`` (deferred mode only).
-    ``x_side`` / ``side = (S, M, stride)``: the fp32 side rows of x the forward normalised (layernorm_fwd)."""
+    ``x_side`` / ``side = (S, M, stride)``: the fp32 side rows of x the forward normalised (layernorm_fwd).
+    ``param_grads=False`` (deferred mode, no column sums): dx only -- the pass's parameter-gradient partial rows stay in its slot
+    and are not registered with ``defer`` (rows another pass has already counted): returns (dx, None, None)."""
     _chk(dy, "dy"); _chk(x, "x", dy.dtype)
     S, M, stride = side if x_side is not None else (0, 0, 0)
     if x_side is not None:
         _chk(x_side, "x_side", torch.float32)
         if not x_side.is_contiguous() or x_side.numel() < ((rows - 1) // S * stride + min(M, S)) * cols:
             raise ValueError("layernorm_bwd: x_side is too small or not contiguous")
+    if not param_grads and (defer is None or dx_colsum or dres_colsum):
+        raise ValueError("layernorm_bwd: param_grads=False needs a DeferredReduce and no column sums")
     dx = torch.empty((rows, cols), dtype=dy.dtype, device=dy.device) if dx is None else dx
-    dgamma = torch.empty(cols, dtype=torch.float32, device=dy.device) if dgamma is None else dgamma
-    dbeta = torch.empty(cols, dtype=torch.float32, device=dy.device) if dbeta is None else dbeta
+    if param_grads:
+        dgamma = torch.empty(cols, dtype=torch.float32, device=dy.device) if dgamma is None else dgamma
+        dbeta = torch.empty(cols, dtype=torch.float32, device=dy.device) if dbeta is None else dbeta
     nb = L.lib().xp_layernorm_bwd_workspace_bytes(rows, cols)
     if defer is not None:     # parameter-gradient partial rows stay in their own slot until defer.flush()
         ws = defer.slot(nb, name)
@@ -280,6 +285,8 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, 
                                                        _p(dres), cols, _p(dx), lddx or cols, 2 if dres_colsum else int(dx_colsum),
                                                        rows, cols, _dt(dy), _p(x_side), S, M, stride, _p(ws), ws.numel(), _stream()),
                 "xp_layernorm_bwd_partials_side")
+        if not param_grads:
+            return dx, None, None
         nrows = L.lib().xp_layernorm_bwd_partial_rows(rows)
         if dres_colsum and not (dx_colsum and dres is not None):
             raise ValueError("layernorm_bwd: dres_colsum needs dx_colsum and dres")
