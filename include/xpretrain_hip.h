@@ -247,6 +247,21 @@ int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, const void* do
                  int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
                  void* workspace, size_t workspace_bytes, float* dqkv_colsum_partials, void* stream);
 
+/* The attention weights themselves (csrc/attention_probs.hip; `output_attentions=True`): what xp_attn_fwd never stores, rebuilt
+ * from the qkv it read (same layout, q already scaled), the stats it wrote and the pad_mask it was given: entry (i, j) =
+ * exp((s'_ij - max_i) - logsum_i), s' = finfo.min for a padded key (as _expand_mask adds it, :50-61) and the score otherwise.
+ * Outputs are fp32 and contiguous, every element is written:
+ *  XP_ATTN_CAUSAL: probs[B,H,S,S] = CLIPAttention.forward's attn_weights_reshaped (:303-311); entries above the diagonal are
+ *                  exactly 0, a padded key of a row that sees a kept key is exactly 0, a row that sees only padded keys is uniform
+ *                  over its i+1 visible keys (the reference's own behaviour).  probs_proxy must be NULL; M,N,L ignored.
+ *  XP_ATTN_PROXY : probs[B,H,N,L,M+L] = forward2's first attn_weights (:350-358: frame-n queries over [M proxies | frame n], in
+ *                  that column order), probs_proxy[B,H,M,S] = its second (:365-370: proxy queries over all keys).  The reference
+ *                  computes both and drops them.  pad_mask must be NULL.
+ * `dtype` is the storage of qkv; arithmetic is fp32.  No workspace; launches only on `stream`. */
+int xp_attn_probs(const void* qkv, int64_t ldqkv, const float* stats, const int64_t* pad_mask,
+                  float* probs, float* probs_proxy, int32_t mode, int64_t B, int64_t H, int64_t S,
+                  int64_t M, int64_t N, int64_t L, int32_t dtype, void* stream);
+
 /* Single-query proxy attention (csrc/attention_pooled.hip): what the LAST layer of the video tower needs when only the pooled
  * feature leaves it (pooled_output = last_hidden_state[:, 0], modeling/CLIP_ViP.py:360-366).  Query row 0 of every sample is a
  * proxy row and attends all S keys (CLIPAttention.forward2): B*H problems of one query against S keys, a memory-bound pass over

@@ -4,7 +4,9 @@ Run on the GPU box:  python tools/bench_kernels.py [gemm|gemmfwd|ln|attn|all]  -
 `python tools/bench_kernels.py loss [n] [d]`: each kind of xp_contrastive_loss (and the two older entry points) back to back,
 loss + all gradients per call, at n = m pairs of width d (default 64 x 512: 8 GPUs x 8 pairs).
 `python tools/bench_kernels.py act [rounds]`: the two GEMMs that carry the MLP activation (fc1 forward with both outputs, dpre with
-fused column sums), quick_gelu (epilogue kinds 3 / 5) against erf GELU (kinds 8 / 9), interleaved."""
+fused column sums), quick_gelu (epilogue kinds 3 / 5) against erf GELU (kinds 8 / 9), interleaved.
+`python tools/bench_kernels.py probs`: xp_attn_probs (the attention weights of one layer, output_attentions) at cfg #2, bf16 and fp32
+storage: the median of individually timed launches after a warm-up, against the time its stores alone need."""
 import sys
 
 import torch
@@ -116,6 +118,28 @@ def bench_attn():
     print(f"attn fwd  text B8 H8 S32: {us:7.1f} us")
 
 
+def bench_probs(launches=200, warmup=300):
+    """one layer's attention weights at cfg #2: 8 * 12 * (12 * 196 * 200 + 4 * 2356) fp32 = 184.2 MB written, 87 MB of bf16 qkv read"""
+    B, Hh, M, N, Lp = 8, 12, 4, 12, 196
+    S = M + N * Lp
+    for dt in (torch.bfloat16, torch.float32):
+        qkv = torch.randn(B * S, 3 * Hh * 64, device="cuda").to(dt)
+        _, stats = H.attn_fwd(qkv, B, S, Hh, size=(M, N, Lp))
+        out = H.attn_probs(qkv, stats, B, S, Hh, size=(M, N, Lp))
+        for _ in range(warmup):
+            H.attn_probs(qkv, stats, B, S, Hh, size=(M, N, Lp), out=out)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
+        for st, en in ev:
+            st.record()
+            H.attn_probs(qkv, stats, B, S, Hh, size=(M, N, Lp), out=out)
+            en.record()
+        torch.cuda.synchronize()
+        us = sorted(st.elapsed_time(en) * 1e3 for st, en in ev)
+        nbytes = 4 * (out[0].numel() + out[1].numel())
+        print(f"attn_probs {str(dt)[6:]:8s} B{B} H{Hh} (4,12,196): median {us[len(us) // 2]:7.1f} us (min {us[0]:.1f}, max {us[-1]:.1f}; both launches)  "
+              f"{nbytes / 1e6:.1f} MB written: {nbytes / us[len(us) // 2] / 1e6:5.2f} TB/s of stores, floor {nbytes / 8e6:.1f} us at 8 TB/s")
+
+
 def bench_loss(n=64, d=512):
     feats = [torch.nn.functional.normalize(torch.randn(n, d, device="cuda"), dim=-1) for _ in range(4)]
     ls = torch.tensor(4.6, device="cuda")
@@ -136,6 +160,8 @@ if __name__ == "__main__":
         bench_act(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
     if what == "loss":
         bench_loss(*(int(a) for a in sys.argv[2:4]))
+    if what == "probs":
+        bench_probs()
     if what in ("ln", "all"):
         bench_ln()
     if what in ("attn", "all"):

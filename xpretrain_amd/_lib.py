@@ -176,6 +176,7 @@ SIGNATURES = {
     "xp_attn_bwd": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, f32, i32, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp]),
     "xp_attn_bwd2": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, f32, i32, i64, i64, i64, i64, i64, i64, i32, vp, sz, vp, vp]),
     "xp_attn_bwd_colsum_rows": (i64, [i32, i64, i64, i64, i64, i64, i64, i32]),
+    "xp_attn_probs": (i32, [vp, i64, vp, vp, vp, vp, i32, i64, i64, i64, i64, i64, i64, i32, vp]),
     "xp_set_attn_bwd_wide": (i32, [i32]),
     "xp_get_attn_bwd_wide": (i32, []),
     "xp_attn_pooled_workspace_bytes": (sz, [i64, i64, i64, i32]),

@@ -1137,6 +1137,25 @@ def _layer_act(layer) -> int:
     return layer._modules["mlp"].__dict__.get("act_kind", L.ACT_QUICK_GELU)
 
 
+def layer_attentions(x, layer, B, S, size, pad_mask, side=None):
+    """The attention weights of a ``CLIPEncoderLayer`` on its input ``x`` (``side``: x's fp32 side rows), for ``output_attentions``:
+    LayerNorm 1, the QKV projection and the fused attention forward as EncoderLayerFn's op-by-op branch calls them -- the native
+    layer call computes the same bits -- then ``hip_ops.attn_probs`` on that qkv and those statistics.  Causal (``size`` None):
+    fp32 ``[B, H, S, S]``; video: ``(proxy [B,H,M,S], frame [B,H,N,L,M+L])``.  No autograd: the weights are detached, new memory."""
+    ln1_w, ln1_b, wq, bq, wk, bk, wv, bv = _layer_params(layer)[:8]
+    heads = layer.num_heads
+    rows, D = x.shape
+    _check_layer_args("layer_attentions", x, heads, L.ACT_QUICK_GELU, side, B * size[0] if size is not None else B * S,
+                      "[B*M, D] (video) / [B*S, D] (text)")
+    with torch.no_grad():
+        Wqkv, bqkv = WEIGHTS.fused((wq, wk, wv), x.dtype), WEIGHTS.fused((bq, bk, bv), torch.float32)
+        lns = None if side is None else ((S, size[0], size[0]) if size is not None else (1, 1, 1))
+        h1, _, _ = H.layernorm_fwd(x.detach(), ln1_w.detach(), ln1_b.detach(), rows, D, x_side=side, side=lns)
+        qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=64 ** -0.5, scale_cols=D)
+        _, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask)
+        return H.attn_probs(qkv, stats, B, S, heads, size=size, pad_mask=pad_mask)
+
+
 def encoder_layer(x, layer, B, S, heads, size, pad_mask, side=None, split=None):
     """Apply ``EncoderLayerFn`` with the parameters of a ``CLIPEncoderLayer`` module.  With ``side`` (the proxy rows of x in fp32)
     returns ``(x3, side_out)``.  ``split``: a ``ForwardSplit`` (the tower runs as two half-batch chains)."""

@@ -8,6 +8,7 @@ Nothing here computes with torch ops.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional
 
 import torch
@@ -538,6 +539,38 @@ def attn_fwd(qkv: torch.Tensor, B: int, S: int, H: int, *, size=None, pad_mask=N
     L.check(L.lib().xp_attn_fwd(_p(qkv), 3 * H * 64, _p(out), H * 64, _p(stats), _p(pad_mask), mode, B, H, S, M, N, Lp,
                                 _dt(qkv), _p(ws), ws.numel(), _stream()), "xp_attn_fwd")
     return out, stats
+
+
+def attn_probs(qkv: torch.Tensor, stats: torch.Tensor, B: int, S: int, H: int, *, size=None, pad_mask=None, out=None):
+    """The attention weights ``attn_fwd`` never stores (xp_attn_probs), from the ``qkv`` it read, the ``stats`` it returned and the
+    ``pad_mask`` it was given; fp32 whatever the storage of qkv.  Causal: ``[B,H,S,S]`` (CLIPAttention.forward's
+    attn_weights_reshaped).  ``size=(M,N,L)``: ``(proxy [B,H,M,S], frame [B,H,N,L,M+L])``, forward2's second and first attn_weights
+    (proxy queries over all keys; frame-n queries over [M proxies | frame n]).  ``out``: the buffer (causal) or the
+    ``(proxy, frame)`` pair to write into -- contiguous fp32 tensors of those element counts, any shape; the results are views."""
+    _chk(qkv, "qkv"); _chk(stats, "stats", torch.float32)
+    mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
+    M, N, Lp = size if size is not None else (0, 1, S)
+    if stats.numel() != B * H * S * 2 or not stats.is_contiguous() or not qkv.is_contiguous() or qkv.numel() != B * S * 3 * H * 64:
+        raise ValueError("attn_probs: qkv must be a contiguous [B*S, 3*H*64] matrix and stats attn_fwd's contiguous [B,H,S,2]")
+    if pad_mask is not None:
+        _chk(pad_mask, "pad_mask", torch.int64)
+    shapes = ((B, H, M, S), (B, H, N, Lp, M + Lp)) if size is not None else ((B, H, S, S),)
+    outs = (out,) if isinstance(out, torch.Tensor) else tuple(out) if out is not None else (None,) * len(shapes)
+    if len(outs) != len(shapes):
+        raise ValueError(f"attn_probs: out must be {'the (proxy, frame) pair' if size is not None else 'one tensor'}")
+    bufs = []
+    for t, shp, nm in zip(outs, shapes, ("out[0]", "out[1]")):
+        if t is None:
+            t = torch.empty(shp, dtype=torch.float32, device=qkv.device)
+        else:
+            _chk(t, nm, torch.float32)
+            if not t.is_contiguous() or t.numel() != math.prod(shp):
+                raise ValueError(f"attn_probs: {nm} must be a contiguous fp32 tensor of {math.prod(shp)} elements")
+        bufs.append(t.view(shp))
+    frame, proxy = (bufs[1], bufs[0]) if size is not None else (bufs[0], None)
+    L.check(L.lib().xp_attn_probs(_p(qkv), 3 * H * 64, _p(stats), _p(pad_mask), _p(frame), _p(proxy), mode, B, H, S, M, N, Lp,
+                                  _dt(qkv), _stream()), "xp_attn_probs")
+    return (proxy, frame) if size is not None else frame
 
 
 def attn_plan(B: int, S: int, H: int, *, size=None, pad_mask=None, dtype=torch.bfloat16, backward=False, cus=0) -> dict:

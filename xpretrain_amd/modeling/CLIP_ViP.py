@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import json
 import os
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -96,6 +97,13 @@ class _Output(dict):
 
     def to_tuple(self):
         return tuple(v for v in self.values() if v is not None)
+
+
+# One video-tower layer's entry of ``attentions`` (``output_attentions=True``): the two softmax matrices of CLIPAttention.forward2
+# (reference CLIP_ViP.py:332-381), fp32 and detached.  ``proxy`` [B, H, M, S]: what each of the M proxy tokens reads from all
+# S = M + N*L tokens (:365-370); ``frame`` [B, H, N, L, M+L]: what patch l of frame n reads from [the M proxies | the L patches of
+# its own frame], in that column order (:350-358).  An extension: the reference computes both and returns None for them.
+ViPAttentions = namedtuple("ViPAttentions", ["proxy", "frame"])
 
 
 class CLIPOutput(_Output):
@@ -240,23 +248,29 @@ class CLIPEncoder(nn.Module):
         self.layers = nn.ModuleList([CLIPEncoderLayer(config) for _ in range(config.num_hidden_layers)])
         self.gradient_checkpointing = False
 
-    def pools_last(self, x, inputs_size, pad_mask, collect) -> bool:
+    def pools_last(self, x, inputs_size, pad_mask, collect, collect_attn=None) -> bool:
         """whether ``forward(pooled_last=True)`` runs the last layer in its pooled form: the video tower on the GPU, token 0 a proxy
-        row, nobody else looking at that layer's output (no padding mask, no ``collect``, no forward hooks on it)"""
-        return (inputs_size is not None and inputs_size[0] >= 1 and pad_mask is None and collect is None and x.is_cuda
-                and len(self.layers) > 0 and not _has_forward_hooks(self.layers[-1:]))
+        row, nobody else looking at that layer's output or weights (no padding mask, no ``collect``, no ``collect_attn``, no forward
+        hooks on it)"""
+        return (inputs_size is not None and inputs_size[0] >= 1 and pad_mask is None and collect is None and collect_attn is None
+                and x.is_cuda and len(self.layers) > 0 and not _has_forward_hooks(self.layers[-1:]))
 
-    def forward(self, x, B, S, inputs_size=None, pad_mask=None, collect=None, side=None, collect_side=None, pooled_last=False):
+    def forward(self, x, B, S, inputs_size=None, pad_mask=None, collect=None, side=None, collect_side=None, pooled_last=False,
+                collect_attn=None):
         """``side``: the proxy rows of ``x`` in fp32 (video tower, bf16 compute: XF.PROXY_SIDE); returns ``(x, side)`` then.
         ``collect`` / ``collect_side``: lists that receive every layer output (compute dtype, as ``last_hidden_state``) and its
         fp32 side rows (``output_hidden_states``).
+        ``collect_attn``: a list that receives every layer's attention weights (``output_attentions``; XF.layer_attentions), computed
+        from the layers' inputs AFTER the last layer and the join of the two chains -- the layer calls themselves are the ones of a
+        run without it.
         ``pooled_last``: the caller reads token 0 of every sample only.  Layers 0..n-2 run as ever, the two chains join, and the
         last layer runs in its pooled form (XF.PooledEncoderLayerFn): the encoder then returns the ``[B, D]`` rows of token 0
         (and their ``[B, D]`` fp32 side rows) instead of the ``[B*S, D]`` stream.  Ignored -- dense last layer, dense result --
         unless ``pools_last``: callers test that to know what they got."""
         ckpt = self.gradient_checkpointing and self.training and torch.is_grad_enabled()
-        pooled_last = bool(pooled_last) and self.pools_last(x, inputs_size, pad_mask, collect)
+        pooled_last = bool(pooled_last) and self.pools_last(x, inputs_size, pad_mask, collect, collect_attn)
         last = len(self.layers) - 1
+        attn_in = [] if collect_attn is not None else None
         # video tower: two half-batch chains on two streams (functional.ForwardSplit), joined after the last layer.  Training passes
         # keep every layer's buffers in the autograd graph; forward-only passes (and layers without a node: everything frozen under
         # grad mode) have the split hold them until the join.
@@ -285,6 +299,8 @@ class CLIPEncoder(nn.Module):
                 return XF.pooled_encoder_layer(x, layer, B, S, heads, inputs_size, side)
             if XF.LATE_WEIGHTS["event"] is not None and x.is_cuda:      # the optimizer's overlapped update of the layers >= K (XF.LATE_WEIGHTS)
                 XF.wait_late_weights(li, *((torch.cuda.current_stream(x.device), split.stream) if split is not None else ()))
+            if attn_in is not None:
+                attn_in.append((x, side))
             if ckpt:
                 # reference CLIP_ViP.py:675-690 (torch.utils.checkpoint around every encoder layer): the layer's saved-activation
                 # arena is dropped after the forward and rebuilt by re-running the layer when its backward starts -- the same
@@ -304,6 +320,10 @@ class CLIPEncoder(nn.Module):
                     collect_side.append(side)
         if split is not None:
             split.join()
+        if attn_in is not None:     # behind the join: the second chain's rows of every layer input are there
+            for layer, (xi, si) in zip(self.layers, attn_in):
+                w = XF.layer_attentions(xi, layer, B, S, inputs_size, pad_mask, si)
+                collect_attn.append(w if inputs_size is None else ViPAttentions(*w))
         return x if side is None else (x, side)
 
 
@@ -321,10 +341,11 @@ class CLIPTextTransformer(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, output_attentions=None,
                 output_hidden_states=None, return_dict=None):
+        """``output_attentions``: ``attentions`` is one fp32 ``[B, H, Lt, Lt]`` tensor per encoder layer, the reference's
+        ``attn_weights_reshaped`` (CLIP_ViP.py:303-311) -- rebuilt by a kernel of its own (XF.layer_attentions) from the bits the layer
+        used, detached (unlike the reference's they carry no gradient) and new memory each call.  The flag changes no other output."""
         if input_ids is None:
             raise ValueError("You have to specify either input_ids")
-        if output_attentions:
-            raise NotImplementedError("the fused attention kernel never materialises attention weights")
         input_ids = input_ids.view(-1, input_ids.shape[-1]).contiguous()
         B, Lt = input_ids.shape
         D = self.config.hidden_size
@@ -332,19 +353,20 @@ class CLIPTextTransformer(nn.Module):
         pad = None if attention_mask is None else attention_mask.to(torch.int64).contiguous()
         idx = XF.H.argmax_rows(input_ids)
         ln = self.final_layer_norm
+        attn = [] if output_attentions else None
         if XF.PROXY_SIDE and self.compute_dtype == torch.bfloat16:
             # the text tower is 256 rows: its WHOLE residual stream is kept in fp32 beside the bf16 rows the kernels read (the same
             # side-row mechanism as the video tower's proxy tokens, with every row a side row)
             emb = self.embeddings
             side = XF.H.text_embed_fwd(input_ids, emb.token_embedding.weight.detach(), emb.position_embedding.weight.detach(), torch.float32)
             hs, hside = ([x], [side]) if output_hidden_states else (None, None)
-            x, side = self.encoder(x, B, Lt, None, pad, hs, side, hside)
+            x, side = self.encoder(x, B, Lt, None, pad, hs, side, hside, collect_attn=attn)
             pooled = XF.LayerNormFn.apply(XF.GatherRowsFn.apply(x, idx, B, Lt), ln.weight, ln.bias,
                                           XF.H.gather_rows(side, idx, B, Lt, D), (1, 1, 1))
             last = _Lazy(lambda: XF.LayerNormFn.apply(x, ln.weight, ln.bias, side, (1, 1, 1)).view(B, Lt, D))
         else:
             hs, hside = ([x] if output_hidden_states else None), None
-            x = self.encoder(x, B, Lt, None, pad, hs)
+            x = self.encoder(x, B, Lt, None, pad, hs, collect_attn=attn)
             # LayerNorm is row-wise, so pooling the EOT rows first and normalising only those is identical to
             # final_layer_norm followed by the gather (:772-776); the full normalised sequence is only produced
             # on request.
@@ -353,7 +375,7 @@ class CLIPTextTransformer(nn.Module):
         out = BaseModelOutputWithPooling(last_hidden_state=last, pooler_output=pooled,
                                          hidden_states=None if hs is None else tuple(h.view(B, Lt, D) for h in hs),
                                          hidden_side_rows=None if hside is None else tuple(h.view(B, Lt, D) for h in hside),
-                                         attentions=None)
+                                         attentions=None if attn is None else tuple(attn))
         return out if return_dict is None or return_dict else out.to_tuple()
 
 
@@ -372,11 +394,14 @@ class CLIPVisionTransformer(nn.Module):
     def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None, pooled_only=False):
         """``pooled_only`` (CLIPModel.pooled_last_layer): the caller reads ``pooler_output`` alone, so the last encoder layer may
         compute token 0 of every sample only; ``last_hidden_state`` is then ``None``.  Without it -- every direct call -- and with
-        ``output_hidden_states`` the tower is dense."""
+        ``output_hidden_states`` the tower is dense.
+        ``output_attentions`` (a documented extension: the reference returns ``(None, ..)`` for this tower): ``attentions`` is one
+        ``ViPAttentions(proxy [B,H,M,S], frame [B,H,N,L,M+L])`` per encoder layer -- fp32 in both compute dtypes, detached, new memory
+        each call (2.2 GB for the 12 layers of ViT-B/16 at batch 8 x 12 frames).  It keeps the last layer dense and changes no other
+        output."""
         if pixel_values is None:
             raise ValueError("You have to specify pixel_values")
-        if output_attentions:
-            raise NotImplementedError("the fused attention kernel never materialises attention weights")
+        attn = [] if output_attentions else None
         B = pixel_values.shape[0]
         D = self.config.hidden_size
         x, size = self.embeddings(pixel_values, self.compute_dtype)
@@ -388,8 +413,8 @@ class CLIPVisionTransformer(nn.Module):
             side = XF.proxy_side_rows(emb.class_embedding, emb.added_cls, emb.position_embedding.weight, B, M)
             x, side = XF.LayerNormFn.apply(x, self.pre_layrnorm.weight, self.pre_layrnorm.bias, side, (S, M, M), True)
             hs, hside = ([x], [side]) if output_hidden_states else (None, None)
-            pooled_only = bool(pooled_only) and self.encoder.pools_last(x, size, None, hs)
-            x, side = self.encoder(x, B, S, size, None, hs, side, hside, pooled_only)
+            pooled_only = bool(pooled_only) and self.encoder.pools_last(x, size, None, hs, attn)
+            x, side = self.encoder(x, B, S, size, None, hs, side, hside, pooled_only, attn)
             if pooled_only:         # x, side: token 0 of every sample already
                 pooled = XF.LayerNormFn.apply(x, self.post_layernorm.weight, self.post_layernorm.bias, side, (1, 1, 1))
             else:
@@ -398,14 +423,14 @@ class CLIPVisionTransformer(nn.Module):
         else:
             x = XF.LayerNormFn.apply(x, self.pre_layrnorm.weight, self.pre_layrnorm.bias)
             hs, hside = ([x] if output_hidden_states else None), None
-            pooled_only = bool(pooled_only) and self.encoder.pools_last(x, size, None, hs)
-            x = self.encoder(x, B, S, size, None, hs, pooled_last=pooled_only)
+            pooled_only = bool(pooled_only) and self.encoder.pools_last(x, size, None, hs, attn)
+            x = self.encoder(x, B, S, size, None, hs, pooled_last=pooled_only, collect_attn=attn)
             pooled = XF.LayerNormFn.apply(x if pooled_only else XF.GatherRowsFn.apply(x, None, B, S), self.post_layernorm.weight,
                                           self.post_layernorm.bias)
         out = BaseModelOutputWithPooling(last_hidden_state=None if pooled_only else x.view(B, S, D), pooler_output=pooled,
                                          hidden_states=None if hs is None else tuple(h.view(B, S, D) for h in hs),
                                          hidden_side_rows=None if hside is None else tuple(h.view(B, M, D) for h in hside),
-                                         attentions=None)
+                                         attentions=None if attn is None else tuple(attn))
         return out if return_dict is None or return_dict else out.to_tuple()
 
 
@@ -592,15 +617,16 @@ class CLIPModel(CLIPPreTrainedModel):
 
     def get_text_features(self, input_ids=None, attention_mask=None, position_ids=None, output_attentions=None,
                           output_hidden_states=None, return_dict=None, if_norm=None):
+        # (output_attentions is accepted, as in the reference, and the features have nowhere to carry the weights: not computed)
         out = self.text_model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
-                              output_attentions=output_attentions, output_hidden_states=output_hidden_states)
+                              output_hidden_states=output_hidden_states)
         feats = XF.ProjectionFn.apply(out["pooler_output"], self.text_projection.weight)
         return XF.L2NormFn.apply(feats) if if_norm else feats.float()
 
     def get_image_features(self, pixel_values=None, output_attentions=None, output_hidden_states=None,
                            return_dict=None, if_norm=None):
-        out = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer)
+        out = self.vision_model(pixel_values=pixel_values, output_hidden_states=output_hidden_states,      # (output_attentions: as above)
+                                pooled_only=self.pooled_last_layer)
         feats = XF.ProjectionFn.apply(out["pooler_output"], self.visual_projection.weight)
         return XF.L2NormFn.apply(feats) if if_norm else feats.float()
 
@@ -627,6 +653,8 @@ class CLIPModel(CLIPPreTrainedModel):
             image_embeds = XF.L2NormFn.apply(XF.ProjectionFn.apply(vision_outputs["pooler_output"], self.visual_projection.weight))
             main.wait_event(text_done)
             text_embeds.record_stream(main)
+            for w in text_outputs["attentions"] or ():      # allocated and written on the text stream, read by the caller on this one
+                w.record_stream(main)
             return self._finish(image_embeds, text_embeds, text_outputs, vision_outputs, return_loss, return_dict,
                                 output_hidden_states)
         vision_outputs = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
