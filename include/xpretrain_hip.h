@@ -409,6 +409,41 @@ int xp_contrastive_loss(int32_t kind, const float* vis, const float* txt, const 
                         float* d_log_scale, int64_t n, int64_t m, int64_t d,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* The four two-argument, fixed-temperature losses of optimization/loss.py (the drivers' `else: loss_func(vis_feat, text_feat)`
+ * branch) behind one entry: loss and both feature gradients in one call, fp32, fixed reduction order (bit-reproducible), every
+ * launch on `stream`, no allocation, no synchronisation, no host-to-device copy (the parameters travel as kernel arguments).
+ * vis [n,d], txt [n*bag,d] (bag = 1 except for XP_PAIR_MILNCE), n*bag <= 16384.  rows(S) / cols(S) as for the family above.
+ *   XP_PAIR_NCE      S = V T^T / temp ; loss = rows(S) + cols(S)                                   NCEContrastiveLoss    :67-83
+ *   XP_PAIR_TRIPLET  S = V T^T, or with order_measure S_ij = -|max(0, t_j - v_i)|_2 (order_sim :13-19)  TripletContrastiveLoss :22-64
+ *                    cs_ij = max(0, margin + S_ij - S_ii), ci_ij = max(0, margin + S_ij - S_jj), both diagonals cleared
+ *                    loss = sum cs + sum ci (sums, not means); with max_violation  sum_i max_j cs_ij + sum_j max_i ci_ij.
+ *                    A hinge is active where its cost is > 0.  The gradient of a maximum goes to ONE element, on an exact tie
+ *                    to the lowest index; a line without a positive cost has no gradient.
+ *                    Order measure: dS_ij/dv_i = max(0, t_j - v_i) / (-S_ij) = -dS_ij/dt_j, a kernel of its own (no GEMM).  A
+ *                    pair at distance exactly 0 contributes ZERO gradient -- the one deliberate deviation: torch gives NaN there.
+ *   XP_PAIR_HARDNEG  S = T V^T (no temperature).  Each row of S and each row of S^T keeps its k = hard_negative_num largest
+ *                    entries after the diagonal entry was lowered by 10000 (in fp32, as the reference subtracts it):
+ *                    loss = mean_i[lse(S_ii U top-k of row i) - S_ii] over both directions.                 HardNegLoss :86-105
+ *                    1 <= k <= n; with k = n the lowered diagonal entry S_ii - 10000 is selected too (last), as in the
+ *                    reference.  On an exact tie at the k-th value the lowest indices are taken (-0 counts as +0).
+ *   XP_PAIR_MILNCE   x = (V T^T / temp) viewed as [n, n, bag] ; nom_i = lse_b x[i,i,b] ;              MILNCEContrastiveLoss :109-124
+ *                    den_i = lse({x[i,j,b] : j != i} U {x[j,i,b] : all j}) ; loss = mean_i(den_i - nom_i)
+ * Gradients: G = dloss/dS (of V T^T, before the temperature), then dV = c G T and dT = c G^T V with c = 1/temp (NCE, MILNCE) or 1
+ * through the fp32 GEMM kernels of the family; the order measure goes through its own backward kernel instead.
+ * Every element of loss, d_vis [n,d] and d_txt [n*bag,d] is written on every call (zeros where there is no gradient, e.g. the
+ * triplet loss at n = 1).  Refused before any launch: an unknown kind, a null pointer, temp <= 0 (NCE, MILNCE),
+ * hard_negative_num outside [1, n] (HARDNEG), bag < 1 or bag != 1 for a kind other than MILNCE, n*bag > 16384, a workspace
+ * below xp_pair_loss_workspace_bytes (which is exact; 0 for arguments that would be refused).  Fields a kind does not read are
+ * ignored.  No time was measured for these losses. */
+enum XpPairLossKind { XP_PAIR_NCE, XP_PAIR_TRIPLET, XP_PAIR_HARDNEG, XP_PAIR_MILNCE };
+typedef struct {
+  float temp, margin;
+  int32_t max_violation, order_measure, hard_negative_num, bag;
+} XpPairLossParams;
+size_t xp_pair_loss_workspace_bytes(int32_t kind, const XpPairLossParams* params, int64_t n, int64_t d);
+int xp_pair_loss(int32_t kind, const XpPairLossParams* params, const float* vis, const float* txt, float* loss,
+                 float* d_vis, float* d_txt, int64_t n, int64_t d, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------- Retrieval evaluation
  * validate() of tasks/run_video_retrieval.py:123-203 on gathered unit-norm features (fp32):
  *   sim = text . vis^T                     cal_cossim, utils/metrics.py:3-5

@@ -28,6 +28,8 @@ ATTN_PROXY, ATTN_CAUSAL = 0, 1
 # XpLossKind, in the header's order
 (XP_LOSS_NCE, XP_LOSS_VSC_FC, XP_LOSS_DSL, XP_LOSS_VS_VC, XP_LOSS_VS_VC_FC, XP_LOSS_VSC, XP_LOSS_VIDIMG,
  XP_LOSS_VIDIMG_DIVIDE) = range(8)
+# XpPairLossKind, in the header's order
+XP_PAIR_NCE, XP_PAIR_TRIPLET, XP_PAIR_HARDNEG, XP_PAIR_MILNCE = range(4)
 
 i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -138,6 +140,11 @@ class XpAdamGroup(C.Structure):
     _fields_ = [("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("step_size", f32)]
 
 
+class XpPairLossParams(C.Structure):
+    _fields_ = [("temp", f32), ("margin", f32), ("max_violation", i32), ("order_measure", i32), ("hard_negative_num", i32),
+                ("bag", i32)]
+
+
 XP_OPT_CHUNK, XP_OPT_MAX_TENSORS, XP_OPT_MAX_GROUPS = 65536, 256, 16
 
 # name -> (restype, argtypes); mirrors include/xpretrain_hip.h one-to-one
@@ -207,6 +214,8 @@ SIGNATURES = {
     "xp_vsc_fc_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "xp_contrastive_loss_workspace_bytes": (sz, [i32, i64, i64, i64]),
     "xp_contrastive_loss": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, sz, vp]),
+    "xp_pair_loss_workspace_bytes": (sz, [i32, C.POINTER(XpPairLossParams), i64, i64]),
+    "xp_pair_loss": (i32, [i32, C.POINTER(XpPairLossParams), vp, vp, vp, vp, vp, i64, i64, vp, sz, vp]),
     "xp_encoder_layer_fwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),
     "xp_encoder_layer_fwd": (i32, [C.POINTER(XpLayerFwd), vp]),
     "xp_encoder_layer_bwd_workspace_bytes": (sz, [C.POINTER(XpLayerDims)]),

@@ -1108,6 +1108,22 @@ class ContrastiveLossFn(torch.autograd.Function):
         return (None, *[next(saved) * g if h else None for h in ctx.has])
 
 
+class PairLossFn(torch.autograd.Function):
+    """One of the fixed-temperature losses (optimization/loss.py:22-124) by its ``XP_PAIR_*`` kind; loss and both feature
+    gradients in one library call.  ``params``: the keyword arguments of ``hip_ops.pair_loss``."""
+
+    @staticmethod
+    def forward(ctx, kind, vis, txt, params):
+        loss, dv, dt = H.pair_loss(kind, vis.contiguous().float(), txt.contiguous().float(), **params)
+        ctx.save_for_backward(dv, dt)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dv, dt = ctx.saved_tensors
+        return None, dv * g, dt * g, None
+
+
 def _layer_params(layer):
     """the 16 parameters of a CLIPEncoderLayer in EncoderLayerFn's argument order.  The sub-module handles are cached on the layer
     (nn.Module.__getattr__ chains cost ~10 us per call otherwise); the Parameter objects are read from the modules' own tables

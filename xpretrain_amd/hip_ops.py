@@ -519,6 +519,31 @@ def contrastive_loss(kind: int, vis, txt, img=None, cap=None, *, log_scale):
     return (loss, *grads, dls)
 
 
+def pair_loss(kind: int, vis, txt, *, temp=1.0, margin=0.0, max_violation=False, order_measure=False, hard_negative_num=1, bag=1):
+    """xp_pair_loss: one of the four fixed-temperature losses (``L.XP_PAIR_*``) and both feature gradients in one call.
+    vis [n,d], txt [n*bag,d] (``bag`` = 1 except for MIL-NCE).  Returns (loss, d_vis, d_txt) -- fp32 device tensors.  A parameter
+    the kind does not read is ignored; what the kind rules out (temp <= 0, hard_negative_num outside [1, n], an unknown kind) is
+    refused by the library before anything is launched."""
+    kind, bag = int(kind), int(bag)
+    for t, name in ((vis, "vis"), (txt, "txt")):
+        _chk(t, name, torch.float32)
+        if t.dim() != 2 or t.shape[1] != vis.shape[-1] or not t.is_contiguous():
+            raise ValueError(f"pair_loss: {name} must be a contiguous [rows, {vis.shape[-1]}] matrix, got {tuple(t.shape)}")
+    n, d = vis.shape
+    if txt.shape[0] != n * bag:
+        raise ValueError(f"pair_loss: txt must have n * bag = {n} * {bag} rows, got {tuple(txt.shape)}")
+    prm = L.XpPairLossParams(float(temp), float(margin), int(bool(max_violation)), int(bool(order_measure)), int(hard_negative_num),
+                             bag)
+    dev = vis.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    dv, dt = torch.empty_like(vis), torch.empty_like(txt)
+    nb = L.lib().xp_pair_loss_workspace_bytes(kind, C.byref(prm), n, d)
+    ws = workspace(nb, dev, "loss")
+    L.check(L.lib().xp_pair_loss(kind, C.byref(prm), _p(vis), _p(txt), _p(loss), _p(dv), _p(dt), n, d, _p(ws), ws.numel(), _stream()),
+            "xp_pair_loss")
+    return loss, dv, dt
+
+
 # --------------------------------------------------------------------------------------- attention
 def _attn_ws(mode, B, H, M, N, Lp, device):
     nb = L.lib().xp_attn_workspace_bytes(mode, B, H, M, N, Lp)

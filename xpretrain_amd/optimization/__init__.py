@@ -1,4 +1,5 @@
-from .loss import (NCELearnableTempDSLLoss, NCELearnableTempLoss, NCELearnableTempLoss_vs_vc,  # noqa: F401
+from .loss import (HardNegLoss, MILNCEContrastiveLoss, NCEContrastiveLoss, TripletContrastiveLoss,  # noqa: F401
+                   NCELearnableTempDSLLoss, NCELearnableTempLoss, NCELearnableTempLoss_vs_vc,
                    NCELearnableTempLoss_vs_vc_fc, NCELearnableTempLoss_vsc, NCELearnableTempLoss_vsc_fc,
                    VidImgDivideNCELearnableTempLoss, VidImgNCELearnableTempLoss, build_loss_func)
 from .adamw import AdamW  # noqa: F401

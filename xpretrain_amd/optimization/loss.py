@@ -4,6 +4,8 @@
 exp(temp) * vis @ text^T, both cross-entropies and all gradients in one call
 (csrc/loss.hip).  The other learnable-temperature losses the reference drivers name (run_pretrain.py:355-363,
 run_video_retrieval.py:333) run through the same library path, one ``XP_LOSS_*`` kind each (xp_contrastive_loss).
+The four two-argument, fixed-temperature losses (loss.py:22-124, reached through the drivers' ``else: loss_func(vis_feat, text_feat)``
+branch) run through xp_pair_loss, one ``XP_PAIR_*`` kind each.
 ``build_loss_func(cfg)`` keeps the reference's factory signature (loss.py:326-328).
 """
 from __future__ import annotations
@@ -87,7 +89,70 @@ class NCELearnableTempLoss_vsc(_FamilyLoss):
         return super().forward(vis_feat, text_feat, img_feat, cap_feat, temp)
 
 
+def _cfg(cfg, key):
+    return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
+
+
+class _PairLoss(nn.Module):
+    """a fixed-temperature loss by its kind; ``self.params``: what its constructor read from `cfg`"""
+    kind = None
+
+    def forward(self, vis_feat, text_feat):
+        return XF.PairLossFn.apply(self.kind, vis_feat, text_feat, self.params)
+
+
+class TripletContrastiveLoss(_PairLoss):
+    """loss.py:22-64: hinge costs of every negative against the positive of its row and of its column, summed, or with
+    `cfg.max_violation` the hardest negative of each row and column only; `cfg.measure` 'order' takes order_sim (:13-19) for the
+    cosine.  A pair at order distance exactly 0 contributes no gradient (torch gives NaN there)."""
+    kind = L.XP_PAIR_TRIPLET
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.params = dict(margin=float(_cfg(cfg, "margin")), order_measure=_cfg(cfg, "measure") == "order",
+                           max_violation=bool(_cfg(cfg, "max_violation")))
+
+    def forward(self, im, s):
+        return super().forward(im, s)
+
+
+class NCEContrastiveLoss(_PairLoss):
+    """loss.py:67-83: both cross-entropies of vis text^T / cfg.temp."""
+    kind = L.XP_PAIR_NCE
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.params = dict(temp=float(_cfg(cfg, "temp")))
+
+
+class HardNegLoss(_PairLoss):
+    """loss.py:86-105: cross-entropy of the positive against the `cfg.hard_negative_num` hardest negatives of its row, both
+    directions; no temperature."""
+    kind = L.XP_PAIR_HARDNEG
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.params = dict(hard_negative_num=int(_cfg(cfg, "hard_negative_num")))
+
+
+class MILNCEContrastiveLoss(_PairLoss):
+    """loss.py:109-124: MIL-NCE over bags of text rows; `text_embd` has n * k rows for n videos (row j * k + b is text b of
+    video j)."""
+    kind = L.XP_PAIR_MILNCE
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.params = dict(temp=float(_cfg(cfg, "temp")))
+
+    def forward(self, video_embd, text_embd):
+        n = video_embd.shape[0]
+        if text_embd.shape[0] % n:
+            raise ValueError(f"MILNCEContrastiveLoss: {text_embd.shape[0]} text rows are no multiple of {n} videos")
+        return XF.PairLossFn.apply(self.kind, video_embd, text_embd, dict(self.params, bag=text_embd.shape[0] // n))
+
+
 _LOSSES = {c.__name__: c for c in (
+    TripletContrastiveLoss, NCEContrastiveLoss, HardNegLoss, MILNCEContrastiveLoss,
     NCELearnableTempLoss, VidImgNCELearnableTempLoss, VidImgDivideNCELearnableTempLoss, NCELearnableTempDSLLoss,
     NCELearnableTempLoss_vs_vc, NCELearnableTempLoss_vs_vc_fc, NCELearnableTempLoss_vsc, NCELearnableTempLoss_vsc_fc)}
 
