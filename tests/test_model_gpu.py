@@ -2,6 +2,8 @@
 (1) the reference-generated fixture tests/golden/tiny_e2e.pt (fp32 outputs of the UNMODIFIED reference) and
 (2) the CPU oracle at BASELINE cfg #1's architecture (ViT-B/32, T=2, Lt=16), bf16 tolerance 2e-2 as
 BASELINE.json:north_star states (on unit-norm features / loss / max-norm-relative gradients)."""
+import functools
+
 import pytest
 import torch
 
@@ -478,43 +480,77 @@ def test_inference_forward_gathers_patches_in_the_gemm(monkeypatch):
     assert calls and model.clipmodel.vision_model.embeddings.patch_embedding.weight.grad is not None
 
 
-@pytest.mark.parametrize("first_late", [0, 1, 2])
-def test_optimizer_overlapping_the_next_forward_trains_bit_identically(first_late):
-    """AdamW.overlap_next_forward: the update of the encoder layers >= K of both towers runs on a stream of its own and the NEXT
-    forward waits for it in front of layer K (functional.LATE_WEIGHTS).  Four training steps (4 layers per tower, clip active) must
-    leave the plain optimizer's parameters, moments, losses and gradient norms -- the same kernel on the same values; the launch
-    partition reorders the norm's chunk partials, so the clip factor may differ in its last bit (1e-6 relative) -- and state_dict()
-    readers wait for the late update too (a reader that did not would see the previous step's weights: 1e-3 relative)."""
-    from xpretrain_amd.modeling import VidCLIP
-    from xpretrain_amd.optimization import AdamW, NCELearnableTempLoss, build_e2e_optimizer_w_lr_mul
-    from xpretrain_amd import functional as XF
-    cfgd = O.hf_config_dict(128, 2, 4, 256, 16, 32, 128, 2, 4, 256, 120, 16, 64)
-    video, ids, mask = [t.cuda() for t in O.synthetic_inputs(4, 2, 32, 8, vocab=120)]
+# ------------------------------------------------------------------------------------------ the optimizer beside the next forward
+# One tiny model for every test below (4 layers per tower: layer K sits strictly inside both towers for K = 1, 2), four optimizer
+# steps with the clip active; a run is made once per (K, calling pattern) and shared.
+_OVL_CFG = O.hf_config_dict(128, 2, 4, 256, 16, 32, 128, 2, 4, 256, 120, 16, 64)
 
-    def train(K):
-        torch.manual_seed(11)
-        model = VidCLIP(_Args(cfgd, 2)).cuda().train()
-        groups = build_e2e_optimizer_w_lr_mul(list(model.named_parameters()), 1e-4, 0.05, lr_mul=1, lr_mul_prefix="")
-        opt = AdamW([g for g in groups if g["params"]], lr=1e-4, betas=(0.9, 0.98))
+
+@functools.lru_cache(maxsize=None)
+def _ovl_inputs():
+    return tuple(t.cuda() for t in O.synthetic_inputs(4, 2, 32, 8, vocab=120))
+
+
+def _ovl_model(K):
+    from xpretrain_amd.modeling import VidCLIP
+    from xpretrain_amd.optimization import AdamW, build_e2e_optimizer_w_lr_mul
+    torch.manual_seed(11)
+    model = VidCLIP(_Args(_OVL_CFG, 2)).cuda().train()
+    groups = build_e2e_optimizer_w_lr_mul(list(model.named_parameters()), 1e-4, 0.05, lr_mul=1, lr_mul_prefix="")
+    opt = AdamW([g for g in groups if g["params"]], lr=1e-4, betas=(0.9, 0.98))
+    if K is not None:
+        opt.overlap_next_forward(model, K)
+    return model, opt
+
+
+def _ovl_records(model):
+    return [m.late_update for m in model.modules() if type(m).__name__ == "CLIPEncoder"]
+
+
+def _ovl_step(model, opt, K, steps=1):
+    """forward, loss, backward, ``steps`` x clip_and_step on those gradients; after each an update is pending on both encoders"""
+    from xpretrain_amd.optimization import NCELearnableTempLoss
+    video, ids, mask = _ovl_inputs()
+    out = model(video, ids, mask)
+    loss = NCELearnableTempLoss()(out["vis_features"], out["text_features"], model.clipmodel.logit_scale)
+    loss.backward()
+    for _ in range(steps):
+        norm = opt.clip_and_step(0.05)
         if K is not None:
-            opt.overlap_next_forward(model, K)
-        loss_fn, trace = NCELearnableTempLoss(), []
-        for _ in range(4):          # (a short, stable run: at lr 1e-3 this toy model amplifies the clip factor's last bit to 1e-4 in 4 steps)
-            out = model(video, ids, mask)
-            loss = loss_fn(out["vis_features"], out["text_features"], model.clipmodel.logit_scale)
-            loss.backward()
-            norm = opt.clip_and_step(0.05)
-            if K is not None:
-                assert XF.LATE_WEIGHTS["event"] is not None and XF.LATE_WEIGHTS["first_layer"] == K
-            opt.zero_grad(set_to_none=True)
-            trace.append((loss.detach().clone(), norm.clone()))
-        sd = {k: v.clone() for k, v in model.state_dict().items()}                 # (pre-hook: waits for the late update)
-        osd = opt.state_dict()["state"]
-        moments = [osd[i][k].clone() for i in sorted(osd) for k in ("exp_avg", "exp_avg_sq")]
-        XF.LATE_WEIGHTS["event"] = None
-        return trace, sd, moments
-    t0, sd0, m0 = train(None)
-    t1, sd1, m1 = train(first_late)
+            recs = _ovl_records(model)
+            assert len(recs) == 2 and all(r is not None and r.event is not None and r.first_layer == K for r in recs)
+    return loss.detach().clone(), norm.clone()
+
+
+def _ovl_final(model, opt):
+    sd = {k: v.clone() for k, v in model.state_dict().items()}                 # (pre-hook: waits for the late update)
+    osd = opt.state_dict()["state"]
+    return sd, [osd[i][k].clone() for i in sorted(osd) for k in ("exp_avg", "exp_avg_sq")]
+
+
+@functools.lru_cache(maxsize=None)
+def _ovl_run(K, pattern="plain"):
+    """(loss / norm trace, parameters, moments) of four steps.  ``plain``: zero_grad(set_to_none=True) after every step;
+    ``zero_in_place``: zero_grad(set_to_none=False); ``double_step``: two clip_and_step calls on the first gradients with no forward
+    between them, then two ordinary steps."""
+    from xpretrain_amd import functional as XF
+    model, opt = _ovl_model(K)
+    trace = []
+    for n in ((2, 1, 1) if pattern == "double_step" else (1, 1, 1, 1)):
+        # (a short, stable run: at lr 1e-3 this toy model amplifies the clip factor's last bit to 1e-4 in 4 steps)
+        trace.append(_ovl_step(model, opt, K, n))
+        opt.zero_grad(set_to_none=pattern != "zero_in_place")
+    sd, moments = _ovl_final(model, opt)
+    if K is not None:       # once the device is idle a join forgets the update: no later forward waits for an event of training
+        torch.cuda.synchronize()
+        XF.join_late_weights()
+        assert all(r.event is None for r in _ovl_records(model))
+    return trace, sd, moments
+
+
+def _ovl_assert_close(run, ref):
+    (t1, sd1, m1), (t0, sd0, m0) = run, ref
+    assert len(t0) == len(t1)
     for (l0, n0), (l1, n1) in zip(t0, t1):
         torch.testing.assert_close(l1, l0, rtol=2e-6, atol=0)
         torch.testing.assert_close(n1, n0, rtol=2e-6, atol=0)
@@ -524,3 +560,59 @@ def test_optimizer_overlapping_the_next_forward_trains_bit_identically(first_lat
     assert len(m0) == len(m1)
     for a, b in zip(m0, m1):
         torch.testing.assert_close(b, a, rtol=1e-5, atol=1e-9)
+
+
+@pytest.mark.parametrize("first_late", [0, 1, 2])
+def test_optimizer_overlapping_the_next_forward_trains_bit_identically(first_late):
+    """AdamW.overlap_next_forward: the update of the encoder layers >= K of both towers runs on a stream of its own and the NEXT
+    forward waits for it in front of layer K (functional.LateUpdate on the encoders).  Four training steps (4 layers per tower, clip
+    active) must leave the plain optimizer's parameters, moments, losses and gradient norms -- the same kernel on the same values; the
+    launch partition reorders the norm's chunk partials, so the clip factor may differ in its last bit (1e-6 relative) -- and
+    state_dict() readers wait for the late update too (a reader that did not would see the previous step's weights: 1e-3 relative)."""
+    _ovl_assert_close(_ovl_run(first_late), _ovl_run(None))
+
+
+@pytest.mark.parametrize("pattern", ["zero_in_place", "double_step"])
+@pytest.mark.parametrize("first_late", [0, 2])
+def test_overlapped_optimizer_under_other_calling_patterns(first_late, pattern):
+    """Gradients zeroed in place after every step, and two steps in a row without a forward between them: the late update of the
+    previous step still reads the gradients and the norm partials, so zero_grad(set_to_none=False) and step() join it first.  Each
+    overlapped run matches the plain optimizer driven the same way, within the gates of the test above."""
+    _ovl_assert_close(_ovl_run(first_late, pattern), _ovl_run(None, pattern))
+
+
+@pytest.mark.parametrize("first_late", [0, 2])
+def test_load_state_dict_right_after_an_overlapped_step_wins(first_late):
+    """model.load_state_dict() waits for the late update (pre-hook): the loaded values are what the parameters hold afterwards,
+    exactly -- a copy, no arithmetic."""
+    model, opt = _ovl_model(first_late)
+    saved = {k: v.clone() for k, v in model.state_dict().items()}
+    _ovl_step(model, opt, first_late)
+    model.load_state_dict(saved)
+    torch.cuda.synchronize()
+    for k, p in model.named_parameters():
+        if p.is_floating_point():
+            assert torch.equal(p.detach(), saved[k]), k
+
+
+def test_two_overlapped_optimizers_in_one_process_keep_their_own_records():
+    """Two models with their own optimizers (K = 1 and K = 2) stepped in alternation: neither step touches the other model's record,
+    and each model ends bit-identical to its solo overlapped run -- the same kernels, the same partition, the same values."""
+    pairs = [(K,) + _ovl_model(K) for K in (1, 2)]
+    for _ in range(4):
+        for i, (K, model, opt) in enumerate(pairs):
+            other = pairs[1 - i]
+            before = [(r, r.event, r.first_layer) for r in _ovl_records(other[1])]
+            _ovl_step(model, opt, K)
+            opt.zero_grad(set_to_none=True)
+            after = _ovl_records(other[1])
+            assert len(before) == 2 and all(r is a and r.event is ev and r.first_layer == fl == other[0]
+                                            for a, (r, ev, fl) in zip(after, before))
+    for K, model, opt in pairs:
+        sd, moments = _ovl_final(model, opt)
+        _, sd0, m0 = _ovl_run(K)
+        for k in sd0:
+            if sd0[k].is_floating_point():
+                assert torch.equal(sd[k], sd0[k]), (K, k)
+        assert len(moments) == len(m0) and all(torch.equal(a, b) for a, b in zip(moments, m0))
+

@@ -326,7 +326,6 @@ def test_whole_training_step(dtype, pooled, monkeypatch):
         assert set(grads) == {n for n, _ in model.named_parameters()}
         norm = opt.clip_and_step(0.05)
         torch.cuda.synchronize()
-        XF.LATE_WEIGHTS["event"] = None
         return loss.detach().clone(), norm.clone(), grads, {n: p.detach().clone() for n, p in model.named_parameters()}
     gw = twice(fn)
     tags = {t for t, _, _ in gw.records}

@@ -86,8 +86,8 @@ def step():
     n[0] += 1
     opt.clip_and_step(5.0)
     mark("opt")
-    if opt._late_stream is not None:
-        mark("late_end", opt._late_stream)        # the overlapped update of THIS step's gradients: ends inside the next step
+    if opt._late_update is not None:
+        mark("late_end", opt._late_update.streams[dev])        # the overlapped update of THIS step's gradients: ends inside the next step
     reducer.zero_grad()
     return loss
 

@@ -65,7 +65,6 @@ int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, bool slac
   d.C = slabs; d.split_k = split;
   int rc = xp_gemm(&d, st);
   if (rc) return rc;
-  if (xp_debug_flag("skip_splitk_reduce")) return XP_OK;      // measurement only (wrong gradients): what the four reduces of a layer cost the step
   return xp_splitk_reduce(slabs, dw, d.M * d.N, split, 0, st);
 }
 // both operands dense: dY[k, n_out], X[k, n_in]
@@ -140,8 +139,7 @@ struct WgradOrder {
     return XP_OK;
   }
   int join() const {                // the weight gradients (and every workspace the side stream read) belong to the main stream again
-    // (XPRETRAIN_DEBUG=no_wgrad_join: measurement only -- races on the shared workspace -- what a lazy join could be worth at most)
-    if (!side || xp_debug_flag("no_wgrad_join")) return XP_OK;
+    if (!side) return XP_OK;
     if (hipEventRecord(side->done, side->side) != hipSuccess || hipStreamWaitEvent(main, side->done, 0) != hipSuccess) {
       xp_set_error("%s: joining the weight-gradient stream failed", name);
       return XP_ERR_LAUNCH;
@@ -175,7 +173,6 @@ int out_proj_mlp_fwd(const Args& a, int64_t n, int64_t ldr, const float* side_x,
   // pre = h2 W1^T + b1 ; act = quick_gelu(pre) or gelu(pre)
   g = gemm_desc(a.h2, a.W1, a.act, n, Dff, D, dt);
   g.epilogue = epi_act_fwd(d); g.bias = a.b1; g.aux = a.pre;
-  if (xp_debug_flag("fc1_no_pre")) g.aux = nullptr;      // measurement only (tools/fc1_one_output.py): the backward then reads garbage
   if ((rc = xp_gemm(&g, st))) return rc;
   // x3 = x2 + act W2^T + b2
   g = gemm_desc(a.act, a.W2, a.x3, n, D, Dff, dt);

@@ -268,27 +268,90 @@ def _native_ok(x, params, pad_mask) -> bool:
 
 # ---- weights the optimizer is still writing (optimization.AdamW(overlap=...)) ---------------------------------------------------
 # AdamW.step can run the update of the encoder layers >= K of both towers on a stream of its own, so that the HBM-bound optimizer
-# pass overlaps the MFMA-bound first layers of the NEXT forward instead of standing between two steps.  It leaves the event here;
-# CLIPEncoder.forward makes every stream that is about to run layer K wait for it.  Anything else that reads those parameters outside a
-# model forward (state_dict(), a checkpoint writer, an evaluation with other code) calls join_late_weights() first -- the model's
-# state_dict pre-hook and utils.load_save do.
-LATE_WEIGHTS = {"event": None, "first_layer": 0}
+# pass overlaps the MFMA-bound first layers of the NEXT forward instead of standing between two steps.  One LateUpdate per
+# overlap_next_forward() call owns that protocol: the side stream, the event of the latest late launch and the encoders whose forward
+# waits for it in front of layer K (CLIPEncoder.late_update).  Anything else that reads or writes those parameters, their moments or
+# their gradients outside a model forward calls join_late_weights() first: the model's state_dict / load_state_dict pre-hooks and the
+# optimizer's state_dict, load_state_dict, zero_grad(set_to_none=False) and step do.
+_LATE_UPDATES = weakref.WeakSet()
 
 
-def wait_late_weights(layer_index, *streams):
-    """Before encoder layer ``layer_index`` runs on ``streams`` (default: the current stream)."""
-    ev = LATE_WEIGHTS["event"]
-    if ev is None or layer_index != LATE_WEIGHTS["first_layer"]:
-        return
-    for st in (streams or (torch.cuda.current_stream(),)):
-        st.wait_event(ev)
+class LateUpdate:
+    """The update of the encoder layers >= ``first_layer`` that ``owner`` (an optimizer) runs beside the next forward."""
+
+    def __init__(self, first_layer, owner=None):
+        self.first_layer = int(first_layer)
+        self.streams = {}               # device -> the side stream the late launches run on
+        self.event = None               # of the latest late launch, until a join finds it finished
+        self.owner = weakref.ref(owner) if owner is not None else None
+        self.encoders = weakref.WeakSet()
+        _LATE_UPDATES.add(self)
+
+    @contextlib.contextmanager
+    def launch(self, main_stream):
+        """The body runs on the side stream (yielded), behind everything ``main_stream`` has enqueued so far; its end is the event
+        the next forward waits for."""
+        side = self.streams.get(main_stream.device)
+        if side is None:
+            side = self.streams[main_stream.device] = torch.cuda.Stream(device=main_stream.device)
+        side.wait_stream(main_stream)
+        with torch.cuda.stream(side):
+            yield side
+            ev = torch.cuda.Event()
+            ev.record(side)
+        self.event = ev
+
+    def _ordered(self) -> bool:
+        # A capturing stream neither queries nor waits: step() refuses to overlap under capture, so a pending event was recorded
+        # before the capture began, and torch.cuda.graph synchronises the device before it begins one.
+        return self.event is None or torch.cuda.is_current_stream_capturing()
+
+    def wait(self, layer_index, *streams):
+        """Before encoder layer ``layer_index`` runs on ``streams`` (default: the current stream)."""
+        if layer_index != self.first_layer or self._ordered():
+            return
+        for st in (streams or (torch.cuda.current_stream(),)):
+            st.wait_event(self.event)
+
+    def join(self):
+        """The current stream is ordered behind the pending update.  A finished update is forgotten; an unfinished one stays pending,
+        other streams may still have to wait for it."""
+        if self._ordered():
+            return
+        if self.event.query():
+            self.event = None
+        else:
+            torch.cuda.current_stream().wait_event(self.event)
+
+    def attach(self, encoders):
+        """``encoders`` wait for this update from now on.  One overlapped optimizer per encoder: a record of the same owner (or of a
+        dead one) is joined and replaced, another live owner's is a ``ValueError`` (raised before anything changed)."""
+        mine = self.owner() if self.owner is not None else None
+        for enc in encoders:
+            other = enc.late_update
+            if other is not None and other.owner is not None and other.owner() not in (None, mine):
+                raise ValueError("overlap_next_forward: this encoder already waits for another optimizer's late update")
+        for enc in encoders:
+            if enc.late_update is not None:
+                enc.late_update.join()
+            enc.late_update = self
+            self.encoders.add(enc)
+
+    def detach(self):
+        self.join()
+        for enc in list(self.encoders):
+            if enc.late_update is self:
+                enc.late_update = None
+        self.encoders.clear()
+
+    def __deepcopy__(self, memo):       # a copy of the model holds other parameters: no optimizer updates them late
+        return None
 
 
 def join_late_weights():
-    """The current stream waits for the optimizer's late update (no-op when none is pending)."""
-    ev = LATE_WEIGHTS["event"]
-    if ev is not None:
-        torch.cuda.current_stream().wait_event(ev)
+    """The current stream waits for every optimizer's late update (no-op when none is pending)."""
+    for lu in list(_LATE_UPDATES):
+        lu.join()
 
 
 # XPRETRAIN_FWD_SPLIT=0: the whole batch as one chain (A/B switch for the two half-batch chains of the video tower's forward)

@@ -247,6 +247,7 @@ class CLIPEncoder(nn.Module):
         self.config = config
         self.layers = nn.ModuleList([CLIPEncoderLayer(config) for _ in range(config.num_hidden_layers)])
         self.gradient_checkpointing = False
+        self.late_update = None     # XF.LateUpdate of the optimizer that updates layers[K:] beside this forward (AdamW.overlap_next_forward)
 
     def pools_last(self, x, inputs_size, pad_mask, collect, collect_attn=None) -> bool:
         """whether ``forward(pooled_last=True)`` runs the last layer in its pooled form: the video tower on the GPU, token 0 a proxy
@@ -286,8 +287,8 @@ class CLIPEncoder(nn.Module):
                 if split is not None:       # the pooled layer reads every row of both chains
                     split.join()
                     split = None
-                if XF.LATE_WEIGHTS["event"] is not None:
-                    XF.wait_late_weights(li)
+                if self.late_update is not None:
+                    self.late_update.wait(li)
                 heads = layer.num_heads
                 if ckpt:
                     from torch.utils.checkpoint import checkpoint
@@ -297,8 +298,8 @@ class CLIPEncoder(nn.Module):
                     return checkpoint(lambda t, sd, _l=layer: XF.pooled_encoder_layer(t, _l, B, S, heads, inputs_size, sd), x, side,
                                       use_reentrant=False)
                 return XF.pooled_encoder_layer(x, layer, B, S, heads, inputs_size, side)
-            if XF.LATE_WEIGHTS["event"] is not None and x.is_cuda:      # the optimizer's overlapped update of the layers >= K (XF.LATE_WEIGHTS)
-                XF.wait_late_weights(li, *((torch.cuda.current_stream(x.device), split.stream) if split is not None else ()))
+            if self.late_update is not None:      # the optimizer's overlapped update of the layers >= K (XF.LateUpdate)
+                self.late_update.wait(li, *((torch.cuda.current_stream(x.device), split.stream) if split is not None else ()))
             if attn_in is not None:
                 attn_in.append((x, side))
             if ckpt:
@@ -601,8 +602,10 @@ class CLIPModel(CLIPPreTrainedModel):
 
     def __init__(self, config):
         super().__init__(config)
-        # parameters the optimizer may still be writing on its own stream (XF.LATE_WEIGHTS): state_dict() readers wait
+        # parameters the optimizer may still be writing on its own stream (XF.LateUpdate): state_dict() readers and load_state_dict()
+        # writers wait
         self.register_state_dict_pre_hook(lambda module, prefix, keep_vars: XF.join_late_weights())
+        self.register_load_state_dict_pre_hook(lambda module, *args: XF.join_late_weights())
         text_config, vision_config = config.text_config, config.vision_config
         additional_vision_config = getattr(config, "vision_additional_config", None)
         self.projection_dim = config.projection_dim

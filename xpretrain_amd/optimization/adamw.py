@@ -10,10 +10,12 @@ Mirrors ``src/optimization/adamw.py:11-103`` (``AdamW(params, lr, betas, eps=1e-
 * the compute-dtype copies of the weights (``functional.WEIGHTS``) are rewritten by the same kernel, so no cast
   kernels run in the next forward.
 * ``overlap_next_forward(model, first_late_layer=K)``: the update of the encoder layers >= K of both towers runs on a stream of its
-  own, behind the gradient norm, and the NEXT forward waits for it in front of layer K (``functional.LATE_WEIGHTS``): the HBM-bound
-  optimizer pass (4.5 GB at ViT-B/16 + text tower, 0.78 ms) overlaps the MFMA-bound first layers instead of standing between two
-  steps.  Same kernel, same arguments, same results; readers of those parameters outside a model forward call
-  ``functional.join_late_weights()`` (``VidCLIP.state_dict`` and ``utils.load_save`` do).
+  own, behind the gradient norm, and the NEXT forward waits for it in front of layer K (``functional.LateUpdate``, one per call,
+  attached to the model's encoders): the HBM-bound optimizer pass (4.5 GB at ViT-B/16 + text tower, 0.78 ms) overlaps the MFMA-bound
+  first layers instead of standing between two steps.  Same kernel, same arguments, same results.  Whoever else touches the late
+  parameters, their moments or their gradients before that forward calls ``functional.join_late_weights()`` first: the model's
+  ``state_dict`` and ``load_state_dict`` pre-hooks do, and so do this optimizer's ``state_dict``, ``load_state_dict``,
+  ``zero_grad(set_to_none=False)`` and ``step``.
 
 There is no eager fallback: without the HIP library the step raises.
 """
@@ -41,21 +43,30 @@ class AdamW(Optimizer):
         self.last_grad_norm = None      # device fp32 scalar after a clipped step
         self._plan = None
         self._late = None               # (ids of the late parameters, first late layer) -- overlap_next_forward()
-        self._late_stream = None
+        self._late_update = None        # functional.LateUpdate: the side stream, the pending event, the encoders that wait for it
 
     def overlap_next_forward(self, model, first_late_layer=2):
         """Run the update of ``encoder.layers[first_late_layer:]`` of the model's towers on a side stream (see the module docstring).
-        ``first_late_layer=None`` switches it off."""
+        ``first_late_layer=None`` switches it off.  One overlapped optimizer per encoder: ``ValueError`` when an encoder already
+        waits for another live optimizer; a second call replaces this optimizer's own record (after joining it)."""
+        from ..functional import LateUpdate
+        ids, encoders = set(), []
+        if first_late_layer is not None:
+            own = {id(p) for group in self.param_groups for p in group["params"]}
+            for m in model.modules():
+                layers = getattr(m, "layers", None)
+                if isinstance(layers, torch.nn.ModuleList) and type(m).__name__ == "CLIPEncoder":
+                    late = {id(p) for layer in layers[first_late_layer:] for p in layer.parameters()}
+                    ids |= late
+                    if late & own:
+                        encoders.append(m)
+        new = LateUpdate(first_late_layer, self) if ids else None
+        if new is not None:
+            new.attach(encoders)                # (raises before anything changed; takes over the encoders of this optimizer's old record)
+        if self._late_update is not None:
+            self._late_update.detach()
         self._plan = None
-        if first_late_layer is None:
-            self._late = None
-            return self
-        ids = set()
-        for m in model.modules():
-            layers = getattr(m, "layers", None)
-            if isinstance(layers, torch.nn.ModuleList) and type(m).__name__ == "CLIPEncoder":
-                for layer in layers[first_late_layer:]:
-                    ids.update(id(p) for p in layer.parameters())
+        self._late_update = new
         self._late = (frozenset(ids), int(first_late_layer)) if ids else None
         return self
 
@@ -121,6 +132,8 @@ class AdamW(Optimizer):
     # ------------------------------------------------------------------------------------------ step
     @torch.no_grad()
     def step(self, closure=None, max_grad_norm=None):
+        if self._late_update is not None:       # a previous step's late update nobody waited for (two steps without a forward) still
+            self._late_update.join()            # reads the gradients and the norm partials
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -178,8 +191,6 @@ class AdamW(Optimizer):
                 L.check(lib.xp_grad_sqnorm_partials(la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"],
                                                     la["grads"], la["n"], part.data_ptr(), stream),
                         "xp_grad_sqnorm_partials")
-        from .. import functional as XF
-        XF.join_late_weights()                      # (a previous step's late update nobody waited for: two steps without a forward)
         late = [la for la in plan["launches"] if la["late"]]
         overlap = bool(late) and not torch.cuda.is_current_stream_capturing()
         dev = plan["norm"].device
@@ -194,7 +205,16 @@ class AdamW(Optimizer):
             # first in program order: beside the early launches and whatever the main stream enqueues next.  (Launching it BEHIND the
             # early launches -- so that those run alone at full bandwidth -- measured the same: 14.385 vs 14.369 ms per step,
             # profiles/r06s_in_step_ab_optimizer_overlap_order.txt)
-            self._launch_late(plan, late, run, dev, XF)
+            # behind everything the current stream has enqueued so far (the gradients, the norm partials)
+            with self._late_update.launch(torch.cuda.current_stream(dev)) as side:
+                seen = set()
+                for la in late:
+                    for _, p, _ in la["part"]:          # the caching allocator must not hand a freed gradient to the next forward
+                        sp = p.grad.untyped_storage().data_ptr()      # while this stream still reads it (zero_grad(set_to_none=True))
+                        if sp not in seen:
+                            seen.add(sp)
+                            p.grad.record_stream(side)
+                    run(la, side.cuda_stream)
         for la in plan["launches"]:
             if not (overlap and la["late"]):
                 run(la, stream)
@@ -207,26 +227,13 @@ class AdamW(Optimizer):
         XF.join_late_weights()           # the moments of the late layers may still be in flight on the optimizer's stream
         return super().state_dict()
 
-    def _launch_late(self, plan, late, run, dev, XF):
-        """the update of the late parameters on the optimizer's own stream, behind everything the current stream has enqueued so far
-        (the gradients, the norm partials and -- when called after them -- the early launches); leaves the event the next forward
-        waits for in functional.LATE_WEIGHTS"""
-        if self._late_stream is None or self._late_stream.device != dev:
-            self._late_stream = torch.cuda.Stream(device=dev)
-        main = torch.cuda.current_stream(dev)
-        self._late_stream.wait_stream(main)
-        with torch.cuda.stream(self._late_stream):
-            seen = set()
-            for la in late:
-                for _, p, _ in la["part"]:          # the caching allocator must not hand a freed gradient to the next forward
-                    sp = p.grad.untyped_storage().data_ptr()      # while this stream still reads it (zero_grad(set_to_none=True))
-                    if sp not in seen:
-                        seen.add(sp)
-                        p.grad.record_stream(self._late_stream)
-                run(la, self._late_stream.cuda_stream)
-            ev = torch.cuda.Event()
-            ev.record(self._late_stream)
-        XF.LATE_WEIGHTS["event"], XF.LATE_WEIGHTS["first_layer"] = ev, self._late[1]
+    def zero_grad(self, set_to_none=True):
+        """``set_to_none=False`` zeroes in place, so it first joins a pending late update, which still reads the late gradients.  The
+        rule for every other writer: an in-place write to a late parameter's gradient between ``step()`` and the next forward comes
+        after ``functional.join_late_weights()``.  (A freed gradient needs no join: ``step()`` recorded it on the side stream.)"""
+        if not set_to_none and self._late_update is not None:
+            self._late_update.join()
+        super().zero_grad(set_to_none=set_to_none)
 
     def load_state_dict(self, state_dict):
         from .. import functional as XF
