@@ -339,7 +339,7 @@ int xp_cast_back(const void* src, float* dst, int64_t n, int32_t dtype, int32_t 
 #define XP_OPT_MAX_TENSORS 256
 #define XP_OPT_MAX_GROUPS 16
 typedef struct {
-  void* p; void* m; void* v;            /* fp32 parameter, exp_avg, exp_avg_sq                          */
+  void* p; void* m; void* v;            /* fp32 parameter, exp_avg, exp_avg_sq (xp_optim_step, XP_OPT_ADAMAX: exp_inf) */
   void* shadow;                         /* optional copy of p in shadow_dtype (NULL: none)              */
   int64_t numel;
   int32_t shadow_dtype;                 /* XP_BF16 / XP_F32                                             */
@@ -357,6 +357,31 @@ int xp_grad_sqnorm_partials(const XpAdamTensor* table, const int32_t* chunk_map,
 int xp_adamw_step(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                   const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                   const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
+                  int32_t n_norm_partials, float max_norm, float* grad_norm_out, void* stream);
+
+/* The other two values of the drivers' `optim` key (configs/config.py:135-137; optimization/utils.py:111-120 hands them to
+ * torch.optim.Adam / torch.optim.Adamax with the grouped parameters, lr and betas): the same multi-tensor launch, clip, shadow
+ * copies and tables as xp_adamw_step, with torch's single-tensor arithmetic (amsgrad = maximize = False); t = step count after the
+ * increment, coef = the clip coefficient or 1:
+ *     g = coef * g;  if (weight_decay != 0) g = g + weight_decay * p        coupled L2 on the CLIPPED gradient, before the moments
+ *     m = beta1 * m + (1 - beta1) * g                                       evaluated as torch's lerp: m + one_minus_beta1 * (g - m)
+ *   XP_OPT_ADAM     v = beta2 * v + (1 - beta2) * g * g
+ *                   p = p - step_size * m / (sqrt(v) / bias2_sqrt + eps)
+ *   XP_OPT_ADAMAX   u = max(beta2 * u, |g| + eps)                           eps inside the max operand; a NaN on either side stays
+ *                   p = p - step_size * m / u
+ * XpAdamTensor::v holds exp_avg_sq (Adam) or exp_inf (Adamax).  An element whose gradient is exactly 0 stays finite from the
+ * first step on (Adam: 0 / (0 + eps); Adamax: u = eps) as long as eps > 0. */
+enum XpOptKind { XP_OPT_ADAM, XP_OPT_ADAMAX };
+typedef struct {
+  float lr, beta1, beta2, eps, weight_decay;
+  float step_size;                      /* lr / (1-beta1^t)                                             */
+  float bias2_sqrt;                     /* sqrt(1-beta2^t); read by XP_OPT_ADAM only                    */
+  float one_minus_beta1;                /* 1-beta1 formed in double, then rounded: the weight torch's lerp_ gets (1 - 0.8f is not 0.2f) */
+} XpOptGroup;
+/* Arguments as for xp_adamw_step.  An unknown kind is refused before any launch. */
+int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                  const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
+                  const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
                   int32_t n_norm_partials, float max_norm, float* grad_norm_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------- Loss

@@ -6,7 +6,9 @@ loss + all gradients per call, at n = m pairs of width d (default 64 x 512: 8 GP
 `python tools/bench_kernels.py act [rounds]`: the two GEMMs that carry the MLP activation (fc1 forward with both outputs, dpre with
 fused column sums), quick_gelu (epilogue kinds 3 / 5) against erf GELU (kinds 8 / 9), interleaved.
 `python tools/bench_kernels.py probs`: xp_attn_probs (the attention weights of one layer, output_attentions) at cfg #2, bf16 and fp32
-storage: the median of individually timed launches after a warm-up, against the time its stores alone need."""
+storage: the median of individually timed launches after a warm-up, against the time its stores alone need.
+`python tools/bench_kernels.py optim [rounds]`: one optimizer step over the parameters of the cfg #2 model (ViT-B/16 + text tower) with
+AdamW, Adam and Adamax, alternating within one process; the median of `rounds` (>= 3) rounds and AdamW's own round-to-round spread."""
 import sys
 
 import torch
@@ -150,6 +152,46 @@ def bench_loss(n=64, d=512):
         print(f"loss n={n} d={d} {name:36s} {timeit(fn):8.1f} us per call (launches back to back, host call included)")
 
 
+def bench_optim(rounds=3):
+    """The update launch alone (`step()`) and with the fused clip (`clip_and_step`: the norm pass in front) per optimizer, on the cfg #2
+    parameter set in the reference's four groups, every matrix with its bf16 copy in the weight cache (rewritten in the same pass).
+    The three optimizers step the SAME parameter, gradient and state buffers (the state tensors are handed to each under its own
+    names): with buffers of their own, the same kernel ran 12 % apart on the three sets on one box and level on another."""
+    from xpretrain_amd import optimization as XO
+    from xpretrain_amd.functional import WEIGHTS
+    from xpretrain_amd.modeling import VidCLIP
+    from xpretrain_amd.workload import ModelArgs, vit_b_config
+    rounds = max(3, rounds)
+    named = [(n, tuple(p.shape)) for n, p in VidCLIP(ModelArgs(vit_b_config())).named_parameters() if p.requires_grad]
+    params = [torch.nn.Parameter(torch.randn(s, device="cuda") * 0.02) for _, s in named]
+    state = [(torch.zeros_like(p), torch.zeros_like(p)) for p in params]
+    for p in params:
+        p.grad = torch.randn_like(p) * 0.01
+        if p.ndim >= 2:
+            WEIGHTS.get(p, torch.bfloat16)
+    runs = {}
+    for name, cls, keys in (("adamw", XO.AdamW, ("exp_avg", "exp_avg_sq")), ("adam", XO.Adam, ("exp_avg", "exp_avg_sq")),
+                            ("adamax", XO.Adamax, ("exp_avg", "exp_inf"))):
+        groups = XO.build_e2e_optimizer_w_lr_mul([(n, p) for (n, _), p in zip(named, params)], 1e-6, 0.2, lr_mul=1, lr_mul_prefix="")
+        runs[name] = cls([g for g in groups if g["params"]], lr=1e-6, betas=(0.9, 0.98))
+        for p, (a, b) in zip(params, state):
+            runs[name].state[p] = {"step": 0, keys[0]: a, keys[1]: b}
+    numel = sum(p.numel() for g in runs["adamw"].param_groups for p in g["params"])
+    print(f"optimizer step, cfg #2 parameter set: {len(named)} tensors, {numel / 1e6:.1f} M elements, {numel * 30 / 1e9:.2f} GB per update pass")
+    times = {k: ([], []) for k in runs}
+    for r in range(rounds):
+        for name, opt in runs.items():
+            times[name][0].append(timeit(opt.step))
+            times[name][1].append(timeit(lambda: opt.clip_and_step(1.0)))
+            print(f"round {r} {name:6s} update {times[name][0][-1]:7.1f} us | norm + clipped update {times[name][1][-1]:7.1f} us")
+    med = {k: [sorted(v)[len(v) // 2] for v in t] for k, t in times.items()}
+    for i, what in enumerate(("update", "norm + clipped update")):
+        base = times["adamw"][i]
+        print(f"{what}: adamw median {med['adamw'][i]:.1f} us ({numel * 30 / med['adamw'][i] / 1e6:.2f} TB/s), round-to-round spread "
+              f"{(max(base) - min(base)) / med['adamw'][i] * 100:.2f} % | "
+              + " | ".join(f"{k} median {med[k][i]:.1f} us = {(med[k][i] / med['adamw'][i] - 1) * 100:+.2f} % of adamw" for k in ("adam", "adamax")))
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     if what in ("gemm", "all"):
@@ -162,6 +204,8 @@ if __name__ == "__main__":
         bench_loss(*(int(a) for a in sys.argv[2:4]))
     if what == "probs":
         bench_probs()
+    if what == "optim":
+        bench_optim(int(sys.argv[2]) if len(sys.argv) > 2 else 3)
     if what in ("ln", "all"):
         bench_ln()
     if what in ("attn", "all"):

@@ -30,6 +30,8 @@ ATTN_PROXY, ATTN_CAUSAL = 0, 1
  XP_LOSS_VIDIMG_DIVIDE) = range(8)
 # XpPairLossKind, in the header's order
 XP_PAIR_NCE, XP_PAIR_TRIPLET, XP_PAIR_HARDNEG, XP_PAIR_MILNCE = range(4)
+# XpOptKind, in the header's order
+XP_OPT_ADAM, XP_OPT_ADAMAX = range(2)
 
 i32, i64, f32, vp, sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 
@@ -140,6 +142,11 @@ class XpAdamGroup(C.Structure):
     _fields_ = [("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("step_size", f32)]
 
 
+class XpOptGroup(C.Structure):
+    _fields_ = [("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("step_size", f32),
+                ("bias2_sqrt", f32), ("one_minus_beta1", f32)]
+
+
 class XpPairLossParams(C.Structure):
     _fields_ = [("temp", f32), ("margin", f32), ("max_violation", i32), ("order_measure", i32), ("hard_negative_num", i32),
                 ("bag", i32)]
@@ -166,6 +173,8 @@ SIGNATURES = {
     "xp_layernorm_bwd_partials": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, i32, i64, i64, i32, vp, sz, vp]),
     "xp_grad_sqnorm_partials": (i32, [vp, vp, i32, C.POINTER(vp), i32, vp, vp]),
     "xp_adamw_step": (i32, [vp, vp, i32, C.POINTER(vp), C.POINTER(C.c_uint8), i32, C.POINTER(XpAdamGroup), i32, vp, i32, f32,
+                            vp, vp]),
+    "xp_optim_step": (i32, [i32, vp, vp, i32, C.POINTER(vp), C.POINTER(C.c_uint8), i32, C.POINTER(XpOptGroup), i32, vp, i32, f32,
                             vp, vp]),
     "xp_splitk_reduce": (i32, [vp, vp, i64, i32, i32, vp]),
     "xp_colsum_workspace_bytes": (sz, [i64, i64]),

@@ -1,11 +1,19 @@
-// On-device optimizer step: global gradient-norm clip + HF-style AdamW over ALL parameter tensors
-// in one multi-tensor launch, fp32 master weights, optional compute-dtype shadow copies written in the same pass.
+// On-device optimizer step: global gradient-norm clip + the update of ALL parameter tensors in one
+// multi-tensor launch, fp32 master weights, optional compute-dtype shadow copies written in the same pass.  Three updates, one
+// per value of the drivers' `optim` key (src/configs/config.py:135-137, src/optimization/utils.py:111-120):
 //
-// Restates  src/optimization/adamw.py:40-103  (AdamW.step: m/v update, denom = sqrt(v) + eps, bias-corrected step size,
-// decoupled weight decay AFTER the Adam update with the group's lr) and torch.nn.utils.clip_grad_norm_ as called by the
-// training loops (run_video_retrieval.py:390-392): coef = min(1, max_norm / (||g||_2 + 1e-6)).
+//   adamw_kernel             restates  src/optimization/adamw.py:40-103  (AdamW.step: m/v update, denom = sqrt(v) + eps,
+//                            bias-corrected step size, decoupled weight decay AFTER the Adam update with the group's lr)
+//   opt_kernel<XP_OPT_ADAM>    torch.optim.Adam   as utils.py:119 builds it (single-tensor path, amsgrad = maximize = False)
+//   opt_kernel<XP_OPT_ADAMAX>  torch.optim.Adamax likewise
+//     both: coupled L2 decay added to the CLIPPED gradient before the moments; the bias corrections applied where torch applies
+//     them (Adam: sqrt(v) / sqrt(1-b2^t) + eps; Adamax: eps inside the max operand) -- see opt1 below
 //
-// HBM-bound: per element 16 B read (p, g, m, v) + 12 B written (p, m, v) + 2 B shadow; the norm pass reads g once more.
+// and torch.nn.utils.clip_grad_norm_ as called by the training loops (run_video_retrieval.py:390-392):
+// coef = min(1, max_norm / (||g||_2 + 1e-6)).
+//
+// HBM-bound: per element 16 B read (p, g, m, v) + 12 B written (p, m, v) + 2 B shadow, the same for all three; the norm pass reads
+// g once more.
 // Work decomposition: fixed 64 Ki-element CHUNKS of one tensor per workgroup (chunk map built once on the host side of
 // the ABI); the gradient pointers, which change every step, travel in the kernel argument block, everything static
 // lives in a device table.  All reductions are fixed-order (deterministic): per-chunk partial sums of squares, and
@@ -129,6 +137,103 @@ __global__ __launch_bounds__(NT) void adamw_kernel(const XpAdamTensor* __restric
   }
 }
 
+// ---------------------------------------------------------------------------------------------- Adam / Adamax (xp_optim_step)
+struct OptArgs {
+  const float* g[MAXT];
+  unsigned char grp[MAXT];
+  XpOptGroup groups[MAXG];
+};
+
+// One element of torch.optim.Adam / Adamax (torch/optim/adam.py::_single_tensor_adam, adamax.py::_single_tensor_adamax).  Every
+// rounding point is written out, as in adam1.  The form chosen:
+//   decay       one fma(wd, p, g)                                  (torch: add with alpha)
+//   exp_avg     torch's lerp_, m + w * (g - m), as fma(w, [g - m], m) with w = 1-b1 formed in double on the host, as torch forms it.
+//               NOT adam1's fma(b1, m, [(1-b1)*g]) with 1-b1 in fp32: 1 - 0.8f is not 0.2f, and over 8 steps that bias alone put
+//               exp_avg 4.6 x torch's own fp32 error away from fp64 torch (lerp with the fp32 difference: 3.1 x; this form: 1.3 x;
+//               the unclipped eps = 1e-3 case of tests/test_optim_family_gpu.py: the first figure from a CPU emulation of the
+//               kernel's arithmetic, the other two on the MI355X)
+//   exp_avg_sq  adam1's fma(b2, v, [g * ((1-b2)*g)])               (torch: mul_ then addcmul_)
+//   denominator torch's own rounding points: sqrt, correctly rounded division by sqrt(1-b2^t), then + eps
+//   parameter   fma(-step_size, [m / denom], p)                    (torch: addcdiv_)
+// Adamax's maximum keeps a NaN from either operand, as torch's amax does (fmaxf would drop it).
+template <int KIND>
+__device__ __forceinline__ void opt1(float& p, float g, float& m, float& v, const XpOptGroup& h, float coef) {
+#pragma clang fp contract(off)
+  g = g * coef;
+  if (h.weight_decay != 0.f) g = __builtin_fmaf(h.weight_decay, p, g);
+  m = __builtin_fmaf(h.one_minus_beta1, g - m, m);
+  float denom;
+  if (KIND == XP_OPT_ADAM) {
+    v = __builtin_fmaf(h.beta2, v, g * ((1.0f - h.beta2) * g));
+    denom = sqrtf(v) / h.bias2_sqrt + h.eps;
+  } else {
+    const float a = h.beta2 * v, b = fabsf(g) + h.eps;
+    v = (a >= b || a != a) ? a : b;
+    denom = v;
+  }
+  p = __builtin_fmaf(-h.step_size, m / denom, p);
+}
+
+// adamw_kernel's decomposition with opt1 in place of adam1.  A copy, not a shared template: adamw_kernel's generated code is pinned
+// (byte-identical section of build/optim.s), and routing it through a template both kernels call, same arithmetic, renamed its
+// registers and moved three instructions.
+template <int KIND>
+__global__ __launch_bounds__(NT) void opt_kernel(const XpAdamTensor* __restrict__ table,
+                                                 const int32_t* __restrict__ chunk_map, OptArgs a,
+                                                 const float* __restrict__ partials, int n_partials, float max_norm,
+                                                 float* __restrict__ norm_out) {
+  float coef = 1.0f;
+  if (partials != nullptr) {
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n_partials; i += NT) s += partials[i];
+    const float norm = sqrtf(block_sum(s));
+    if (max_norm > 0.f) { const float c = max_norm / (norm + 1e-6f); coef = c < 1.0f ? c : 1.0f; }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+  }
+  const int t = chunk_map[2 * blockIdx.x], c = chunk_map[2 * blockIdx.x + 1];
+  const XpAdamTensor tt = table[t];
+  const XpOptGroup h = a.groups[a.grp[t]];
+  const int64_t beg = (int64_t)c * CHUNK;
+  const int64_t len = tt.numel - beg < CHUNK ? tt.numel - beg : CHUNK;
+  float* p = reinterpret_cast<float*>(tt.p) + beg;
+  float* m = reinterpret_cast<float*>(tt.m) + beg;
+  float* v = reinterpret_cast<float*>(tt.v) + beg;
+  const float* g = a.g[t] + beg;
+  bf16_t* sb = tt.shadow && tt.shadow_dtype == XP_BF16 ? reinterpret_cast<bf16_t*>(tt.shadow) + beg : nullptr;
+  float* sf = tt.shadow && tt.shadow_dtype == XP_F32 ? reinterpret_cast<float*>(tt.shadow) + beg : nullptr;
+  const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                          reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(sf) |
+                          (reinterpret_cast<uintptr_t>(sb) << 1);
+  int64_t done = 0;
+  if ((align & 15) == 0) {
+    const int64_t n4 = len >> 2;
+    for (int64_t i = threadIdx.x; i < n4; i += NT) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + 4 * i), mm = *reinterpret_cast<f32x4*>(m + 4 * i),
+            vv = *reinterpret_cast<f32x4*>(v + 4 * i);
+      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        opt1<KIND>(pe, gg[e], me, ve, h, coef);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
+      *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
+      *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
+      if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
+      if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + threadIdx.x; i < len; i += NT) {
+    float pp = p[i], mm = m[i], vv = v[i];
+    opt1<KIND>(pp, g[i], mm, vv, h, coef);
+    p[i] = pp; m[i] = mm; v[i] = vv;
+    if (sb) sb[i] = (bf16_t)pp;
+    if (sf) sf[i] = pp;
+  }
+}
+
 }  // namespace
 
 extern "C" int xp_grad_sqnorm_partials(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
@@ -168,5 +273,36 @@ extern "C" int xp_adamw_step(const XpAdamTensor* table, const int32_t* chunk_map
   adamw_kernel<<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials, max_norm,
                                                          grad_norm_out);
   XP_CHECK_LAUNCH("xp_adamw_step");
+  return XP_OK;
+}
+
+extern "C" int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                             const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
+                             const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
+                             int32_t n_norm_partials, float max_norm, float* grad_norm_out, void* stream) {
+  XP_REQUIRE(kind == XP_OPT_ADAM || kind == XP_OPT_ADAMAX, "xp_optim_step: unknown kind %d (XP_OPT_ADAM = %d, XP_OPT_ADAMAX = %d)",
+             kind, (int)XP_OPT_ADAM, (int)XP_OPT_ADAMAX);
+  XP_REQUIRE(table && chunk_map && grads_host && group_of_host && groups_host && n_chunks > 0, "xp_optim_step: null argument");
+  XP_REQUIRE(n_tensors > 0 && n_tensors <= MAXT, "xp_optim_step: n_tensors=%d not in 1..%d", n_tensors, MAXT);
+  XP_REQUIRE(n_groups > 0 && n_groups <= MAXG, "xp_optim_step: n_groups=%d not in 1..%d", n_groups, MAXG);
+  XP_REQUIRE(norm_partials || max_norm <= 0.f, "xp_optim_step: max_norm > 0 needs the gradient-norm partials");
+  XP_REQUIRE(!norm_partials || n_norm_partials > 0, "xp_optim_step: n_norm_partials must be positive");
+  OptArgs a;
+  for (int i = 0; i < MAXT; ++i) { a.g[i] = nullptr; a.grp[i] = 0; }
+  for (int i = 0; i < n_tensors; ++i) {
+    XP_REQUIRE(grads_host[i], "xp_optim_step: gradient %d is null", i);
+    XP_REQUIRE(group_of_host[i] < n_groups, "xp_optim_step: tensor %d has group %d >= %d", i, group_of_host[i], n_groups);
+    a.g[i] = reinterpret_cast<const float*>(grads_host[i]);
+    a.grp[i] = group_of_host[i];
+  }
+  for (int i = 0; i < n_groups; ++i) a.groups[i] = groups_host[i];
+  for (int i = n_groups; i < MAXG; ++i) a.groups[i] = groups_host[0];
+  if (kind == XP_OPT_ADAM)
+    opt_kernel<XP_OPT_ADAM><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials,
+                                                                      max_norm, grad_norm_out);
+  else
+    opt_kernel<XP_OPT_ADAMAX><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials,
+                                                                        max_norm, grad_norm_out);
+  XP_CHECK_LAUNCH("xp_optim_step");
   return XP_OK;
 }

@@ -2,8 +2,10 @@
 
 Mirrors ``src/optimization/utils.py``: ``build_e2e_optimizer_w_lr_mul`` :124-154 (four groups: {lr_mul prefix, rest} x
 {decay, no-decay}; no-decay = names containing ``bias`` / ``LayerNorm.bias`` / ``LayerNorm.weight`` / ``logit_scale``)
-and ``setup_e2e_optimizer`` :91-121 with ``optim == "adamw"`` (the only optimizer the CLIP-ViP configs use).
+and ``setup_e2e_optimizer`` :96-121 for the three values of ``optim`` the command line takes (``configs/config.py:135-137``;
+the CLIP-ViP configs use ``"adamw"``).
 """
+from .adam import Adam, Adamax
 from .adamw import AdamW
 
 NO_DECAY = ("bias", "LayerNorm.bias", "LayerNorm.weight", "logit_scale")
@@ -28,8 +30,15 @@ def build_e2e_optimizer_w_lr_mul(model_param_optimizer, learning_rate, weight_de
 
 
 def setup_e2e_optimizer(model, opts):
-    if getattr(opts, "optim", "adamw") != "adamw":
-        raise ValueError("invalid optimizer")     # adam / adamax of the reference are not on the CLIP-ViP path
     groups = build_e2e_optimizer_w_lr_mul(list(model.named_parameters()), opts.learning_rate, opts.weight_decay,
                                           lr_mul=opts.lr_mul, lr_mul_prefix=opts.lr_mul_prefix)
-    return AdamW(groups, lr=opts.learning_rate, betas=tuple(opts.betas))
+    optim = getattr(opts, "optim", "adamw")
+    if optim == "adam":                           # :111-118
+        OptimCls = Adam
+    elif optim == "adamax":
+        OptimCls = Adamax
+    elif optim == "adamw":
+        OptimCls = AdamW
+    else:
+        raise ValueError("invalid optimizer")
+    return OptimCls(groups, lr=opts.learning_rate, betas=tuple(opts.betas))
