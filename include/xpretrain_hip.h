@@ -294,6 +294,36 @@ int xp_im2col(const float* video, void* patches, int64_t BT, int64_t H, int64_t 
  * float[3]. */
 int xp_im2col_u8(const uint8_t* frames, const float* mean3_host, const float* std3_host, void* patches, int64_t BT,
                  int64_t H, int64_t W, int64_t P, int32_t dtype, void* stream);
+/* Raw decoded uint8 frames of ANY source resolution -> the fp32 model input, in one launch for a batch of videos: the CPU-worker
+ * arithmetic of both dataset classes (datasets/dataset_video_retrieval.py:102-105: `.permute(0, 3, 1, 2).float() / 255.`, then
+ * init_transform_dict_simple, datasets/dataloader.py:209-233: Resize(input_res, BICUBIC), CenterCrop(input_res), Normalize) on the
+ * float image: bicubic overshoot outside [0, 1] is kept, nothing is re-quantised, no antialias filter (the reference's torch
+ * predates it).  Each video has its own resolution and memory layout; out is fp32 [sum of T, 3, oh, ow], contiguous, in video
+ * order, every element written and nothing else.  For output pixel (y, x) of a frame, X = flip ? ow-1-x : x:
+ *     ry = top + y, rx = left + X                                     coordinates in the (never materialised) resized box
+ *     sy = (ry + 0.5) * box_h / rh - 0.5;  iy = floor(sy), t = sy - iy   formed from the exact rational ((2 ry + 1) box_h - rh) / (2 rh)
+ *     taps iy-1 .. iy+2, each clamped to [0, box_h-1], then + box_y;  Keys cubic-convolution weights, A = -0.75;  the same in x
+ *     v = sum_j wy[j] * (sum_i wx[i] * u8[tap_y j][tap_x i])          fp32, the row sums first, fixed order: bit-reproducible
+ *     out = (v / 255 - mean[c]) / std[c]
+ * i.e. F.interpolate(box / 255, size=(rh, rw), mode="bicubic", align_corners=False)[top:top+oh, left:left+ow], normalised.
+ * The descriptor table, mean and std are HOST arrays (copied into the kernel-argument block, so a call takes at most
+ * XP_FRAMES_MAX_VIDEOS videos; callers with more issue several calls).  Refused before any launch, naming the argument: a null
+ * pointer, n_videos outside [1, XP_FRAMES_MAX_VIDEOS], a non-positive size, a size above XP_FRAMES_MAX_SIZE, a box outside the
+ * image, a window outside the resized image (there is no padding path), std <= 0, and a descriptor one of whose taps lies in
+ * front of `src` or at or beyond `src + src_bytes`. */
+#define XP_FRAMES_MAX_VIDEOS 32
+#define XP_FRAMES_MAX_SIZE 16384              /* H, W, rh, rw, oh, ow: keeps (2 r + 1) * box inside int32 */
+typedef struct {
+  const uint8_t* src; int64_t src_bytes;        /* first byte of frame 0; extent of the allocation from there   */
+  int64_t stride_t, stride_y, stride_x, stride_c; /* bytes: THWC, TCHW and sliced views are all just strides   */
+  int32_t T, H, W;                              /* frames, source size                                          */
+  int32_t box_y, box_x, box_h, box_w;           /* source region that is resized; taps clamp to ITS edges        */
+  int32_t rh, rw;                               /* size of the (never materialised) resized image of the box     */
+  int32_t top, left;                            /* where the oh x ow output window sits in the resized image     */
+  int32_t flip;                                 /* != 0: output column x shows resized column left + ow-1-x      */
+} XpFrameSrc;
+int xp_frames_resize_norm(const XpFrameSrc* videos_host, int32_t n_videos, const float* mean3_host,
+                          const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream);
 /* proxy rows: x[b, 0] = class_emb + pos[0]; x[b, 1+i] = added_cls[i] + pos[0]   (:187-191) */
 int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const float* pos, void* x,
                       int64_t B, int64_t S, int64_t M, int64_t D, int32_t dtype, void* stream);

@@ -154,6 +154,15 @@ class XpPairLossParams(C.Structure):
 
 XP_OPT_CHUNK, XP_OPT_MAX_TENSORS, XP_OPT_MAX_GROUPS = 65536, 256, 16
 
+
+class XpFrameSrc(C.Structure):
+    _fields_ = [("src", vp), ("src_bytes", i64), ("stride_t", i64), ("stride_y", i64), ("stride_x", i64), ("stride_c", i64),
+                ("T", i32), ("H", i32), ("W", i32), ("box_y", i32), ("box_x", i32), ("box_h", i32), ("box_w", i32),
+                ("rh", i32), ("rw", i32), ("top", i32), ("left", i32), ("flip", i32)]
+
+
+XP_FRAMES_MAX_VIDEOS, XP_FRAMES_MAX_SIZE = 32, 16384
+
 # name -> (restype, argtypes); mirrors include/xpretrain_hip.h one-to-one
 SIGNATURES = {
     "xp_abi_version": (i32, []),
@@ -202,6 +211,7 @@ SIGNATURES = {
     "xp_attn_pooled_bwd": (i32, [vp, vp, i64, vp, vp, vp, vp, i64, vp, i64, f32, i64, i64, i64, i32, vp, sz, vp, vp]),
     "xp_im2col": (i32, [vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_im2col_u8": (i32, [vp, C.POINTER(f32), C.POINTER(f32), vp, i64, i64, i64, i64, i32, vp]),
+    "xp_frames_resize_norm": (i32, [C.POINTER(XpFrameSrc), i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp]),
     "xp_vip_proxy_rows": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_vip_embed_bwd_workspace_bytes": (sz, [i64, i64, i64, i64]),
     "xp_vip_embed_bwd": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, i32, vp, sz, vp]),

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -358,6 +358,66 @@ def im2col_u8(frames: torch.Tensor, P: int, dtype, mean=CLIP_MEAN, std=CLIP_STD)
     m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     L.check(L.lib().xp_im2col_u8(_p(frames), m, sd, _p(out), BT, H, W, P, _DT[dtype], _stream()), "xp_im2col_u8")
     return out
+
+
+class FrameGeometry(NamedTuple):
+    """XpFrameSrc's geometry fields: the source box that is resized, the size of its (never materialised) resized image, where
+    the output window sits in that image, and the horizontal flip"""
+    box_y: int
+    box_x: int
+    box_h: int
+    box_w: int
+    rh: int
+    rw: int
+    top: int = 0
+    left: int = 0
+    flip: int = 0
+
+
+def frames_resize_norm(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=CLIP_STD, out=None) -> torch.Tensor:
+    """Decoded uint8 videos -> normalised fp32 frames [sum of T, 3, oh, ow] in video order: bicubic resize of each video's box,
+    window, flip, /255, (x - mean) / std (include/xpretrain_hip.h: xp_frames_resize_norm).  ``videos``: uint8 GPU tensors indexed
+    [T, H, W, 3] with ANY strides (the decoder's THWC, a ``permute``d TCHW tensor, a sliced view); ``geometry``: one FrameGeometry
+    (or any object with its fields) per video, or a single one for all.  Strides and the readable extent come from each tensor's
+    storage; batches beyond XP_FRAMES_MAX_VIDEOS are split into several launches."""
+    videos = list(videos)
+    geometry = [geometry] * len(videos) if hasattr(geometry, "box_y") else list(geometry)
+    if not videos or len(geometry) != len(videos):
+        raise ValueError(f"frames_resize_norm: {len(videos)} videos with {len(geometry)} geometries")
+    for v in videos:
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or not v.is_cuda:
+            raise TypeError("frames_resize_norm: every video must be a uint8 tensor on the GPU (no CPU path)")
+        if v.dim() != 4 or v.shape[3] != 3:
+            raise ValueError(f"frames_resize_norm: a video must be indexed [T, H, W, 3], got {tuple(v.shape)}")
+    frames = sum(v.shape[0] for v in videos)
+    if out is None:
+        out = torch.empty((frames, 3, oh, ow), dtype=torch.float32, device=videos[0].device)
+    else:
+        _chk(out, "out", torch.float32)
+        if tuple(out.shape) != (frames, 3, oh, ow) or not out.is_contiguous():
+            raise ValueError(f"frames_resize_norm: out must be a contiguous [{frames}, 3, {oh}, {ow}] tensor")
+    m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    done = 0
+    for lo in range(0, len(videos), L.XP_FRAMES_MAX_VIDEOS):
+        part = videos[lo:lo + L.XP_FRAMES_MAX_VIDEOS]
+        tab = frame_table(part, geometry[lo:])
+        L.check(L.lib().xp_frames_resize_norm(tab, len(part), m, sd, C.c_void_p(out.data_ptr() + done * 3 * oh * ow * 4), oh, ow,
+                                              _stream()), "xp_frames_resize_norm")
+        done += sum(v.shape[0] for v in part)
+    return out
+
+
+def frame_table(videos, geometry):
+    """the XpFrameSrc array of one xp_frames_resize_norm call: pointer, byte strides and readable extent of each [T, H, W, 3]-indexed
+    uint8 tensor, with its geometry"""
+    tab = (L.XpFrameSrc * len(videos))()
+    for d, v, g in zip(tab, videos, geometry):
+        d.src, d.src_bytes = v.data_ptr(), v.untyped_storage().nbytes() - v.storage_offset()
+        d.stride_t, d.stride_y, d.stride_x, d.stride_c = v.stride()
+        d.T, d.H, d.W = v.shape[:3]
+        d.box_y, d.box_x, d.box_h, d.box_w = g.box_y, g.box_x, g.box_h, g.box_w
+        d.rh, d.rw, d.top, d.left, d.flip = g.rh, g.rw, g.top, g.left, int(bool(g.flip))
+    return tab
 
 
 def vip_proxy_rows(class_emb, added_cls, pos, x, B, S, M, D):

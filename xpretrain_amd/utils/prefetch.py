@@ -8,7 +8,11 @@ the text tower on -- the step then touches no more HIP streams than it does with
 the runtime maps streams onto shared hardware queues and the step's overlap degrades); the copy of batch i+1 is then enqueued right
 behind the text tower's forward of step i (``CLIPModel.defer_to_text_stream``), where that stream idles until the backward.
 ``stream="auto"``: the text tower's stream when a process group with more than one rank exists (its collectives already own a
-stream), a stream of the loader's own otherwise.  Measured: profiles/r05g_prefetch_stream_environment.txt."""
+stream), a stream of the loader's own otherwise.  Measured: profiles/r05g_prefetch_stream_environment.txt.
+
+``frame_transform=`` (a ``utils.transforms.FrameTransform``): raw decoded uint8 frames of any resolution under ``frame_keys`` are resized,
+cropped and normalised on the copy stream right behind their copies, and ``next()`` hands over the fp32 batch ``VidCLIP.forward(**batch)``
+takes; without it the class does exactly what it did."""
 import torch
 
 
@@ -35,10 +39,22 @@ def record_cuda_stream(batch):
     _map(batch, lambda t: (t.record_stream(cur), t)[1] if t.is_cuda else t)
 
 
+def _is_u8_frames(entry):
+    if isinstance(entry, torch.Tensor):
+        return entry.dtype == torch.uint8
+    return isinstance(entry, (list, tuple)) and len(entry) > 0 and all(isinstance(t, torch.Tensor) and t.dtype == torch.uint8 for t in entry)
+
+
 class PrefetchLoader(object):
-    def __init__(self, loader, img_normalize=None, stream=None):
+    def __init__(self, loader, img_normalize=None, stream=None, frame_transform=None, frame_keys=("video", "image")):
         self.loader = loader
         self.img_normalize = img_normalize
+        # utils.transforms.FrameTransform: the decoded uint8 frames under `frame_keys` (a tensor, or a list of per-video tensors
+        # when the resolutions of a batch differ) become the model's fp32 pixel_values on the copy stream, right behind their
+        # copies.  The raw device buffers are allocated, read and dropped inside that one stream's context, so the caching
+        # allocator reuses them in stream order and only the fp32 result is handed over (wait_stream + record_stream, as before).
+        self.frame_transform = frame_transform
+        self.frame_keys = tuple(frame_keys)
         self._stream_arg = stream
         self.stream = None
         self._defer = None          # set with the text tower's stream: enqueue the next copy behind the tower's forward
@@ -89,9 +105,17 @@ class PrefetchLoader(object):
             return
         with torch.cuda.stream(self._copy_stream()):
             if isinstance(self.batch, tuple) and len(self.batch) == 2 and isinstance(self.batch[0], str):     # (task, batch) of MetaLoader
-                self.batch = (self.batch[0], move_to_cuda(self.batch[1]))
+                self.batch = (self.batch[0], self._transform_frames(move_to_cuda(self.batch[1])))
             else:
-                self.batch = move_to_cuda(self.batch)
+                self.batch = self._transform_frames(move_to_cuda(self.batch))
+
+    def _transform_frames(self, batch):
+        """(inside the copy stream's context, on the device copy ``move_to_cuda`` made: the loader's own batch is not touched)"""
+        if self.frame_transform is not None and isinstance(batch, dict):
+            for k in self.frame_keys:
+                if k in batch and _is_u8_frames(batch[k]):
+                    batch[k] = self.frame_transform(batch[k])
+        return batch
 
     @staticmethod
     def _data_parallel():
