@@ -324,6 +324,47 @@ typedef struct {
 } XpFrameSrc;
 int xp_frames_resize_norm(const XpFrameSrc* videos_host, int32_t n_videos, const float* mean3_host,
                           const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream);
+/* The same launch with a choice of filter and an optional colour stage: the other two transform factories of the reference
+ * (datasets/dataloader.py:180-207 init_transform_dict, :235-260 init_transform_dict_image).  xp_frames_resize_norm is untouched;
+ * with XP_FRAMES_FILTER_BICUBIC and n_color = 0 this entry point returns its bits.
+ *   filter XP_FRAMES_FILTER_BICUBIC    src.* read as above: RandomResizedCrop(BICUBIC) is box = the drawn crop, (rh, rw) = the output
+ *                                      size, RandomHorizontalFlip is src.flip.  mid_*, crop_* are ignored.
+ *   filter XP_FRAMES_FILTER_BILINEAR2  Resize(video_res), CenterCrop, Resize(input_res), all bilinear, without an intermediate image:
+ *       the box is resized to mid_h x mid_w, the crop_h x crop_w window at (crop_y, crop_x) of THAT image is resized to rh x rw, and
+ *       the output is the oh x ow window at (top, left) of the result.  Per axis, for resized coordinate r:
+ *           s2 = max(0, ((2 r + 1) crop - out) / (2 out));  i = floor(s2), l2 = s2 - i;  m0 = crop0 + i, m1 = crop0 + min(i + 1, crop - 1)
+ *           for m in (m0, m1): s1 = max(0, ((2 m + 1) box - mid) / (2 mid));  j = floor(s1), l1 = s1 - j;  taps box0 + j, box0 + min(j + 1, box - 1)
+ *       (floor and fraction from integer division of the exact rational, as for the cubic) -- four taps per axis with the product
+ *       weights (1-l2)(1-l1), (1-l2) l1, l2 (1-l1'), l2 l1': F.interpolate(mode="bilinear", align_corners=False) twice with the crop
+ *       between, no antialias.  Accumulated exactly like the cubic: row sums first, fixed order.
+ *   colour stage, n_color = 0 .. 3 ops applied in the order of color_op[] to x = v / 255 (overshoot kept up to here), before Normalize;
+ *   torchvision's tensor backend (ColorJitter without contrast):
+ *       XP_FRAMES_COLOR_BRIGHTNESS  x = clamp(f x, 0, 1)
+ *       XP_FRAMES_COLOR_SATURATION  x = clamp(f x + (1 - f) gray, 0, 1),  gray = 0.2989 r + 0.587 g + 0.114 b
+ *       XP_FRAMES_COLOR_HUE         x = hsv2rgb(h + f mod 1, s, v) of (h, s, v) = rgb2hsv(clamp(x, 0, 1)), |f| <= 0.5.  The clamp in front
+ *                                   is this library's: torchvision's _rgb2hsv divides by maxc, which bicubic overshoot can make <= 0
+ *                                   (a non-finite pixel); on in-range input the clamp is the identity.
+ *       color_factor[k] belongs to color_op[k].  An op kind may appear once.
+ * Calling rules and refusals are xp_frames_resize_norm's (at most XP_FRAMES_TRANSFORM_MAX_VIDEOS videos a call: the descriptor is
+ * larger; the videos of one call share one filter, their colour stages may differ); in addition: an unknown filter, a filter that
+ * differs from video 0's, a stage-1 size outside [1, XP_FRAMES_MAX_SIZE], a crop window outside the stage-1 image,
+ * n_color outside [0, 3], an unknown or repeated colour op, a negative or non-finite brightness / saturation factor, a hue factor
+ * outside [-0.5, 0.5]. */
+#define XP_FRAMES_TRANSFORM_MAX_VIDEOS 24     /* 24 x (152 + 4) bytes of table in the 4 KiB kernel-argument block */
+enum { XP_FRAMES_FILTER_BICUBIC = 0, XP_FRAMES_FILTER_BILINEAR2 = 1 };
+/* (torchvision's ColorJitter op indices; 1 is contrast, which the reference never sets and this library does not provide) */
+enum { XP_FRAMES_COLOR_BRIGHTNESS = 0, XP_FRAMES_COLOR_SATURATION = 2, XP_FRAMES_COLOR_HUE = 3 };
+typedef struct {
+  XpFrameSrc src;
+  int32_t filter;                               /* XP_FRAMES_FILTER_*                                            */
+  int32_t mid_h, mid_w;                         /* BILINEAR2: size of the (never materialised) stage-1 image     */
+  int32_t crop_y, crop_x, crop_h, crop_w;       /* BILINEAR2: the window of the stage-1 image stage 2 resizes    */
+  int32_t n_color;                              /* colour ops, 0 .. 3                                            */
+  int32_t color_op[3];                          /* XP_FRAMES_COLOR_*, in the order of application                */
+  float color_factor[3];                        /* the factor of color_op[k]                                     */
+} XpFrameTransform;
+int xp_frames_transform(const XpFrameTransform* videos_host, int32_t n_videos, const float* mean3_host,
+                        const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream);
 /* proxy rows: x[b, 0] = class_emb + pos[0]; x[b, 1+i] = added_cls[i] + pos[0]   (:187-191) */
 int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const float* pos, void* x,
                       int64_t B, int64_t S, int64_t M, int64_t D, int32_t dtype, void* stream);

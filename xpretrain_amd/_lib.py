@@ -163,6 +163,17 @@ class XpFrameSrc(C.Structure):
 
 XP_FRAMES_MAX_VIDEOS, XP_FRAMES_MAX_SIZE = 32, 16384
 
+
+class XpFrameTransform(C.Structure):
+    _fields_ = [("src", XpFrameSrc), ("filter", i32), ("mid_h", i32), ("mid_w", i32), ("crop_y", i32), ("crop_x", i32),
+                ("crop_h", i32), ("crop_w", i32), ("n_color", i32), ("color_op", i32 * 3), ("color_factor", f32 * 3)]
+
+
+XP_FRAMES_TRANSFORM_MAX_VIDEOS = 24
+XP_FRAMES_FILTER_BICUBIC, XP_FRAMES_FILTER_BILINEAR2 = 0, 1
+# torchvision's ColorJitter op indices (1 would be contrast: not provided)
+XP_FRAMES_COLOR_BRIGHTNESS, XP_FRAMES_COLOR_SATURATION, XP_FRAMES_COLOR_HUE = 0, 2, 3
+
 # name -> (restype, argtypes); mirrors include/xpretrain_hip.h one-to-one
 SIGNATURES = {
     "xp_abi_version": (i32, []),
@@ -212,6 +223,7 @@ SIGNATURES = {
     "xp_im2col": (i32, [vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_im2col_u8": (i32, [vp, C.POINTER(f32), C.POINTER(f32), vp, i64, i64, i64, i64, i32, vp]),
     "xp_frames_resize_norm": (i32, [C.POINTER(XpFrameSrc), i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp]),
+    "xp_frames_transform": (i32, [C.POINTER(XpFrameTransform), i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp]),
     "xp_vip_proxy_rows": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_vip_embed_bwd_workspace_bytes": (sz, [i64, i64, i64, i64]),
     "xp_vip_embed_bwd": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, i32, vp, sz, vp]),

@@ -374,28 +374,34 @@ class FrameGeometry(NamedTuple):
     flip: int = 0
 
 
-def frames_resize_norm(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=CLIP_STD, out=None) -> torch.Tensor:
-    """Decoded uint8 videos -> normalised fp32 frames [sum of T, 3, oh, ow] in video order: bicubic resize of each video's box,
-    window, flip, /255, (x - mean) / std (include/xpretrain_hip.h: xp_frames_resize_norm).  ``videos``: uint8 GPU tensors indexed
-    [T, H, W, 3] with ANY strides (the decoder's THWC, a ``permute``d TCHW tensor, a sliced view); ``geometry``: one FrameGeometry
-    (or any object with its fields) per video, or a single one for all.  Strides and the readable extent come from each tensor's
-    storage; batches beyond XP_FRAMES_MAX_VIDEOS are split into several launches."""
+def _frames_args(what, videos, geometry, oh, ow, out):
+    """the argument checks frames_resize_norm and frames_transform share: (videos, geometry per video, frames, out)"""
     videos = list(videos)
     geometry = [geometry] * len(videos) if hasattr(geometry, "box_y") else list(geometry)
     if not videos or len(geometry) != len(videos):
-        raise ValueError(f"frames_resize_norm: {len(videos)} videos with {len(geometry)} geometries")
+        raise ValueError(f"{what}: {len(videos)} videos with {len(geometry)} geometries")
     for v in videos:
         if not isinstance(v, torch.Tensor) or v.dtype != torch.uint8 or not v.is_cuda:
-            raise TypeError("frames_resize_norm: every video must be a uint8 tensor on the GPU (no CPU path)")
+            raise TypeError(f"{what}: every video must be a uint8 tensor on the GPU (no CPU path)")
         if v.dim() != 4 or v.shape[3] != 3:
-            raise ValueError(f"frames_resize_norm: a video must be indexed [T, H, W, 3], got {tuple(v.shape)}")
+            raise ValueError(f"{what}: a video must be indexed [T, H, W, 3], got {tuple(v.shape)}")
     frames = sum(v.shape[0] for v in videos)
     if out is None:
         out = torch.empty((frames, 3, oh, ow), dtype=torch.float32, device=videos[0].device)
     else:
         _chk(out, "out", torch.float32)
         if tuple(out.shape) != (frames, 3, oh, ow) or not out.is_contiguous():
-            raise ValueError(f"frames_resize_norm: out must be a contiguous [{frames}, 3, {oh}, {ow}] tensor")
+            raise ValueError(f"{what}: out must be a contiguous [{frames}, 3, {oh}, {ow}] tensor")
+    return videos, geometry, out
+
+
+def frames_resize_norm(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=CLIP_STD, out=None) -> torch.Tensor:
+    """Decoded uint8 videos -> normalised fp32 frames [sum of T, 3, oh, ow] in video order: bicubic resize of each video's box,
+    window, flip, /255, (x - mean) / std (include/xpretrain_hip.h: xp_frames_resize_norm).  ``videos``: uint8 GPU tensors indexed
+    [T, H, W, 3] with ANY strides (the decoder's THWC, a ``permute``d TCHW tensor, a sliced view); ``geometry``: one FrameGeometry
+    (or any object with its fields) per video, or a single one for all.  Strides and the readable extent come from each tensor's
+    storage; batches beyond XP_FRAMES_MAX_VIDEOS are split into several launches."""
+    videos, geometry, out = _frames_args("frames_resize_norm", videos, geometry, oh, ow, out)
     m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     done = 0
     for lo in range(0, len(videos), L.XP_FRAMES_MAX_VIDEOS):
@@ -407,16 +413,83 @@ def frames_resize_norm(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=C
     return out
 
 
+def _fill_frame_src(d, v, g):
+    d.src, d.src_bytes = v.data_ptr(), v.untyped_storage().nbytes() - v.storage_offset()
+    d.stride_t, d.stride_y, d.stride_x, d.stride_c = v.stride()
+    d.T, d.H, d.W = v.shape[:3]
+    d.box_y, d.box_x, d.box_h, d.box_w = g.box_y, g.box_x, g.box_h, g.box_w
+    d.rh, d.rw, d.top, d.left, d.flip = g.rh, g.rw, g.top, g.left, int(bool(g.flip))
+
+
 def frame_table(videos, geometry):
     """the XpFrameSrc array of one xp_frames_resize_norm call: pointer, byte strides and readable extent of each [T, H, W, 3]-indexed
     uint8 tensor, with its geometry"""
     tab = (L.XpFrameSrc * len(videos))()
     for d, v, g in zip(tab, videos, geometry):
-        d.src, d.src_bytes = v.data_ptr(), v.untyped_storage().nbytes() - v.storage_offset()
-        d.stride_t, d.stride_y, d.stride_x, d.stride_c = v.stride()
-        d.T, d.H, d.W = v.shape[:3]
-        d.box_y, d.box_x, d.box_h, d.box_w = g.box_y, g.box_x, g.box_h, g.box_w
-        d.rh, d.rw, d.top, d.left, d.flip = g.rh, g.rw, g.top, g.left, int(bool(g.flip))
+        _fill_frame_src(d, v, g)
+    return tab
+
+
+class FrameTwoStage(NamedTuple):
+    """XpFrameTransform's two-stage fields: the size of the (never materialised) stage-1 image the box is resized to, and the window
+    of it that stage 2 resizes to FrameGeometry's (rh, rw)"""
+    mid_h: int
+    mid_w: int
+    crop_y: int
+    crop_x: int
+    crop_h: int
+    crop_w: int
+
+
+COLOR_OPS = {"brightness": L.XP_FRAMES_COLOR_BRIGHTNESS, "saturation": L.XP_FRAMES_COLOR_SATURATION, "hue": L.XP_FRAMES_COLOR_HUE}
+
+
+def frames_transform(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=CLIP_STD, out=None, two_stage=None,
+                     color=None) -> torch.Tensor:
+    """frames_resize_norm with a choice of filter and a colour stage (include/xpretrain_hip.h: xp_frames_transform).
+    ``two_stage``: None -- the one-stage bicubic of frames_resize_norm, same bits -- or a FrameTwoStage per video (or one for all):
+    box -> stage-1 image -> its crop window -> (rh, rw), both bilinear, in one launch.  ``color``: None, or per video a sequence of up
+    to three ``(op, factor)`` pairs in the order of application, ``op`` one of "brightness", "saturation", "hue" (or the
+    XP_FRAMES_COLOR_* value); an empty sequence leaves that video's colours alone.  Batches beyond
+    XP_FRAMES_TRANSFORM_MAX_VIDEOS are split into several launches."""
+    videos, geometry, out = _frames_args("frames_transform", videos, geometry, oh, ow, out)
+    n = len(videos)
+    if two_stage is not None:
+        two_stage = [two_stage] * n if hasattr(two_stage, "mid_h") else list(two_stage)
+        if len(two_stage) != n:
+            raise ValueError(f"frames_transform: {n} videos with {len(two_stage)} two-stage records")
+    if color is not None:
+        color = [tuple(c) if c is not None else () for c in color]
+        if len(color) != n:
+            raise ValueError(f"frames_transform: {n} videos with {len(color)} colour records")
+        if any(len(c) > 3 for c in color):
+            raise ValueError("frames_transform: at most three colour ops per video (brightness, saturation, hue)")
+    m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+    done = 0
+    for lo in range(0, n, L.XP_FRAMES_TRANSFORM_MAX_VIDEOS):
+        hi = min(n, lo + L.XP_FRAMES_TRANSFORM_MAX_VIDEOS)
+        tab = frame_transform_table(videos[lo:hi], geometry[lo:hi], two_stage and two_stage[lo:hi], color and color[lo:hi])
+        L.check(L.lib().xp_frames_transform(tab, hi - lo, m, sd, C.c_void_p(out.data_ptr() + done * 3 * oh * ow * 4), oh, ow,
+                                            _stream()), "xp_frames_transform")
+        done += sum(v.shape[0] for v in videos[lo:hi])
+    return out
+
+
+def frame_transform_table(videos, geometry, two_stage=None, color=None):
+    """the XpFrameTransform array of one xp_frames_transform call (frame_table's fields, the filter, the colour ops)"""
+    tab = (L.XpFrameTransform * len(videos))()
+    for i, (e, v, g) in enumerate(zip(tab, videos, geometry)):
+        _fill_frame_src(e.src, v, g)
+        e.filter = L.XP_FRAMES_FILTER_BICUBIC
+        if two_stage is not None:
+            e.filter = L.XP_FRAMES_FILTER_BILINEAR2
+            e.mid_h, e.mid_w, e.crop_y, e.crop_x, e.crop_h, e.crop_w = two_stage[i]
+        ops = color[i] if color is not None else ()
+        e.n_color = len(ops)
+        for k, (op, factor) in enumerate(ops):
+            if isinstance(op, str) and op not in COLOR_OPS:
+                raise ValueError(f"frames_transform: unknown colour op {op!r} (one of {sorted(COLOR_OPS)})")
+            e.color_op[k], e.color_factor[k] = COLOR_OPS[op] if isinstance(op, str) else int(op), float(factor)
     return tab
 
 
