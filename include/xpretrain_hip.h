@@ -373,6 +373,22 @@ size_t xp_vip_embed_bwd_workspace_bytes(int64_t B, int64_t T, int64_t L, int64_t
 int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, float* d_pos, float* d_time,
                      int64_t B, int64_t M, int64_t T, int64_t L, int64_t D, int32_t dtype, int32_t accumulate,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* The position table resampled to a patch grid it was not trained for: transformers' CLIPVisionEmbeddings.interpolate_pos_encoding
+ * (the reference has no such step: its table must match the frame).  pos fp32 [1 + g0*g0, D] -> out fp32 [1 + gh*gw, D], every
+ * element written and nothing else:
+ *     out[0] = pos[0]                                                  bit for bit
+ *     out[1 + y*gw + x] = sum_j wy[j] * (sum_i wx[i] * pos[1 + ty[j]*g0 + tx[i]])      fp32, the row sums first, fixed order
+ *     per axis (length g, coordinate d): s = (d + 0.5) * g0 / g - 0.5;  i = floor(s), t = s - i from the exact rational
+ *     ((2 d + 1) g0 - g) / (2 g);  taps i-1 .. i+2, each clamped to [0, g0-1];  Keys cubic-convolution weights, A = -0.75
+ * i.e. F.interpolate(pos[1:].view(1,g0,g0,D).permute(0,3,1,2), size=(gh,gw), mode="bicubic", align_corners=False), no antialias.
+ * xp_pos_resample_bwd is the transpose: d_out fp32 [1 + gh*gw, D] -> d_pos fp32 [1 + g0*g0, D] (overwritten, every element),
+ *     d_pos[0] = d_out[0];   d_pos[1 + sy*g0 + sx] = sum_y sum_x (Wy[y,sy] * Wx[x,sx]) * d_out[1 + y*gw + x]
+ * with Wy[y,sy] the sum (taps ascending) of row y's tap weights whose clamped index is sy; y ascending, then x ascending, zero
+ * weights skipped, one thread per element, no atomics: bit-reproducible.  gh == gw == g0 is an exact identity (weights 0, 1, 0, 0),
+ * but callers are expected not to launch it.  No workspace.  Refused before any launch: a null or not 16-byte aligned pointer,
+ * g0 / gh / gw outside [1, 16384], D not a positive multiple of 4. */
+int xp_pos_resample_fwd(const float* pos, float* out, int32_t g0, int32_t gh, int32_t gw, int32_t D, void* stream);
+int xp_pos_resample_bwd(const float* d_out, float* d_pos, int32_t g0, int32_t gh, int32_t gw, int32_t D, void* stream);
 /* CLIPTextEmbeddings.forward (:210-227): x[b,t] = tok[ids[b,t]] + pos[t] */
 int xp_text_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void* x,
                       int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, void* stream);

@@ -227,6 +227,8 @@ SIGNATURES = {
     "xp_vip_proxy_rows": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_vip_embed_bwd_workspace_bytes": (sz, [i64, i64, i64, i64]),
     "xp_vip_embed_bwd": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, i32, vp, sz, vp]),
+    "xp_pos_resample_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "xp_pos_resample_bwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "xp_text_embed_fwd": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_text_embed_bwd": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, i32, vp]),
     "xp_argmax_rows": (i32, [vp, vp, i64, i64, vp]),

@@ -97,7 +97,9 @@ def setup_model(cfg, device=None, allow_random_init=False) -> VidCLIP:
     args.clip_weights = weights or ""
     model = VidCLIP(args)
     if getattr(cfg, "e2e_weights_path", None):
-        load_state_dict_with_mismatch(model, cfg.e2e_weights_path)
+        # resize_embeddings (default 0; not a reference key): a checkpoint's position / temporal tables of another size are resampled
+        # once here instead of being left at their random initialisation
+        load_state_dict_with_mismatch(model, cfg.e2e_weights_path, bool(getattr(cfg, "resize_embeddings", 0)))
     if getattr(cfg, "freeze_text_model", 0):
         model.freeze_text_encoder(bool(getattr(cfg, "freeze_text_proj", 0)))
     model.clipmodel.set_compute_dtype(compute_dtype(cfg))

@@ -984,6 +984,29 @@ class VisionEmbedFn(torch.autograd.Function):
         return None, dwp, d_class, d_added[:nadd], d_pos, d_time, None, None
 
 
+class PosResampleFn(torch.autograd.Function):
+    """``interpolate_pos_encoding`` (transformers' CLIPVisionEmbeddings): the position table [1 + g0*g0, D] resampled to the frame's
+    gh x gw patch grid -- row 0 copied, the grid bicubic -- as the table VisionEmbedFn then reads; the backward is the transposed
+    map, in a fixed summation order, onto the parameter's own shape.  Callers skip it on the native grid (``pos_table``)."""
+
+    @staticmethod
+    def forward(ctx, pos_w, gh, gw):
+        ctx.meta = (H.pos_grid(pos_w.shape[0]), gh, gw)
+        return H.pos_resample_fwd(pos_w.detach().contiguous(), gh, gw)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return H.pos_resample_bwd(d_out.contiguous(), *ctx.meta), None, None
+
+
+def pos_table(pos_w, gh: int, gw: int):
+    """the position table of a gh x gw patch grid: the parameter itself on its own grid (no kernel, no autograd node), else resampled"""
+    if gh < 1 or gw < 1:
+        raise ValueError(f"interpolate_pos_encoding: the frame is smaller than one patch (grid {gh} x {gw})")
+    g0 = H.pos_grid(pos_w.shape[0])
+    return pos_w if gh == gw == g0 else PosResampleFn.apply(pos_w, gh, gw)
+
+
 class TextEmbedFn(torch.autograd.Function):
     """CLIPTextEmbeddings.forward (modeling/CLIP_ViP.py:210-227): token_embedding[ids] + position_embedding[:Lt]."""
 

@@ -512,6 +512,46 @@ def vip_embed_bwd(dx, B, M, T, Lp, D, want_time=True):
     return d_class, d_added[: M - 1], d_pos, d_time
 
 
+def pos_grid(rows: int) -> int:
+    """g0 of a position table of ``rows`` = 1 + g0*g0 rows (ValueError for any other row count)"""
+    g0 = math.isqrt(max(int(rows) - 1, 0))
+    if g0 < 1 or g0 * g0 != rows - 1:
+        raise ValueError(f"position table has {rows} rows: not 1 + a square grid, so it cannot be resampled")
+    return g0
+
+
+def _pos_table(t, name, rows=None):
+    _chk(t, name, torch.float32)
+    if t.dim() != 2 or not t.is_contiguous() or (rows is not None and t.shape[0] != rows):
+        raise ValueError(f"{name}: expected a contiguous [{'rows' if rows is None else rows}, D] fp32 table, got {tuple(t.shape)}")
+    return t
+
+
+def pos_resample_fwd(pos: torch.Tensor, gh: int, gw: int, out=None) -> torch.Tensor:
+    """position table fp32 [1 + g0*g0, D] -> [1 + gh*gw, D]: row 0 copied, the g0 x g0 grid resampled bicubically
+    (include/xpretrain_hip.h: xp_pos_resample_fwd; transformers' interpolate_pos_encoding)"""
+    _pos_table(pos, "pos")
+    g0, D = pos_grid(pos.shape[0]), pos.shape[1]
+    if out is None:
+        out = torch.empty((1 + gh * gw, D), dtype=torch.float32, device=pos.device)
+    else:
+        _pos_table(out, "out", 1 + gh * gw)
+    L.check(L.lib().xp_pos_resample_fwd(_p(pos), _p(out), g0, gh, gw, D, _stream()), "xp_pos_resample_fwd")
+    return out
+
+
+def pos_resample_bwd(d_out: torch.Tensor, g0: int, gh: int, gw: int, d_pos=None) -> torch.Tensor:
+    """the transpose: d_out fp32 [1 + gh*gw, D] -> d_pos fp32 [1 + g0*g0, D], fixed summation order"""
+    _pos_table(d_out, "d_out", 1 + gh * gw)
+    D = d_out.shape[1]
+    if d_pos is None:
+        d_pos = torch.empty((1 + g0 * g0, D), dtype=torch.float32, device=d_out.device)
+    else:
+        _pos_table(d_pos, "d_pos", 1 + g0 * g0)
+    L.check(L.lib().xp_pos_resample_bwd(_p(d_out), _p(d_pos), g0, gh, gw, D, _stream()), "xp_pos_resample_bwd")
+    return d_pos
+
+
 def text_embed_fwd(ids, tok, pos, dtype):
     _chk(ids, "ids", torch.int64)
     B, Lt = ids.shape

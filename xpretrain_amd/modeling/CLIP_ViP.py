@@ -145,7 +145,11 @@ class CLIPVisionViPEmbeddings(nn.Module):
         if self.if_use_temporal_embed:
             self.temporal_embedding = nn.Parameter(torch.zeros(1, self.temporal_size, self.embed_dim))
 
-    def forward(self, pixel_values: torch.Tensor, dtype=torch.bfloat16):
+    def forward(self, pixel_values: torch.Tensor, dtype=torch.bfloat16, interpolate_pos_encoding: bool = False):
+        """``interpolate_pos_encoding`` (transformers' name; the reference has no such step): frames of any ``H, W >= patch_size``,
+        non-square included -- the position table is resampled to the frame's patch grid (XF.PosResampleFn: row 0 copied, the grid
+        bicubic, the gradient reaches the parameter).  On the table's own grid the parameter is used as it is.  Off: a frame off
+        that grid is refused (ValueError)."""
         B, T, C, H, W = pixel_values.shape
         if self.if_use_temporal_embed:
             te = self.temporal_embedding
@@ -155,7 +159,10 @@ class CLIPVisionViPEmbeddings(nn.Module):
         else:
             time_table = torch.zeros(T, self.embed_dim, device=pixel_values.device)
         pw = self.patch_embedding.weight
-        x = XF.VisionEmbedFn.apply(pixel_values, pw, self.class_embedding, self.added_cls, self.position_embedding.weight, time_table, dtype,
+        pos_w = self.position_embedding.weight
+        if interpolate_pos_encoding:
+            pos_w = XF.pos_table(pos_w, H // self.patch_size, W // self.patch_size)
+        x = XF.VisionEmbedFn.apply(pixel_values, pw, self.class_embedding, self.added_cls, pos_w, time_table, dtype,
                                    torch.is_grad_enabled() and pw.requires_grad)
         M = 1 + self.add_cls_num
         L = (H // self.patch_size) * (W // self.patch_size)
@@ -392,8 +399,11 @@ class CLIPVisionTransformer(nn.Module):
         self.post_layernorm = nn.LayerNorm(config.hidden_size)
         self.compute_dtype = torch.bfloat16
 
-    def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None, pooled_only=False):
-        """``pooled_only`` (CLIPModel.pooled_last_layer): the caller reads ``pooler_output`` alone, so the last encoder layer may
+    def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None, pooled_only=False,
+                interpolate_pos_encoding: bool = False):
+        """``interpolate_pos_encoding``: accept frames off the position table's grid (CLIPVisionViPEmbeddings.forward); it sits in
+        front of everything else here and changes nothing on the native grid.
+        ``pooled_only`` (CLIPModel.pooled_last_layer): the caller reads ``pooler_output`` alone, so the last encoder layer may
         compute token 0 of every sample only; ``last_hidden_state`` is then ``None``.  Without it -- every direct call -- and with
         ``output_hidden_states`` the tower is dense.
         ``output_attentions`` (a documented extension: the reference returns ``(None, ..)`` for this tower): ``attentions`` is one
@@ -405,7 +415,7 @@ class CLIPVisionTransformer(nn.Module):
         attn = [] if output_attentions else None
         B = pixel_values.shape[0]
         D = self.config.hidden_size
-        x, size = self.embeddings(pixel_values, self.compute_dtype)
+        x, size = self.embeddings(pixel_values, self.compute_dtype, interpolate_pos_encoding)
         S, M = size[0] + size[1] * size[2], size[0]
         if XF.PROXY_SIDE and self.compute_dtype == torch.bfloat16:
             # the M proxy tokens of every sample travel through the residual stream in fp32 beside the bf16 rows (4 of 2356 rows:
@@ -581,9 +591,11 @@ class CLIPVisionModel(CLIPPreTrainedModel):
     def get_input_embeddings(self):
         return self.vision_model.embeddings.patch_embedding
 
-    def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None):
+    def forward(self, pixel_values=None, output_attentions=None, output_hidden_states=None, return_dict=None,
+                interpolate_pos_encoding: bool = False):
         return self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                 output_hidden_states=output_hidden_states, return_dict=return_dict)
+                                 output_hidden_states=output_hidden_states, return_dict=return_dict,
+                                 interpolate_pos_encoding=interpolate_pos_encoding)
 
 
 def contrastive_loss(logits):
@@ -627,14 +639,14 @@ class CLIPModel(CLIPPreTrainedModel):
         return XF.L2NormFn.apply(feats) if if_norm else feats.float()
 
     def get_image_features(self, pixel_values=None, output_attentions=None, output_hidden_states=None,
-                           return_dict=None, if_norm=None):
+                           return_dict=None, if_norm=None, interpolate_pos_encoding: bool = False):
         out = self.vision_model(pixel_values=pixel_values, output_hidden_states=output_hidden_states,      # (output_attentions: as above)
-                                pooled_only=self.pooled_last_layer)
+                                pooled_only=self.pooled_last_layer, interpolate_pos_encoding=interpolate_pos_encoding)
         feats = XF.ProjectionFn.apply(out["pooler_output"], self.visual_projection.weight)
         return XF.L2NormFn.apply(feats) if if_norm else feats.float()
 
     def forward(self, input_ids=None, pixel_values=None, attention_mask=None, position_ids=None, return_loss=None,
-                output_attentions=None, output_hidden_states=None, return_dict=None):
+                output_attentions=None, output_hidden_states=None, return_dict=None, interpolate_pos_encoding: bool = False):
         # The text tower is ~250 rows: its ~700 kernels per step are launch-latency bound and occupy a few CUs each.
         # Run it (whole tower incl. its projection) on a side HIP stream so it overlaps the video tower's large
         # GEMMs; autograd replays each backward op on its forward stream, so the text backward overlaps too.
@@ -652,7 +664,8 @@ class CLIPModel(CLIPPreTrainedModel):
                 text_done.record(side)                          # the join below waits for the TOWER, not for what is queued behind it
                 CLIPModel.run_deferred_text_stream_work()       # (e.g. the loader's copy of the NEXT batch: behind the text tower's forward)
             vision_outputs = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                               output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer)
+                                               output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer,
+                                               interpolate_pos_encoding=interpolate_pos_encoding)
             image_embeds = XF.L2NormFn.apply(XF.ProjectionFn.apply(vision_outputs["pooler_output"], self.visual_projection.weight))
             main.wait_event(text_done)
             text_embeds.record_stream(main)
@@ -661,7 +674,8 @@ class CLIPModel(CLIPPreTrainedModel):
             return self._finish(image_embeds, text_embeds, text_outputs, vision_outputs, return_loss, return_dict,
                                 output_hidden_states)
         vision_outputs = self.vision_model(pixel_values=pixel_values, output_attentions=output_attentions,
-                                           output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer)
+                                           output_hidden_states=output_hidden_states, pooled_only=self.pooled_last_layer,
+                                           interpolate_pos_encoding=interpolate_pos_encoding)
         text_outputs = self.text_model(input_ids=input_ids, attention_mask=attention_mask, position_ids=position_ids,
                                        output_attentions=output_attentions, output_hidden_states=output_hidden_states)
         image_embeds = XF.L2NormFn.apply(XF.ProjectionFn.apply(vision_outputs["pooler_output"], self.visual_projection.weight))

@@ -4,7 +4,8 @@
   for ``VidCLIP`` the 402 ``clipmodel.*`` tensors -- and, with an optimizer, ``{prefix}_step_{N}_train_state.pt`` =
   ``{'step', 'optimizer'}``.
 * ``load_state_dict_with_mismatch`` (:86-115): in-place, non-strict load that skips tensors whose shape differs (a
-  checkpoint trained with another ``temporal_size`` / resolution) and reports the three key sets.
+  checkpoint trained with another ``temporal_size`` / resolution) and reports the three key sets; with ``resize_embeddings=True``
+  (not in the reference) the vision position table and the temporal table of another size are converted instead of skipped.
 * ``E2E_TrainingRestorer`` (:260-327): ``restore.pt`` + ``restore_backup.pt`` holding ``global_step``,
   ``model_state_dict`` and ``optim_state_dict`` with floating tensors stored as fp16 on CPU (:177-192) and widened back
   to fp32 on load (:159-174).  There is no ``amp_state_dict`` here (no loss scaling on this path); one found in a
@@ -14,6 +15,7 @@ All writes go through a bounded retry (the reference retries 10 times because it
 """
 import json
 import logging
+import math
 import os
 from typing import Callable, Dict, Union
 
@@ -70,20 +72,59 @@ class ModelSaver:
         return _retry(f"ModelSaver.save(step={step})", write)
 
 
-def load_state_dict_with_mismatch(model, loaded_state_dict_or_path: Union[str, Dict[str, torch.Tensor]]):
-    """In place.  Returns ``{'unexpected': [...], 'missing': [...], 'mismatched': [...]}`` (the reference only logs them)."""
+POS_TABLE_KEY = "vision_model.embeddings.position_embedding.weight"
+TEMPORAL_TABLE_KEY = "vision_model.embeddings.temporal_embedding"
+
+
+def _is_pos_table(shape) -> bool:
+    g = math.isqrt(shape[0] - 1) if len(shape) == 2 and shape[0] > 1 else 0
+    return g >= 1 and g * g == shape[0] - 1
+
+
+def _resized(name, tensor, shape):
+    """``tensor`` converted to the model's ``shape`` if ``name`` is one of the two tables that have a conversion, else None"""
+    have = tuple(tensor.shape)
+    if name.endswith(POS_TABLE_KEY) and _is_pos_table(have) and _is_pos_table(shape) and have[1] == shape[1]:
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"load_state_dict_with_mismatch(resize_embeddings=True): resampling {name} {have} -> {tuple(shape)} runs "
+                               "the HIP kernel and needs a GPU -- xpretrain_amd has no CPU path")
+        from .. import hip_ops as H
+        g = H.pos_grid(shape[0])
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return H.pos_resample_fwd(tensor.detach().to(dev, torch.float32).contiguous(), g, g).to(tensor.device, tensor.dtype)
+    if name.endswith(TEMPORAL_TABLE_KEY) and len(have) == 3 and len(shape) == 3 and have[0] == shape[0] == 1 and have[2] == shape[2]:
+        # the expression of CLIPVisionViPEmbeddings.forward for T != temporal_size (reference CLIP_ViP.py:171-174)
+        te = tensor.detach().float()
+        return torch.nn.functional.interpolate(te.transpose(1, 2), size=shape[1], mode="linear").transpose(1, 2).contiguous().to(tensor.dtype)
+    return None
+
+
+def load_state_dict_with_mismatch(model, loaded_state_dict_or_path: Union[str, Dict[str, torch.Tensor]], resize_embeddings: bool = False):
+    """In place.  Returns ``{'unexpected': [...], 'missing': [...], 'mismatched': [...]}`` (the reference only logs them).
+
+    ``resize_embeddings`` (not in the reference): a vision ``position_embedding.weight`` of another grid (both shapes 1 + a square,
+    same width) is resampled once by the forward kernel of ``interpolate_pos_encoding`` (hip_ops.pos_resample_fwd: on the current
+    GPU and back; RuntimeError without one), a ``temporal_embedding`` of another length by the linear expression the model's forward
+    uses; both are loaded and reported under a fourth key ``'resized'`` instead of ``'mismatched'``."""
     loaded = (torch.load(loaded_state_dict_or_path, map_location="cpu") if isinstance(loaded_state_dict_or_path, str)
               else loaded_state_dict_or_path)
     own = model.state_dict()
-    usable, mismatched = {}, []
+    usable, mismatched, resized = {}, [], []
     for name, tensor in own.items():
         if name in loaded:
             if tuple(loaded[name].shape) == tuple(tensor.shape):
                 usable[name] = loaded[name]
-            else:
+                continue
+            new = _resized(name, loaded[name], tuple(tensor.shape)) if resize_embeddings else None
+            if new is None:
                 mismatched.append(name)
+            else:
+                usable[name] = new
+                resized.append(name)
     report = {"unexpected": sorted(set(loaded) - set(own)), "missing": sorted(set(own) - set(loaded)),
               "mismatched": sorted(mismatched)}
+    if resize_embeddings:
+        report["resized"] = sorted(resized)
     for kind, names in report.items():
         LOGGER.info("load_state_dict_with_mismatch: %d %s keys %s", len(names), kind, names)
     model.load_state_dict(usable, strict=False)
