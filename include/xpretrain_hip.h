@@ -365,6 +365,34 @@ typedef struct {
 } XpFrameTransform;
 int xp_frames_transform(const XpFrameTransform* videos_host, int32_t n_videos, const float* mean3_host,
                         const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream);
+/* xp_frames_transform with an antialias filter: what torchvision >= 0.17 computes for Resize / RandomResizedCrop on a float tensor
+ * (antialias=True), i.e. F.interpolate(..., align_corners=False, antialias=True).  A SECOND definition, not a correction of the
+ * first: the support widens with the scale, the weights are normalised per output coordinate, the window is truncated (not
+ * clamped) at the box edge, and the cubic is Keys' with A = -0.5.  Per axis, `box` source pixels resized to `out`, k = 4 (BICUBIC)
+ * or 2 (BILINEAR2):
+ *     scale = box / out;  support = (k / 2) max(scale, 1);  inv = 1 / max(scale, 1)
+ *     for resized coordinate r:  c = scale (r + 0.5);  x0 = max(int(c - support + 0.5), 0);  n = min(int(c + support + 0.5), box) - x0
+ *     w_j = f((j + x0 - c + 0.5) inv) / sum_j f(...),  j = 0 .. n - 1;  f: Keys' cubic (A = -0.5) or the triangle
+ *     resized pixel = sum_j w_j u8[box0 + x0 + j]: the horizontal pass first, then the vertical, taps in ascending order
+ * (x0 and n come from integer arithmetic on (2 r + 1) box +- k max(box, out) + out over 2 out; where that quotient is an integer the
+ * tap it adds or drops has weight f(k / 2) = 0.)  XP_FRAMES_FILTER_BILINEAR2 is box -> mid, the crop window, -> (rh, rw), each by
+ * the rule above; both stages are separable and linear, so the library applies the composite per-axis rows W2[r, :] W1[crop0 + ., :]
+ * and no intermediate image exists.  The window (top, left), the flip, the colour stage, /255 and Normalize are xp_frames_transform's.
+ * Two launches on `stream` inside the one call: a table kernel writes x0, n and the weights -- formed in fp64, rounded once to
+ * fp32 -- of every needed output coordinate of every video into `workspace`; the apply kernel stages the uint8 footprint of an
+ * output tile in LDS and runs the horizontal pass, the vertical pass, the colour stage and Normalize in a fixed summation order
+ * (two runs agree to the bit).  No allocation, no host synchronisation, no atomics.  `workspace` is device memory, 4-byte aligned,
+ * of at least xp_frames_transform_aa_workspace_bytes(...) bytes (0 where the arguments would be refused); nothing outside
+ * workspace[0, workspace_bytes) and `out` is written, nothing outside [src, src + src_bytes) is read.
+ * Refused before any launch, naming the argument: everything xp_frames_transform refuses (the tap extent being this filter's), a
+ * null or misaligned workspace, workspace_bytes below the sizing function's value, and a per-axis tap count above
+ * XP_FRAMES_AA_MAX_TAPS.  The tap count of an axis is the width of its table rows, 2 ceil(support) + 1 (n never exceeds it); for
+ * BILINEAR2 the composite's, ceil(scale1 (taps2 - 1)) + taps1.  3840 -> 224 bicubic has 71. */
+#define XP_FRAMES_AA_MAX_TAPS 128
+size_t xp_frames_transform_aa_workspace_bytes(const XpFrameTransform* videos_host, int32_t n_videos, int32_t oh, int32_t ow);
+int xp_frames_transform_aa(const XpFrameTransform* videos_host, int32_t n_videos, const float* mean3_host,
+                           const float* std3_host, float* out, int32_t oh, int32_t ow, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* proxy rows: x[b, 0] = class_emb + pos[0]; x[b, 1+i] = added_cls[i] + pos[0]   (:187-191) */
 int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const float* pos, void* x,
                       int64_t B, int64_t S, int64_t M, int64_t D, int32_t dtype, void* stream);

@@ -173,6 +173,7 @@ XP_FRAMES_TRANSFORM_MAX_VIDEOS = 24
 XP_FRAMES_FILTER_BICUBIC, XP_FRAMES_FILTER_BILINEAR2 = 0, 1
 # torchvision's ColorJitter op indices (1 would be contrast: not provided)
 XP_FRAMES_COLOR_BRIGHTNESS, XP_FRAMES_COLOR_SATURATION, XP_FRAMES_COLOR_HUE = 0, 2, 3
+XP_FRAMES_AA_MAX_TAPS = 128
 
 # name -> (restype, argtypes); mirrors include/xpretrain_hip.h one-to-one
 SIGNATURES = {
@@ -224,6 +225,8 @@ SIGNATURES = {
     "xp_im2col_u8": (i32, [vp, C.POINTER(f32), C.POINTER(f32), vp, i64, i64, i64, i64, i32, vp]),
     "xp_frames_resize_norm": (i32, [C.POINTER(XpFrameSrc), i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp]),
     "xp_frames_transform": (i32, [C.POINTER(XpFrameTransform), i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp]),
+    "xp_frames_transform_aa_workspace_bytes": (sz, [C.POINTER(XpFrameTransform), i32, i32, i32]),
+    "xp_frames_transform_aa": (i32, [C.POINTER(XpFrameTransform), i32, C.POINTER(f32), C.POINTER(f32), vp, i32, i32, vp, sz, vp]),
     "xp_vip_proxy_rows": (i32, [vp, vp, vp, vp, i64, i64, i64, i64, i32, vp]),
     "xp_vip_embed_bwd_workspace_bytes": (sz, [i64, i64, i64, i64]),
     "xp_vip_embed_bwd": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i32, i32, vp, sz, vp]),

@@ -25,6 +25,7 @@
 #include <cfloat>
 
 #include "common.h"
+#include "frames_common.h"
 
 namespace {
 
@@ -87,48 +88,6 @@ __device__ __forceinline__ void bilinear2_axis(int r, int box, int mid, int crop
     tap[2 * k + 1] = box0 + j1;
     w[2 * k] = w2[k] * s1;
     w[2 * k + 1] = w2[k] * l1;
-  }
-}
-
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-
-// torchvision's adjust_hue on a float pixel (_rgb2hsv, h = (h + f) % 1, _hsv2rgb), behind a clamp of the input to [0, 1]
-__device__ __forceinline__ void hue_shift(float (&x)[3], float f) {
-  const float r = clamp01(x[0]), g = clamp01(x[1]), b = clamp01(x[2]);
-  const float maxc = fmaxf(r, fmaxf(g, b)), minc = fminf(r, fminf(g, b));
-  const bool eqc = maxc == minc;
-  const float cr = maxc - minc;
-  const float s = cr / (eqc ? 1.0f : maxc);
-  const float dv = eqc ? 1.0f : cr;
-  const float rc = (maxc - r) / dv, gc = (maxc - g) / dv, bc = (maxc - b) / dv;
-  float h = maxc == r ? bc - gc : (maxc == g ? 2.0f + rc - bc : 4.0f + gc - rc);
-  h = fmodf(h / 6.0f + 1.0f, 1.0f);
-  h += f;
-  h -= floorf(h);                            // Python's % 1: into [0, 1]
-  const float h6 = h * 6.0f, fl = floorf(h6), fr = h6 - fl;
-  const int i = (int)fl % 6;
-  const float v = maxc;
-  const float p = clamp01(v * (1.0f - s)), q = clamp01(v * (1.0f - s * fr)), t = clamp01(v * (1.0f - s * (1.0f - fr)));
-  x[0] = (i == 0 || i == 5) ? v : (i == 1 ? q : (i == 4 ? t : p));
-  x[1] = (i == 1 || i == 2) ? v : (i == 0 ? t : (i == 3 ? q : p));
-  x[2] = (i == 3 || i == 4) ? v : (i == 2 ? t : (i == 5 ? q : p));
-}
-
-// the colour ops of one video on the float pixel x (v / 255, overshoot included), in the descriptor's order
-__device__ __forceinline__ void color_stage(const XpFrameTransform& e, float (&x)[3]) {
-  for (int k = 0; k < e.n_color; ++k) {
-    const float f = e.color_factor[k];
-    const int op = e.color_op[k];
-    if (op == XP_FRAMES_COLOR_BRIGHTNESS) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) x[c] = clamp01(f * x[c]);
-    } else if (op == XP_FRAMES_COLOR_SATURATION) {
-      const float gray = 0.2989f * x[0] + 0.587f * x[1] + 0.114f * x[2];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) x[c] = clamp01(f * x[c] + (1.0f - f) * gray);
-    } else {
-      hue_shift(x, f);
-    }
   }
 }
 
@@ -232,13 +191,6 @@ void axis_extent(int r_lo, int r_hi, int box, int out, int box0, int64_t* lo, in
   *hi = box0 + clampi(fl(r_hi) + 2);
 }
 
-// adds the smallest / largest value of stride * index over [lo, hi] to *mn / *mx; false on int64 overflow
-bool add_span(int64_t stride, int64_t lo, int64_t hi, int64_t* mn, int64_t* mx) {
-  int64_t p, q;
-  if (__builtin_mul_overflow(stride, lo, &p) || __builtin_mul_overflow(stride, hi, &q)) return false;
-  return !__builtin_add_overflow(*mn, p < q ? p : q, mn) && !__builtin_add_overflow(*mx, p < q ? q : p, mx);
-}
-
 // the same for the two-stage axis (host side of bilinear2_axis: both stages never decrease, so the first tap of the window's first
 // coordinate and the last tap of its last coordinate bound every tap between)
 void axis_extent2(int r_lo, int r_hi, int box, int mid, int crop0, int crop, int out, int box0, int64_t* lo, int64_t* hi) {
@@ -251,10 +203,32 @@ void axis_extent2(int r_lo, int r_hi, int box, int mid, int crop0, int crop, int
   *hi = box0 + next(fl(crop0 + next(fl(r_hi, crop, out), crop), box, mid), box);
 }
 
-// Everything both entry points ask of call-level arguments, then of one video's source descriptor (`e`: the transform descriptor it
-// belongs to, null for xp_frames_resize_norm); `fn` is the entry point's name in the message.
-int check_call(const char* fn, const void* videos_host, int n_videos, int max_videos, const float* mean3_host, const float* std3_host,
-               const float* out, int oh, int ow) {
+// adds the smallest / largest value of stride * index over [lo, hi] to *mn / *mx; false on int64 overflow
+bool add_span(int64_t stride, int64_t lo, int64_t hi, int64_t* mn, int64_t* mx) {
+  int64_t p, q;
+  if (__builtin_mul_overflow(stride, lo, &p) || __builtin_mul_overflow(stride, hi, &q)) return false;
+  return !__builtin_add_overflow(*mn, p < q ? p : q, mn) && !__builtin_add_overflow(*mx, p < q ? q : p, mx);
+}
+
+// one video's source descriptor with the tap extent of this file's two filters
+int check_video(const char* fn, const XpFrameSrc& d, const XpFrameTransform* e, int i, int oh, int ow) {
+  if (int rc = xp_frames_check_geometry(fn, d, e, i, oh, ow)) return rc;
+  int64_t y0, y1, x0, x1;
+  if (e && e->filter == BILINEAR2) {
+    axis_extent2(d.top, d.top + oh - 1, d.box_h, e->mid_h, e->crop_y, e->crop_h, d.rh, d.box_y, &y0, &y1);
+    axis_extent2(d.left, d.left + ow - 1, d.box_w, e->mid_w, e->crop_x, e->crop_w, d.rw, d.box_x, &x0, &x1);
+  } else {
+    axis_extent(d.top, d.top + oh - 1, d.box_h, d.rh, d.box_y, &y0, &y1);
+    axis_extent(d.left, d.left + ow - 1, d.box_w, d.rw, d.box_x, &x0, &x1);
+  }
+  return xp_frames_check_extent(fn, d, i, y0, y1, x0, x1);
+}
+
+}  // namespace
+
+// Everything the entry points ask of call-level arguments, then of one video's source descriptor (frames_common.h)
+int xp_frames_check_call(const char* fn, const void* videos_host, int n_videos, int max_videos, const float* mean3_host,
+                         const float* std3_host, const float* out, int oh, int ow) {
   XP_REQUIRE(videos_host, "%s: videos_host is null", fn);
   XP_REQUIRE(mean3_host, "%s: mean3_host is null", fn);
   XP_REQUIRE(std3_host, "%s: std3_host is null", fn);
@@ -267,7 +241,7 @@ int check_call(const char* fn, const void* videos_host, int n_videos, int max_vi
   return XP_OK;
 }
 
-int check_video(const char* fn, const XpFrameSrc& d, const XpFrameTransform* e, int i, int oh, int ow) {
+int xp_frames_check_geometry(const char* fn, const XpFrameSrc& d, const XpFrameTransform* e, int i, int oh, int ow) {
   XP_REQUIRE(d.src, "%s: videos_host[%d].src is null", fn, i);
   XP_REQUIRE(d.src_bytes > 0, "%s: videos_host[%d].src_bytes=%lld is not positive", fn, i, (long long)d.src_bytes);
   XP_REQUIRE(d.T > 0 && d.T <= (1 << 24), "%s: videos_host[%d].T=%d not in 1..%d", fn, i, d.T, 1 << 24);
@@ -277,8 +251,7 @@ int check_video(const char* fn, const XpFrameSrc& d, const XpFrameTransform* e, 
   XP_REQUIRE(d.box_y >= 0 && d.box_x >= 0 && d.box_y <= d.H - d.box_h && d.box_x <= d.W - d.box_w,
              "%s: videos_host[%d]: box (box_y=%d box_x=%d box_h=%d box_w=%d) lies outside the %d x %d image", fn, i, d.box_y, d.box_x,
              d.box_h, d.box_w, d.H, d.W);
-  const bool two = e && e->filter == BILINEAR2;
-  if (two) {
+  if (e && e->filter == BILINEAR2) {
     XP_REQUIRE(e->mid_h > 0 && e->mid_h <= XP_FRAMES_MAX_SIZE && e->mid_w > 0 && e->mid_w <= XP_FRAMES_MAX_SIZE,
                "%s: videos_host[%d]: stage-1 size mid_h=%d mid_w=%d not in 1..%d", fn, i, e->mid_h, e->mid_w, XP_FRAMES_MAX_SIZE);
     XP_REQUIRE(e->crop_h > 0 && e->crop_w > 0 && e->crop_y >= 0 && e->crop_x >= 0 && e->crop_y <= e->mid_h - e->crop_h &&
@@ -291,14 +264,11 @@ int check_video(const char* fn, const XpFrameSrc& d, const XpFrameTransform* e, 
   XP_REQUIRE(d.top >= 0 && d.left >= 0 && d.top <= d.rh - oh && d.left <= d.rw - ow,
              "%s: videos_host[%d]: window (top=%d left=%d, %d x %d) lies outside the %d x %d resized image "
              "(there is no padding path)", fn, i, d.top, d.left, oh, ow, d.rh, d.rw);
-  int64_t y0, y1, x0, x1, mn = 0, mx = 0;
-  if (two) {
-    axis_extent2(d.top, d.top + oh - 1, d.box_h, e->mid_h, e->crop_y, e->crop_h, d.rh, d.box_y, &y0, &y1);
-    axis_extent2(d.left, d.left + ow - 1, d.box_w, e->mid_w, e->crop_x, e->crop_w, d.rw, d.box_x, &x0, &x1);
-  } else {
-    axis_extent(d.top, d.top + oh - 1, d.box_h, d.rh, d.box_y, &y0, &y1);
-    axis_extent(d.left, d.left + ow - 1, d.box_w, d.rw, d.box_x, &x0, &x1);
-  }
+  return XP_OK;
+}
+
+int xp_frames_check_extent(const char* fn, const XpFrameSrc& d, int i, int64_t y0, int64_t y1, int64_t x0, int64_t x1) {
+  int64_t mn = 0, mx = 0;
   const bool fits = add_span(d.stride_t, 0, d.T - 1, &mn, &mx) && add_span(d.stride_y, y0, y1, &mn, &mx) &&
                     add_span(d.stride_x, x0, x1, &mn, &mx) && add_span(d.stride_c, 0, 2, &mn, &mx);
   XP_REQUIRE(fits && mn >= 0 && mx < d.src_bytes,
@@ -308,7 +278,7 @@ int check_video(const char* fn, const XpFrameSrc& d, const XpFrameTransform* e, 
   return XP_OK;
 }
 
-int check_color(const char* fn, const XpFrameTransform& e, int i) {
+int xp_frames_check_color(const char* fn, const XpFrameTransform& e, int i) {
   XP_REQUIRE(e.n_color >= 0 && e.n_color <= 3, "%s: videos_host[%d].n_color=%d not in 0..3", fn, i, e.n_color);
   for (int k = 0; k < e.n_color; ++k) {
     const int op = e.color_op[k];
@@ -327,12 +297,10 @@ int check_color(const char* fn, const XpFrameTransform& e, int i) {
   return XP_OK;
 }
 
-}  // namespace
-
 extern "C" int xp_frames_resize_norm(const XpFrameSrc* videos_host, int32_t n_videos, const float* mean3_host,
                                      const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream) {
   static const char* const fn = "xp_frames_resize_norm";
-  if (int rc = check_call(fn, videos_host, n_videos, MAXV, mean3_host, std3_host, out, oh, ow)) return rc;
+  if (int rc = xp_frames_check_call(fn, videos_host, n_videos, MAXV, mean3_host, std3_host, out, oh, ow)) return rc;
   FramesArgs a;
   for (int c = 0; c < 3; ++c) {
     a.mean[c] = mean3_host[c];
@@ -358,7 +326,7 @@ extern "C" int xp_frames_resize_norm(const XpFrameSrc* videos_host, int32_t n_vi
 extern "C" int xp_frames_transform(const XpFrameTransform* videos_host, int32_t n_videos, const float* mean3_host,
                                    const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream) {
   static const char* const fn = "xp_frames_transform";
-  if (int rc = check_call(fn, videos_host, n_videos, MAXT, mean3_host, std3_host, out, oh, ow)) return rc;
+  if (int rc = xp_frames_check_call(fn, videos_host, n_videos, MAXT, mean3_host, std3_host, out, oh, ow)) return rc;
   TransformArgs a;
   for (int c = 0; c < 3; ++c) {
     a.mean[c] = mean3_host[c];
@@ -374,7 +342,7 @@ extern "C" int xp_frames_transform(const XpFrameTransform* videos_host, int32_t 
     XP_REQUIRE(e.filter == filter, "%s: videos_host[%d].filter=%d differs from videos_host[0].filter=%d (one filter per call)", fn, i,
                e.filter, filter);
     if (int rc = check_video(fn, e.src, &e, i, oh, ow)) return rc;
-    if (int rc = check_color(fn, e, i)) return rc;
+    if (int rc = xp_frames_check_color(fn, e, i)) return rc;
     color = color || e.n_color > 0;
     a.v[i] = e;
     frames += e.src.T;

@@ -445,13 +445,17 @@ COLOR_OPS = {"brightness": L.XP_FRAMES_COLOR_BRIGHTNESS, "saturation": L.XP_FRAM
 
 
 def frames_transform(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=CLIP_STD, out=None, two_stage=None,
-                     color=None) -> torch.Tensor:
+                     color=None, antialias=False) -> torch.Tensor:
     """frames_resize_norm with a choice of filter and a colour stage (include/xpretrain_hip.h: xp_frames_transform).
     ``two_stage``: None -- the one-stage bicubic of frames_resize_norm, same bits -- or a FrameTwoStage per video (or one for all):
     box -> stage-1 image -> its crop window -> (rh, rw), both bilinear, in one launch.  ``color``: None, or per video a sequence of up
     to three ``(op, factor)`` pairs in the order of application, ``op`` one of "brightness", "saturation", "hue" (or the
     XP_FRAMES_COLOR_* value); an empty sequence leaves that video's colours alone.  Batches beyond
-    XP_FRAMES_TRANSFORM_MAX_VIDEOS are split into several launches."""
+    XP_FRAMES_TRANSFORM_MAX_VIDEOS are split into several launches.
+    ``antialias=True``: the same call through xp_frames_transform_aa -- ``F.interpolate(..., antialias=True)``, what torchvision >= 0.17
+    computes: a second definition (Keys A = -0.5, a support that widens with the scale, normalised weights), not these bits.  Its
+    tables live in a workspace of exactly xp_frames_transform_aa_workspace_bytes; a geometry with more than XP_FRAMES_AA_MAX_TAPS taps
+    on an axis is refused."""
     videos, geometry, out = _frames_args("frames_transform", videos, geometry, oh, ow, out)
     n = len(videos)
     if two_stage is not None:
@@ -469,8 +473,14 @@ def frames_transform(videos, geometry, oh: int, ow: int, mean=CLIP_MEAN, std=CLI
     for lo in range(0, n, L.XP_FRAMES_TRANSFORM_MAX_VIDEOS):
         hi = min(n, lo + L.XP_FRAMES_TRANSFORM_MAX_VIDEOS)
         tab = frame_transform_table(videos[lo:hi], geometry[lo:hi], two_stage and two_stage[lo:hi], color and color[lo:hi])
-        L.check(L.lib().xp_frames_transform(tab, hi - lo, m, sd, C.c_void_p(out.data_ptr() + done * 3 * oh * ow * 4), oh, ow,
-                                            _stream()), "xp_frames_transform")
+        outp = C.c_void_p(out.data_ptr() + done * 3 * oh * ow * 4)
+        if antialias:
+            nbytes = L.lib().xp_frames_transform_aa_workspace_bytes(tab, hi - lo, oh, ow)
+            ws = workspace(nbytes, out.device, "frames_aa") if nbytes else None       # (0: the call below says what is refused)
+            L.check(L.lib().xp_frames_transform_aa(tab, hi - lo, m, sd, outp, oh, ow, _p(ws), nbytes, _stream()),
+                    "xp_frames_transform_aa")
+        else:
+            L.check(L.lib().xp_frames_transform(tab, hi - lo, m, sd, outp, oh, ow, _stream()), "xp_frames_transform")
         done += sum(v.shape[0] for v in videos[lo:hi])
     return out
 

@@ -12,9 +12,13 @@ frames").  Each transform takes the raw decoded uint8 frames, whatever their res
 ``Resize(input_res)``, ``Normalize``, bilinear -- ``TwoStageTransform``.
 
 The geometry follows torchvision's rules and is resolved on the host by pure functions.  The deliberate reading of the reference: the
-float path (no clamp of the bicubic overshoot before the colour ops or Normalize, no re-quantisation), no antialias filter (the
-reference's pinned torch has none), and a pair ``input_res`` -- the shipped ``[224, 224]`` -- squashes the aspect, as ``Resize((h, w))``
-does.  One deviation: the hue op clamps its input to [0, 1] first.  torchvision documents float images as lying in [0, 1]; a bicubic
+float path (no clamp of the bicubic overshoot before the colour ops or Normalize, no re-quantisation), and a pair ``input_res`` -- the
+shipped ``[224, 224]`` -- squashes the aspect, as ``Resize((h, w))`` does.  ``antialias=False``, the default, is the reference's pinned
+torch 1.8, whose ``interpolate`` has no antialias filter (and torchvision < 0.17 on a tensor).  The reference pins no torchvision, and
+every torchvision since 0.17 runs ``Resize`` and ``RandomResizedCrop`` on a float tensor with ``antialias=True``: each transform and
+each factory takes ``antialias=True`` for that second definition (``hip_ops.frames_transform(..., antialias=True)``: Keys A = -0.5, a
+support that widens with the scale, weights normalised per output coordinate; two launches a batch: a small table kernel, then the
+resample).  One deviation: the hue op clamps its input to [0, 1] first.  torchvision documents float images as lying in [0, 1]; a bicubic
 overshoot pixel with max(r, g, b) <= 0 is outside its ``_rgb2hsv``'s domain (at exactly 0 it divides by zero: a non-finite pixel).  On in-range input the clamp
 is the identity.
 
@@ -22,6 +26,7 @@ The random parameters are drawn on the host from torch's CPU generator (the glob
 video shared by all of its frames -- the reference applies its transform to one video tensor --, with torchvision's calls in
 torchvision's order (``draw_augment``).  torchvision is not installed where this was written: that the random STREAM matches
 torchvision's holds by construction from its published ``get_params`` functions and was not tested against it."""
+import functools
 import math
 import numbers
 from typing import NamedTuple, Optional, Tuple
@@ -113,11 +118,11 @@ class FrameTransform:
     of per-video tensors of differing resolution and equal T (-> ``[B, T, 3, h, w]``).  ``layout="TCHW"`` takes ``[T, 3, H, W]``
     (and ``[B, T, 3, H, W]``) instead; any strides are accepted, nothing is copied."""
 
-    def __init__(self, input_res=(224, 224), norm_mean=H.CLIP_MEAN, norm_std=H.CLIP_STD, layout="THWC"):
+    def __init__(self, input_res=(224, 224), norm_mean=H.CLIP_MEAN, norm_std=H.CLIP_STD, layout="THWC", antialias=False):
         _pair(input_res, "input_res")
         if layout not in ("THWC", "TCHW"):
             raise ValueError(f"layout must be 'THWC' or 'TCHW', got {layout!r}")
-        self.input_res, self.layout = input_res, layout
+        self.input_res, self.layout, self.antialias = input_res, layout, bool(antialias)
         self.mean, self.std = tuple(float(m) for m in norm_mean), tuple(float(s) for s in norm_std)
 
     def geometry(self, H_src, W_src):
@@ -128,17 +133,22 @@ class FrameTransform:
         single, videos = _videos("FrameTransform", frames, layout or self.layout)
         geo = [self.geometry(v.shape[1], v.shape[2]) for v in videos]
         oh, ow = geo[0][1:]
-        out = H.frames_resize_norm(videos, [g for g, _, _ in geo], oh, ow, self.mean, self.std)
+        if self.antialias:
+            out = H.frames_transform(videos, [g for g, _, _ in geo], oh, ow, self.mean, self.std, antialias=True)
+        else:
+            out = H.frames_resize_norm(videos, [g for g, _, _ in geo], oh, ow, self.mean, self.std)
         return out if single else out.view(len(videos), videos[0].shape[0], 3, oh, ow)
 
 
 class TwoStageTransform(FrameTransform):
     """``init_transform_dict``'s val / test: ``Resize(video_res)``, ``CenterCrop(0.9 video_res)``, ``Resize(input_res)``, ``Normalize``,
-    bilinear (``F.interpolate(mode="bilinear", align_corners=False)``, no antialias), without an intermediate image: one launch
-    whose four taps per axis carry the product weights of the two stages.  FrameTransform's calling convention."""
+    bilinear (``F.interpolate(mode="bilinear", align_corners=False)``), without an intermediate image: one launch whose four taps per
+    axis carry the product weights of the two stages (``antialias=True``: whose table rows are the product of the two stages'
+    antialiased rows).  FrameTransform's calling convention."""
 
-    def __init__(self, video_res=(240, 320), input_res=(224, 224), norm_mean=H.CLIP_MEAN, norm_std=H.CLIP_STD, layout="THWC"):
-        super().__init__(input_res, norm_mean, norm_std, layout)
+    def __init__(self, video_res=(240, 320), input_res=(224, 224), norm_mean=H.CLIP_MEAN, norm_std=H.CLIP_STD, layout="THWC",
+                 antialias=False):
+        super().__init__(input_res, norm_mean, norm_std, layout, antialias)
         self.video_res = video_res
         two_stage_geometry(1, 1, video_res, input_res)
 
@@ -151,7 +161,8 @@ class TwoStageTransform(FrameTransform):
         single, videos = _videos("TwoStageTransform", frames, layout or self.layout)
         geo = [self.geometry(v.shape[1], v.shape[2]) for v in videos]
         oh, ow = geo[0][2:]
-        out = H.frames_transform(videos, [g[0] for g in geo], oh, ow, self.mean, self.std, two_stage=[g[1] for g in geo])
+        out = H.frames_transform(videos, [g[0] for g in geo], oh, ow, self.mean, self.std, two_stage=[g[1] for g in geo],
+                                 antialias=self.antialias)
         return out if single else out.view(len(videos), videos[0].shape[0], 3, oh, ow)
 
 
@@ -249,8 +260,8 @@ class AugmentTransform(FrameTransform):
     augmentation.  Without ``params`` the call draws (``generator=`` as for ``draw``)."""
 
     def __init__(self, input_res=(224, 224), randcrop_scale=(0.8, 1.0), color_jitter=(0, 0, 0), norm_mean=H.CLIP_MEAN,
-                 norm_std=H.CLIP_STD, layout="THWC", generator=None):
-        super().__init__(input_res, norm_mean, norm_std, layout)
+                 norm_std=H.CLIP_STD, layout="THWC", generator=None, antialias=False):
+        super().__init__(input_res, norm_mean, norm_std, layout, antialias)
         self.size = _pair(input_res, "input_res")[1]
         if not isinstance(randcrop_scale, (tuple, list)) or len(randcrop_scale) != 2 or \
                 not 0 < randcrop_scale[0] <= randcrop_scale[1]:
@@ -286,10 +297,27 @@ class AugmentTransform(FrameTransform):
         oh, ow = self.size
         geo = [self.geometry(v.shape[1], v.shape[2], p)[0] for v, p in zip(videos, params)]
         color = [p.color_ops() for p in params]
-        out = H.frames_transform(videos, geo, oh, ow, self.mean, self.std, color=color if any(color) else None)
+        out = H.frames_transform(videos, geo, oh, ow, self.mean, self.std, color=color if any(color) else None,
+                                 antialias=self.antialias)
         return out if single else out.view(len(videos), videos[0].shape[0], 3, oh, ow)
 
 
+def _with_antialias(factory):
+    """``factory`` with a trailing ``antialias=False`` (the seventh positional argument, or the keyword) that goes to all three modes.
+    The introspected signature stays the reference's six parameters (``inspect.signature`` follows ``__wrapped__``): code written
+    against the reference's factory sees the reference's factory; the keyword is this package's addition."""
+    @functools.wraps(factory)
+    def with_antialias(*args, antialias=False, **kwargs):
+        if len(args) == 7:
+            *args, antialias = args
+        modes = factory(*args, **kwargs)
+        for transform in modes.values():
+            transform.antialias = bool(antialias)
+        return modes
+    return with_antialias
+
+
+@_with_antialias
 def init_transform_dict(video_res=(240, 320),
                         input_res=(224, 224),
                         randcrop_scale=(0.8, 1.0),
@@ -302,6 +330,7 @@ def init_transform_dict(video_res=(240, 320),
             "test": TwoStageTransform(video_res, input_res, norm_mean, norm_std)}
 
 
+@_with_antialias
 def init_transform_dict_simple(video_res=(240, 320),
                                input_res=(224, 224),
                                randcrop_scale=(0.8, 1.0),
@@ -312,6 +341,7 @@ def init_transform_dict_simple(video_res=(240, 320),
     return {mode: FrameTransform(input_res, norm_mean, norm_std) for mode in ("train", "val", "test")}
 
 
+@_with_antialias
 def init_transform_dict_image(video_res=(240, 320),
                               input_res=(224, 224),
                               randcrop_scale=(0.8, 1.0),
