@@ -176,7 +176,9 @@ size_t xp_layernorm_bwd_workspace_bytes(int64_t rows, int64_t cols);
  * [dgamma | dbeta | colsum(dx)] (pitch 3*cols; the column sums of the dx just written = the bias gradient of the
  * Linear in front of this residual add); with with_dx_colsum == 2 (needs dres) [dgamma | dbeta | colsum(dx) | colsum(dres)]
  * (pitch 4*cols; in CLIPEncoderLayer's second LayerNorm, CLIP_ViP.py:455-458, dres is the layer's incoming gradient, whose
- * column sums are fc2's bias gradient) -- for xp_reduce_rows_batch. */
+ * column sums are fc2's bias gradient) -- for xp_reduce_rows_batch.
+ * colsum(dx) sums the fp32 values of dx BEFORE they are rounded to `dtype` (as the GEMM's fused column sums do): with bf16 it is
+ * not the column sum of the stored dx.  dres may alias dx here too (same pointer and pitch: every row is read before it is written). */
 int64_t xp_layernorm_bwd_partial_rows(int64_t rows);
 int xp_layernorm_bwd_partials(const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* gamma,
                               const float* mean, const float* rstd, const void* dres, int64_t lddres,

@@ -237,15 +237,27 @@ def colsum_deferred(X: torch.Tensor, rows: int, cols: int, defer: DeferredReduce
 
 # --------------------------------------------------------------------------------------- LayerNorm
 def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows: int, cols: int, ldx=None,
-                  eps: float = 1e-5, x_side=None, y_side=None, side=None):
+                  eps: float = 1e-5, x_side=None, y_side=None, side=None, ldy=None, y=None, mean=None, rstd=None):
     """``side = (S, M, stride)`` with ``x_side`` / ``y_side`` (fp32 [.., cols]): rows r with r % S < M are read from x_side
-    instead of x / also written in fp32 to y_side, at side row (r // S) * stride + r % S (xp_layernorm_fwd_side)."""
+    instead of x / also written in fp32 to y_side, at side row (r // S) * stride + r % S (xp_layernorm_fwd_side).
+    ``y`` (row pitch ``ldy``, default cols), ``mean``, ``rstd``: the caller's output buffers."""
     _chk(x, "x"); _chk(gamma, "gamma", torch.float32); _chk(beta, "beta", torch.float32)
-    y = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
-    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    ldy = ldy or cols
+    if y is None:
+        y = torch.empty((rows, ldy), dtype=x.dtype, device=x.device)
+    else:
+        _chk(y, "y", x.dtype)
+        if not y.is_contiguous() or y.numel() < (rows - 1) * ldy + cols:
+            raise ValueError("layernorm_fwd: y is too small or not contiguous")
+    for t, nm in ((mean, "mean"), (rstd, "rstd")):
+        if t is not None:
+            _chk(t, nm, torch.float32)
+            if not t.is_contiguous() or t.numel() < rows:
+                raise ValueError(f"layernorm_fwd: {nm} is too small or not contiguous")
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device) if mean is None else mean
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if rstd is None else rstd
     if x_side is None and y_side is None:
-        L.check(L.lib().xp_layernorm_fwd(_p(x), ldx or cols, _p(gamma), _p(beta), _p(y), cols, _p(mean), _p(rstd),
+        L.check(L.lib().xp_layernorm_fwd(_p(x), ldx or cols, _p(gamma), _p(beta), _p(y), ldy, _p(mean), _p(rstd),
                                          rows, cols, eps, _dt(x), _stream()), "xp_layernorm_fwd")
     else:
         S, M, stride = side
@@ -254,7 +266,7 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows
                 _chk(t, nm, torch.float32)
                 if not t.is_contiguous() or t.numel() < ((rows - 1) // S * stride + min(M, S)) * cols:
                     raise ValueError(f"layernorm_fwd: {nm} is too small or not contiguous")
-        L.check(L.lib().xp_layernorm_fwd_side(_p(x), ldx or cols, _p(gamma), _p(beta), _p(y), cols, _p(mean), _p(rstd),
+        L.check(L.lib().xp_layernorm_fwd_side(_p(x), ldx or cols, _p(gamma), _p(beta), _p(y), ldy, _p(mean), _p(rstd),
                                               rows, cols, eps, _dt(x), _p(x_side), _p(y_side), S, M, stride, _stream()),
                 "xp_layernorm_fwd_side")
     return y, mean, rstd
@@ -262,8 +274,9 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, dres=None, dx=None, lddx=None,
                   dgamma=None, dbeta=None, accumulate=False, defer: "DeferredReduce" = None, dx_colsum=False, dres_colsum=False,
-                  name="ln", x_side=None, side=None, param_grads=True):
+                  name="ln", x_side=None, side=None, param_grads=True, lddres=None):
     """Returns (dx, dgamma, dbeta) -- plus colsum(dx) when ``dx_colsum``, plus colsum(dres) when ``dres_colsum`` (deferred mode only).
+    ``lddres``: row pitch of ``dres`` (default cols); ``dres`` may be ``dx`` itself.
     ``x_side`` / ``side = (S, M, stride)``: the fp32 side rows of x the forward normalised (layernorm_fwd).
     ``param_grads=False`` (deferred mode, no column sums): dx only -- the pass's parameter-gradient partial rows stay in its slot
     and are not registered with ``defer`` (rows another pass has already counted): returns (dx, None, None)."""
@@ -283,7 +296,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, 
     if defer is not None:     # parameter-gradient partial rows stay in their own slot until defer.flush()
         ws = defer.slot(nb, name)
         L.check(L.lib().xp_layernorm_bwd_partials_side(_p(dy), lddy or cols, _p(x), ldx or cols, _p(gamma), _p(mean), _p(rstd),
-                                                       _p(dres), cols, _p(dx), lddx or cols, 2 if dres_colsum else int(dx_colsum),
+                                                       _p(dres), lddres or cols, _p(dx), lddx or cols, 2 if dres_colsum else int(dx_colsum),
                                                        rows, cols, _dt(dy), _p(x_side), S, M, stride, _p(ws), ws.numel(), _stream()),
                 "xp_layernorm_bwd_partials_side")
         if not param_grads:
@@ -307,7 +320,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, 
         raise ValueError("layernorm_bwd: dx_colsum needs a DeferredReduce")
     ws = workspace(nb, dy.device, "ln")
     L.check(L.lib().xp_layernorm_bwd_side(_p(dy), lddy or cols, _p(x), ldx or cols, _p(gamma), _p(mean), _p(rstd),
-                                          _p(dres), cols, _p(dx), lddx or cols, _p(dgamma), _p(dbeta), int(accumulate),
+                                          _p(dres), lddres or cols, _p(dx), lddx or cols, _p(dgamma), _p(dbeta), int(accumulate),
                                           rows, cols, _dt(dy), _p(x_side), S, M, stride, _p(ws), ws.numel(), _stream()),
             "xp_layernorm_bwd_side")
     return dx, dgamma, dbeta
