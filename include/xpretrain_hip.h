@@ -19,6 +19,7 @@
  *   - returns 0 on success, a negative XP_ERR_* otherwise; xp_last_error() gives the thread-local message.
  *   - `dtype`: element type of activations / GEMM operands (XP_BF16 or XP_F32).  Parameters that are read
  *     directly from the fp32 master copy (biases, LayerNorm affine, embedding tables) are always float.
+ *     Every bf16 store of an fp32 value is one round-to-nearest-even, subnormals included (see xp_cast).
  *   - sizes are int64_t elements; `ld*` are row strides in elements.
  */
 #ifndef XPRETRAIN_HIP_H
@@ -398,7 +399,11 @@ int xp_frames_transform_aa(const XpFrameTransform* videos_host, int32_t n_videos
 /* proxy rows: x[b, 0] = class_emb + pos[0]; x[b, 1+i] = added_cls[i] + pos[0]   (:187-191) */
 int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const float* pos, void* x,
                       int64_t B, int64_t S, int64_t M, int64_t D, int32_t dtype, void* stream);
-/* gradients of class_embedding, added_cls, position_embedding[1+L], time table [T,D] from dx[B,S,D] */
+/* gradients of class_embedding, added_cls, position_embedding[1+L], time table [T,D] from dx[B,S,D], S = M + T*L; each is an
+ * fp32 sum in a fixed order (bit-reproducible) that is stored (accumulate == 0) or added to the destination with one add
+ * (accumulate != 0).  LIMIT: D % 4 == 0 and D <= 1024 (one 256-thread block, four columns per lane); a larger D is refused.
+ * d_added may be NULL when M == 1; d_time may be NULL (then no workspace is needed), otherwise `workspace` holds at least
+ * xp_vip_embed_bwd_workspace_bytes(B, T, L, D) bytes.  Every refusal comes before the first launch: a refused call writes nothing. */
 size_t xp_vip_embed_bwd_workspace_bytes(int64_t B, int64_t T, int64_t L, int64_t D);
 int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, float* d_pos, float* d_time,
                      int64_t B, int64_t M, int64_t T, int64_t L, int64_t D, int32_t dtype, int32_t accumulate,
@@ -423,18 +428,25 @@ int xp_pos_resample_bwd(const float* d_out, float* d_pos, int32_t g0, int32_t gh
 int xp_text_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void* x,
                       int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, void* stream);
 /* d_tok[id] (+)= sum of dx[b,t] over the occurrences of id in (b,t) order (fixed order, no atomics: bit-reproducible);
- * d_pos[t] (+)= sum_b dx[b,t] */
+ * d_pos[t] (+)= sum_b dx[b,t].  The rows of d_tok whose id does not occur in ids are zero with accumulate == 0 (all `vocab` rows
+ * are cleared by one hipMemsetAsync on `stream`) and are left untouched with accumulate != 0.  Only rows 0 .. Lt-1 of d_pos are
+ * written, in either mode: a longer position table keeps its other rows.  ids are not range-checked on the device. */
 int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_tok, float* d_pos,
                       int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, int32_t accumulate, void* stream);
 /* pooled[b] = x[b, idx[b]] (text: idx = ids.argmax(-1), :776 ; vision: idx = 0, :892) and its scatter */
 int xp_argmax_rows(const int64_t* ids, int64_t* idx, int64_t B, int64_t Lt, void* stream);
 int xp_gather_rows(const void* x, const int64_t* idx, void* out, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream);
 int xp_scatter_rows(const void* dout, const int64_t* idx, void* dx, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream);
-/* x / ||x||_2 per row (:1148-1149); in `dtype`, out fp32 features; inv_norm saved */
+/* x / ||x||_2 per row (:1148-1149); in `dtype`, out fp32 features; inv_norm saved.  No epsilon, like the reference's
+ * x / x.norm(dim=-1, keepdim=True): a row of zeros gives inv_norm = +inf and a row of NaN in y (and in xp_l2norm_bwd's dx); the
+ * other rows are not affected. */
 int xp_l2norm_fwd(const void* x, float* y, float* inv_norm, int64_t rows, int64_t cols, int32_t dtype, void* stream);
 int xp_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, void* dx, int64_t rows, int64_t cols,
                   int32_t dtype, void* stream);
-/* fp32 master -> compute dtype copy */
+/* fp32 master -> compute dtype copy (n % 4 == 0).  To bf16 it is round-to-nearest-even: ties to the even mantissa, a carry may
+ * reach the exponent, values from 0x7F7F8000 up round to infinity, infinities and the sign of zero are kept, a NaN stays a NaN, and
+ * fp32 subnormals are NOT flushed: they round onto the bf16 subnormals (measured on MI355X, tests/test_embed_contract_gpu.py).
+ * xp_cast_back widens exactly; with accumulate != 0 it is dst = src + dst, one add per element. */
 int xp_cast(const float* src, void* dst, int64_t n, int32_t dtype, void* stream);
 int xp_cast_back(const void* src, float* dst, int64_t n, int32_t dtype, int32_t accumulate, void* stream);
 

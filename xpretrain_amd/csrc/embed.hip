@@ -347,6 +347,10 @@ extern "C" int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, 
                                 void* workspace, size_t workspace_bytes, void* stream) {
   XP_REQUIRE(dx && d_class && d_pos && (M == 1 || d_added), "xp_vip_embed_bwd: null pointer");
   XP_REQUIRE(D % 4 == 0 && D <= 1024 && B > 0 && T > 0 && L > 0 && M >= 1, "xp_vip_embed_bwd: bad sizes (D<=1024, D%%4==0)");
+  // every refusal comes before the first launch: a refused call writes nothing
+  XP_REQUIRE(dtype == XP_BF16 || dtype == XP_F32, "xp_vip_embed_bwd: bad dtype %d", (int)dtype);
+  XP_REQUIRE(!d_time || (workspace && workspace_bytes >= xp_vip_embed_bwd_workspace_bytes(B, T, L, D)),
+             "xp_vip_embed_bwd: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype,
            (vip_embed_bwd_pos_kernel<bf16_t><<<(unsigned)(L + M + 1), 256, 0, st>>>((const bf16_t*)dx, d_class, d_added, d_pos, B, (int)M, (int)T, (int)L, (int)D, accumulate)),
@@ -354,7 +358,6 @@ extern "C" int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, 
            "xp_vip_embed_bwd");
   XP_CHECK_LAUNCH("xp_vip_embed_bwd(pos)");
   if (d_time) {
-    XP_REQUIRE(workspace && workspace_bytes >= xp_vip_embed_bwd_workspace_bytes(B, T, L, D), "xp_vip_embed_bwd: workspace too small");
     float* part = (float*)workspace;
     DISPATCH(dtype,
              (vip_embed_bwd_time_kernel<bf16_t><<<(unsigned)(B * T), 256, 0, st>>>((const bf16_t*)dx, part, (int)M, (int)T, (int)L, (int)D)),
@@ -380,6 +383,7 @@ extern "C" int xp_text_embed_fwd(const int64_t* ids, const float* tok, const flo
 extern "C" int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_tok, float* d_pos,
                                  int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, int32_t accumulate, void* stream) {
   XP_REQUIRE(ids && dx && d_tok && d_pos && B > 0 && Lt > 0 && D % 4 == 0 && vocab > 0, "xp_text_embed_bwd: bad arguments");
+  XP_REQUIRE(dtype == XP_BF16 || dtype == XP_F32, "xp_text_embed_bwd: bad dtype %d", (int)dtype);     // before the memset: a refused call writes nothing
   hipStream_t st = (hipStream_t)stream;
   if (!accumulate) {
     hipError_t e = hipMemsetAsync(d_tok, 0, (size_t)vocab * D * sizeof(float), st);
