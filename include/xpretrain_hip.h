@@ -216,6 +216,10 @@ int xp_layernorm_bwd_side(const void* dy, int64_t lddy, const void* x, int64_t l
  *                       int64 [B,S] (1 = keep) or NULL.  M,N,L ignored (pass 0,1,S).
  *
  * out[B,S,H*64] (row stride ldo).  stats[B,H,S,2] fp32 = (row max, log row sum) for the backward.
+ *
+ * Addressing limit (bf16; xp_attn_fwd, xp_attn_bwd, xp_attn_bwd2): the kernels reach one sample's rows through 32-bit offsets, so
+ * S*ldqkv*2 and S*ldo*2 (the bytes from a sample's first row to its last) must both be < 4 GiB - 256 (0xFFFFFF00); a larger pitch
+ * is refused with XP_ERR_ARG before any launch.  The whole operand (B samples) may be of any size.  fp32 mode has no such limit.
  */
 enum { XP_ATTN_PROXY = 0, XP_ATTN_CAUSAL = 1 };
 size_t xp_attn_workspace_bytes(int32_t mode, int64_t B, int64_t H, int64_t M, int64_t N, int64_t L);

@@ -1770,6 +1770,13 @@ int check_common(const char* name, int32_t mode, int64_t B, int64_t H, int64_t S
                                         name, (long long)S, (long long)M, (long long)N, (long long)L);
   XP_REQUIRE(ldqkv >= 3 * H * DH && ldqkv % 8 == 0 && ldo >= H * DH && ldo % 8 == 0, "%s: bad leading dimensions", name);
   XP_REQUIRE(B * H * (mode == XP_ATTN_PROXY ? N : 1) <= 65535 * 32, "%s: too many problems", name);
+  // bf16 kernels: the loaders address one sample through a buffer resource of S * ld * 2 bytes with 32-bit token * pitch offsets
+  // (rsrc_q / rsrc_kv / rsrc_o), and OOB must stay out of range.  (The fp32 kernels use 64-bit pointers throughout.)
+  if (dtype == XP_BF16)
+    XP_REQUIRE(S * ldqkv * 2 < (int64_t)OOB && S * ldo * 2 < (int64_t)OOB,
+               "%s: one sample's rows span S*ldqkv*2 = %lld / S*ldo*2 = %lld bytes; the bf16 kernels address a sample with 32-bit "
+               "offsets: both must stay below 4 GiB - 256 (%lld)", name, (long long)(S * ldqkv * 2), (long long)(S * ldo * 2),
+               (long long)OOB);
   return XP_OK;
 }
 
