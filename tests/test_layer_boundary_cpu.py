@@ -111,7 +111,9 @@ def _four_structs(kind, dtype, training=True):
 def test_the_table_covers_every_pointer_of_the_four_structs(kind, dtype):
     """A training pass (with side rows in bf16): every pointer field is set but ``pad_mask`` of a video layer, the side pointers of
     an fp32 pass -- and ``workspace``, which building a struct leaves alone (_call_native takes it at the launch).  A forward-only
-    pass nulls exactly ``pre`` (and the dense forward's ``side_x2``).  The pieces sit 256-byte aligned, disjoint, inside the arena."""
+    pass nulls exactly ``pre`` (and the dense forward's ``side_x2``).  The pieces sit 256-byte aligned, disjoint, inside the arena, and the
+    typed views of the op-by-op path (_piece_views) are those pieces: same addresses as the struct fields, each exactly its piece."""
+    import xpretrain_amd.functional as XF
     sides = {"side_in", "side_out", "side_x2"}
     for training in (True, False):
         structs = _four_structs(kind, dtype, training)
@@ -134,6 +136,18 @@ def test_the_table_covers_every_pointer_of_the_four_structs(kind, dtype):
                     assert getattr(a, name) == arena.data_ptr() + off
                 end = off + n * bpr
             assert end <= plan.arena_bytes == arena.numel()
+            # the typed views the op-by-op sequencers compute through: one per piece, at the address the struct field of the same
+            # name holds, covering exactly its piece, in the dtype and shape the hip_ops wrappers expect
+            views = XF._piece_views(plan, arena)
+            assert list(views) == [n for n, _, _ in plan.pieces]
+            for (name, n, bpr), (_, off, _) in zip(plan.pieces, plan.fill):
+                v = views[name]
+                f32 = name == "stats" or name[:4] in ("mean", "rstd")          # (fp32 statistics: flat, taken by element count)
+                assert v.dtype == (torch.float32 if f32 else dtype) and v.is_contiguous(), name
+                assert tuple(v.shape) == ((n * bpr // 4,) if f32 else (n, bpr // v.element_size())), name
+                assert v.data_ptr() == arena.data_ptr() + off and v.numel() * v.element_size() == n * bpr, name
+                if getattr(a, name):
+                    assert v.data_ptr() == getattr(a, name), name
             # ... and nothing but the pieces points into the arena
             inside = {n for n in _pointer_fields(a) if arena.data_ptr() <= (getattr(a, n) or 0) < arena.data_ptr() + arena.numel()}
             assert inside == {n for n, _, _ in plan.pieces} - null

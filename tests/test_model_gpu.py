@@ -347,6 +347,78 @@ def test_native_layer_calls_equal_the_op_by_op_path(dtype):
             assert torch.equal(g0[n], g1[n]), n
 
 
+LAYER_CASES = [(torch.bfloat16, True), (torch.bfloat16, False), (torch.float32, False)]
+LAYER_IDS = ["bf16-side", "bf16", "fp32"]
+
+
+def _dense_layer_case(kind, dtype, sided):
+    """EncoderLayerFn's arguments at the tiny shape (B 4, S 10, D 128, heads 2, Dff 512): the video layer of size (2, 2, 4) with
+    [B*M, D] side rows, or the causal text layer whose int64 padding mask keeps 10, 7, 3 and 1 keys, with [B*S, D] side rows"""
+    from tests.layer_paths import layer_input, layer_params
+    B, S, size, D, heads, Dff = 4, 10, (2, 2, 4), 128, 2, 512
+    params = layer_params(D, Dff)
+    pad = None
+    if kind == "text":
+        size = None
+        pad = (torch.arange(S, device="cuda")[None, :] < torch.tensor([10, 7, 3, 1], device="cuda")[:, None]).to(torch.int64)
+    x, side = layer_input(B, S, D, dtype, (size[0] if size else S) if sided else 0)
+    return x, params, (B, S, heads, size, pad, True, side), torch.randn(B * S, D, device="cuda")
+
+
+@pytest.mark.parametrize("dtype,sided", LAYER_CASES, ids=LAYER_IDS)
+@pytest.mark.parametrize("kind", ["video", "text"])
+def test_one_dense_layer_saves_and_returns_the_same_bits_on_either_path(kind, dtype, sided):
+    """EncoderLayerFn applied directly with LAYER_CALLS on and off: both sequencers fill the same arena -- every saved piece equal
+    view by view (the bytes between the 256-aligned pieces are nobody's) -- and give the same x3, side_out, side_x2, dx and sixteen
+    gradients; again with a frozen subset, whose gradients are None on both paths"""
+    import xpretrain_amd.functional as XF
+    from tests.layer_paths import FROZEN, both_paths
+    x, params, tail, w = _dense_layer_case(kind, dtype, sided)
+    for frozen in ((), FROZEN):
+        got = both_paths(XF.EncoderLayerFn, x, params, tail, w, frozen)
+        assert len([n for n in got if n.startswith("piece:")]) == 12
+        assert (got["side_out"] is not None) == (got["side_x2"] is not None) == sided
+
+
+def test_either_path_writes_the_layer_gradients_into_a_claimed_sink():
+    """with the layer's sink registered in XF.GRAD_SINKS and every .grad None, the native and the op-by-op backward both return
+    gradients that ARE the sink's slices, and leave the same bytes there; with one .grad already set (gradient accumulation)
+    neither touches the sink"""
+    import xpretrain_amd.functional as XF
+    from tests.layer_paths import PARAMS, assert_same, run_layer
+    x, params, tail, w = _dense_layer_case("video", torch.bfloat16, True)
+    by = dict(zip(PARAMS, params))
+    flat_order = [by[n] for n in ("ln1_w", "ln1_b", "wq", "wk", "wv", "bq", "bk", "bv", "wo", "bo", "ln2_w", "ln2_b", "w1", "b1", "w2", "b2")]
+    key = XF.grad_sink_key(flat_order)
+    sink = torch.empty(sum(p.numel() for p in flat_order), device="cuda")
+    XF.GRAD_SINKS[key] = sink
+    try:
+        filled = []
+        for native in (True, False):
+            for t in [x] + params:
+                t.grad = None
+            sink.fill_(float("nan"))
+            got = run_layer(XF.EncoderLayerFn, native, x, params, tail, w)
+            off = 0
+            for p in flat_order:
+                assert p.grad.data_ptr() == sink.data_ptr() + 4 * off, "a gradient is not its slice of the sink"
+                off += p.numel()
+            filled.append(({n: None if t is None else t.clone() for n, t in got.items()}, sink.clone()))      # (copies: the next run rewrites the sink)
+        assert_same(filled[0][0], filled[1][0])
+        assert not torch.isnan(filled[0][1]).any() and torch.equal(filled[0][1], filled[1][1])
+        for native in (True, False):
+            for t in [x] + params:
+                t.grad = None
+            by["w2"].grad = torch.zeros_like(by["w2"])
+            sink.fill_(float("nan"))
+            got = run_layer(XF.EncoderLayerFn, native, x, params, tail, w)
+            assert torch.isnan(sink).all()
+            assert_same(got, filled[0][0])
+    finally:
+        XF.GRAD_SINKS.pop(key, None)
+        XF.release_grad_sinks()
+
+
 def test_gradient_checkpointing_recomputes_bit_identically():
     """CLIPEncoder.gradient_checkpointing (reference CLIP_ViP.py:626,675-690): with it the saved-activation arenas are dropped after the
     forward and every layer is re-run when its backward starts -- same kernels, same inputs: features, loss and all gradients are

@@ -234,6 +234,60 @@ def test_pooled_op_by_op_backward_makes_every_layernorm_call_through_hip_ops(mon
         assert torch.equal(a, b), f"gradient {i} differs between the native call and the op-by-op path"
 
 
+def _pooled_layer_case(dtype, sided):
+    """PooledEncoderLayerFn's arguments at the one-layer shape: B 2, S 9 = 1 + 2*4, D 128, heads 2, Dff 512"""
+    from tests.layer_paths import layer_input, layer_params
+    B, S, size, D, heads, Dff = 2, 9, (1, 2, 4), 128, 2, 512
+    params = layer_params(D, Dff)
+    x, side = layer_input(B, S, D, dtype, size[0] if sided else 0)
+    return x, params, (B, S, heads, size, True, side), torch.randn(B, D, device="cuda")
+
+
+@pytest.mark.parametrize("dtype,sided", [(torch.bfloat16, True), (torch.float32, False)], ids=["bf16-side", "fp32"])
+def test_one_pooled_layer_saves_and_returns_the_same_bits_on_either_path(dtype, sided):
+    """PooledEncoderLayerFn applied directly with LAYER_CALLS on and off: both sequencers fill the same arena -- all sixteen saved
+    pieces equal view by view -- and give the same x3, side_out, side_x2, dx and sixteen gradients; again with a frozen subset,
+    whose gradients are None on both paths"""
+    import xpretrain_amd.functional as XF
+    from tests.layer_paths import FROZEN, both_paths
+    x, params, tail, w = _pooled_layer_case(dtype, sided)
+    for frozen in ((), FROZEN):
+        got = both_paths(XF.PooledEncoderLayerFn, x, params, tail, w, frozen)
+        assert len([n for n in got if n.startswith("piece:")]) == 16
+        assert (got["side_out"] is not None) == (got["side_x2"] is not None) == sided
+
+
+def test_pooled_op_by_op_backward_runs_under_the_fingerprinting_wrappers():
+    """tools/determinism_hunt.install wraps every hip_ops entry (and replaces colsum_deferred): one pooled op-by-op pass at the
+    one-layer shape completes under it -- the replacement forwards ``out=`` -- records fingerprints, and gives the native gradients"""
+    import importlib.util
+    import os
+    import xpretrain_amd.functional as XF
+    from xpretrain_amd import hip_ops as H
+    from tests.layer_paths import assert_same, run_layer
+    spec = importlib.util.spec_from_file_location(
+        "determinism_hunt", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "determinism_hunt.py"))
+    hunt = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(hunt)
+    x, params, tail, w = _pooled_layer_case(torch.bfloat16, True)
+    native = run_layer(XF.PooledEncoderLayerFn, True, x, params, tail, w)
+    for t in [x] + params:
+        t.grad = None
+    rec = hunt.Recorder("sum")
+    saved, flush = dict(vars(H)), H.DeferredReduce.flush
+    try:
+        hunt.install(rec)
+        ops = run_layer(XF.PooledEncoderLayerFn, False, x, params, tail, w)
+    finally:
+        for n, f in saved.items():
+            setattr(H, n, f)
+        H.DeferredReduce.flush = flush
+    assert_same(native, ops)
+    labels = [l for l, _ in rec.items]
+    assert sum(l.startswith("colsum_deferred") for l in labels) == 2 and not rec.deferred      # db1 and dbq, finished by the flush
+    assert any(l.startswith("attn_pooled_bwd") for l in labels) and sum(l.startswith("layernorm_bwd") for l in labels) >= 3
+
+
 # ------------------------------------------------------------------------------------------------ where the switch applies
 def test_switch_falls_back_to_dense_where_the_stream_is_read(monkeypatch):
     """output_hidden_states=True, the vision tower called directly, a forward hook on the last layer: torch.equal to the

@@ -106,7 +106,7 @@ def install(rec):
                 r = orig(*a, **kw)
                 outs = [t for t in tensors_in(r) if t.dtype != torch.uint8]      # uint8 = untyped workspaces
                 seen = {t.data_ptr() for t in outs}
-                for key in ("out", "dx", "dgamma", "dbeta", "aux"):
+                for key in ("out", "dx", "dgamma", "dbeta", "aux", "stats", "colsum_out", "dx_colsum_out", "dres_colsum_out"):
                     t = kw.get(key)
                     if isinstance(t, torch.Tensor) and t.data_ptr() not in seen and t.dtype != torch.uint8:
                         outs.append(t)
@@ -124,8 +124,8 @@ def install(rec):
     # colsum_deferred: its output is final only after flush
     orig_cd = H.colsum_deferred
 
-    def cd(X, rows, cols, defer, ldx=None, name="colsum"):
-        out = orig_cd(X, rows, cols, defer, ldx=ldx, name=name)
+    def cd(X, rows, cols, defer, **kw):
+        out = orig_cd(X, rows, cols, defer, **kw)
         rec.add("colsum_deferred", [out], {out.data_ptr()})
         return out
     H.colsum_deferred = cd

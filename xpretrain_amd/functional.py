@@ -164,7 +164,7 @@ def _wgrad(dy: torch.Tensor, x: torch.Tensor, rows: int, n_out: int, n_in: int, 
     ``ldx``, split-K), into ``out`` when given."""
     lddy, ldx = lddy or n_out, ldx or n_in
     split = _split_for(n_out, n_in, rows, dy.dtype, tuple(a_remap), slack, lddy, ldx)
-    dw = torch.empty((n_out, n_in), dtype=torch.float32, device=dy.device) if out is None else out
+    dw = torch.empty((n_out, n_in), dtype=torch.float32, device=dy.device) if out is None else out.view(n_out, n_in)
     if split <= 1:
         H.gemm(dy, x, n_out, n_in, rows, a_kstrided=True, b_kstrided=True, lda=lddy, ldb=ldx, out=dw,
                out_dtype=torch.float32, a_remap=a_remap)
@@ -206,9 +206,22 @@ def _arena_layout(pieces):
     return tuple(fill), o
 
 
-def _finish_plan(plan, dims, rD, pieces, queries):
+def _piece_views(plan, arena):
+    """The saved pieces of ``arena`` as tensors by field name, as the hip_ops wrappers take them (the op-by-op sequencers' buffers;
+    the native calls take the same addresses from _layer_args): [n, .] matrices in the compute dtype; the LayerNorm and attention
+    statistics flat in fp32 (the wrappers take those by element count)."""
+    views = {}
+    for (name, n, bpr), (_, o, _) in zip(plan.pieces, plan.fill):
+        raw = arena[o:o + n * bpr]
+        views[name] = raw.view(torch.float32) if name[:4] in ("mean", "rstd", "stat") else raw.view(plan.dtype).view(n, -1)
+    return views
+
+
+def _finish_plan(plan, dims, dtype, pieces, queries):
     """what _LayerPlan and _PooledLayerPlan derive from their table of saved pieces and their two workspace queries"""
-    plan.dims, plan.pieces, plan.rD, plan.side_row = dims, pieces, rD, dims.D * 4      # rD: bytes of a [., D] compute-dtype row
+    plan.dims, plan.pieces, plan.dtype, plan.side_row = dims, pieces, dtype, dims.D * 4
+    plan.rD, plan.size = dims.D * _ES[dtype], (dims.M, dims.N, dims.L) if dims.attn_mode == L.ATTN_PROXY else None
+    # (rD: bytes of a [., D] compute-dtype row; size: None for the causal text layer)
     plan.side_S, plan.side_M = (dims.S, dims.M) if dims.attn_mode == L.ATTN_PROXY else (1, 1)      # fp32 side rows: [B*M, D] / [rows, D]
     plan.fill, plan.arena_bytes = _arena_layout(pieces)
     plan.fwd_ws, plan.bwd_ws = (int(getattr(L.lib(), q)(C.byref(dims))) for q in queries)
@@ -235,7 +248,7 @@ class _LayerPlan:
         d.dtype, d.q_scale, d.ln_eps = _DT_CODE[dtype], (D // heads) ** -0.5, 1e-5
         d.act = act                 # the MLP's activation (L.ACTS): the fc1 / dpre epilogue kinds the native stages pick
         rD, rF = D * _ES[dtype], Dff * _ES[dtype]      # bytes of a [., D] / [., Dff] row
-        _finish_plan(self, d, rD, (("h1", rows, rD), ("qkv", rows, 3 * rD), ("attn_o", rows, rD), ("x2", rows, rD), ("h2", rows, rD),
+        _finish_plan(self, d, dtype, (("h1", rows, rD), ("qkv", rows, 3 * rD), ("attn_o", rows, rD), ("x2", rows, rD), ("h2", rows, rD),
                                    ("pre", rows, rF), ("act", rows, rF), ("mean1", rows, 4), ("rstd1", rows, 4), ("mean2", rows, 4),
                                    ("rstd2", rows, 4), ("stats", rows, heads * 2 * 4)),
                      ("xp_encoder_layer_fwd_workspace_bytes", "xp_encoder_layer_bwd_workspace_bytes"))
@@ -466,13 +479,8 @@ def _layer_fwd_args(plan, dims, x, params, pad_mask, arena, x3, keep_pre, side, 
     return a
 
 
-def _layer_fwd_native(x, params, plan, pad_mask, keep_pre=True, side=None, split=None):
-    dev = x.device
-    arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
-    x3 = torch.empty_like(x)
-    side_out = None if side is None else torch.empty_like(side)
-    side_x2 = torch.empty_like(side) if side is not None and keep_pre else None      # training: kept for the backward's second LayerNorm
-    d = plan.dims
+def _layer_fwd_native(plan, x, params, pad_mask, arena, x3, keep_pre, side, side_out, side_x2, split):
+    dev, d = x.device, plan.dims
     if split is None:
         parts = [(plan, 0, None)]
     else:                       # two half-batch chains: (plan of half the batch, first row, stream)
@@ -484,7 +492,6 @@ def _layer_fwd_native(x, params, plan, pad_mask, keep_pre=True, side=None, split
         with (torch.cuda.stream(stream) if stream is not None else _NULLCTX):
             a = _layer_fwd_args(plan, pl.dims, x, params, pad_mask, arena, x3, keep_pre, side, side_out, side_x2, r0)
             _call_native("xp_encoder_layer_fwd", a, pl.fwd_ws, dev, "layer_fwd")
-    return x3, arena, side_out, side_x2
 
 
 # Gradient sinks (distributed.GradBucketReducer(layout_groups=...)): flat fp32 buffers -- slices of the reducer's all-reduce
@@ -552,12 +559,13 @@ def _qkv_grads(dwqkv, dbqkv, need, D):
             pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]))
 
 
-def _run_native_bwd(ctx, build, entry, ws_tag, plan, x, *rest):
-    """The parameter-gradient plumbing of a native layer backward and the call itself.  ``build(plan, x, *rest, dx, grads)``: the
-    argument struct of ``entry`` (_layer_bwd_args for xp_encoder_layer_bwd, _pooled_bwd_args for xp_encoder_layer_pooled_bwd).  The
-    gradients go to the layer's sink or a private flat buffer (plan.gnames order); a frozen parameter's pointer stays NULL.
-    Returns the 17 leading outputs of the Function's backward: dx and the gradients in forward's argument order."""
-    dev, need = x.device, ctx.needs_input_grad
+def _layer_backward(ctx, build, entry, ws_tag, ops, x, *rest):
+    """The parameter-gradient plumbing of a layer backward and the pass itself: the native call ``entry`` on the argument struct
+    ``build(plan, x, *rest, dx, grads)`` (_layer_bwd_args / _pooled_bwd_args) or, where the forward ran op by op, the sequencer
+    ``ops`` on the same arguments.  The gradients go to the layer's sink or a private flat buffer (plan.gnames order); a frozen
+    parameter has no entry in ``grads`` (natively: its pointer stays NULL).  Returns the 17 leading outputs of the Function's
+    backward: dx and the gradients in forward's argument order."""
+    plan, dev, need = ctx.plan, x.device, ctx.needs_input_grad
     flat = None
     if GRAD_SINKS and ctx.sink_key is not None and all(need[1:17]):
         flat = _claim_sink(ctx.sink_key, GRAD_SINKS.get(ctx.sink_key), plan.gtotal, dev, ctx.sink_params)
@@ -568,7 +576,10 @@ def _run_native_bwd(ctx, build, entry, ws_tag, plan, x, *rest):
                 dwo=need[9], dbo=need[10], dln2_w=need[11], dln2_b=need[12], dw1=need[13], db1=need[14], dw2=need[15], db2=need[16])
     g = {name: t for name, t in zip(plan.gnames, flat.split_with_sizes(plan.gsizes)) if want[name]}
     dx = torch.empty_like(x)
-    _call_native(entry, build(plan, x, *rest, dx, g), plan.bwd_ws, dev, ws_tag)
+    if ctx.native:
+        _call_native(entry, build(plan, x, *rest, dx, g), plan.bwd_ws, dev, ws_tag)
+    else:
+        ops(plan, x, *rest, dx, g)
     D, Dff = plan.dims.D, plan.dims.Dff
     gw = lambda n, shape: g[n].view(shape) if n in g else None
     return (dx, g.get("dln1_w"), g.get("dln1_b"), *_qkv_grads(gw("dwqkv", (3 * D, D)), g.get("dbqkv"), need, D),
@@ -588,50 +599,99 @@ def _layer_bwd_args(plan, x, params, arena, dx3, pad_mask, side, side_x2, dx, gr
 # The same entry points in the same order with the same arguments as csrc/layer.hip issues them (XPRETRAIN_DEBUG=op_by_op, or
 # arguments the native calls do not take).  The stages the dense and the pooled layer share are written once, as in layer.hip
 # (out_proj_mlp_fwd, mlp_out_proj_bwd): out_proj onward over ``n`` rows -- all rows, or the B pooled ones.  Every operator is
-# looked up on ``H`` at call time (tools/determinism_hunt.py wraps those attributes).
-def _mlp_fwd_ops(x, ldr, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, n, training, side_x, side_x2, side_out, sd, out=None,
-                 act=L.ACT_QUICK_GELU):
-    """x2 = x + attn_o Wo^T + bo (x read with row pitch ``ldr``), x3 = x2 + fc2(act(fc1(LN2(x2)))), into ``out`` when given.
+# looked up on ``H`` at call time (tools/determinism_hunt.py wraps those attributes).  The four sequencers (_layer_fwd_ops,
+# _layer_bwd_ops, _pooled_fwd_ops, _pooled_bwd_ops) take what the native calls take -- the arena (as _piece_views), the outputs, the
+# named slices of the flat gradient buffer -- so the Functions save, and _layer_backward plumbs, one thing whoever issues the launches;
+# only the workspace temporaries (dpre, dqkv ...) are torch allocations here.
+def _attn_front_ops(v, x, ln1_w, ln1_b, Wqkv, bqkv, B, S, heads, size, pad_mask, side, lns):
+    """h1 = LN1(x), qkv = h1 Wqkv^T + bqkv (q columns scaled), the fused attention forward: into the buffers ``v`` names (h1, mean1,
+    rstd1, qkv, attn_o, stats; one it does not name is allocated).  Returns ``(qkv, stats)``."""
+    rows, D = x.shape
+    h1, _, _ = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns, y=v.get("h1"), mean=v.get("mean1"), rstd=v.get("rstd1"))
+    qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=64 ** -0.5, scale_cols=D, out=v.get("qkv"))
+    _, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask, out=v.get("attn_o"), stats=v.get("stats"))
+    return qkv, stats
+
+
+def _mlp_fwd_ops(v, p, x, ldr, n, training, side_x, side_x2, side_out, sd, x3, act):
+    """x2 = x + attn_o Wo^T + bo (x read with row pitch ``ldr``), x3 = x2 + fc2(act(fc1(LN2(x2)))) over ``n`` rows, from attn_o of the
+    saved pieces ``v`` into its x2, h2, mean2, rstd2, act (``training``: and pre) and into ``x3``.  ``p``: the parameters by _FWD_PARAMS name.
     ``sd = (S, M)``: geometry of the fp32 side rows of the n rows (``side_x`` of x, ``side_x2`` / ``side_out`` written), or None.
     ``act``: the activation (L.ACT_*), i.e. which of the two fc1 epilogue kinds runs."""
-    D, Dff = Wo.shape[0], W1.shape[0]
+    D, Dff = p["Wo"].shape[0], p["W1"].shape[0]
     lns = None if sd is None else (sd[0], sd[1], sd[1])
-    x2 = H.gemm(attn_o, Wo, n, D, D, epilogue=L.EPI_BIAS_RESID, bias=bo.detach(), resid=x, ldr=ldr,
+    x2 = H.gemm(v["attn_o"], p["Wo"], n, D, D, epilogue=L.EPI_BIAS_RESID, bias=p["bo"].detach(), resid=x, ldr=ldr, out=v["x2"],
                 resid_side=side_x, out_side=side_x2, side=sd)
-    h2, mean2, rstd2 = H.layernorm_fwd(x2, ln2_w, ln2_b, n, D, x_side=side_x2, side=lns)
-    pre = torch.empty((n, Dff), dtype=x.dtype, device=x.device) if training else None
-    a = H.gemm(h2, W1, n, Dff, D, epilogue=L.EPI_ACT_FWD[act], bias=b1.detach(), aux=pre)
-    x3 = H.gemm(a, W2, n, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=b2.detach(), resid=x2, out=out,
-                resid_side=side_x2, out_side=side_out, side=sd)
-    return x2, mean2, rstd2, h2, pre, a, x3
+    h2, _, _ = H.layernorm_fwd(x2, p["ln2_w"], p["ln2_b"], n, D, x_side=side_x2, side=lns, y=v["h2"], mean=v["mean2"], rstd=v["rstd2"])
+    a = H.gemm(h2, p["W1"], n, Dff, D, epilogue=L.EPI_ACT_FWD[act], bias=p["b1"].detach(), aux=v["pre"] if training else None,
+               out=v["act"])
+    H.gemm(a, p["W2"], n, D, Dff, epilogue=L.EPI_BIAS_RESID, bias=p["b2"].detach(), resid=x2, out=x3,
+           resid_side=side_x2, out_side=side_out, side=sd)
 
 
-def _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, n, need, defer, db1_fused, side_x2, lns,
-                 act_kind=L.ACT_QUICK_GELU):
-    """The backward of ``_mlp_fwd_ops`` down to ``dattn = dx2 . Wo``: returns ``(dx2, dattn, dwo, dbo, dln2_w, dln2_b, dw1, db1,
-    dw2, db2)``; the bias / LayerNorm gradients are final after ``defer.flush()``, frozen weights' gradients are None (``need``:
-    the Function's needs_input_grad).  ``db1_fused``: fc1's bias gradient out of the dpre GEMM's epilogue where the library offers
-    it (the dense layer), else always a column-sum pass over dpre (the pooled layer).  ``act_kind``: the activation (L.ACT_*) whose
-    derivative the dpre epilogue applies."""
-    D, Dff = Wo.shape[0], W1.shape[0]
-    epi = L.EPI_ACT_BWD[act_kind]
-    if need[14] and db1_fused:
-        dpre, db1 = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=epi, resid=pre, colsum_defer=defer,
-                           colsum_name="db1")
+def _mlp_bwd_ops(v, p, g, dx3, n, defer, db1_fused, side_x2, lns, act):
+    """The backward of ``_mlp_fwd_ops`` down to ``dattn = dx2 . Wo``: returns ``(dx2, dattn)`` and writes the gradients ``g`` names
+    (final after ``defer.flush()``; without a name a weight's GEMM and fc1's bias sum are skipped, a sum that rides on the LayerNorm
+    pass lands in a buffer nobody reads).  ``p``: the parameters by _BWD_PARAMS name.  ``db1_fused``: fc1's bias gradient out of the
+    dpre GEMM's epilogue where the library offers it (the dense layer), else always a column-sum pass over dpre (the pooled layer).
+    ``act``: the activation (L.ACT_*) whose derivative the dpre epilogue applies."""
+    D, Dff = p["Wo"].shape[0], p["W1"].shape[0]
+    epi = L.EPI_ACT_BWD[act]
+    if "db1" in g and db1_fused:
+        dpre, _ = H.gemm(dx3, p["W2"], n, Dff, D, b_kstrided=True, epilogue=epi, resid=v["pre"], colsum_defer=defer,
+                         colsum_name="db1", colsum_out=g["db1"])
     else:
-        dpre = H.gemm(dx3, W2, n, Dff, D, b_kstrided=True, epilogue=epi, resid=pre)
-        db1 = H.colsum_deferred(dpre, n, Dff, defer, name="db1") if need[14] else None
-    dw2 = _wgrad(dx3, act, n, D, Dff, slack=True) if need[15] else None
-    dh2 = H.gemm(dpre, W1, n, D, Dff, b_kstrided=True)
-    dw1 = _wgrad(dpre, h2, n, Dff, D, slack=True) if need[13] else None
+        dpre = H.gemm(dx3, p["W2"], n, Dff, D, b_kstrided=True, epilogue=epi, resid=v["pre"])
+        if "db1" in g:
+            H.colsum_deferred(dpre, n, Dff, defer, name="db1", out=g["db1"])
+    if "dw2" in g:
+        _wgrad(dx3, v["act"], n, D, Dff, slack=True, out=g["dw2"])
+    dh2 = H.gemm(dpre, p["W1"], n, D, Dff, b_kstrided=True)
+    if "dw1" in g:
+        _wgrad(dpre, v["h2"], n, Dff, D, slack=True, out=g["dw1"])
     # out_proj's bias gradient = column sums of dx2, fc2's = column sums of dx3: both accumulated by the LayerNorm backward
     # that reads dx3 and writes dx2
-    dx2, dln2_w, dln2_b, dbo, db2 = H.layernorm_bwd(dh2, x2, ln2_w, mean2, rstd2, n, D, dres=dx3, defer=defer,
-                                                    dx_colsum=True, dres_colsum=True, name="ln2", x_side=side_x2, side=lns)
-    dattn = H.gemm(dx2, Wo, n, D, D, b_kstrided=True)
-    dwo = _wgrad(dx2, attn_o, n, D, D, slack=True) if need[9] else None
-    keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter / bias sums ride on passes that run anyway)
-    return dx2, dattn, dwo, keep(10, dbo), keep(11, dln2_w), keep(12, dln2_b), dw1, db1, dw2, keep(16, db2)
+    dx2 = H.layernorm_bwd(dh2, v["x2"], p["ln2_w"], v["mean2"], v["rstd2"], n, D, dres=dx3, defer=defer, dx_colsum=True,
+                          dres_colsum=True, name="ln2", x_side=side_x2, side=lns, dgamma=g.get("dln2_w"), dbeta=g.get("dln2_b"),
+                          dx_colsum_out=g.get("dbo"), dres_colsum_out=g.get("db2"))[0]
+    dattn = H.gemm(dx2, p["Wo"], n, D, D, b_kstrided=True)
+    if "dwo" in g:
+        _wgrad(dx2, v["attn_o"], n, D, D, slack=True, out=g["dwo"])
+    return dx2, dattn
+
+
+def _layer_fwd_ops(plan, x, params, pad_mask, arena, x3, training, side, side_out, side_x2):
+    """xp_encoder_layer_fwd, op by op"""
+    d = plan.dims
+    v, p = _piece_views(plan, arena), dict(zip(_FWD_PARAMS, params))
+    sd, lns = (None, None) if side is None else ((plan.side_S, plan.side_M), (plan.side_S, plan.side_M, plan.side_M))
+    if side is not None and side_x2 is None:       # a forward-only pass: nobody keeps the x2 side rows (natively: in the workspace)
+        side_x2 = torch.empty_like(side)
+    _attn_front_ops(v, x, p["ln1_w"], p["ln1_b"], p["Wqkv"], p["bqkv"], d.B, d.S, d.heads, plan.size, pad_mask, side, lns)
+    _mlp_fwd_ops(v, p, x, None, d.rows, training, side, side_x2, side_out, sd, x3, d.act)
+
+
+def _layer_bwd_ops(plan, x, params, arena, dx3, pad_mask, side, side_x2, dx, g):
+    """xp_encoder_layer_bwd, op by op"""
+    d = plan.dims
+    rows, D = d.rows, d.D
+    v, p = _piece_views(plan, arena), dict(zip(_BWD_PARAMS, params))
+    lns = None if side is None else (plan.side_S, plan.side_M, plan.side_M)
+    defer = H.DeferredReduce(x.device)       # the 4 bias + 4 LayerNorm-parameter reductions finish in 2 launches
+    # ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo
+    dx2, dattn = _mlp_bwd_ops(v, p, g, dx3, rows, defer, True, side_x2, lns, d.act)
+    # ---- attention: x2 = x + out_proj(attn(qkv(LN1(x))))
+    # the q/k/v bias gradients (column sums of dqkv) come out of the attention backward kernels: ``(dqkv, sums)`` with ``colsum_defer``
+    dbqkv = g.get("dbqkv")
+    dqkv = H.attn_bwd(v["qkv"], v["attn_o"], dattn, v["stats"], d.B, d.S, d.heads, size=plan.size, pad_mask=pad_mask,
+                      q_scale=64 ** -0.5, colsum_defer=None if dbqkv is None else defer, colsum_name="dbqkv", colsum_out=dbqkv)
+    dqkv = dqkv if dbqkv is None else dqkv[0]
+    dh1 = H.gemm(dqkv, p["Wqkv"], rows, D, 3 * D, b_kstrided=True)
+    if "dwqkv" in g:
+        _wgrad(dqkv, v["h1"], rows, 3 * D, D, out=g["dwqkv"])
+    H.layernorm_bwd(dh1, x, p["ln1_w"], v["mean1"], v["rstd1"], rows, D, dres=dx2, dx=dx, defer=defer, name="ln1", x_side=side,
+                    side=lns, dgamma=g.get("dln1_w"), dbeta=g.get("dln1_b"))
+    defer.flush()
 
 
 # ---- what EncoderLayerFn and PooledEncoderLayerFn share ---------------------------------------------------------------------------
@@ -684,75 +744,37 @@ class EncoderLayerFn(torch.autograd.Function):
                           "[B*M, D] (video) / [B*S, D] (text)")
         rows, D = x.shape
         Dff = w1.shape[0]
-        q_scale = 64 ** -0.5
         casts0 = WEIGHTS.casts
         Wqkv, bqkv, Wo, W1, W2 = _compute_weights(dt, wq, bq, wk, bk, wv, bv, wo, w1, w2)
         params = (ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2)          # (_FWD_PARAMS)
-        if LAYER_CALLS and _native_ok(x, params, pad_mask):
-            plan = _layer_plan(rows, D, Dff, B, S, heads, size, dt, act)
+        plan = _layer_plan(rows, D, Dff, B, S, heads, size, dt, act)
+        arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=x.device)
+        x3 = torch.empty_like(x)
+        side_out = None if side is None else torch.empty_like(side)
+        side_x2 = torch.empty_like(side) if side is not None and training else None      # kept for the backward's second LayerNorm
+        ctx.plan, ctx.native = plan, LAYER_CALLS and _native_ok(x, params, pad_mask)      # (native: who issues both passes' launches)
+        if ctx.native:
             if split is not None and (size is None or B % 2 or pad_mask is not None):
                 split = None
             if split is not None and WEIGHTS.casts != casts0:       # a weight copy was (re)made on this stream just now: the second
                 split.stream.wait_stream(torch.cuda.current_stream())   # chain must not read it before the cast has run
-            x3, arena, side_out, side_x2 = _layer_fwd_native(x, params, plan, pad_mask, keep_pre=training, side=side, split=split)
+            _layer_fwd_native(plan, x, params, pad_mask, arena, x3, training, side, side_out, side_x2, split)
             if split is not None:
                 split.hold(x, arena, x3, side, side_out, side_x2)
-            ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
-            ctx.plan = plan
-            _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
         else:
-            ctx.plan = None
-            sd = None if side is None else ((S, size[0]) if size is not None else (1, 1))
-            side_x2 = None if side is None else torch.empty_like(side)
-            side_out = None if side is None else torch.empty_like(side)
-            lns = None if side is None else (sd[0], sd[1], sd[1])
-            h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
-            qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
-            attn_o, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask)
-            x2, mean2, rstd2, h2, pre, a, x3 = _mlp_fwd_ops(x, None, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, rows, training,
-                                                            side, side_x2, side_out, sd, act=act)
-            if training:
-                ctx.save_for_backward(x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, a,
-                                      Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
-            ctx.meta = (B, S, heads, size, q_scale, D, Dff, act)
-            ctx.lns = lns
+            _layer_fwd_ops(plan, x, params, pad_mask, arena, x3, training, side, side_out, side_x2)
+        ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, pad_mask, side, side_x2)
+        _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
         return _layer_outputs(ctx, x3, side_out)
 
     @staticmethod
     def backward(ctx, dx3, _dside=None):
         if dx3 is None:             # (set_materialize_grads(False): the layer output did not reach the loss)
             return (None,) * 26
-        if ctx.plan is not None:
-            x, arena, *params, pad_mask, side, side_x2 = ctx.saved_tensors          # (params: _BWD_PARAMS)
-            dx3 = _check_dx3("EncoderLayerFn", dx3, x, x.shape)
-            return _run_native_bwd(ctx, _layer_bwd_args, "xp_encoder_layer_bwd", "layer_bwd", ctx.plan, x, params, arena, dx3, pad_mask,
-                                   side, side_x2) + (None,) * 9
-        (x, ln1_w, mean1, rstd1, h1, qkv, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
-         Wqkv, Wo, W1, W2, pad_mask, side, side_x2) = ctx.saved_tensors
-        B, S, heads, size, q_scale, D, Dff, act_kind = ctx.meta
-        rows = x.shape[0]
-        dx3 = dx3.contiguous()
-        defer = H.DeferredReduce(x.device)       # the 4 bias + 4 LayerNorm-parameter reductions finish in 2 launches
-        # parameter gradients are skipped for frozen parameters (freeze_text_encoder, VidCLIP.py:96-103): positions in
-        # forward's argument list -- 1,2 ln1 | 3..8 q,k,v | 9,10 out_proj | 11,12 ln2 | 13,14 fc1 | 15,16 fc2
-        need = ctx.needs_input_grad
-        # ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo
-        dx2, dattn, *tail = _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, rows, need, defer, True,
-                                         side_x2, ctx.lns, act_kind)
-        # ---- attention: x2 = x + out_proj(attn(qkv(LN1(x))))
-        want_bqkv = need[4] or need[6] or need[8]
-        if want_bqkv:       # the q/k/v bias gradients (column sums of dqkv) come out of the attention backward kernels
-            dqkv, dbqkv = H.attn_bwd(qkv, attn_o, dattn, stats, B, S, heads, size=size, pad_mask=pad_mask, q_scale=q_scale,
-                                     colsum_defer=defer, colsum_name="dbqkv")
-        else:
-            dqkv, dbqkv = H.attn_bwd(qkv, attn_o, dattn, stats, B, S, heads, size=size, pad_mask=pad_mask, q_scale=q_scale), None
-        dh1 = H.gemm(dqkv, Wqkv, rows, D, 3 * D, b_kstrided=True)
-        dwqkv = _wgrad(dqkv, h1, rows, 3 * D, D) if need[3] or need[5] or need[7] else None
-        dx, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dres=dx2, defer=defer, name="ln1", x_side=side,
-                                             side=ctx.lns)
-        defer.flush()
-        keep = lambda i, g: g if need[i] else None          # (LayerNorm parameter sums ride on a pass that runs anyway)
-        return (dx, keep(1, dln1_w), keep(2, dln1_b), *_qkv_grads(dwqkv, dbqkv, need, D), *tail) + (None,) * 9
+        x, arena, *params, pad_mask, side, side_x2 = ctx.saved_tensors          # (params: _BWD_PARAMS)
+        dx3 = _check_dx3("EncoderLayerFn", dx3, x, x.shape)
+        return _layer_backward(ctx, _layer_bwd_args, "xp_encoder_layer_bwd", "layer_bwd", _layer_bwd_ops, x, params, arena, dx3,
+                               pad_mask, side, side_x2) + (None,) * 9
 
 
 # ------------------------------------------------------------------------------------------ pooled last layer (video tower)
@@ -762,7 +784,7 @@ class _PooledLayerPlan:
 
     def __init__(self, rows, D, Dff, B, S, heads, size, dtype, act=L.ACT_QUICK_GELU):
         rD, rF = D * _ES[dtype], Dff * _ES[dtype]
-        _finish_plan(self, _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act).dims, rD,
+        _finish_plan(self, _layer_plan(rows, D, Dff, B, S, heads, size, dtype, act).dims, dtype,
                      (("h1", rows, rD), ("kv", rows, 2 * rD), ("mean1", rows, 4), ("rstd1", rows, 4), ("h1p", B, rD), ("q", B, rD),
                       ("attn_o", B, rD), ("x2", B, rD), ("h2", B, rD), ("pre", B, rF), ("act", B, rF), ("mean1p", B, 4),
                       ("rstd1p", B, 4), ("mean2", B, 4), ("rstd2", B, 4), ("stats", B, heads * 2 * 4)),
@@ -787,6 +809,55 @@ def _pooled_bwd_args(plan, x, params, arena, dx3, side, side_x2, dx, grads):
                        side_x2=side_x2, **grads)
 
 
+def _pooled_fwd_ops(plan, x, params, arena, x3, training, side, side_out, side_x2):
+    """xp_encoder_layer_pooled_fwd, op by op"""
+    d = plan.dims
+    rows, D, B, S, M = d.rows, d.D, d.B, d.S, d.M
+    v, p = _piece_views(plan, arena), dict(zip(_FWD_PARAMS, params))
+    Wqkv, bqkv = p["Wqkv"], p["bqkv"]
+    lns, p1, sd = (None, None, None) if side is None else ((S, M, M), (1, 1, 1), (1, 1))
+    h1, _, _ = H.layernorm_fwd(x, p["ln1_w"], p["ln1_b"], rows, D, x_side=side, side=lns, y=v["h1"], mean=v["mean1"], rstd=v["rstd1"])
+    side0 = None if side is None else H.gather_rows(side, None, B, M, D)
+    h1p, _, _ = H.layernorm_fwd(x, p["ln1_w"], p["ln1_b"], B, D, ldx=S * D, x_side=side0, side=p1, y=v["h1p"], mean=v["mean1p"],
+                                rstd=v["rstd1p"])
+    kv = H.gemm(h1, Wqkv[D:], rows, 2 * D, D, epilogue=L.EPI_BIAS, bias=bqkv[D:], out=v["kv"])
+    q = H.gemm(h1p, Wqkv, B, D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=64 ** -0.5, scale_cols=D, out=v["q"])
+    H.attn_pooled_fwd(q, kv, B, S, d.heads, out=v["attn_o"], stats=v["stats"])
+    _mlp_fwd_ops(v, p, x, S * D, B, training, side0, side_x2, side_out, sd, x3, d.act)
+
+
+def _pooled_bwd_ops(plan, x, params, arena, dx3, side, side_x2, dx, g):
+    """xp_encoder_layer_pooled_bwd, op by op"""
+    d = plan.dims
+    rows, D, B, S, M = d.rows, d.D, d.B, d.S, d.M
+    v, p = _piece_views(plan, arena), dict(zip(_BWD_PARAMS, params))
+    Wqkv, dbqkv = p["Wqkv"], g.get("dbqkv")
+    lns, p1 = (None, None) if side is None else ((S, M, M), (1, 1, 1))
+    defer = H.DeferredReduce(x.device)
+    # ---- MLP and dattn = dx2 . Wo on the pooled rows
+    dx2, dattn = _mlp_bwd_ops(v, p, g, dx3, B, defer, False, side_x2, p1, d.act)
+    # ---- attention.  dqkv [rows, 3D]: dk / dv in the k / v columns of every row, dq in the q columns of the pooled rows only
+    dqkv = torch.empty((rows, 3 * D), dtype=x.dtype, device=x.device)
+    dq_view, dkv = dqkv.view(B, S * 3 * D)[:, :D], dqkv[:, D:]
+    # (the k / v bias gradients come out of the attention backward kernel; without ``colsum_defer`` it gets no partial rows)
+    H.attn_pooled_bwd(v["q"], v["kv"], v["attn_o"], dattn, v["stats"], B, S, d.heads, q_scale=64 ** -0.5, dq=dq_view, dkv=dkv,
+                      colsum_defer=None if dbqkv is None else defer, colsum_name="dbkv", colsum_out=None if dbqkv is None else dbqkv[D:])
+    dh1 = H.gemm(dkv, Wqkv[D:], rows, D, 2 * D, lda=3 * D, b_kstrided=True, ldb=D)
+    H.gemm(dqkv, Wqkv, B, D, 3 * D, b_kstrided=True, ldb=D, a_remap=(1, S, 0), c_remap=(1, S, 0), out=dh1)
+    if "dwqkv" in g:
+        dwqkv = g["dwqkv"].view(3 * D, D)
+        _wgrad(dqkv, v["h1p"], B, D, D, a_remap=(1, S, 0), slack=True, lddy=3 * D, out=dwqkv[:D])
+        _wgrad(dkv, v["h1"], rows, 2 * D, D, lddy=3 * D, out=dwqkv[D:])
+    if dbqkv is not None:
+        H.colsum_deferred(dqkv, B, D, defer, ldx=S * 3 * D, name="dbq", out=dbqkv)
+    H.layernorm_bwd(dh1, x, p["ln1_w"], v["mean1"], v["rstd1"], rows, D, dx=dx, defer=defer, name="ln1", x_side=side, side=lns,
+                    dgamma=g.get("dln1_w"), dbeta=g.get("dln1_b"))
+    # the pooled rows once more, with their residual gradient (the parameter-gradient partial rows of this pass are dropped)
+    H.layernorm_bwd(dh1, x, p["ln1_w"], v["mean1p"], v["rstd1p"], B, D, ldx=S * D, lddy=S * D, dres=dx2, dx=dx, lddx=S * D, defer=defer,
+                    param_grads=False, name="ln1_pooled", x_side=side, side=(1, 1, M))
+    defer.flush()
+
+
 class PooledEncoderLayerFn(torch.autograd.Function):
     """The LAST CLIPEncoderLayer of the video tower when only the pooled feature leaves it (``pooled_output =
     last_hidden_state[:, 0]``, modeling/CLIP_ViP.py:360-366): returns row ``b*S`` of ``EncoderLayerFn``'s output for every sample
@@ -807,7 +878,6 @@ class PooledEncoderLayerFn(torch.autograd.Function):
         Dff = w1.shape[0]
         if M < 1 or S != M + size[1] * size[2] or rows != B * S:
             raise RuntimeError(f"PooledEncoderLayerFn: token 0 must be a proxy row of a [B*S, D] stream (size={size}, S={S}, rows={rows})")
-        q_scale = 64 ** -0.5
         Wqkv, bqkv, Wo, W1, W2 = _compute_weights(dt, wq, bq, wk, bk, wv, bv, wo, w1, w2)
         dev = x.device
         x3 = torch.empty((B, D), dtype=dt, device=dev)
@@ -816,79 +886,26 @@ class PooledEncoderLayerFn(torch.autograd.Function):
             side_out = torch.empty((B, D), dtype=torch.float32, device=dev)
             side_x2 = torch.empty((B, D), dtype=torch.float32, device=dev)
         params = (ln1_w, ln1_b, Wqkv, bqkv, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2)          # (_FWD_PARAMS)
-        if LAYER_CALLS and _native_ok(x, params, None):
-            plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt, act)
-            arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
+        plan = _pooled_plan(rows, D, Dff, B, S, heads, tuple(size), dt, act)
+        arena = torch.empty(plan.arena_bytes, dtype=torch.uint8, device=dev)
+        ctx.plan, ctx.native = plan, LAYER_CALLS and _native_ok(x, params, None)
+        if ctx.native:
             a = _pooled_fwd_args(plan, x, params, arena, x3, training, side, side_out, side_x2)
             _call_native("xp_encoder_layer_pooled_fwd", a, plan.fwd_ws, dev, "layer_pooled_fwd")
-            ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2)
-            ctx.plan = plan
-            _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
         else:
-            ctx.plan = None
-            lns, p1, sd = (None, None, None) if side is None else ((S, M, M), (1, 1, 1), (1, 1))
-            h1, mean1, rstd1 = H.layernorm_fwd(x, ln1_w, ln1_b, rows, D, x_side=side, side=lns)
-            side0 = None if side is None else H.gather_rows(side, None, B, M, D)
-            h1p, mean1p, rstd1p = H.layernorm_fwd(x, ln1_w, ln1_b, B, D, ldx=S * D, x_side=side0, side=p1)
-            kv = H.gemm(h1, Wqkv[D:], rows, 2 * D, D, epilogue=L.EPI_BIAS, bias=bqkv[D:])
-            q = H.gemm(h1p, Wqkv, B, D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=q_scale, scale_cols=D)
-            attn_o, stats = H.attn_pooled_fwd(q, kv, B, S, heads)
-            x2, mean2, rstd2, h2, pre, a, _ = _mlp_fwd_ops(x, S * D, attn_o, Wo, bo, ln2_w, ln2_b, W1, b1, W2, b2, B, training,
-                                                           side0, side_x2, side_out, sd, out=x3, act=act)
-            if training:
-                ctx.save_for_backward(x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2,
-                                      h2, pre, a, Wqkv, Wo, W1, W2, side, side_x2)
-        ctx.meta = (B, S, heads, M, q_scale, D, Dff, act)
+            _pooled_fwd_ops(plan, x, params, arena, x3, training, side, side_out, side_x2)
+        ctx.save_for_backward(x, arena, ln1_w, ln2_w, Wqkv, Wo, W1, W2, side, side_x2)
+        _record_sink(ctx, ln1_w, ln1_b, wq, bq, wk, bk, wv, bv, wo, bo, ln2_w, ln2_b, w1, b1, w2, b2)
         return _layer_outputs(ctx, x3, side_out)
 
     @staticmethod
     def backward(ctx, dx3, _dside=None):
         if dx3 is None:
             return (None,) * 24
-        B, S, heads, M, q_scale, D, Dff, act_kind = ctx.meta
-        need = ctx.needs_input_grad
-        saved = ctx.saved_tensors          # (read once: a checkpointed layer's tensors unpack once)
-        dx3 = _check_dx3("PooledEncoderLayerFn", dx3, saved[0], (B, D))
-        if ctx.plan is not None:
-            x, arena, *params, side, side_x2 = saved          # (params: _BWD_PARAMS)
-            return _run_native_bwd(ctx, _pooled_bwd_args, "xp_encoder_layer_pooled_bwd", "layer_pooled_bwd", ctx.plan, x, params, arena,
-                                   dx3, side, side_x2) + (None,) * 7
-        (x, ln1_w, mean1, rstd1, mean1p, rstd1p, h1, h1p, kv, q, attn_o, stats, x2, ln2_w, mean2, rstd2, h2, pre, act,
-         Wqkv, Wo, W1, W2, side, side_x2) = saved
-        rows, dev, dt = x.shape[0], x.device, x.dtype
-        dx = torch.empty_like(x)
-        lns, p1 = (None, None) if side is None else ((S, M, M), (1, 1, 1))
-        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
-        defer = H.DeferredReduce(dev)
-        # ---- MLP and dattn = dx2 . Wo on the pooled rows
-        dx2, dattn, *tail = _mlp_bwd_ops(dx3, pre, act, h2, x2, attn_o, ln2_w, mean2, rstd2, W1, W2, Wo, B, need, defer, False,
-                                         side_x2, p1, act_kind)
-        # ---- attention.  dqkv [rows, 3D]: dk / dv in the k / v columns of every row, dq in the q columns of the pooled rows only
-        dqkv = torch.empty((rows, 3 * D), dtype=dt, device=dev)
-        dq_view, dkv = dqkv.view(B, S * 3 * D)[:, :D], dqkv[:, D:]
-        want_b = need[4] or need[6] or need[8]
-        dbqkv = f32(3 * D) if want_b else None
-        if want_b:
-            H.attn_pooled_bwd(q, kv, attn_o, dattn, stats, B, S, heads, q_scale=q_scale, dq=dq_view, dkv=dkv,
-                              colsum_defer=defer, colsum_name="dbkv", colsum_out=dbqkv[D:])
-        else:
-            H.attn_pooled_bwd(q, kv, attn_o, dattn, stats, B, S, heads, q_scale=q_scale, dq=dq_view, dkv=dkv)
-        dh1 = H.gemm(dkv, Wqkv[D:], rows, D, 2 * D, lda=3 * D, b_kstrided=True, ldb=D)
-        H.gemm(dqkv, Wqkv, B, D, 3 * D, b_kstrided=True, ldb=D, a_remap=(1, S, 0), c_remap=(1, S, 0), out=dh1)
-        dwqkv = None
-        if need[3] or need[5] or need[7]:
-            dwqkv = f32(3 * D, D)
-            _wgrad(dqkv, h1p, B, D, D, a_remap=(1, S, 0), slack=True, lddy=3 * D, out=dwqkv[:D])
-            _wgrad(dkv, h1, rows, 2 * D, D, lddy=3 * D, out=dwqkv[D:])
-        if want_b:
-            H.colsum_deferred(dqkv, B, D, defer, ldx=S * 3 * D, name="dbq", out=dbqkv)
-        _, dln1_w, dln1_b = H.layernorm_bwd(dh1, x, ln1_w, mean1, rstd1, rows, D, dx=dx, defer=defer, name="ln1", x_side=side, side=lns)
-        # the pooled rows once more, with their residual gradient (the parameter-gradient partial rows of this pass are dropped)
-        H.layernorm_bwd(dh1, x, ln1_w, mean1p, rstd1p, B, D, ldx=S * D, lddy=S * D, dres=dx2, dx=dx, lddx=S * D, defer=defer,
-                        param_grads=False, name="ln1_pooled", x_side=side, side=(1, 1, M))
-        defer.flush()
-        keep = lambda i, t: t if need[i] else None
-        return (dx, keep(1, dln1_w), keep(2, dln1_b), *_qkv_grads(dwqkv, dbqkv, need, D), *tail) + (None,) * 7
+        x, arena, *params, side, side_x2 = ctx.saved_tensors          # (params: _BWD_PARAMS)
+        dx3 = _check_dx3("PooledEncoderLayerFn", dx3, x, (ctx.plan.dims.B, x.shape[1]))
+        return _layer_backward(ctx, _pooled_bwd_args, "xp_encoder_layer_pooled_bwd", "layer_pooled_bwd", _pooled_bwd_ops, x, params,
+                               arena, dx3, side, side_x2) + (None,) * 7
 
 
 def pooled_encoder_layer(x, layer, B, S, heads, size, side=None):
@@ -1241,20 +1258,17 @@ def _layer_act(layer) -> int:
 
 def layer_attentions(x, layer, B, S, size, pad_mask, side=None):
     """The attention weights of a ``CLIPEncoderLayer`` on its input ``x`` (``side``: x's fp32 side rows), for ``output_attentions``:
-    LayerNorm 1, the QKV projection and the fused attention forward as EncoderLayerFn's op-by-op branch calls them -- the native
-    layer call computes the same bits -- then ``hip_ops.attn_probs`` on that qkv and those statistics.  Causal (``size`` None):
+    LayerNorm 1, the QKV projection and the fused attention forward as the op-by-op layer forward calls them (_attn_front_ops) -- the
+    native layer call computes the same bits -- then ``hip_ops.attn_probs`` on that qkv and those statistics.  Causal (``size`` None):
     fp32 ``[B, H, S, S]``; video: ``(proxy [B,H,M,S], frame [B,H,N,L,M+L])``.  No autograd: the weights are detached, new memory."""
     ln1_w, ln1_b, wq, bq, wk, bk, wv, bv = _layer_params(layer)[:8]
     heads = layer.num_heads
-    rows, D = x.shape
     _check_layer_args("layer_attentions", x, heads, L.ACT_QUICK_GELU, side, B * size[0] if size is not None else B * S,
                       "[B*M, D] (video) / [B*S, D] (text)")
     with torch.no_grad():
         Wqkv, bqkv = WEIGHTS.fused((wq, wk, wv), x.dtype), WEIGHTS.fused((bq, bk, bv), torch.float32)
         lns = None if side is None else ((S, size[0], size[0]) if size is not None else (1, 1, 1))
-        h1, _, _ = H.layernorm_fwd(x.detach(), ln1_w.detach(), ln1_b.detach(), rows, D, x_side=side, side=lns)
-        qkv = H.gemm(h1, Wqkv, rows, 3 * D, D, epilogue=L.EPI_BIAS_QSCALE, bias=bqkv, scale=64 ** -0.5, scale_cols=D)
-        _, stats = H.attn_fwd(qkv, B, S, heads, size=size, pad_mask=pad_mask)
+        qkv, stats = _attn_front_ops({}, x.detach(), ln1_w.detach(), ln1_b.detach(), Wqkv, bqkv, B, S, heads, size, pad_mask, side, lns)
         return H.attn_probs(qkv, stats, B, S, heads, size=size, pad_mask=pad_mask)
 
 

@@ -61,7 +61,7 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
          a_kstrided=False, b_kstrided=False, out_dtype=None, epilogue=L.EPI_NONE, bias=None, scale=1.0,
          scale_cols=0, resid=None, ldr=None, aux=None, ldaux=None, tab1=None, tab2=None, tab_L=0,
          a_remap=(0, 0, 0), c_remap=(0, 0, 0), split_k=1, out_rows=None, colsum_defer=None, colsum_name="gemm_colsum",
-         resid_side=None, out_side=None, side=None, frames=None, frame_patch=0, frame_norm=None, plan_only=False):
+         colsum_out=None, resid_side=None, out_side=None, side=None, frames=None, frame_patch=0, frame_norm=None, plan_only=False):
     """C[M,N] = epilogue(sum_k A(m,k) B(n,k)); see include/xpretrain_hip.h::XpGemmDesc.
 
     ``plan_only``: launch nothing and return the plan xp_gemm would launch for this call's descriptor (``gemm_plan_of``).
@@ -71,7 +71,7 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
 
     ``colsum_defer`` (a DeferredReduce): also return the column sums of C (a bias gradient), as ``(C, colsum)``; the
     sums come out of the GEMM epilogue where the library supports it, otherwise from a separate pass over C; either
-    way they are final only after ``colsum_defer.flush()``."""
+    way they are final only after ``colsum_defer.flush()``; written to ``colsum_out`` if given."""
     if frames is not None:
         _chk(frames, "frames"); _chk(B, "B", torch.bfloat16)
         if A is not None or frames.dim() != 4 or frames.shape[1] != 3 or not frames.is_contiguous() or \
@@ -123,17 +123,16 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
         if colsum_defer is not None and L.lib().xp_gemm_colsum_rows(C.byref(d)) > 0:
             d.colsum_partials = 1          # (the planner reads the pointer only as present / absent)
         return gemm_plan_of(d)
-    if colsum_defer is None:
-        L.check(L.lib().xp_gemm(C.byref(d), _stream()), "xp_gemm")
-        return out
-    nrows = L.lib().xp_gemm_colsum_rows(C.byref(d))
-    if nrows == 0:
-        L.check(L.lib().xp_gemm(C.byref(d), _stream()), "xp_gemm")
-        return out, colsum_deferred(out, M, N, colsum_defer, ldx=d.ldc, name=colsum_name)
-    cs = torch.empty(N, dtype=torch.float32, device=A.device)
-    part = colsum_defer.slot(nrows * N * 4, colsum_name)
-    d.colsum_partials = part.data_ptr()
+    nrows = L.lib().xp_gemm_colsum_rows(C.byref(d)) if colsum_defer is not None else 0
+    if nrows:
+        part = colsum_defer.slot(nrows * N * 4, colsum_name)
+        d.colsum_partials = part.data_ptr()
     L.check(L.lib().xp_gemm(C.byref(d), _stream()), "xp_gemm")
+    if colsum_defer is None:
+        return out
+    if not nrows:
+        return out, colsum_deferred(out, M, N, colsum_defer, ldx=d.ldc, name=colsum_name, out=colsum_out)
+    cs = torch.empty(N, dtype=torch.float32, device=A.device) if colsum_out is None else colsum_out
     colsum_defer.add(part, 0, cs, nrows, N, N)
     return out, cs
 
@@ -274,8 +273,9 @@ def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, rows
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, dres=None, dx=None, lddx=None,
                   dgamma=None, dbeta=None, accumulate=False, defer: "DeferredReduce" = None, dx_colsum=False, dres_colsum=False,
-                  name="ln", x_side=None, side=None, param_grads=True, lddres=None):
-    """Returns (dx, dgamma, dbeta) -- plus colsum(dx) when ``dx_colsum``, plus colsum(dres) when ``dres_colsum`` (deferred mode only).
+                  name="ln", x_side=None, side=None, param_grads=True, lddres=None, dx_colsum_out=None, dres_colsum_out=None):
+    """Returns (dx, dgamma, dbeta) -- plus colsum(dx) when ``dx_colsum``, plus colsum(dres) when ``dres_colsum`` (deferred mode only;
+    written to ``dx_colsum_out`` / ``dres_colsum_out`` if given).
     ``lddres``: row pitch of ``dres`` (default cols); ``dres`` may be ``dx`` itself.
     ``x_side`` / ``side = (S, M, stride)``: the fp32 side rows of x the forward normalised (layernorm_fwd).
     ``param_grads=False`` (deferred mode, no column sums): dx only -- the pass's parameter-gradient partial rows stay in its slot
@@ -308,10 +308,10 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, rows, cols, *, ldx=None, lddy=None, 
         defer.add(ws, 0, dgamma, nrows, cols, pitch, accumulate)
         defer.add(ws, cols, dbeta, nrows, cols, pitch, accumulate)
         if dx_colsum:
-            dxs = torch.empty(cols, dtype=torch.float32, device=dy.device)
+            dxs = torch.empty(cols, dtype=torch.float32, device=dy.device) if dx_colsum_out is None else dx_colsum_out
             defer.add(ws, 2 * cols, dxs, nrows, cols, pitch)
             if dres_colsum:
-                drs = torch.empty(cols, dtype=torch.float32, device=dy.device)
+                drs = torch.empty(cols, dtype=torch.float32, device=dy.device) if dres_colsum_out is None else dres_colsum_out
                 defer.add(ws, 3 * cols, drs, nrows, cols, pitch)
                 return dx, dgamma, dbeta, dxs, drs
             return dx, dgamma, dbeta, dxs
@@ -746,14 +746,24 @@ def _attn_ws(mode, B, H, M, N, Lp, device):
     return workspace(nb, device, "attn")
 
 
-def attn_fwd(qkv: torch.Tensor, B: int, S: int, H: int, *, size=None, pad_mask=None):
+def _dest(what, t, name, dtype, shape, device):
+    """an attention output: a new tensor, or the caller's contiguous buffer ``t`` of that element count (any shape), viewed as ``shape``"""
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _chk(t, name, dtype)
+    if not t.is_contiguous() or t.numel() != math.prod(shape):
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor of {math.prod(shape)} elements")
+    return t.view(shape)
+
+
+def attn_fwd(qkv: torch.Tensor, B: int, S: int, H: int, *, size=None, pad_mask=None, out=None, stats=None):
     """qkv [B*S, 3*H*64] (q pre-scaled).  size=(M,N,L) selects the video-proxy pattern, otherwise the
-    causal(+padding) text pattern.  Returns (out [B*S, H*64], stats [B,H,S,2])."""
+    causal(+padding) text pattern.  Returns (out [B*S, H*64], stats [B,H,S,2]): the caller's buffers if given."""
     _chk(qkv, "qkv")
     mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
     M, N, Lp = size if size is not None else (0, 1, S)
-    out = torch.empty((B * S, H * 64), dtype=qkv.dtype, device=qkv.device)
-    stats = torch.empty((B, H, S, 2), dtype=torch.float32, device=qkv.device)
+    out = _dest("attn_fwd", out, "out", qkv.dtype, (B * S, H * 64), qkv.device)
+    stats = _dest("attn_fwd", stats, "stats", torch.float32, (B, H, S, 2), qkv.device)
     if pad_mask is not None:
         _chk(pad_mask, "pad_mask", torch.int64)
     ws = _attn_ws(mode, B, H, M, N, Lp, qkv.device)
@@ -779,15 +789,7 @@ def attn_probs(qkv: torch.Tensor, stats: torch.Tensor, B: int, S: int, H: int, *
     outs = (out,) if isinstance(out, torch.Tensor) else tuple(out) if out is not None else (None,) * len(shapes)
     if len(outs) != len(shapes):
         raise ValueError(f"attn_probs: out must be {'the (proxy, frame) pair' if size is not None else 'one tensor'}")
-    bufs = []
-    for t, shp, nm in zip(outs, shapes, ("out[0]", "out[1]")):
-        if t is None:
-            t = torch.empty(shp, dtype=torch.float32, device=qkv.device)
-        else:
-            _chk(t, nm, torch.float32)
-            if not t.is_contiguous() or t.numel() != math.prod(shp):
-                raise ValueError(f"attn_probs: {nm} must be a contiguous fp32 tensor of {math.prod(shp)} elements")
-        bufs.append(t.view(shp))
+    bufs = [_dest("attn_probs", t, nm, torch.float32, shp, qkv.device) for t, shp, nm in zip(outs, shapes, ("out[0]", "out[1]"))]
     frame, proxy = (bufs[1], bufs[0]) if size is not None else (bufs[0], None)
     L.check(L.lib().xp_attn_probs(_p(qkv), 3 * H * 64, _p(stats), _p(pad_mask), _p(frame), _p(proxy), mode, B, H, S, M, N, Lp,
                                   _dt(qkv), _stream()), "xp_attn_probs")
@@ -821,9 +823,10 @@ def get_attn_bwd_wide() -> bool:
 
 
 def attn_bwd(qkv, out, dout, stats, B, S, H, *, size=None, pad_mask=None, q_scale=1.0, colsum_defer=None,
-             colsum_name="dbqkv"):
+             colsum_name="dbqkv", colsum_out=None):
     """dqkv; with ``colsum_defer`` (a DeferredReduce) also the column sums of dqkv (the q/k/v bias gradients) as ``(dqkv, colsum)``:
-    out of the backward kernels where the library supports it, otherwise from a separate pass; final after ``flush()``."""
+    out of the backward kernels where the library supports it, otherwise from a separate pass; final after ``flush()``; written to
+    ``colsum_out`` if given."""
     mode = L.ATTN_PROXY if size is not None else L.ATTN_CAUSAL
     M, N, Lp = size if size is not None else (0, 1, S)
     dqkv = torch.empty_like(qkv)
@@ -836,8 +839,8 @@ def attn_bwd(qkv, out, dout, stats, B, S, H, *, size=None, pad_mask=None, q_scal
     if colsum_defer is None:
         return dqkv
     if not nrows:
-        return dqkv, colsum_deferred(dqkv, B * S, 3 * H * 64, colsum_defer, name=colsum_name)
-    cs = torch.empty(3 * H * 64, dtype=torch.float32, device=qkv.device)
+        return dqkv, colsum_deferred(dqkv, B * S, 3 * H * 64, colsum_defer, name=colsum_name, out=colsum_out)
+    cs = torch.empty(3 * H * 64, dtype=torch.float32, device=qkv.device) if colsum_out is None else colsum_out
     colsum_defer.add(part, 0, cs, nrows, 3 * H * 64, 3 * H * 64)
     return dqkv, cs
 
@@ -851,15 +854,15 @@ def _rows_ld(t: torch.Tensor, name: str, width: int) -> int:
     return t.stride(0)
 
 
-def attn_pooled_fwd(q: torch.Tensor, kv: torch.Tensor, B: int, S: int, H: int):
+def attn_pooled_fwd(q: torch.Tensor, kv: torch.Tensor, B: int, S: int, H: int, *, out=None, stats=None):
     """Token 0 of every sample against all S keys (the pooled last layer of the video tower).  q [B, H*64] (pre-scaled), kv
-    [B*S, 2*H*64] = [k | v] rows (any row pitch).  Returns (out [B, H*64], stats [B, H, 2])."""
+    [B*S, 2*H*64] = [k | v] rows (any row pitch).  Returns (out [B, H*64], stats [B, H, 2]): the caller's buffers if given."""
     _chk(q, "q")
     ld = _rows_ld(kv, "kv", 2 * H * 64)
     if not q.is_contiguous() or tuple(q.shape) != (B, H * 64) or kv.shape[0] != B * S or kv.dtype != q.dtype:
         raise TypeError("attn_pooled_fwd: q must be a contiguous [B, H*64] matrix and kv [B*S, 2*H*64] of the same dtype")
-    out = torch.empty_like(q)
-    stats = torch.empty((B, H, 2), dtype=torch.float32, device=q.device)
+    out = _dest("attn_pooled_fwd", out, "out", q.dtype, (B, H * 64), q.device)
+    stats = _dest("attn_pooled_fwd", stats, "stats", torch.float32, (B, H, 2), q.device)
     ws = workspace(L.lib().xp_attn_pooled_workspace_bytes(B, H, S, _dt(q)), q.device, "attn_pooled")
     L.check(L.lib().xp_attn_pooled_fwd(_p(q), _p(kv), ld, _p(out), _p(stats), B, H, S, _dt(q), _p(ws), ws.numel(), _stream()),
             "xp_attn_pooled_fwd")
