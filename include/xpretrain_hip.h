@@ -616,6 +616,41 @@ int xp_dsl_rerank(float* sim, int64_t n, int64_t m, float theta, int32_t multipl
 int xp_retrieval_ranks(const float* sim, const int64_t* labels, int64_t n, int64_t m, int32_t transpose,
                        int32_t* greater, int32_t* equal, void* stream);
 
+/* ----------------------------------------------------------------------- Retrieval at gallery scale (csrc/retrieval_stream.hip)
+ * The same evaluation, and top-k search, straight from the features: q [nq, d] (queries: text), g [ng, d] (gallery: videos), both
+ * row-major fp32, any d >= 1.  The score s_ij = sum_k q[i,k] g[j,k] is an fp32 fmaf chain in a k order that depends on d alone
+ * (f32-input MFMA), so its bits depend on row i of q, row j of g and d only -- not on where the rows lie, on nq, ng, tiles or
+ * splits: duplicate gallery rows tie exactly, and a label's own entry always counts as equal.  No score is ever written to global
+ * memory; the workspaces have no nq * ng term.  Outputs are identical from run to run (no float atomics).
+ *
+ * xp_retrieval_ranks_streamed: x_ij = s_ij (dsl == 0) or s_ij * exp(theta s_ij - mx_j) / sum_j with mx_j = max_i theta s_ij and
+ *   sum_j = sum_i exp(theta s_ij - mx_j) (dsl != 0: the arithmetic of xp_dsl_rerank, streamed over query tiles in a fixed order).
+ *   Row direction (t2v): greater_q[i] / equal_q[i] = #{j : x_ij > x_il} / #{j : x_ij == x_il}, l = labels_q[i] (NULL: l = i, needs
+ *   nq <= ng).  Column direction (v2t): greater_g[j] / equal_g[j] = the same over i against x_lj, l = labels_g[j] (NULL: l = j,
+ *   needs ng <= nq).  Either pair of outputs may be NULL (not both); both directions come from one pass.  Counts are exact int32.
+ *   Labels in memory the host can read (ordinary, pinned or managed) are range-checked before anything is launched, and ordinary
+ *   host memory is copied to the device by the call; the range of labels in DEVICE memory is the caller's duty -- an out-of-range
+ *   one reads nothing and gives greater = equal = 0.
+ * xp_retrieval_topk: vals [nq, k] / idx [nq, k] = each query's k best (score, index_base + j), score descending, ties to the lowest
+ *   index; 1 <= k <= min(XP_RETRIEVAL_MAX_K, ng).  accumulate != 0: the incoming vals / idx (a previous call's result) are
+ *   candidates under the same order -- a gallery fed shard by shard (index_base = the shard's first row) gives exactly the
+ *   one-shot result, values bit for bit.
+ * Both return XP_ERR_ARG before any launch for null or empty operands, k out of range, host-readable labels out of range or a
+ * workspace below *_workspace_bytes (which return 0 and set xp_last_error for shapes they refuse).
+ * xp_retrieval_stream_plan: the tiling the calls use, for tests that place rows on its boundaries: scores are computed in tiles of
+ *   XP_RETRIEVAL_TILE x XP_RETRIEVAL_TILE; the DSL statistics split the query tiles into runs of *stat_tiles_per_split, the top-k
+ *   search splits the gallery tiles into runs of *topk_tiles_per_split. */
+#define XP_RETRIEVAL_TILE 128
+#define XP_RETRIEVAL_MAX_K 128
+int xp_retrieval_stream_plan(int64_t nq, int64_t ng, int32_t k, int32_t* stat_tiles_per_split, int32_t* topk_tiles_per_split);
+size_t xp_retrieval_ranks_streamed_workspace_bytes(int64_t nq, int64_t ng, int64_t d, int32_t dsl);
+int xp_retrieval_ranks_streamed(const float* q, const float* g, const int64_t* labels_q, const int64_t* labels_g, int64_t nq,
+                                int64_t ng, int64_t d, int32_t dsl, float theta, int32_t* greater_q, int32_t* equal_q,
+                                int32_t* greater_g, int32_t* equal_g, void* workspace, size_t workspace_bytes, void* stream);
+size_t xp_retrieval_topk_workspace_bytes(int64_t nq, int64_t ng, int64_t d, int32_t k);
+int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
+                      int32_t accumulate, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------ Encoder layer
  * One CLIPEncoderLayer.forward / backward per call (modeling/CLIP_ViP.py:444-460: x + Attn(LN1(x)), then x + MLP(LN2(x));
  * attention = CLIPAttention.forward2 :332-381 (XP_ATTN_PROXY) or .forward :266-330 (XP_ATTN_CAUSAL); MLP = CLIPMLP :392-396).

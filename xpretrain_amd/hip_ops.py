@@ -905,3 +905,85 @@ def attn_pooled_plan(B: int, S: int, H: int, *, dtype=torch.bfloat16, backward=F
     plan = {f: getattr(info, f) for f, _ in info._fields_}
     plan.update({f: tuple(plan[f]) for f in ("part_ml", "part_acc", "part_dq")})
     return plan
+
+
+# --------------------------------------------------------------------------------------- retrieval at gallery scale
+RETRIEVAL_TILE, RETRIEVAL_MAX_K = L.XP_RETRIEVAL_TILE, L.XP_RETRIEVAL_MAX_K
+
+
+def _feature_rows(t, name, d=None):
+    _chk(t, name, torch.float32)
+    if t.dim() != 2 or not t.is_contiguous() or t.shape[0] == 0 or t.shape[1] == 0 or (d is not None and t.shape[1] != d):
+        raise ValueError(f"{name}: expected a contiguous non-empty [rows, {'d' if d is None else d}] fp32 matrix, got {tuple(t.shape)}")
+    return t
+
+
+def _labels(labels, name, n, limit, device):
+    """int64 [n] on the device, every entry in [0, limit) -- checked here, on the host's copy, when the labels come from the host"""
+    if labels is None:
+        return None
+    if isinstance(labels, torch.Tensor) and labels.is_cuda:
+        lab = labels.to(torch.int64).contiguous()
+    else:
+        host = torch.as_tensor(labels, dtype=torch.int64).reshape(-1)
+        if host.numel() and (int(host.min()) < 0 or int(host.max()) >= limit):
+            raise ValueError(f"{name}: labels must lie in [0, {limit})")
+        lab = host.to(device)
+    if lab.dim() != 1 or lab.numel() != n:
+        raise ValueError(f"{name}: expected one label per query ({n}), got {tuple(lab.shape)}")
+    return lab
+
+
+def retrieval_stream_plan(nq: int, ng: int, k: int = 1) -> dict:
+    """the tiling xp_retrieval_ranks_streamed / xp_retrieval_topk use at this shape (include/xpretrain_hip.h)"""
+    a, b = C.c_int32(0), C.c_int32(0)
+    L.check(L.lib().xp_retrieval_stream_plan(nq, ng, k, C.byref(a), C.byref(b)), "xp_retrieval_stream_plan")
+    return dict(tile=RETRIEVAL_TILE, stat_tiles_per_split=a.value, topk_tiles_per_split=b.value)
+
+
+def retrieval_ranks_streamed(q: torch.Tensor, g: torch.Tensor, labels_q=None, labels_g=None, *, rows=True, cols=True, dsl=False,
+                             theta=100.0):
+    """(greater_q, equal_q, greater_g, equal_g): int32 count vectors of the directions asked for (None for the other), straight
+    from the features q [nq, d] / g [ng, d] -- the [nq, ng] matrix is never built (include/xpretrain_hip.h)"""
+    _feature_rows(q, "q")
+    _feature_rows(g, "g", q.shape[1])
+    nq, ng, d = q.shape[0], g.shape[0], q.shape[1]
+    if not (rows or cols):
+        raise ValueError("retrieval_ranks_streamed: no direction asked for")
+    lq = _labels(labels_q, "labels_q", nq, ng, q.device) if rows else None
+    lg = _labels(labels_g, "labels_g", ng, nq, q.device) if cols else None
+    need = L.lib().xp_retrieval_ranks_streamed_workspace_bytes(nq, ng, d, int(bool(dsl)))
+    if need == 0:
+        raise ValueError(f"xp_retrieval_ranks_streamed_workspace_bytes: {L.lib().xp_last_error().decode()}")
+    ws = workspace(need, q.device, "retrieval_ranks")
+    new = lambda n: torch.empty(n, dtype=torch.int32, device=q.device)
+    gq, eq = (new(nq), new(nq)) if rows else (None, None)
+    gg, eg = (new(ng), new(ng)) if cols else (None, None)
+    L.check(L.lib().xp_retrieval_ranks_streamed(_p(q), _p(g), _p(lq), _p(lg), nq, ng, d, int(bool(dsl)), float(theta), _p(gq), _p(eq),
+                                                _p(gg), _p(eg), _p(ws), ws.numel(), _stream()), "xp_retrieval_ranks_streamed")
+    return gq, eq, gg, eg
+
+
+def retrieval_topk(q: torch.Tensor, g: torch.Tensor, k: int, index_base: int = 0, out=None):
+    """(vals [nq, k] fp32, idx [nq, k] int64): each query's k best gallery rows, score descending, ties to the lowest index;
+    ``out`` = (vals, idx) of an earlier call: its entries compete as candidates and the pair is updated in place"""
+    _feature_rows(q, "q")
+    _feature_rows(g, "g", q.shape[1])
+    nq, ng, d = q.shape[0], g.shape[0], q.shape[1]
+    k = int(k)
+    need = L.lib().xp_retrieval_topk_workspace_bytes(nq, ng, d, k)
+    if need == 0:
+        raise ValueError(f"xp_retrieval_topk_workspace_bytes: {L.lib().xp_last_error().decode()}")
+    if out is None:
+        vals = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        idx = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    else:
+        vals, idx = out
+        _chk(vals, "out[0]", torch.float32)
+        _chk(idx, "out[1]", torch.int64)
+        if tuple(vals.shape) != (nq, k) or tuple(idx.shape) != (nq, k) or not (vals.is_contiguous() and idx.is_contiguous()):
+            raise ValueError(f"out: expected contiguous ([{nq}, {k}] fp32, [{nq}, {k}] int64), got {tuple(vals.shape)}, {tuple(idx.shape)}")
+    ws = workspace(need, q.device, "retrieval_topk")
+    L.check(L.lib().xp_retrieval_topk(_p(q), _p(g), nq, ng, d, k, int(index_base), int(out is not None), _p(vals), _p(idx), _p(ws),
+                                      ws.numel(), _stream()), "xp_retrieval_topk")
+    return vals, idx

@@ -90,3 +90,52 @@ def retrieval_metrics(text_feats: torch.Tensor, vis_feats: torch.Tensor):
             sim = dsl_rerank(sim, 100.0)
         out[setting] = {"v2t": _summarise(*_rank_counts(sim, transpose=True)), "t2v": _summarise(*_rank_counts(sim))}
     return out
+
+
+# ---- retrieval at gallery scale: the same evaluation, and top-k search, without the [queries, gallery] matrix -----------------
+def _feats(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (xpretrain_amd has no CPU path)")
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: expected float32 features, got {t.dtype} (ranks turn on differences of 1e-6)")
+    return t.contiguous()
+
+
+def rank_counts_streamed(text_feats, vis_feats, labels=None, v2t_labels=None, dsl_theta=None):
+    """((greater, equal) of the t2v direction, (greater, equal) of the v2t direction) as numpy int32 vectors -- what
+    ``_rank_counts`` gives for the rows and for the columns of ``cal_cossim(text_feats, vis_feats)`` (re-ranked with
+    ``dsl_rerank(sim, dsl_theta)`` when ``dsl_theta`` is given), computed tile by tile from the features in one pass.
+    ``labels`` [n_text]: each text's video (default: the diagonal); ``v2t_labels`` [n_video]: each video's text."""
+    q, g = _feats(text_feats, "text_feats"), _feats(vis_feats, "vis_feats")
+    gq, eq, gg, eg = H.retrieval_ranks_streamed(q, g, labels, v2t_labels, dsl=dsl_theta is not None,
+                                                theta=100.0 if dsl_theta is None else float(dsl_theta))
+    return (gq.cpu().numpy(), eq.cpu().numpy()), (gg.cpu().numpy(), eg.cpu().numpy())
+
+
+def retrieval_metrics_streamed(text_feats, vis_feats, labels=None, v2t_labels=None, theta=100.0):
+    """``retrieval_metrics`` without the matrix: the same {setting: {direction: (R@1, R@5, R@10, median, mean)}}, memory and
+    traffic O(n_text + n_video).  Two calls: 'simple', then 'DSL'."""
+    out = {}
+    for setting, th in (("simple", None), ("DSL", theta)):
+        t2v, v2t = rank_counts_streamed(text_feats, vis_feats, labels, v2t_labels, dsl_theta=th)
+        out[setting] = {"v2t": _summarise(*v2t), "t2v": _summarise(*t2v)}
+    return out
+
+
+def topk(query_feats, gallery_feats, k, index_base=0, out=None):
+    """(values [n_query, k] fp32, indices [n_query, k] int64): each query's k best gallery rows by dot product, best first, ties to
+    the lowest index; ``index_base`` is added to every index.  ``out`` = (values, indices) of an earlier call: its entries compete
+    with this gallery's and the pair is updated in place -- shard by shard gives exactly the one-shot result."""
+    return H.retrieval_topk(_feats(query_feats, "query_feats"), _feats(gallery_feats, "gallery_feats"), k, index_base, out)
+
+
+def search(query_feats, shards, k):
+    """``topk`` over a gallery that arrives as an iterable of [rows, d] shards; indices count rows across the shards.  Every shard
+    needs at least k rows (a shard's own best k are what it can contribute)."""
+    out, base = None, 0
+    for shard in shards:
+        out = topk(query_feats, shard, k, index_base=base, out=out)
+        base += shard.shape[0]
+    if out is None:
+        raise ValueError("search: no gallery shards")
+    return out
