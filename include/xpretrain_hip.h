@@ -517,6 +517,44 @@ int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_
                   const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
                   int32_t n_norm_partials, float max_norm, float* grad_norm_out, void* stream);
 
+/* The step guard (opt-in): a step whose global gradient norm is not finite leaves p, m, v untouched.  What apex's dynamic loss
+ * scaling did beside scaling (a step with overflowing gradients is skipped; run_pretrain.py:234-236, 374-377 under amp), decided
+ * on the device: no host synchronisation between the partials and the update.  Three kinds of call on ONE stream, in this order:
+ *   xp_grad_sqnorm_partials   per launch table, into one partials array (always, also without clipping: the verdict needs it)
+ *   xp_step_verdict           once, over ALL n_partials chunks of the step
+ *   xp_*_step_guarded         per launch table, all reading the same verdict (a stream that forks behind xp_step_verdict may run some)
+ * xp_step_verdict sums partials[0..n) in the order xp_adamw_step / xp_optim_step sum them, so `norm` has the bits their
+ * grad_norm_out gets.  A gradient element that is finite but whose square overflows fp32 makes its partial, and the norm, infinite:
+ * that step is skipped too.  `verdict` is a DEVICE struct the caller zeroes once and then only reads (copy it to the host behind
+ * the launch to learn what happened); the counters are plain loads and stores by one lane, ordered by the stream. */
+typedef struct {
+  float norm;                           /* ||g||_2 over every chunk of the step, before clipping                              */
+  int32_t finite;                       /* 1 iff isfinite(norm)                                                               */
+  int32_t first_bad_chunk;              /* lowest chunk index whose OWN partial is not finite; -1: only the sum overflowed    */
+  int32_t reserved;
+  int64_t applied, skipped;             /* monotonic: each xp_step_verdict call adds 1 to exactly one of them                 */
+} XpStepVerdict;
+int xp_step_verdict(const float* partials, int32_t n_partials, XpStepVerdict* verdict, void* stream);
+/* Arguments as for xp_adamw_step / xp_optim_step, plus the verdict (device pointer, written by an earlier launch on an ordered stream).
+ *   finite == 1: the twin's arithmetic, element for element, in the same rounding order; coef = min(1, max_norm / (verdict->norm + 1e-6)),
+ *                max_norm <= 0: coef = 1.  norm_partials is not read again: it is here so that a caller swaps twin for twin, and
+ *                max_norm > 0 without it is refused as in the twin.
+ *   finite == 0: a workgroup neither reads nor writes m, v or the gradient and does not write p.  It rewrites its chunk of the shadow
+ *                copy from the unchanged p (one read, a half-width write): whoever relies on "this step rewrote every shadow" still may.
+ * grad_norm_out (nullable) receives verdict->norm in both cases.  The step count behind XpAdamGroup::step_size / XpOptGroup's bias
+ * factors is the caller's: a skipped step must not count (optimization/multi_tensor.py takes the increment back).
+ * A null verdict, an unknown kind and every argument error of the twin are refused before any launch. */
+int xp_adamw_step_guarded(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                          const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
+                          const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
+                          int32_t n_norm_partials, float max_norm, float* grad_norm_out,
+                          const XpStepVerdict* verdict, void* stream);
+int xp_optim_step_guarded(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                          const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
+                          const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
+                          int32_t n_norm_partials, float max_norm, float* grad_norm_out,
+                          const XpStepVerdict* verdict, void* stream);
+
 /* ------------------------------------------------------------------------------------------- Loss
  * NCELearnableTempLoss.forward (optimization/loss.py:134-141) on gathered unit-norm features
  * vis[n,d], txt[n,d] (fp32) and the LOG scale parameter: loss = CE(s V T^T, diag) + CE(s T V^T, diag).

@@ -7,7 +7,9 @@ opt_level=cfg.amp_level)`), `:324` (`build_loss_func(cfg.loss_config)`), `:222` 
 + clipping), and the shipped `src/configs/pretrain/pretrain_vip_base_16.json`.
 
 What changes, and only this: `fp16: 1` with apex `amp_level` O1 / O2 ("half-precision compute, fp32 master weights, dynamic loss scale")
-becomes bf16 compute on fp32 masters WITHOUT loss scaling (`set_compute_dtype(torch.bfloat16)`; `fp16: 0` -> float32); hub names
+becomes bf16 compute on fp32 masters WITHOUT loss scaling (`set_compute_dtype(torch.bfloat16)`; `fp16: 0` -> float32) -- the other thing
+the dynamic loss scale did, skipping a step whose gradients overflow, is the opt-in key `skip_nonfinite_steps: 1` (not a reference key;
+`setup_e2e_optimizer` reads it: the optimizer then leaves weights, moments and step counts alone on a non-finite gradient norm); hub names
 (`openai/clip-vit-base-patch16`) resolve to a local directory of that name if there is one, else -- there is no hub access -- to the
 architecture's dimensions (`KNOWN_CLIP_CONFIGS`), and weights that are not on disk are an error unless random init is asked for.
 """

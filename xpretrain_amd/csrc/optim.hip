@@ -12,6 +12,9 @@
 // and torch.nn.utils.clip_grad_norm_ as called by the training loops (run_video_retrieval.py:390-392):
 // coef = min(1, max_norm / (||g||_2 + 1e-6)).
 //
+// Opt-in, at the end of the file: the step guard.  verdict_kernel decides once per step whether the norm is finite;
+// guarded_kernel<KIND> is each of the three updates behind that verdict (not finite: p, m, v untouched, shadows rewritten from p).
+//
 // HBM-bound: per element 16 B read (p, g, m, v) + 12 B written (p, m, v) + 2 B shadow, the same for all three; the norm pass reads
 // g once more.
 // Work decomposition: fixed 64 Ki-element CHUNKS of one tensor per workgroup (chunk map built once on the host side of
@@ -304,5 +307,190 @@ extern "C" int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int3
     opt_kernel<XP_OPT_ADAMAX><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials,
                                                                         max_norm, grad_norm_out);
   XP_CHECK_LAUNCH("xp_optim_step");
+  return XP_OK;
+}
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------- the step guard (xp_step_verdict)
+// One workgroup behind the partials of ALL launch tables of the step.  The norm is summed exactly as adamw_kernel / opt_kernel sum it
+// (thread-strided, then block_sum), so it has the bits grad_norm_out gets from them.  Launches on one stream are ordered: the counters
+// are a plain load and store by one lane.  (A template only to be emitted where templates are, behind opt_kernel's instantiations:
+// as a plain function it lands in front of them in build/optim.s and renumbers their labels.)
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void verdict_kernel(const float* __restrict__ partials, int n_partials,
+                                                     XpStepVerdict* __restrict__ verdict) {
+  static_assert(THREADS == NT, "block_sum is written for NT threads");
+  __shared__ int first[NT / 64];
+  float s = 0.f;
+  int bad = n_partials;                        // lowest chunk of this thread whose own partial is not finite
+  for (int i = threadIdx.x; i < n_partials; i += NT) {
+    const float x = partials[i];
+    s += x;
+    if (!__builtin_isfinite(x) && i < bad) bad = i;
+  }
+  const float norm = sqrtf(block_sum(s));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const int b = __shfl_xor(bad, o); bad = b < bad ? b : bad; }
+  if ((threadIdx.x & 63) == 0) first[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) bad = first[i] < bad ? first[i] : bad;
+    const bool finite = __builtin_isfinite(norm);
+    verdict->norm = norm;
+    verdict->finite = finite ? 1 : 0;
+    verdict->first_bad_chunk = bad < n_partials ? bad : -1;
+    if (finite) verdict->applied = verdict->applied + 1;
+    else verdict->skipped = verdict->skipped + 1;
+  }
+}
+
+// The three updates behind a verdict.  finite: adamw_kernel's / opt_kernel's decomposition and adam1 / opt1 unchanged, the clip
+// coefficient from verdict->norm.  Not finite: the workgroup touches neither m, v nor the gradient and does not write p; it rewrites
+// its chunk of the shadow copy from the unchanged p, so that the weight cache's "this step rewrote every entry" holds either way.
+// A copy once more, for the reason given at opt_kernel: the two kernels above keep their generated code.
+constexpr int KIND_ADAMW = -1;                 // beside XpOptKind, inside this file only
+
+template <int KIND, typename Args>
+__global__ __launch_bounds__(NT) void guarded_kernel(const XpAdamTensor* __restrict__ table,
+                                                     const int32_t* __restrict__ chunk_map, Args a, float max_norm,
+                                                     const XpStepVerdict* __restrict__ verdict,
+                                                     float* __restrict__ norm_out) {
+  const float norm = verdict->norm;
+  const bool finite = verdict->finite != 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+  const int t = chunk_map[2 * blockIdx.x], c = chunk_map[2 * blockIdx.x + 1];
+  const XpAdamTensor tt = table[t];
+  const int64_t beg = (int64_t)c * CHUNK;
+  const int64_t len = tt.numel - beg < CHUNK ? tt.numel - beg : CHUNK;
+  float* p = reinterpret_cast<float*>(tt.p) + beg;
+  bf16_t* sb = tt.shadow && tt.shadow_dtype == XP_BF16 ? reinterpret_cast<bf16_t*>(tt.shadow) + beg : nullptr;
+  float* sf = tt.shadow && tt.shadow_dtype == XP_F32 ? reinterpret_cast<float*>(tt.shadow) + beg : nullptr;
+  if (!finite) {
+    if (!sb && !sf) return;
+    const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(sf) | (reinterpret_cast<uintptr_t>(sb) << 1);
+    int64_t done = 0;
+    if ((align & 15) == 0) {
+      const int64_t n4 = len >> 2;
+      for (int64_t i = threadIdx.x; i < n4; i += NT) {
+        const f32x4 pp = *reinterpret_cast<const f32x4*>(p + 4 * i);
+        if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
+        if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
+      }
+      done = n4 << 2;
+    }
+    for (int64_t i = done + threadIdx.x; i < len; i += NT) {
+      const float pp = p[i];
+      if (sb) sb[i] = (bf16_t)pp;
+      if (sf) sf[i] = pp;
+    }
+    return;
+  }
+  float coef = 1.0f;
+  if (max_norm > 0.f) { const float cc = max_norm / (norm + 1e-6f); coef = cc < 1.0f ? cc : 1.0f; }
+  const auto h = a.groups[a.grp[t]];
+  float* m = reinterpret_cast<float*>(tt.m) + beg;
+  float* v = reinterpret_cast<float*>(tt.v) + beg;
+  const float* g = a.g[t] + beg;
+  const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
+                          reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(sf) |
+                          (reinterpret_cast<uintptr_t>(sb) << 1);
+  int64_t done = 0;
+  if ((align & 15) == 0) {
+    const int64_t n4 = len >> 2;
+    for (int64_t i = threadIdx.x; i < n4; i += NT) {
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + 4 * i), mm = *reinterpret_cast<f32x4*>(m + 4 * i),
+            vv = *reinterpret_cast<f32x4*>(v + 4 * i);
+      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pp[e], me = mm[e], ve = vv[e];
+        if constexpr (KIND == KIND_ADAMW) adam1(pe, gg[e], me, ve, h, coef);
+        else opt1<KIND>(pe, gg[e], me, ve, h, coef);
+        pp[e] = pe; mm[e] = me; vv[e] = ve;
+      }
+      *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
+      *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
+      *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
+      if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
+      if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
+    }
+    done = n4 << 2;
+  }
+  for (int64_t i = done + threadIdx.x; i < len; i += NT) {
+    float pp = p[i], mm = m[i], vv = v[i];
+    if constexpr (KIND == KIND_ADAMW) adam1(pp, g[i], mm, vv, h, coef);
+    else opt1<KIND>(pp, g[i], mm, vv, h, coef);
+    p[i] = pp; m[i] = mm; v[i] = vv;
+    if (sb) sb[i] = (bf16_t)pp;
+    if (sf) sf[i] = pp;
+  }
+}
+
+// The argument checks and the argument block of a guarded call (the twins' checks, word for word, plus the verdict).
+template <typename Args, typename Group>
+int guarded_args(const char* name, Args& a, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                 const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors, const Group* groups_host,
+                 int32_t n_groups, const float* norm_partials, int32_t n_norm_partials, float max_norm,
+                 const XpStepVerdict* verdict) {
+  XP_REQUIRE(verdict, "%s: null verdict (xp_step_verdict writes it, behind the partials of the whole step)", name);
+  XP_REQUIRE(table && chunk_map && grads_host && group_of_host && groups_host && n_chunks > 0, "%s: null argument", name);
+  XP_REQUIRE(n_tensors > 0 && n_tensors <= MAXT, "%s: n_tensors=%d not in 1..%d", name, n_tensors, MAXT);
+  XP_REQUIRE(n_groups > 0 && n_groups <= MAXG, "%s: n_groups=%d not in 1..%d", name, n_groups, MAXG);
+  XP_REQUIRE(norm_partials || max_norm <= 0.f, "%s: max_norm > 0 needs the gradient-norm partials", name);
+  XP_REQUIRE(!norm_partials || n_norm_partials > 0, "%s: n_norm_partials must be positive", name);
+  for (int i = 0; i < MAXT; ++i) { a.g[i] = nullptr; a.grp[i] = 0; }
+  for (int i = 0; i < n_tensors; ++i) {
+    XP_REQUIRE(grads_host[i], "%s: gradient %d is null", name, i);
+    XP_REQUIRE(group_of_host[i] < n_groups, "%s: tensor %d has group %d >= %d", name, i, group_of_host[i], n_groups);
+    a.g[i] = reinterpret_cast<const float*>(grads_host[i]);
+    a.grp[i] = group_of_host[i];
+  }
+  for (int i = 0; i < n_groups; ++i) a.groups[i] = groups_host[i];
+  for (int i = n_groups; i < MAXG; ++i) a.groups[i] = groups_host[0];
+  return XP_OK;
+}
+
+}  // namespace
+
+extern "C" int xp_step_verdict(const float* partials, int32_t n_partials, XpStepVerdict* verdict, void* stream) {
+  XP_REQUIRE(partials && verdict, "xp_step_verdict: null argument");
+  XP_REQUIRE(n_partials > 0, "xp_step_verdict: n_partials=%d must be positive", n_partials);
+  verdict_kernel<NT><<<1, NT, 0, (hipStream_t)stream>>>(partials, n_partials, verdict);
+  XP_CHECK_LAUNCH("xp_step_verdict");
+  return XP_OK;
+}
+
+extern "C" int xp_adamw_step_guarded(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                                     const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
+                                     const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
+                                     int32_t n_norm_partials, float max_norm, float* grad_norm_out,
+                                     const XpStepVerdict* verdict, void* stream) {
+  StepArgs a;
+  const int rc = guarded_args("xp_adamw_step_guarded", a, table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host,
+                              n_groups, norm_partials, n_norm_partials, max_norm, verdict);
+  if (rc != XP_OK) return rc;
+  guarded_kernel<KIND_ADAMW><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, max_norm, verdict, grad_norm_out);
+  XP_CHECK_LAUNCH("xp_adamw_step_guarded");
+  return XP_OK;
+}
+
+extern "C" int xp_optim_step_guarded(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
+                                     const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
+                                     const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
+                                     int32_t n_norm_partials, float max_norm, float* grad_norm_out,
+                                     const XpStepVerdict* verdict, void* stream) {
+  XP_REQUIRE(kind == XP_OPT_ADAM || kind == XP_OPT_ADAMAX,
+             "xp_optim_step_guarded: unknown kind %d (XP_OPT_ADAM = %d, XP_OPT_ADAMAX = %d)", kind, (int)XP_OPT_ADAM, (int)XP_OPT_ADAMAX);
+  OptArgs a;
+  const int rc = guarded_args("xp_optim_step_guarded", a, table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host,
+                              n_groups, norm_partials, n_norm_partials, max_norm, verdict);
+  if (rc != XP_OK) return rc;
+  if (kind == XP_OPT_ADAM)
+    guarded_kernel<XP_OPT_ADAM><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, max_norm, verdict, grad_norm_out);
+  else
+    guarded_kernel<XP_OPT_ADAMAX><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, max_norm, verdict, grad_norm_out);
+  XP_CHECK_LAUNCH("xp_optim_step_guarded");
   return XP_OK;
 }

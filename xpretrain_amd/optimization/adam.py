@@ -7,8 +7,8 @@ arguments, run torch's own argument checks, and keep torch's state keys (``step`
 Python int here.  The arithmetic is torch's single-tensor path with ``amsgrad = maximize = False`` (include/xpretrain_hip.h,
 ``xp_optim_step``): coupled L2 weight decay on the clipped gradient, bias corrections where torch applies them.
 
-The fused clip, the rewritten compute-dtype weight copies and ``overlap_next_forward`` come from
-``multi_tensor.MultiTensorOptimizer``, as for ``AdamW``.  There is no eager fallback: without the HIP library the step raises.
+The fused clip, the rewritten compute-dtype weight copies, ``overlap_next_forward`` and the opt-in step guard (``skip_nonfinite=True``,
+``xp_optim_step_guarded``) come from ``multi_tensor.MultiTensorOptimizer``, as for ``AdamW``.  There is no eager fallback: without the HIP library the step raises.
 """
 import math
 
@@ -35,7 +35,12 @@ class _TorchFamily(MultiTensorOptimizer):
         return L.XpOptGroup(lr, b1, b2, group["eps"], group["weight_decay"], lr / (1.0 - b1 ** step),
                             math.sqrt(1.0 - b2 ** step), 1.0 - b1)
 
-    def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream):
+    def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream, verdict=None):
+        if verdict is not None:
+            L.check(lib.xp_optim_step_guarded(self._KIND, la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"],
+                                              la["grp"], la["n"], groups, n_groups, partials, n_partials, max_norm, norm, verdict, stream),
+                    "xp_optim_step_guarded")
+            return
         L.check(lib.xp_optim_step(self._KIND, la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"],
                                   la["grp"], la["n"], groups, n_groups, partials, n_partials, max_norm, norm, stream),
                 "xp_optim_step")
@@ -45,15 +50,17 @@ class Adam(_TorchFamily):
     _STATE = ("exp_avg", "exp_avg_sq")
     _KIND = L.XP_OPT_ADAM
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, skip_nonfinite=False):
         if amsgrad:
             raise NotImplementedError("xpretrain_amd Adam: amsgrad=True is not implemented")
-        super().__init__(params, _checked(torch.optim.Adam, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+        super().__init__(params, _checked(torch.optim.Adam, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False),
+                         skip_nonfinite=skip_nonfinite)
 
 
 class Adamax(_TorchFamily):
     _STATE = ("exp_avg", "exp_inf")
     _KIND = L.XP_OPT_ADAMAX
 
-    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
-        super().__init__(params, _checked(torch.optim.Adamax, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, skip_nonfinite=False):
+        super().__init__(params, _checked(torch.optim.Adamax, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         skip_nonfinite=skip_nonfinite)

@@ -2,8 +2,9 @@
 
 Mirrors ``src/optimization/adamw.py:11-103`` (``AdamW(params, lr, betas, eps=1e-6, weight_decay, correct_bias)``,
 ``.step(closure)``; state keys ``step`` / ``exp_avg`` / ``exp_avg_sq`` as ``E2E_TrainingRestorer`` checkpoints them,
-``utils/load_save.py:306-314``).  On top of the reference surface, the fused clip (``step(max_grad_norm=...)`` / ``clip_and_step``), the rewritten compute-dtype weight copies and
-``overlap_next_forward`` come from ``multi_tensor.MultiTensorOptimizer``, which ``Adam`` and ``Adamax`` (``adam.py``) share.
+``utils/load_save.py:306-314``).  On top of the reference surface, the fused clip (``step(max_grad_norm=...)`` / ``clip_and_step``), the rewritten compute-dtype weight copies,
+``overlap_next_forward`` and the opt-in step guard (``skip_nonfinite=True``: a step with a non-finite gradient norm changes nothing) come
+from ``multi_tensor.MultiTensorOptimizer``, which ``Adam`` and ``Adamax`` (``adam.py``) share.
 
 There is no eager fallback: without the HIP library the step raises.
 """
@@ -16,7 +17,7 @@ from .multi_tensor import MultiTensorOptimizer
 class AdamW(MultiTensorOptimizer):
     _STATE = ("exp_avg", "exp_avg_sq")
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, skip_nonfinite=False):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if not 0.0 <= betas[0] < 1.0:
@@ -25,7 +26,8 @@ class AdamW(MultiTensorOptimizer):
             raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
         if not 0.0 <= eps:
             raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias))
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias),
+                         skip_nonfinite=skip_nonfinite)
 
     def _group_struct(self, group, step):
         b1, b2 = group["betas"]
@@ -34,6 +36,11 @@ class AdamW(MultiTensorOptimizer):
             step_size = step_size * math.sqrt(1.0 - b2 ** step) / (1.0 - b1 ** step)
         return L.XpAdamGroup(group["lr"], b1, b2, group["eps"], group["weight_decay"], step_size)
 
-    def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream):
+    def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream, verdict=None):
+        if verdict is not None:
+            L.check(lib.xp_adamw_step_guarded(la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"], la["grp"],
+                                              la["n"], groups, n_groups, partials, n_partials, max_norm, norm, verdict, stream),
+                    "xp_adamw_step_guarded")
+            return
         L.check(lib.xp_adamw_step(la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"], la["grp"],
                                   la["n"], groups, n_groups, partials, n_partials, max_norm, norm, stream), "xp_adamw_step")

@@ -41,4 +41,9 @@ def setup_e2e_optimizer(model, opts):
         OptimCls = AdamW
     else:
         raise ValueError("invalid optimizer")
-    return OptimCls(groups, lr=opts.learning_rate, betas=tuple(opts.betas))
+    # skip_nonfinite_steps: what amp's dynamic loss scaling also did in the reference's loop (a step whose gradients overflow changes
+    # nothing), without the scaling bf16 does not need; the names let a skipped step say which parameter it was
+    optimizer = OptimCls(groups, lr=opts.learning_rate, betas=tuple(opts.betas),
+                         skip_nonfinite=bool(getattr(opts, "skip_nonfinite_steps", 0)))
+    optimizer.param_names = {id(p): n for n, p in model.named_parameters()}
+    return optimizer
