@@ -5,7 +5,7 @@ the step's phases as the trace shows them (first / last kernel of the video towe
 
     python tools/step_timeline.py <kernel_trace.csv> [--step K] [--min-us D] > profiles/rNN_step_timeline.txt
 
-The step boundaries are the ends of the LAST adamw_kernel launch of each step (a step has 3 such launches, or 2 + late ones)."""
+The step boundaries are the ends of the LAST update_kernel launch (csrc/optim.hip) of each step (a step has 3 such launches, or 2 + late ones)."""
 import argparse
 import csv
 
@@ -31,8 +31,8 @@ def main():
         ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"]), r.get("Queue_Id", "?"),
                    (gx // wx) * (gy // max(wy, 1)) * (gz // max(wz, 1))))
     ev.sort()
-    # step boundary: the sqnorm_partials launches open the optimizer of a step; the step ends with the last adamw of that group
-    ad = [i for i, e in enumerate(ev) if e[2].startswith("adamw_kernel")]
+    # step boundary: the sqnorm_partials launches open the optimizer of a step; the step ends with the last update of that group
+    ad = [i for i, e in enumerate(ev) if e[2].startswith("update_kernel")]
     groups, cur = [], [ad[0]]
     for i in ad[1:]:
         if ev[i][0] - ev[cur[-1]][1] > 3_000_000:        # > 3 ms apart: another step
@@ -43,8 +43,8 @@ def main():
     ends = [max(ev[i][1] for i in g) for g in groups]
     k = a.step if a.step >= 0 else len(ends) + a.step
     lo, hi = ends[k - 1], ends[k]
-    win = [e for e in ev if e[0] >= lo - 2_000_000 and e[0] < hi]       # (late adamw launches of the previous step overlap this one)
-    win = [e for e in win if e[1] > lo or not e[2].startswith("adamw")]
+    win = [e for e in ev if e[0] >= lo - 2_000_000 and e[0] < hi]       # (late update launches of the previous step overlap this one)
+    win = [e for e in win if e[1] > lo or not e[2].startswith("update_kernel")]
     win = [e for e in win if e[0] >= lo or e[1] > lo]
     t0 = min(e[0] for e in win if e[0] >= lo)
     qs = {q: i for i, q in enumerate(sorted({e[3] for e in win}))}

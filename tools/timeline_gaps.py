@@ -7,11 +7,11 @@ import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 ev = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", r.get("Stream_Id", "?"))) for r in rows))
-# steady state: the window between the 40 % and 80 % marks of the run's adamw launches (a few whole steps)
-ad = [e for e in ev if "adamw_kernel" in e[2]]
+# steady state: the window between the 40 % and 80 % marks of the run's optimizer update launches (update_kernel, csrc/optim.hip) (a few whole steps)
+ad = [e for e in ev if "update_kernel" in e[2]]
 lo, hi = ad[len(ad) * 4 // 10][1], ad[len(ad) * 8 // 10][1]
 win = [e for e in ev if lo <= e[0] and e[1] <= hi]
-nsteps = sum(1 for e in win if "adamw_kernel" in e[2]) / 2
+nsteps = sum(1 for e in win if "update_kernel" in e[2]) / 2
 busy, cur_s, cur_e, gaps = 0, None, None, []
 for s, e, name, q in win:
     if cur_e is None or s > cur_e:

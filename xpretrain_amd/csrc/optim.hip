@@ -2,18 +2,26 @@
 // multi-tensor launch, fp32 master weights, optional compute-dtype shadow copies written in the same pass.  Three updates, one
 // per value of the drivers' `optim` key (src/configs/config.py:135-137, src/optimization/utils.py:111-120):
 //
-//   adamw_kernel             restates  src/optimization/adamw.py:40-103  (AdamW.step: m/v update, denom = sqrt(v) + eps,
-//                            bias-corrected step size, decoupled weight decay AFTER the Adam update with the group's lr)
-//   opt_kernel<XP_OPT_ADAM>    torch.optim.Adam   as utils.py:119 builds it (single-tensor path, amsgrad = maximize = False)
-//   opt_kernel<XP_OPT_ADAMAX>  torch.optim.Adamax likewise
+//   adam1                   restates  src/optimization/adamw.py:40-103  (AdamW.step: m/v update, denom = sqrt(v) + eps,
+//                           bias-corrected step size, decoupled weight decay AFTER the Adam update with the group's lr)
+//   opt1<XP_OPT_ADAM>       torch.optim.Adam   as utils.py:119 builds it (single-tensor path, amsgrad = maximize = False)
+//   opt1<XP_OPT_ADAMAX>     torch.optim.Adamax likewise
 //     both: coupled L2 decay added to the CLIPPED gradient before the moments; the bias corrections applied where torch applies
 //     them (Adam: sqrt(v) / sqrt(1-b2^t) + eps; Adamax: eps inside the max operand) -- see opt1 below
 //
 // and torch.nn.utils.clip_grad_norm_ as called by the training loops (run_video_retrieval.py:390-392):
 // coef = min(1, max_norm / (||g||_2 + 1e-6)).
 //
-// Opt-in, at the end of the file: the step guard.  verdict_kernel decides once per step whether the norm is finite;
-// guarded_kernel<KIND> is each of the three updates behind that verdict (not finite: p, m, v untouched, shadows rewritten from p).
+// One decomposition for all of them:
+//   walk<UPDATE>(tensor, chunk, g, one)   one workgroup over one 64 Ki-element chunk: the 16-byte path where every pointer it touches
+//                                         allows it, the scalar tail, the bf16 / fp32 shadow stores.  UPDATE: `one` on (p, g, m, v);
+//                                         else the shadows alone, rewritten from p
+//   norm_of / clip_coef                   the gradient norm from the per-chunk partials and the clip coefficient, written once
+//   update_kernel<KIND, GUARDED>          the six update kernels: norm and coefficient (unguarded: from the partials, when given;
+//                                         guarded: from the step's verdict), then walk with adam1 or opt1<KIND>
+//   verdict_kernel                        the opt-in step guard: decides once per step whether norm_of is finite.  Behind a verdict
+//                                         that is not, a guarded update leaves p, m, v alone and rewrites the shadows from p
+// The bits of the three updates are held by tests/test_optim_bits_gpu.py.
 //
 // HBM-bound: per element 16 B read (p, g, m, v) + 12 B written (p, m, v) + 2 B shadow, the same for all three; the norm pass reads
 // g once more.
@@ -28,11 +36,13 @@ namespace {
 constexpr int NT = 256;                      // threads per workgroup
 constexpr int CHUNK = XP_OPT_CHUNK;          // elements per workgroup
 constexpr int MAXT = XP_OPT_MAX_TENSORS, MAXG = XP_OPT_MAX_GROUPS;
+constexpr int KIND_ADAMW = -1;               // beside XpOptKind, inside this file only
 
-struct StepArgs {
+template <typename Group>                    // XpAdamGroup (AdamW) or XpOptGroup (Adam, Adamax)
+struct UpdateArgs {
   const float* g[MAXT];
   unsigned char grp[MAXT];
-  XpAdamGroup groups[MAXG];
+  Group groups[MAXG];
 };
 struct NormArgs { const float* g[MAXT]; };
 
@@ -84,69 +94,6 @@ __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, con
   if (h.weight_decay > 0.f) p = __builtin_fmaf(-(h.lr * h.weight_decay), p, p);
 }
 
-__global__ __launch_bounds__(NT) void adamw_kernel(const XpAdamTensor* __restrict__ table,
-                                                   const int32_t* __restrict__ chunk_map, StepArgs a,
-                                                   const float* __restrict__ partials, int n_partials, float max_norm,
-                                                   float* __restrict__ norm_out) {
-  float coef = 1.0f;
-  if (partials != nullptr) {
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n_partials; i += NT) s += partials[i];
-    const float norm = sqrtf(block_sum(s));
-    if (max_norm > 0.f) { const float c = max_norm / (norm + 1e-6f); coef = c < 1.0f ? c : 1.0f; }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
-  }
-  const int t = chunk_map[2 * blockIdx.x], c = chunk_map[2 * blockIdx.x + 1];
-  const XpAdamTensor tt = table[t];
-  const XpAdamGroup h = a.groups[a.grp[t]];
-  const int64_t beg = (int64_t)c * CHUNK;
-  const int64_t len = tt.numel - beg < CHUNK ? tt.numel - beg : CHUNK;
-  float* p = reinterpret_cast<float*>(tt.p) + beg;
-  float* m = reinterpret_cast<float*>(tt.m) + beg;
-  float* v = reinterpret_cast<float*>(tt.v) + beg;
-  const float* g = a.g[t] + beg;
-  bf16_t* sb = tt.shadow && tt.shadow_dtype == XP_BF16 ? reinterpret_cast<bf16_t*>(tt.shadow) + beg : nullptr;
-  float* sf = tt.shadow && tt.shadow_dtype == XP_F32 ? reinterpret_cast<float*>(tt.shadow) + beg : nullptr;
-  const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-                          reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(sf) |
-                          (reinterpret_cast<uintptr_t>(sb) << 1);
-  int64_t done = 0;
-  if ((align & 15) == 0) {
-    const int64_t n4 = len >> 2;
-    for (int64_t i = threadIdx.x; i < n4; i += NT) {
-      f32x4 pp = *reinterpret_cast<f32x4*>(p + 4 * i), mm = *reinterpret_cast<f32x4*>(m + 4 * i),
-            vv = *reinterpret_cast<f32x4*>(v + 4 * i);
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pp[e], me = mm[e], ve = vv[e];
-        adam1(pe, gg[e], me, ve, h, coef);
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
-      }
-      *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
-      *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
-      *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
-      if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
-      if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
-    }
-    done = n4 << 2;
-  }
-  for (int64_t i = done + threadIdx.x; i < len; i += NT) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    adam1(pp, g[i], mm, vv, h, coef);
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (sb) sb[i] = (bf16_t)pp;
-    if (sf) sf[i] = pp;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- Adam / Adamax (xp_optim_step)
-struct OptArgs {
-  const float* g[MAXT];
-  unsigned char grp[MAXT];
-  XpOptGroup groups[MAXG];
-};
-
 // One element of torch.optim.Adam / Adamax (torch/optim/adam.py::_single_tensor_adam, adamax.py::_single_tensor_adamax).  Every
 // rounding point is written out, as in adam1.  The form chosen:
 //   decay       one fma(wd, p, g)                                  (torch: add with alpha)
@@ -177,33 +124,37 @@ __device__ __forceinline__ void opt1(float& p, float g, float& m, float& v, cons
   p = __builtin_fmaf(-h.step_size, m / denom, p);
 }
 
-// adamw_kernel's decomposition with opt1 in place of adam1.  A copy, not a shared template: adamw_kernel's generated code is pinned
-// (byte-identical section of build/optim.s), and routing it through a template both kernels call, same arithmetic, renamed its
-// registers and moved three instructions.
-template <int KIND>
-__global__ __launch_bounds__(NT) void opt_kernel(const XpAdamTensor* __restrict__ table,
-                                                 const int32_t* __restrict__ chunk_map, OptArgs a,
-                                                 const float* __restrict__ partials, int n_partials, float max_norm,
-                                                 float* __restrict__ norm_out) {
-  float coef = 1.0f;
-  if (partials != nullptr) {
-    float s = 0.f;
-    for (int i = threadIdx.x; i < n_partials; i += NT) s += partials[i];
-    const float norm = sqrtf(block_sum(s));
-    if (max_norm > 0.f) { const float c = max_norm / (norm + 1e-6f); coef = c < 1.0f ? c : 1.0f; }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+// The gradient norm from the per-chunk partials: thread-strided, then block_sum.  Every workgroup of an unguarded clipped update and
+// the verdict kernel call this, so they hold the same bits.  each(i, partials[i]) sees every partial on its way into the sum.
+template <typename F>
+__device__ __forceinline__ float norm_of(const float* __restrict__ partials, int n, F each) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += NT) {
+    const float x = partials[i];
+    s += x;
+    each(i, x);
   }
-  const int t = chunk_map[2 * blockIdx.x], c = chunk_map[2 * blockIdx.x + 1];
-  const XpAdamTensor tt = table[t];
-  const XpOptGroup h = a.groups[a.grp[t]];
+  return sqrtf(block_sum(s));
+}
+
+__device__ __forceinline__ float clip_coef(float norm, float max_norm) {
+  if (max_norm > 0.f) { const float c = max_norm / (norm + 1e-6f); return c < 1.0f ? c : 1.0f; }
+  return 1.0f;
+}
+
+// Chunk c of one tensor.  UPDATE: one(p, g, m, v) on every element, p, m, v stored back, the shadow copy written from the new p.
+// Not UPDATE: neither m, v nor g is touched and p is not written; the shadow copy, if there is one, is rewritten from p.
+template <bool UPDATE, typename F>
+__device__ __forceinline__ void walk(const XpAdamTensor& tt, int c, const float* gt, F one) {
   const int64_t beg = (int64_t)c * CHUNK;
   const int64_t len = tt.numel - beg < CHUNK ? tt.numel - beg : CHUNK;
   float* p = reinterpret_cast<float*>(tt.p) + beg;
-  float* m = reinterpret_cast<float*>(tt.m) + beg;
-  float* v = reinterpret_cast<float*>(tt.v) + beg;
-  const float* g = a.g[t] + beg;
   bf16_t* sb = tt.shadow && tt.shadow_dtype == XP_BF16 ? reinterpret_cast<bf16_t*>(tt.shadow) + beg : nullptr;
   float* sf = tt.shadow && tt.shadow_dtype == XP_F32 ? reinterpret_cast<float*>(tt.shadow) + beg : nullptr;
+  if (!UPDATE && !sb && !sf) return;
+  float* m = UPDATE ? reinterpret_cast<float*>(tt.m) + beg : nullptr;
+  float* v = UPDATE ? reinterpret_cast<float*>(tt.v) + beg : nullptr;
+  const float* g = UPDATE ? gt + beg : nullptr;
   const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
                           reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(sf) |
                           (reinterpret_cast<uintptr_t>(sb) << 1);
@@ -211,30 +162,138 @@ __global__ __launch_bounds__(NT) void opt_kernel(const XpAdamTensor* __restrict_
   if ((align & 15) == 0) {
     const int64_t n4 = len >> 2;
     for (int64_t i = threadIdx.x; i < n4; i += NT) {
-      f32x4 pp = *reinterpret_cast<f32x4*>(p + 4 * i), mm = *reinterpret_cast<f32x4*>(m + 4 * i),
-            vv = *reinterpret_cast<f32x4*>(v + 4 * i);
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
+      f32x4 pp = *reinterpret_cast<f32x4*>(p + 4 * i);
+      if constexpr (UPDATE) {
+        f32x4 mm = *reinterpret_cast<f32x4*>(m + 4 * i), vv = *reinterpret_cast<f32x4*>(v + 4 * i);
+        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pp[e], me = mm[e], ve = vv[e];
-        opt1<KIND>(pe, gg[e], me, ve, h, coef);
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
+        for (int e = 0; e < 4; ++e) {
+          float pe = pp[e], me = mm[e], ve = vv[e];
+          one(pe, gg[e], me, ve);
+          pp[e] = pe; mm[e] = me; vv[e] = ve;
+        }
+        *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
+        *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
+        *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
       }
-      *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
-      *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
-      *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
       if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
       if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
     }
     done = n4 << 2;
   }
   for (int64_t i = done + threadIdx.x; i < len; i += NT) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    opt1<KIND>(pp, g[i], mm, vv, h, coef);
-    p[i] = pp; m[i] = mm; v[i] = vv;
+    float pp = p[i];
+    if constexpr (UPDATE) {
+      float mm = m[i], vv = v[i];
+      one(pp, g[i], mm, vv);
+      p[i] = pp; m[i] = mm; v[i] = vv;
+    }
     if (sb) sb[i] = (bf16_t)pp;
     if (sf) sf[i] = pp;
   }
+}
+
+// The three updates, unguarded and behind a verdict.  Unguarded: the norm and the coefficient from the partials when they are given
+// (then norm_out, if not null, gets the norm); the verdict is not read.  GUARDED: both from the verdict xp_step_verdict left (norm_out,
+// if not null, always gets its norm); the partials are not touched.  Behind a verdict that is not finite the workgroup touches neither
+// m, v nor the gradient and does not write p; it rewrites its chunk of the shadow copy from the unchanged p, so that the weight cache's
+// "this step rewrote every entry" holds either way.
+template <int KIND, bool GUARDED, typename Group>
+__global__ __launch_bounds__(NT) void update_kernel(const XpAdamTensor* __restrict__ table, const int32_t* __restrict__ chunk_map,
+                                                    UpdateArgs<Group> a, const float* __restrict__ partials, int n_partials,
+                                                    float max_norm, const XpStepVerdict* __restrict__ verdict,
+                                                    float* __restrict__ norm_out) {
+  float coef = 1.0f;
+  if (GUARDED || partials != nullptr) {
+    float norm;
+    if constexpr (GUARDED) norm = verdict->norm;
+    else norm = norm_of(partials, n_partials, [](int, float) {});
+    coef = clip_coef(norm, max_norm);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+  }
+  const int t = chunk_map[2 * blockIdx.x], c = chunk_map[2 * blockIdx.x + 1];
+  const XpAdamTensor tt = table[t];
+  if constexpr (GUARDED) {
+    if (verdict->finite == 0) { walk<false>(tt, c, nullptr, nullptr); return; }
+  }
+  const Group h = a.groups[a.grp[t]];
+  walk<true>(tt, c, a.g[t], [&](float& p, float g, float& m, float& v) {
+    if constexpr (KIND == KIND_ADAMW) adam1(p, g, m, v, h, coef);
+    else opt1<KIND>(p, g, m, v, h, coef);
+  });
+}
+
+// ---------------------------------------------------------------------------------------------- the step guard (xp_step_verdict)
+// One workgroup behind the partials of ALL launch tables of the step.  Launches on one stream are ordered: the counters are a plain
+// load and store by one lane.
+__global__ __launch_bounds__(NT) void verdict_kernel(const float* __restrict__ partials, int n_partials,
+                                                     XpStepVerdict* __restrict__ verdict) {
+  __shared__ int first[NT / 64];
+  int bad = n_partials;                        // lowest chunk of this thread whose own partial is not finite
+  const float norm = norm_of(partials, n_partials, [&](int i, float x) { if (!__builtin_isfinite(x) && i < bad) bad = i; });
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { const int b = __shfl_xor(bad, o); bad = b < bad ? b : bad; }
+  if ((threadIdx.x & 63) == 0) first[threadIdx.x >> 6] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < NT / 64; ++i) bad = first[i] < bad ? first[i] : bad;
+    const bool finite = __builtin_isfinite(norm);
+    verdict->norm = norm;
+    verdict->finite = finite ? 1 : 0;
+    verdict->first_bad_chunk = bad < n_partials ? bad : -1;
+    if (finite) verdict->applied = verdict->applied + 1;
+    else verdict->skipped = verdict->skipped + 1;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- host side of the four update calls
+template <typename Group>
+struct UpdateCall {                            // the arguments of xp_adamw_step[_guarded] / xp_optim_step[_guarded], as the ABI names them
+  const XpAdamTensor* table; const int32_t* chunk_map; int32_t n_chunks;
+  const void* const* grads_host; const uint8_t* group_of_host; int32_t n_tensors;
+  const Group* groups_host; int32_t n_groups;
+  const float* norm_partials; int32_t n_norm_partials; float max_norm; float* grad_norm_out;
+  const XpStepVerdict* verdict; void* stream;
+};
+
+// The argument checks and the argument block of an update call.
+template <typename Group>
+int check_and_fill(const char* name, const UpdateCall<Group>& u, bool guarded, UpdateArgs<Group>& a) {
+  XP_REQUIRE(!guarded || u.verdict, "%s: null verdict (xp_step_verdict writes it, behind the partials of the whole step)", name);
+  XP_REQUIRE(u.table && u.chunk_map && u.grads_host && u.group_of_host && u.groups_host && u.n_chunks > 0, "%s: null argument", name);
+  XP_REQUIRE(u.n_tensors > 0 && u.n_tensors <= MAXT, "%s: n_tensors=%d not in 1..%d", name, u.n_tensors, MAXT);
+  XP_REQUIRE(u.n_groups > 0 && u.n_groups <= MAXG, "%s: n_groups=%d not in 1..%d", name, u.n_groups, MAXG);
+  XP_REQUIRE(u.norm_partials || u.max_norm <= 0.f, "%s: max_norm > 0 needs the gradient-norm partials", name);
+  XP_REQUIRE(!u.norm_partials || u.n_norm_partials > 0, "%s: n_norm_partials must be positive", name);
+  for (int i = 0; i < MAXT; ++i) { a.g[i] = nullptr; a.grp[i] = 0; }
+  for (int i = 0; i < u.n_tensors; ++i) {
+    XP_REQUIRE(u.grads_host[i], "%s: gradient %d is null", name, i);
+    XP_REQUIRE(u.group_of_host[i] < u.n_groups, "%s: tensor %d has group %d >= %d", name, i, u.group_of_host[i], u.n_groups);
+    a.g[i] = reinterpret_cast<const float*>(u.grads_host[i]);
+    a.grp[i] = u.group_of_host[i];
+  }
+  for (int i = 0; i < u.n_groups; ++i) a.groups[i] = u.groups_host[i];
+  for (int i = u.n_groups; i < MAXG; ++i) a.groups[i] = u.groups_host[0];
+  return XP_OK;
+}
+
+template <int KIND, bool GUARDED, typename Group>
+int launch_update(const char* name, const UpdateCall<Group>& u) {
+  UpdateArgs<Group> a;
+  const int rc = check_and_fill(name, u, GUARDED, a);
+  if (rc != XP_OK) return rc;
+  update_kernel<KIND, GUARDED><<<u.n_chunks, NT, 0, (hipStream_t)u.stream>>>(u.table, u.chunk_map, a, u.norm_partials, u.n_norm_partials,
+                                                                             u.max_norm, u.verdict, u.grad_norm_out);
+  XP_CHECK_LAUNCH(name);
+  return XP_OK;
+}
+
+template <bool GUARDED>
+int launch_optim(const char* name, int32_t kind, const UpdateCall<XpOptGroup>& u) {
+  XP_REQUIRE(kind == XP_OPT_ADAM || kind == XP_OPT_ADAMAX, "%s: unknown kind %d (XP_OPT_ADAM = %d, XP_OPT_ADAMAX = %d)", name, kind,
+             (int)XP_OPT_ADAM, (int)XP_OPT_ADAMAX);
+  return kind == XP_OPT_ADAM ? launch_update<XP_OPT_ADAM, GUARDED>(name, u) : launch_update<XP_OPT_ADAMAX, GUARDED>(name, u);
 }
 
 }  // namespace
@@ -258,206 +317,23 @@ extern "C" int xp_adamw_step(const XpAdamTensor* table, const int32_t* chunk_map
                              const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                              const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
                              int32_t n_norm_partials, float max_norm, float* grad_norm_out, void* stream) {
-  XP_REQUIRE(table && chunk_map && grads_host && group_of_host && groups_host && n_chunks > 0, "xp_adamw_step: null argument");
-  XP_REQUIRE(n_tensors > 0 && n_tensors <= MAXT, "xp_adamw_step: n_tensors=%d not in 1..%d", n_tensors, MAXT);
-  XP_REQUIRE(n_groups > 0 && n_groups <= MAXG, "xp_adamw_step: n_groups=%d not in 1..%d", n_groups, MAXG);
-  XP_REQUIRE(norm_partials || max_norm <= 0.f, "xp_adamw_step: max_norm > 0 needs the gradient-norm partials");
-  XP_REQUIRE(!norm_partials || n_norm_partials > 0, "xp_adamw_step: n_norm_partials must be positive");
-  StepArgs a;
-  for (int i = 0; i < MAXT; ++i) { a.g[i] = nullptr; a.grp[i] = 0; }
-  for (int i = 0; i < n_tensors; ++i) {
-    XP_REQUIRE(grads_host[i], "xp_adamw_step: gradient %d is null", i);
-    XP_REQUIRE(group_of_host[i] < n_groups, "xp_adamw_step: tensor %d has group %d >= %d", i, group_of_host[i], n_groups);
-    a.g[i] = reinterpret_cast<const float*>(grads_host[i]);
-    a.grp[i] = group_of_host[i];
-  }
-  for (int i = 0; i < n_groups; ++i) a.groups[i] = groups_host[i];
-  for (int i = n_groups; i < MAXG; ++i) a.groups[i] = groups_host[0];
-  adamw_kernel<<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials, max_norm,
-                                                         grad_norm_out);
-  XP_CHECK_LAUNCH("xp_adamw_step");
-  return XP_OK;
+  return launch_update<KIND_ADAMW, false, XpAdamGroup>(
+      "xp_adamw_step", {table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host, n_groups, norm_partials,
+                        n_norm_partials, max_norm, grad_norm_out, nullptr, stream});
 }
 
 extern "C" int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                              const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                              const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
                              int32_t n_norm_partials, float max_norm, float* grad_norm_out, void* stream) {
-  XP_REQUIRE(kind == XP_OPT_ADAM || kind == XP_OPT_ADAMAX, "xp_optim_step: unknown kind %d (XP_OPT_ADAM = %d, XP_OPT_ADAMAX = %d)",
-             kind, (int)XP_OPT_ADAM, (int)XP_OPT_ADAMAX);
-  XP_REQUIRE(table && chunk_map && grads_host && group_of_host && groups_host && n_chunks > 0, "xp_optim_step: null argument");
-  XP_REQUIRE(n_tensors > 0 && n_tensors <= MAXT, "xp_optim_step: n_tensors=%d not in 1..%d", n_tensors, MAXT);
-  XP_REQUIRE(n_groups > 0 && n_groups <= MAXG, "xp_optim_step: n_groups=%d not in 1..%d", n_groups, MAXG);
-  XP_REQUIRE(norm_partials || max_norm <= 0.f, "xp_optim_step: max_norm > 0 needs the gradient-norm partials");
-  XP_REQUIRE(!norm_partials || n_norm_partials > 0, "xp_optim_step: n_norm_partials must be positive");
-  OptArgs a;
-  for (int i = 0; i < MAXT; ++i) { a.g[i] = nullptr; a.grp[i] = 0; }
-  for (int i = 0; i < n_tensors; ++i) {
-    XP_REQUIRE(grads_host[i], "xp_optim_step: gradient %d is null", i);
-    XP_REQUIRE(group_of_host[i] < n_groups, "xp_optim_step: tensor %d has group %d >= %d", i, group_of_host[i], n_groups);
-    a.g[i] = reinterpret_cast<const float*>(grads_host[i]);
-    a.grp[i] = group_of_host[i];
-  }
-  for (int i = 0; i < n_groups; ++i) a.groups[i] = groups_host[i];
-  for (int i = n_groups; i < MAXG; ++i) a.groups[i] = groups_host[0];
-  if (kind == XP_OPT_ADAM)
-    opt_kernel<XP_OPT_ADAM><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials,
-                                                                      max_norm, grad_norm_out);
-  else
-    opt_kernel<XP_OPT_ADAMAX><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, norm_partials, n_norm_partials,
-                                                                        max_norm, grad_norm_out);
-  XP_CHECK_LAUNCH("xp_optim_step");
-  return XP_OK;
+  return launch_optim<false>("xp_optim_step", kind, {table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host,
+                                                     n_groups, norm_partials, n_norm_partials, max_norm, grad_norm_out, nullptr, stream});
 }
-
-namespace {
-
-// ---------------------------------------------------------------------------------------------- the step guard (xp_step_verdict)
-// One workgroup behind the partials of ALL launch tables of the step.  The norm is summed exactly as adamw_kernel / opt_kernel sum it
-// (thread-strided, then block_sum), so it has the bits grad_norm_out gets from them.  Launches on one stream are ordered: the counters
-// are a plain load and store by one lane.  (A template only to be emitted where templates are, behind opt_kernel's instantiations:
-// as a plain function it lands in front of them in build/optim.s and renumbers their labels.)
-template <int THREADS>
-__global__ __launch_bounds__(THREADS) void verdict_kernel(const float* __restrict__ partials, int n_partials,
-                                                     XpStepVerdict* __restrict__ verdict) {
-  static_assert(THREADS == NT, "block_sum is written for NT threads");
-  __shared__ int first[NT / 64];
-  float s = 0.f;
-  int bad = n_partials;                        // lowest chunk of this thread whose own partial is not finite
-  for (int i = threadIdx.x; i < n_partials; i += NT) {
-    const float x = partials[i];
-    s += x;
-    if (!__builtin_isfinite(x) && i < bad) bad = i;
-  }
-  const float norm = sqrtf(block_sum(s));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const int b = __shfl_xor(bad, o); bad = b < bad ? b : bad; }
-  if ((threadIdx.x & 63) == 0) first[threadIdx.x >> 6] = bad;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 1; i < NT / 64; ++i) bad = first[i] < bad ? first[i] : bad;
-    const bool finite = __builtin_isfinite(norm);
-    verdict->norm = norm;
-    verdict->finite = finite ? 1 : 0;
-    verdict->first_bad_chunk = bad < n_partials ? bad : -1;
-    if (finite) verdict->applied = verdict->applied + 1;
-    else verdict->skipped = verdict->skipped + 1;
-  }
-}
-
-// The three updates behind a verdict.  finite: adamw_kernel's / opt_kernel's decomposition and adam1 / opt1 unchanged, the clip
-// coefficient from verdict->norm.  Not finite: the workgroup touches neither m, v nor the gradient and does not write p; it rewrites
-// its chunk of the shadow copy from the unchanged p, so that the weight cache's "this step rewrote every entry" holds either way.
-// A copy once more, for the reason given at opt_kernel: the two kernels above keep their generated code.
-constexpr int KIND_ADAMW = -1;                 // beside XpOptKind, inside this file only
-
-template <int KIND, typename Args>
-__global__ __launch_bounds__(NT) void guarded_kernel(const XpAdamTensor* __restrict__ table,
-                                                     const int32_t* __restrict__ chunk_map, Args a, float max_norm,
-                                                     const XpStepVerdict* __restrict__ verdict,
-                                                     float* __restrict__ norm_out) {
-  const float norm = verdict->norm;
-  const bool finite = verdict->finite != 0;
-  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
-  const int t = chunk_map[2 * blockIdx.x], c = chunk_map[2 * blockIdx.x + 1];
-  const XpAdamTensor tt = table[t];
-  const int64_t beg = (int64_t)c * CHUNK;
-  const int64_t len = tt.numel - beg < CHUNK ? tt.numel - beg : CHUNK;
-  float* p = reinterpret_cast<float*>(tt.p) + beg;
-  bf16_t* sb = tt.shadow && tt.shadow_dtype == XP_BF16 ? reinterpret_cast<bf16_t*>(tt.shadow) + beg : nullptr;
-  float* sf = tt.shadow && tt.shadow_dtype == XP_F32 ? reinterpret_cast<float*>(tt.shadow) + beg : nullptr;
-  if (!finite) {
-    if (!sb && !sf) return;
-    const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(sf) | (reinterpret_cast<uintptr_t>(sb) << 1);
-    int64_t done = 0;
-    if ((align & 15) == 0) {
-      const int64_t n4 = len >> 2;
-      for (int64_t i = threadIdx.x; i < n4; i += NT) {
-        const f32x4 pp = *reinterpret_cast<const f32x4*>(p + 4 * i);
-        if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
-        if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
-      }
-      done = n4 << 2;
-    }
-    for (int64_t i = done + threadIdx.x; i < len; i += NT) {
-      const float pp = p[i];
-      if (sb) sb[i] = (bf16_t)pp;
-      if (sf) sf[i] = pp;
-    }
-    return;
-  }
-  float coef = 1.0f;
-  if (max_norm > 0.f) { const float cc = max_norm / (norm + 1e-6f); coef = cc < 1.0f ? cc : 1.0f; }
-  const auto h = a.groups[a.grp[t]];
-  float* m = reinterpret_cast<float*>(tt.m) + beg;
-  float* v = reinterpret_cast<float*>(tt.v) + beg;
-  const float* g = a.g[t] + beg;
-  const uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v) |
-                          reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(sf) |
-                          (reinterpret_cast<uintptr_t>(sb) << 1);
-  int64_t done = 0;
-  if ((align & 15) == 0) {
-    const int64_t n4 = len >> 2;
-    for (int64_t i = threadIdx.x; i < n4; i += NT) {
-      f32x4 pp = *reinterpret_cast<f32x4*>(p + 4 * i), mm = *reinterpret_cast<f32x4*>(m + 4 * i),
-            vv = *reinterpret_cast<f32x4*>(v + 4 * i);
-      const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float pe = pp[e], me = mm[e], ve = vv[e];
-        if constexpr (KIND == KIND_ADAMW) adam1(pe, gg[e], me, ve, h, coef);
-        else opt1<KIND>(pe, gg[e], me, ve, h, coef);
-        pp[e] = pe; mm[e] = me; vv[e] = ve;
-      }
-      *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
-      *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
-      *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
-      if (sb) *reinterpret_cast<bf16x4*>(sb + 4 * i) = bf16x4{(bf16_t)pp[0], (bf16_t)pp[1], (bf16_t)pp[2], (bf16_t)pp[3]};
-      if (sf) *reinterpret_cast<f32x4*>(sf + 4 * i) = pp;
-    }
-    done = n4 << 2;
-  }
-  for (int64_t i = done + threadIdx.x; i < len; i += NT) {
-    float pp = p[i], mm = m[i], vv = v[i];
-    if constexpr (KIND == KIND_ADAMW) adam1(pp, g[i], mm, vv, h, coef);
-    else opt1<KIND>(pp, g[i], mm, vv, h, coef);
-    p[i] = pp; m[i] = mm; v[i] = vv;
-    if (sb) sb[i] = (bf16_t)pp;
-    if (sf) sf[i] = pp;
-  }
-}
-
-// The argument checks and the argument block of a guarded call (the twins' checks, word for word, plus the verdict).
-template <typename Args, typename Group>
-int guarded_args(const char* name, Args& a, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
-                 const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors, const Group* groups_host,
-                 int32_t n_groups, const float* norm_partials, int32_t n_norm_partials, float max_norm,
-                 const XpStepVerdict* verdict) {
-  XP_REQUIRE(verdict, "%s: null verdict (xp_step_verdict writes it, behind the partials of the whole step)", name);
-  XP_REQUIRE(table && chunk_map && grads_host && group_of_host && groups_host && n_chunks > 0, "%s: null argument", name);
-  XP_REQUIRE(n_tensors > 0 && n_tensors <= MAXT, "%s: n_tensors=%d not in 1..%d", name, n_tensors, MAXT);
-  XP_REQUIRE(n_groups > 0 && n_groups <= MAXG, "%s: n_groups=%d not in 1..%d", name, n_groups, MAXG);
-  XP_REQUIRE(norm_partials || max_norm <= 0.f, "%s: max_norm > 0 needs the gradient-norm partials", name);
-  XP_REQUIRE(!norm_partials || n_norm_partials > 0, "%s: n_norm_partials must be positive", name);
-  for (int i = 0; i < MAXT; ++i) { a.g[i] = nullptr; a.grp[i] = 0; }
-  for (int i = 0; i < n_tensors; ++i) {
-    XP_REQUIRE(grads_host[i], "%s: gradient %d is null", name, i);
-    XP_REQUIRE(group_of_host[i] < n_groups, "%s: tensor %d has group %d >= %d", name, i, group_of_host[i], n_groups);
-    a.g[i] = reinterpret_cast<const float*>(grads_host[i]);
-    a.grp[i] = group_of_host[i];
-  }
-  for (int i = 0; i < n_groups; ++i) a.groups[i] = groups_host[i];
-  for (int i = n_groups; i < MAXG; ++i) a.groups[i] = groups_host[0];
-  return XP_OK;
-}
-
-}  // namespace
 
 extern "C" int xp_step_verdict(const float* partials, int32_t n_partials, XpStepVerdict* verdict, void* stream) {
   XP_REQUIRE(partials && verdict, "xp_step_verdict: null argument");
   XP_REQUIRE(n_partials > 0, "xp_step_verdict: n_partials=%d must be positive", n_partials);
-  verdict_kernel<NT><<<1, NT, 0, (hipStream_t)stream>>>(partials, n_partials, verdict);
+  verdict_kernel<<<1, NT, 0, (hipStream_t)stream>>>(partials, n_partials, verdict);
   XP_CHECK_LAUNCH("xp_step_verdict");
   return XP_OK;
 }
@@ -467,13 +343,9 @@ extern "C" int xp_adamw_step_guarded(const XpAdamTensor* table, const int32_t* c
                                      const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
                                      int32_t n_norm_partials, float max_norm, float* grad_norm_out,
                                      const XpStepVerdict* verdict, void* stream) {
-  StepArgs a;
-  const int rc = guarded_args("xp_adamw_step_guarded", a, table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host,
-                              n_groups, norm_partials, n_norm_partials, max_norm, verdict);
-  if (rc != XP_OK) return rc;
-  guarded_kernel<KIND_ADAMW><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, max_norm, verdict, grad_norm_out);
-  XP_CHECK_LAUNCH("xp_adamw_step_guarded");
-  return XP_OK;
+  return launch_update<KIND_ADAMW, true, XpAdamGroup>(
+      "xp_adamw_step_guarded", {table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host, n_groups, norm_partials,
+                                n_norm_partials, max_norm, grad_norm_out, verdict, stream});
 }
 
 extern "C" int xp_optim_step_guarded(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
@@ -481,16 +353,7 @@ extern "C" int xp_optim_step_guarded(int32_t kind, const XpAdamTensor* table, co
                                      const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
                                      int32_t n_norm_partials, float max_norm, float* grad_norm_out,
                                      const XpStepVerdict* verdict, void* stream) {
-  XP_REQUIRE(kind == XP_OPT_ADAM || kind == XP_OPT_ADAMAX,
-             "xp_optim_step_guarded: unknown kind %d (XP_OPT_ADAM = %d, XP_OPT_ADAMAX = %d)", kind, (int)XP_OPT_ADAM, (int)XP_OPT_ADAMAX);
-  OptArgs a;
-  const int rc = guarded_args("xp_optim_step_guarded", a, table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host,
-                              n_groups, norm_partials, n_norm_partials, max_norm, verdict);
-  if (rc != XP_OK) return rc;
-  if (kind == XP_OPT_ADAM)
-    guarded_kernel<XP_OPT_ADAM><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, max_norm, verdict, grad_norm_out);
-  else
-    guarded_kernel<XP_OPT_ADAMAX><<<n_chunks, NT, 0, (hipStream_t)stream>>>(table, chunk_map, a, max_norm, verdict, grad_norm_out);
-  XP_CHECK_LAUNCH("xp_optim_step_guarded");
-  return XP_OK;
+  return launch_optim<true>("xp_optim_step_guarded", kind, {table, chunk_map, n_chunks, grads_host, group_of_host, n_tensors, groups_host,
+                                                            n_groups, norm_partials, n_norm_partials, max_norm, grad_norm_out, verdict,
+                                                            stream});
 }

@@ -25,7 +25,7 @@ def _checked(cls, **kw):
 
 
 class _TorchFamily(MultiTensorOptimizer):
-    _KIND = None
+    _ENTRY = ("xp_optim_step", "xp_optim_step_guarded")      # (_KIND: XP_OPT_ADAM or XP_OPT_ADAMAX, by the subclass)
 
     def _group_struct(self, group, step):
         if group.get("amsgrad") or group.get("maximize"):       # (a loaded torch checkpoint brings its param groups along)
@@ -34,16 +34,6 @@ class _TorchFamily(MultiTensorOptimizer):
         lr = float(group["lr"])
         return L.XpOptGroup(lr, b1, b2, group["eps"], group["weight_decay"], lr / (1.0 - b1 ** step),
                             math.sqrt(1.0 - b2 ** step), 1.0 - b1)
-
-    def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream, verdict=None):
-        if verdict is not None:
-            L.check(lib.xp_optim_step_guarded(self._KIND, la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"],
-                                              la["grp"], la["n"], groups, n_groups, partials, n_partials, max_norm, norm, verdict, stream),
-                    "xp_optim_step_guarded")
-            return
-        L.check(lib.xp_optim_step(self._KIND, la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"],
-                                  la["grp"], la["n"], groups, n_groups, partials, n_partials, max_norm, norm, stream),
-                "xp_optim_step")
 
 
 class Adam(_TorchFamily):

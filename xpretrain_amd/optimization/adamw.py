@@ -16,6 +16,7 @@ from .multi_tensor import MultiTensorOptimizer
 
 class AdamW(MultiTensorOptimizer):
     _STATE = ("exp_avg", "exp_avg_sq")
+    _ENTRY = ("xp_adamw_step", "xp_adamw_step_guarded")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, skip_nonfinite=False):
         if lr < 0.0:
@@ -35,12 +36,3 @@ class AdamW(MultiTensorOptimizer):
         if group["correct_bias"]:
             step_size = step_size * math.sqrt(1.0 - b2 ** step) / (1.0 - b1 ** step)
         return L.XpAdamGroup(group["lr"], b1, b2, group["eps"], group["weight_decay"], step_size)
-
-    def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream, verdict=None):
-        if verdict is not None:
-            L.check(lib.xp_adamw_step_guarded(la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"], la["grp"],
-                                              la["n"], groups, n_groups, partials, n_partials, max_norm, norm, verdict, stream),
-                    "xp_adamw_step_guarded")
-            return
-        L.check(lib.xp_adamw_step(la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"], la["grp"],
-                                  la["n"], groups, n_groups, partials, n_partials, max_norm, norm, stream), "xp_adamw_step")

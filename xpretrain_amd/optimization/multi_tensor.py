@@ -5,8 +5,8 @@ A subclass supplies three things:
 
 * ``_STATE``: the names of its two state tensors, in the order of ``XpAdamTensor``'s ``m`` and ``v`` slots;
 * ``_group_struct(group, step)``: a param group and a step count (after the increment) as the kernel's group struct;
-* ``_launch(lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream, verdict=None)``: the checked kernel call for one
-  launch record ``la`` of the plan; with a ``verdict`` the guarded twin of that call.
+* ``_ENTRY`` and ``_KIND``: the names of its update entry point and of that call's guarded twin, and the ``kind`` argument in front of
+  their common argument list (``None``: the entry points take none).  ``_launch`` here makes the checked call from them.
 
 On top of the ``torch.optim.Optimizer`` surface:
 
@@ -63,6 +63,8 @@ def take_back(states, finite, first_bad_chunk, chunk_params):
 
 class MultiTensorOptimizer(Optimizer):
     _STATE = None           # (name of the m-slot state tensor, name of the v-slot state tensor)
+    _ENTRY = None           # (the unguarded entry point of the update, its guarded twin)
+    _KIND = None            # the entry points' leading ``kind`` argument; None: they take none
 
     def __init__(self, params, defaults, skip_nonfinite=False):
         super().__init__(params, defaults)
@@ -83,8 +85,13 @@ class MultiTensorOptimizer(Optimizer):
         raise NotImplementedError
 
     def _launch(self, lib, la, groups, n_groups, partials, n_partials, max_norm, norm, stream, verdict=None):
-        """``verdict`` None: the unguarded entry point; else the device address of the step's XpStepVerdict and the guarded twin"""
-        raise NotImplementedError
+        """The checked kernel call for one launch record ``la`` of the plan.  ``verdict`` None: the unguarded entry point; else the
+        device address of the step's XpStepVerdict and the guarded twin."""
+        entry = self._ENTRY[verdict is not None]
+        lead = () if self._KIND is None else (self._KIND,)
+        tail = (stream,) if verdict is None else (verdict, stream)
+        L.check(getattr(lib, entry)(*lead, la["table"].data_ptr(), la["chunk_map"].data_ptr(), la["n_chunks"], la["grads"], la["grp"],
+                                    la["n"], groups, n_groups, partials, n_partials, max_norm, norm, *tail), entry)
 
     # ------------------------------------------------------------------------------------------ the step guard
     def _reconcile(self):
