@@ -104,6 +104,18 @@ typedef struct XpGemmDesc {
    * values are rounded to bf16 exactly as xp_im2col / xp_im2col_u8 round them (same result as the materialised matrix, bit for
    * bit).  bf16 compute, P % 8 == 0, no split-K. */
   const void* a_frames; int32_t a_frames_u8; int32_t fr_H, fr_W, fr_P; float fr_mean[3], fr_std[3];
+  /* optional tile lists (all zero: the dense launch).  For operands that are zero outside a few tiles by construction: the launch
+   * is PLANNED as the dense problem of the same M, N, K (family, split, slab length, grid order, epilogue) and only the listed
+   * tiles are walked, so what it writes is bit-identical to the dense launch over such operands -- every skipped term is
+   * acc + (+-0).  256-wide-family plans only, no row remap, no a_frames; anything else is refused.
+   *   m_tiles (device, n_m_tiles ascending indices of 256-row tiles of M; the dX form: A k-contiguous, B k-strided): only these row
+   *     tiles are computed; the output, aux and colsum_partials rows of every other tile are NOT written.
+   *   k_tiles + k_tile_begin (device; the dW form: both operands k-strided): slab z (z < max(split_k, 1)) walks the 64-row k-tiles
+   *     k_tiles[k_tile_begin[z] .. k_tile_begin[z + 1]) -- indices into the whole K, ascending, inside the slab's own k range.
+   *     Every slab lists at least 2 (the pipeline depth; pad with k-tiles whose A rows are zero) and writes its output slab.
+   *     k_tile_begin_host: the same split + 1 numbers in host memory, which the call validates. */
+  const int32_t* m_tiles; int32_t n_m_tiles; int32_t reserved1;
+  const int32_t* k_tiles; const int32_t* k_tile_begin; const int32_t* k_tile_begin_host;
 } XpGemmDesc;
 
 int xp_gemm(const XpGemmDesc* desc, void* stream);
@@ -730,6 +742,14 @@ typedef struct XpLayerFwd {
 size_t xp_encoder_layer_fwd_workspace_bytes(const XpLayerDims* dims);
 int xp_encoder_layer_fwd(const XpLayerFwd* args, void* stream);
 
+/* The rows of a layer's dx3 that can be non-zero, as tile lists (xp_encoder_layer_bwd_listed).  m_tiles: every 256-row tile that holds a listed k-tile of ANY of the three lists (padding tiles included: dW1 reads dpre, which is
+ * written in those tiles only).  Weight gradient w (0: dW2, 1: dW1, 2: dWo): split[w] must be the split the library plans for it
+ * (xp_gemm_auto_split_slack); k_tiles[w] / k_tile_begin[w] (device) and k_tile_begin_host[w] as in XpGemmDesc. */
+typedef struct XpDx3Support {
+  const int32_t* m_tiles; int32_t n_m_tiles; int32_t reserved;
+  const int32_t* k_tiles[3]; const int32_t* k_tile_begin[3]; const int32_t* k_tile_begin_host[3];
+  int32_t split[3]; int32_t reserved1;
+} XpDx3Support;
 typedef struct XpLayerBwd {
   XpLayerDims dims;
   /* saved by the forward */
@@ -748,6 +768,14 @@ typedef struct XpLayerBwd {
 } XpLayerBwd;
 size_t xp_encoder_layer_bwd_workspace_bytes(const XpLayerDims* dims);
 int xp_encoder_layer_bwd(const XpLayerBwd* args, void* stream);
+/* xp_encoder_layer_bwd for a dx3 that is zero outside a few rows, given as tile lists.  The caller vouches that args->dx3 is +-0
+ * outside the 64-row k-tiles listed; the MLP / out_proj part of the backward then runs its three dX GEMMs (dpre, dh2, dattn) over
+ * m_tiles and its three weight gradients (dW2, dW1, dWo) over k-tile lists (XpGemmDesc::m_tiles / k_tiles): bit-identical to
+ * xp_encoder_layer_bwd for finite activations.  (With a non-finite activation in a row that carries no gradient the dense
+ * product 0 * Inf poisons a weight gradient; the listed one never forms it.)  LayerNorm 2', attention', dh1, dWqkv, LayerNorm 1'
+ * and the reductions stay dense.  Same workspace.  Needs the 256-wide-family plans of all six GEMMs (bf16, large shapes): an
+ * error otherwise, nothing is launched dense in its place. */
+int xp_encoder_layer_bwd_listed(const XpLayerBwd* args, const XpDx3Support* dx3_support, void* stream);
 /* The LAST video-tower layer when only the pooled feature (token 0 of every sample, a proxy row) leaves the tower: the same
  * function of x as row b*S of xp_encoder_layer_fwd's x3, computed without the dead rows.  LayerNorm 1 and the K/V projection
  * (Wqkv rows D..3D) see every row, because token 0 attends all S keys; the Q projection, the single-query attention

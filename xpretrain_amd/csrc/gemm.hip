@@ -638,7 +638,32 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
   if (split > 1) XP_REQUIRE(ep == XP_EPI_NONE && d->out_dtype == XP_F32 && d->c_grp == 0 && d->ldc == d->N,
                             "xp_gemm: split_k needs EPI_NONE, f32 output, dense C");
 
-  const GemmPlan plan = plan_gemm(d, split);
+  GemmPlan plan = plan_gemm(d, split);
+  // Tile lists: the plan above is the dense problem's, untouched; only the dX form's grid shrinks to the listed row tiles.
+  const bool mlist = d->m_tiles || d->n_m_tiles, klist = d->k_tiles || d->k_tile_begin || d->k_tile_begin_host;
+  if (mlist || klist) {
+    XP_REQUIRE(plan.family == Family::G256, "xp_gemm: tile lists need a 256-wide-family plan (xp_debug_gemm_plan)");
+    XP_REQUIRE(d->a_grp == 0 && d->c_grp == 0 && !d->a_frames, "xp_gemm: tile lists take no row remap and no a_frames");
+    XP_REQUIRE(!(mlist && klist), "xp_gemm: m_tiles and k_tiles are for different operand layouts");
+    if (mlist) {
+      XP_REQUIRE(!d->a_kstrided && d->b_kstrided && split == 1, "xp_gemm: m_tiles is for the dX form (A k-contiguous, B k-strided, no split-K)");
+      XP_REQUIRE(d->m_tiles && d->n_m_tiles >= 1 && d->n_m_tiles <= plan.tiles_m && (uintptr_t)d->m_tiles % 4 == 0,
+                 "xp_gemm: m_tiles needs 1..%d entries, got %d", plan.tiles_m, d->n_m_tiles);
+      plan.grid = dim3(d->n_m_tiles * plan.tiles_n, 1, 1);
+    } else {
+      XP_REQUIRE(d->a_kstrided && d->b_kstrided && ep == XP_EPI_NONE, "xp_gemm: k_tiles is for the dW form (both operands k-strided, EPI_NONE)");
+      XP_REQUIRE(d->k_tiles && d->k_tile_begin && d->k_tile_begin_host && ((uintptr_t)d->k_tiles | (uintptr_t)d->k_tile_begin) % 4 == 0,
+                 "xp_gemm: k_tiles needs k_tile_begin and k_tile_begin_host");
+      const int32_t* kb = d->k_tile_begin_host;
+      XP_REQUIRE(kb[0] >= 0, "xp_gemm: k_tile_begin_host[0] is negative");
+      for (int z = 0; z < split; ++z) {
+        const int64_t k0 = (int64_t)z * plan.k_per_split, k1 = k0 + plan.k_per_split < d->K ? k0 + plan.k_per_split : d->K;
+        const int64_t n = (int64_t)kb[z + 1] - kb[z];
+        XP_REQUIRE(n >= 2 && n <= cdiv(k1 - k0, 64), "xp_gemm: slab %d lists %lld k-tiles, needs 2..%lld", z, (long long)n,
+                   (long long)cdiv(k1 - k0, 64));
+      }
+    }
+  }
   KParams kp;
   kp.A = d->A; kp.B = d->B; kp.C = d->C;
   kp.M = d->M; kp.N = d->N; kp.K = d->K; kp.lda = d->lda; kp.ldb = d->ldb; kp.ldc = d->ldc;
@@ -656,6 +681,9 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
   kp.tiles_m = plan.tiles_m; kp.tiles_n = plan.tiles_n; kp.group_n = plan.group_n; kp.xcd_remap = plan.xcd_remap;
   kp.flat_split = plan.flat_split; kp.wide = plan.wide; kp.fast_epi = plan.fast_epi;
   kp.colsum = d->colsum_partials;
+  if (mlist || klist) {                // (in the bytes of the im_* fields: gemm_common.h)
+    kp.m_tiles = d->m_tiles; kp.n_m_tiles = d->n_m_tiles; kp.k_tiles = d->k_tiles; kp.k_tile_begin = d->k_tile_begin;
+  }
   kp.rside = d->resid_side; kp.oside = d->out_side; kp.side_S = (unsigned)d->side_S; kp.side_M = (unsigned)d->side_M;
   if (d->resid_side || d->out_side)
     XP_REQUIRE(d->resid_side && d->out_side && ep == XP_EPI_BIAS_RESID && d->out_dtype == d->in_dtype && d->c_grp == 0 &&

@@ -22,6 +22,8 @@
 //   epilogue   wave-private LDS staging (rounds of 32 rows x 64 cols fp32), row-major read-back: full 512-byte rows per store
 //              instruction group, shared fused epilogue (gemm_common.h::FastEpi, incl. the fp32 side rows and the fused column sums).
 //   split-K    (dW: k = the token dimension) 1-D grid over (k-chunk, tile), chunk-major per XCD: see the kernel.
+//   tile lists (TileListTag instantiations) the same launch over the listed row tiles (dX form) / the listed k-tiles of each slab (dW
+//              form), for operands that are zero elsewhere by construction: same plan, same loop, same bits (see the kernel).
 //
 // Tried and not kept (all correct; numbers under profiles/): v_mfma_f32_32x32x16_bf16 in the same loop (8 % fewer cycles per k-tile,
 // 6-10 % slower in wall time: the chip is power-limited under MFMA load, tools/clock_probe.hip); 64-byte-row 4-stage ring; 256x128
@@ -120,12 +122,18 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 template <bool AKS, bool BKS, typename... Act>
 __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
   constexpr int ACT = ActOf<Act...>::value;
+  // TileListTag: the dX form (k-contiguous A) runs only the row tiles p.m_tiles names, the dW form (k-strided A) walks only the
+  // k-tiles p.k_tiles names for its slab.  Everything else is the dense launch of the same M, N, K: the tile a workgroup computes
+  // keeps its PHYSICAL index (operands, output, resid, column sums, the partial last tile), a walked k-tile its physical offset.
+  constexpr bool LISTED = HasTag<TileListTag, Act...>::value;
+  constexpr bool MLIST = LISTED && !AKS, KLIST = LISTED && AKS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WAVES_N, wn = wave % WAVES_N;
 
-  const int nwg = p.tiles_m * p.tiles_n;
+  const int rows_m = MLIST ? p.n_m_tiles : p.tiles_m;      // tile rows the grid covers
+  const int nwg = rows_m * p.tiles_n;
   // Split-K launches (dW: k = the token dimension) with flat_split > 0 use a 1-D grid over (k-chunk, tile) pairs, CHUNK-MAJOR in
   // the XCD-contiguous order: an XCD's ~32 concurrent workgroups are (almost) all the tiles of ONE k-chunk, so its L2 fetches every
   // operand panel of that chunk once.  With the (tile, z) grid each XCD held ~4.5 tiles of EVERY chunk and each of the chunk's
@@ -138,12 +146,32 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
     bid = xcd_remap(blockIdx.x, nwg, p.xcd_remap); zs = blockIdx.z; nsplit = gridDim.z;
   }
   int tm, tn;
-  tile_of(bid, p.tiles_m, p.tiles_n, p.group_n, tm, tn);
+  tile_of(bid, rows_m, p.tiles_n, p.group_n, tm, tn);
+  if constexpr (MLIST) {
+    tm = p.m_tiles[tm];                                    // rank -> physical row tile
+    if ((unsigned)tm >= (unsigned)p.tiles_m) return;       // (a list entry outside the problem writes nothing; workgroup-uniform)
+  }
   const int64_t m0 = (int64_t)tm * TM, n0 = (int64_t)tn * TN;
 
-  const int64_t kbeg = (int64_t)zs * p.k_per_split;
-  const int64_t kend = (kbeg + p.k_per_split < p.K) ? kbeg + p.k_per_split : p.K;
-  const int nk = (int)((kend - kbeg + KE - 1) / KE);       // >= 2 (launcher)
+  const int64_t kslab = (int64_t)zs * p.k_per_split;
+  const int64_t kend = (kslab + p.k_per_split < p.K) ? kslab + p.k_per_split : p.K;
+  // listed k-tiles are indices into the whole K: the stagers then start at k = 0 (the buffer bound stays this slab's end)
+  const int64_t kbeg = KLIST ? 0 : kslab;
+  const int* klist = nullptr;
+  int nk;                                                  // >= 2 (launcher)
+  if constexpr (KLIST) {
+    const int b0 = p.k_tile_begin[zs];
+    klist = p.k_tiles + b0;
+    nk = p.k_tile_begin[zs + 1] - b0;
+  } else {
+    nk = (int)((kend - kbeg + KE - 1) / KE);
+  }
+  // physical k-tile of logical k-tile t (ring slots advance by t).  Past the list (the pipeline names t + 2 at most, and issues
+  // nothing for it in the tail steps) the index is not used.
+  auto phys = [&](int t) -> int {
+    if constexpr (KLIST) return t < nk ? __builtin_amdgcn_readfirstlane(klist[t]) : 0;
+    else return t;
+  };
 
   HalfStager<AKS, 64> ga;
   HalfStager<BKS, 32> gb;
@@ -169,8 +197,12 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
   auto slot = [&](int kt, int w) -> char* { return smem + (((kt & 1) << 2) + w) * HALF_BYTES; };
 
   // prologue: B0(0) and half-tiles 0..3 in flight; B0(0), A0(0), B1(0) landed everywhere before the first phase
-  gb.issue(slot(1, 3), 0, 0);
-  ga.issue(slot(0, 0), 0, 0); gb.issue(slot(0, 1), 1, 0); ga.issue(slot(0, 2), 1, 0); gb.issue(slot(0, 3), 0, 1);
+  int kc1 = phys(1), kc2 = phys(2);                 // (lists only) physical k-tiles of logical t + 1, t + 2, rolled by ktile
+  auto next1 = [&](int t) -> int { if constexpr (KLIST) return kc1; else return t + 1; };
+  auto next2 = [&](int t) -> int { if constexpr (KLIST) return kc2; else return t + 2; };
+  const int kfirst = phys(0);
+  gb.issue(slot(1, 3), 0, kfirst);
+  ga.issue(slot(0, 0), 0, kfirst); gb.issue(slot(0, 1), 1, kfirst); ga.issue(slot(0, 2), 1, kfirst); gb.issue(slot(0, 3), 0, next1(0));
   wait_vmcnt<4>();
   __builtin_amdgcn_s_barrier();
   if (wm == 1) __builtin_amdgcn_s_barrier();       // the wm==1 group runs one barrier behind
@@ -200,6 +232,9 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
     _Pragma("unroll") for (int nt = 0; nt < 2; ++nt) DST[ks][nt] = frag<BKS>(TILE, wn * 2 + nt, ks, lane)
 
   XP_READ_B(fbn, slot(1, 3));                       // B0 of k-tile 0
+  // (lists: the loop bound comes from memory and the compiler copies fbn at the loop head instead of renaming it -- the copy must
+  // not run ahead of the asynchronous reads above; tools/check_isa.py holds every instantiation to that)
+  if constexpr (KLIST) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 
   // One k-tile = 2 phases of 32 MFMAs: A0 x (B0, B1), then A1 x (B0, B1); 12 fragment reads and 2 half-tile DMAs each.
   // TAIL 0: steady state, 1: k-tile nk-2, 2: k-tile nk-1 (fewer half-tiles left to issue / await).
@@ -214,7 +249,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
     __builtin_amdgcn_sched_barrier(0);
     XP_READ_A(slot(t, 0));
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TAIL <= 1) { ga.issue(slot(t + 1, 0), 0, t + 1); gb.issue(slot(t + 1, 1), 1, t + 1); }
+    if constexpr (TAIL <= 1) { ga.issue(slot(t + 1, 0), 0, next1(t)); gb.issue(slot(t + 1, 1), 1, next1(t)); }
     wait_vmcnt<(TAIL <= 1 ? 4 : 0)>();
     XP_PHASE_MMA(0);
     // ---- phase 1: A1 x (B0, B1); issues A1(t+1), B0(t+2); afterwards A0, B1 of k-tile t+1 have landed ----
@@ -222,10 +257,11 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
     __builtin_amdgcn_sched_barrier(0);
     XP_READ_A(slot(t, 2));
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TAIL <= 1) ga.issue(slot(t + 1, 2), 1, t + 1);
-    if constexpr (TAIL == 0) gb.issue(slot(t + 1, 3), 0, t + 2);
+    if constexpr (TAIL <= 1) ga.issue(slot(t + 1, 2), 1, next1(t));
+    if constexpr (TAIL == 0) gb.issue(slot(t + 1, 3), 0, next2(t));
     wait_vmcnt<(TAIL == 0 ? 4 : (TAIL == 1 ? 2 : 0))>();
     XP_PHASE_MMA(1);
+    if constexpr (KLIST && TAIL == 0) { kc1 = kc2; kc2 = phys(t + 3); }
   };
   for (int t = 0; t < nk - 2; ++t) ktile(t, std::integral_constant<int, 0>{});
   ktile(nk - 2, std::integral_constant<int, 1>{});
@@ -312,12 +348,14 @@ __global__ __launch_bounds__(NTH, 2) void gemm256_kernel(KParams p) {
   if (tline) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); tr[64 + bid * 4 + 2] = __builtin_amdgcn_s_memrealtime(); }
 }
 
-template <bool AKS, bool BKS>
-bool launch_one(int act, const KParams& kp, dim3 grid, hipStream_t st) {
-  auto kern = act == XP_ACT_GELU ? gemm256_kernel<AKS, BKS, GeluErfTag> : gemm256_kernel<AKS, BKS>;
+bool launch_kernel(void (*kern)(KParams), const KParams& kp, dim3 grid, hipStream_t st) {
   if (!xp_device_cus(reinterpret_cast<const void*>(kern), LDS_BYTES)) return false;      // the 128 KiB opt-in (xp_gemm reports a refusal)
   kern<<<grid, NTH, LDS_BYTES, st>>>(kp);
   return true;
+}
+template <bool AKS, bool BKS, typename... List>
+bool launch_one(int act, const KParams& kp, dim3 grid, hipStream_t st) {
+  return launch_kernel(act == XP_ACT_GELU ? gemm256_kernel<AKS, BKS, GeluErfTag, List...> : gemm256_kernel<AKS, BKS, List...>, kp, grid, st);
 }
 
 // explicit instantiations (hipcc otherwise drops the host stubs of the k-strided variants)
@@ -329,6 +367,10 @@ template __global__ void gemm256_kernel<false, false, GeluErfTag>(KParams);
 template __global__ void gemm256_kernel<false, true, GeluErfTag>(KParams);
 template __global__ void gemm256_kernel<true, true, GeluErfTag>(KParams);
 template __global__ void gemm256_kernel<true, false, GeluErfTag>(KParams);
+// tile lists: the dX form (row tiles) under either activation, the dW form (k-tiles; EPI_NONE only)
+template __global__ void gemm256_kernel<false, true, TileListTag>(KParams);
+template __global__ void gemm256_kernel<false, true, GeluErfTag, TileListTag>(KParams);
+template __global__ void gemm256_kernel<true, true, TileListTag>(KParams);
 
 }  // namespace
 
@@ -363,6 +405,9 @@ int xp_gemm256_group_n(const XpGemmDesc* d, int tiles_n) {
 // Launches a problem gemm.hip::plan_gemm gave to this family (kp and grid as planned).  false: the dynamic-LDS opt-in was refused.
 bool xp_gemm256_launch(const XpGemmDesc* d, const xpgemm::KParams& kp, dim3 grid, hipStream_t st) {
   const int act = xpgemm::epi_act(d->epilogue);
+  // tile lists (xp_gemm has checked the form): row tiles on the dX form, k-tiles on the dW form
+  if (d->m_tiles) return launch_one<false, true, xpgemm::TileListTag>(act, kp, grid, st);
+  if (d->k_tiles) return launch_kernel(gemm256_kernel<true, true, xpgemm::TileListTag>, kp, grid, st);      // (EPI_NONE: no activation)
   if (!d->a_kstrided && !d->b_kstrided)      return launch_one<false, false>(act, kp, grid, st);
   else if (!d->a_kstrided && d->b_kstrided)  return launch_one<false, true>(act, kp, grid, st);
   else if (d->a_kstrided && d->b_kstrided)   return launch_one<true, true>(act, kp, grid, st);

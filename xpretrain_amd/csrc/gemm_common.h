@@ -26,8 +26,11 @@ __host__ __device__ constexpr int epi_act(int epilogue) {
 // names as profilers print them (`gemm256_kernel<false, false>`: tools and records match on those) and the pack adds nothing to
 // their code.
 struct GeluErfTag {};
-template <typename... Tag> struct ActOf { static constexpr int value = XP_ACT_QUICK_GELU; };
-template <> struct ActOf<GeluErfTag> { static constexpr int value = XP_ACT_GELU; };
+// TileListTag (256-wide family only): the workgroups take their row tile / the k-tiles of their slab from device lists
+// (XpGemmDesc::m_tiles / k_tiles) -- instantiations of their own, so the dense kernels keep their code.
+struct TileListTag {};
+template <typename T, typename... Tag> struct HasTag { static constexpr bool value = (std::is_same<T, Tag>::value || ...); };
+template <typename... Tag> struct ActOf { static constexpr int value = HasTag<GeluErfTag, Tag...>::value ? XP_ACT_GELU : XP_ACT_QUICK_GELU; };
 
 struct KParams {
   const void* A; const void* B; void* C;
@@ -49,7 +52,16 @@ struct KParams {
   unsigned long long* dbg;   // optional cycle-stamp trace buffer (xp_debug_set_gemm_trace), else null
   int flat_split;            // gemm256s split-K launches: > 0 = the grid is 1-D over (k-chunk, tile), chunk-major per XCD (see kernel)
   // A gathered from a frame tensor by the loader (XpGemmDesc::a_frames): frames [BT,3,H,W] fp32 (im_u8 == 0) or uint8 (im_u8 == 1)
-  const void* im_src; int im_u8, im_H, im_W, im_P, im_gw, im_L; float im_mean[3], im_std[3];
+  // The tile lists of the 256-wide family (TileListTag instantiations; XpGemmDesc::m_tiles / k_tiles) share the bytes of the frame
+  // gather's fields: a launch has one or the other (xp_gemm refuses lists with a_frames), and the argument block every kernel
+  // of the family is compiled against keeps its size.
+  union {
+    struct { const void* im_src; int im_u8, im_H, im_W, im_P, im_gw, im_L; float im_mean[3], im_std[3]; };
+    struct {
+      const int* m_tiles; int n_m_tiles;               // dX form: physical row tile of each listed rank
+      const int* k_tiles; const int* k_tile_begin;     // dW form: slab zs walks k_tiles[k_tile_begin[zs] .. k_tile_begin[zs + 1])
+    };
+  };
 };
 
 

@@ -57,8 +57,14 @@ XpGemmDesc wgrad_desc(const void* dy, int64_t lddy, const void* x, int64_t ldx, 
   return d;
 }
 // slack: nothing waits for this launch soon (xp_gemm_auto_split_slack: fewer, longer slabs)
-int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, bool slack) {
+// sup / w: the k-tile lists of weight gradient w of xp_encoder_layer_bwd_listed (nullptr: dense)
+int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, bool slack, const XpDx3Support* sup = nullptr, int w = 0) {
   const int split = slack ? xp_gemm_auto_split_slack(&d) : xp_gemm_auto_split(&d);
+  if (sup) {
+    XP_REQUIRE(sup->split[w] == (split > 1 ? split : 1), "encoder layer backward: dx3_support lists weight gradient %d for split %d, "
+               "the library plans %d", w, sup->split[w], split);
+    d.k_tiles = sup->k_tiles[w]; d.k_tile_begin = sup->k_tile_begin[w]; d.k_tile_begin_host = sup->k_tile_begin_host[w];
+  }
   if (split <= 1) return xp_gemm(&d, st);
   XP_REQUIRE(slab_bytes >= (size_t)split * d.M * d.N * sizeof(float), "encoder layer backward: split-K slab space too small");
   float* dw = (float*)d.C;
@@ -207,26 +213,41 @@ TailBwd carve_tail_bwd(Carver& ws, int64_t n, int64_t D, int64_t Dff, int dt, in
 
 // x3 = x2 + fc2(act(fc1(LN2(x2)))) and x2 = resid + out_proj(attn_o), backwards: leaves dx2 and dattn in the workspace,
 // issues dW2, dW1, dWo and defers db1, dln2_w, dln2_b, dbo, db2.  Marks 1 and 2 of the weight-gradient stream.
+// sup (xp_encoder_layer_bwd_listed only): dx3 is zero outside the listed tiles.  The three dX GEMMs then run over
+// sup->m_tiles and the three dW GEMMs over their k-tile lists; what the dense GEMMs would have written elsewhere -- +0: dh2,
+// dattn, fc1's bias-gradient partial rows -- is a fill on the launching stream in front of the listed launch.  dpre's unlisted
+// tiles are neither written nor read (dh2 and dW1 walk the same tiles).  LayerNorm 2' stays dense: it reads the filled dh2.
 template <class Args>
 int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwd& t, float* slabs, size_t slab_bytes, int64_t sS,
-                     int32_t sM, Defer& df, const WgradOrder& wg, void* st) {
+                     int32_t sM, Defer& df, const WgradOrder& wg, void* st, const XpDx3Support* sup = nullptr) {
   const int64_t D = a.dims.D, Dff = a.dims.Dff;
   const int dt = a.dims.dtype;
   int rc;
+  auto listed = [&](XpGemmDesc& g, void* fill, size_t bytes) -> int {         // g over sup->m_tiles, its output pre-filled with +0
+    if (!sup) return XP_OK;
+    g.m_tiles = sup->m_tiles; g.n_m_tiles = sup->n_m_tiles;
+    if (fill && hipMemsetAsync(fill, 0, bytes, (hipStream_t)st) != hipSuccess) {
+      xp_set_error("%s: zero fill in front of a listed GEMM failed", wg.name);
+      return XP_ERR_LAUNCH;
+    }
+    return XP_OK;
+  };
   XpGemmDesc g = gemm_desc(a.dx3, a.W2, t.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * act'(pre)
   g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(a.dims); g.resid = a.pre; g.ldr = Dff;
   if (a.db1 && t.db1_fused_rows > 0) g.colsum_partials = t.cs_pre;
+  if ((rc = listed(g, g.colsum_partials, (size_t)t.cs_pre_rows * Dff * sizeof(float)))) return rc;
   if ((rc = xp_gemm(&g, st))) return rc;
   if (a.db1) {
     if (t.db1_fused_rows == 0 && (rc = xp_colsum_partials(t.dpre, n, Dff, Dff, dt, t.cs_pre, t.cs_pre_bytes, st))) return rc;
     df.add(t.cs_pre, a.db1, Dff, (int)t.cs_pre_rows, (int)Dff);
   }
-  if (a.dw2 && (rc = run_wgrad(wgrad_desc(a.dx3, a.act, a.dw2, n, D, Dff, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  if (a.dw2 && (rc = run_wgrad(wgrad_desc(a.dx3, a.act, a.dw2, n, D, Dff, dt), slabs, slab_bytes, wg.stream(), true, sup, 0))) return rc;
   if ((rc = wg.mark(1))) return rc;                                           // dpre is ready for dW1
   g = gemm_desc(t.dpre, a.W1, t.dh2, n, D, Dff, dt);                          // dh2 = dpre . W1
   g.b_kstrided = 1; g.ldb = D;
+  if ((rc = listed(g, t.dh2, (size_t)n * D * t.esz))) return rc;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a.dw1 && (rc = run_wgrad(wgrad_desc(t.dpre, a.h2, a.dw1, n, Dff, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  if (a.dw1 && (rc = run_wgrad(wgrad_desc(t.dpre, a.h2, a.dw1, n, Dff, D, dt), slabs, slab_bytes, wg.stream(), true, sup, 1))) return rc;
   // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)] -- out_proj's and fc2's bias gradients
   if ((rc = xp_layernorm_bwd_partials_side(t.dh2, D, a.x2, D, a.ln2_w, a.mean2, a.rstd2, a.dx3, D, t.dx2, D, 2, n, D, dt,
                                            a.side_x2, sS, sM, sM, t.ln2_part, t.ln2_bytes, st))) return rc;
@@ -237,8 +258,9 @@ int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwd& t, float* slabs, s
   if ((rc = wg.mark(2))) return rc;                                           // dx2 is ready for dWo
   g = gemm_desc(t.dx2, a.Wo, t.dattn, n, D, D, dt);                           // dattn = dx2 . Wo
   g.b_kstrided = 1; g.ldb = D;
+  if ((rc = listed(g, t.dattn, (size_t)n * D * t.esz))) return rc;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a.dwo && (rc = run_wgrad(wgrad_desc(t.dx2, a.attn_o, a.dwo, n, D, D, dt), slabs, slab_bytes, wg.stream(), true))) return rc;
+  if (a.dwo && (rc = run_wgrad(wgrad_desc(t.dx2, a.attn_o, a.dwo, n, D, D, dt), slabs, slab_bytes, wg.stream(), true, sup, 2))) return rc;
   return XP_OK;
 }
 
@@ -356,7 +378,14 @@ extern "C" size_t xp_encoder_layer_bwd_workspace_bytes(const XpLayerDims* d) {
   return carve_bwd(*d, nullptr, 0).ws.bytes();
 }
 
-extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
+static int encoder_layer_bwd(const XpLayerBwd* a, const XpDx3Support* sup, void* st);
+extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) { return encoder_layer_bwd(a, nullptr, st); }
+extern "C" int xp_encoder_layer_bwd_listed(const XpLayerBwd* a, const XpDx3Support* sup, void* st) {
+  XP_REQUIRE(sup, "xp_encoder_layer_bwd_listed: null dx3_support");
+  return encoder_layer_bwd(a, sup, st);
+}
+
+static int encoder_layer_bwd(const XpLayerBwd* a, const XpDx3Support* sup, void* st) {
   XP_REQUIRE(a, "xp_encoder_layer_bwd: null argument");
   const XpLayerDims& d = a->dims;
   int rc = check_dims("xp_encoder_layer_bwd", d);
@@ -376,7 +405,13 @@ extern "C" int xp_encoder_layer_bwd(const XpLayerBwd* a, void* st) {
   const WgradOrder wg{(d.attn_mode == XP_ATTN_PROXY && rows >= 4096) ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_bwd"};
   if ((rc = wg.mark(0))) return rc;
   // ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo of x2 = x + out_proj(attn(qkv(LN1(x))))
-  if ((rc = mlp_out_proj_bwd(*a, rows, w.t, w.slabs, w.slab_bytes, a->side_S, a->side_M, df, wg, st))) return rc;
+  if (sup) {
+    XP_REQUIRE(w.t.db1_fused_rows > 0 && sup->m_tiles && sup->n_m_tiles >= 1, "xp_encoder_layer_bwd: dx3_support needs the 256-wide "
+               "GEMM plans of this shape (fused fc1 bias sums) and a non-empty m_tiles");
+    for (int i = 0; i < 3; ++i)
+      XP_REQUIRE(sup->k_tiles[i] && sup->k_tile_begin[i] && sup->k_tile_begin_host[i], "xp_encoder_layer_bwd: dx3_support list %d is null", i);
+  }
+  if ((rc = mlp_out_proj_bwd(*a, rows, w.t, w.slabs, w.slab_bytes, a->side_S, a->side_M, df, wg, st, sup))) return rc;
   // ---- attention
   if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, w.t.dattn, D, a->stats, a->pad_mask, w.dqkv, d.q_scale, d.attn_mode, d.B, d.heads,
                          d.S, d.M, d.N, d.L, dt, w.attn, w.attn_bytes, (a->dbqkv && w.cs_qkv_fused) ? w.cs_qkv : nullptr, st))) return rc;

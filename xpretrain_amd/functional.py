@@ -181,6 +181,9 @@ def _wgrad(dy: torch.Tensor, x: torch.Tensor, rows: int, n_out: int, n_in: int, 
 # the same order with the same arguments as the op-by-op path below, issued from native code; XPRETRAIN_DEBUG=op_by_op keeps the
 # op-by-op path (tools/determinism_hunt.py fingerprints every call of it; tests compare the two paths bit for bit).
 LAYER_CALLS = "op_by_op" not in L.DEBUG
+# XPRETRAIN_SPARSE_LAST_BWD=0: the last video layer's backward runs dense even where its incoming gradient is known to be zero outside
+# "row r0 of every sample" (default: the MLP / out_proj GEMMs of that backward run over tile lists -- _dx3_support; same bits)
+SPARSE_LAST_BWD = os.environ.get("XPRETRAIN_SPARSE_LAST_BWD", "1") != "0"
 _DT_CODE = {torch.bfloat16: L.XP_BF16, torch.float32: L.XP_F32}
 _NULLCTX = contextlib.nullcontext()
 _ES = {torch.bfloat16: 2, torch.float32: 4}
@@ -464,10 +467,11 @@ def _side_args(a, plan, r0, **sides):
             setattr(a, n, t.data_ptr() + first)
 
 
-def _call_native(entry, a, ws_bytes, device, ws_tag):
+def _call_native(entry, a, ws_bytes, device, ws_tag, *extra):
+    """``extra``: what the entry point takes between the argument struct and the stream"""
     ws = H.workspace(ws_bytes, device, ws_tag)          # (per stream)
     a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    L.check(getattr(L.lib(), entry)(C.byref(a), H._stream()), entry)
+    L.check(getattr(L.lib(), entry)(C.byref(a), *extra, H._stream()), entry)
 
 
 def _layer_fwd_args(plan, dims, x, params, pad_mask, arena, x3, keep_pre, side, side_out, side_x2, r0=0):
@@ -559,7 +563,7 @@ def _qkv_grads(dwqkv, dbqkv, need, D):
             pick(dwqkv, 2, need[7]), pick(dbqkv, 2, need[8]))
 
 
-def _layer_backward(ctx, build, entry, ws_tag, ops, x, *rest):
+def _layer_backward(ctx, build, entry, ws_tag, ops, x, *rest, extra=()):
     """The parameter-gradient plumbing of a layer backward and the pass itself: the native call ``entry`` on the argument struct
     ``build(plan, x, *rest, dx, grads)`` (_layer_bwd_args / _pooled_bwd_args) or, where the forward ran op by op, the sequencer
     ``ops`` on the same arguments.  The gradients go to the layer's sink or a private flat buffer (plan.gnames order); a frozen
@@ -577,7 +581,7 @@ def _layer_backward(ctx, build, entry, ws_tag, ops, x, *rest):
     g = {name: t for name, t in zip(plan.gnames, flat.split_with_sizes(plan.gsizes)) if want[name]}
     dx = torch.empty_like(x)
     if ctx.native:
-        _call_native(entry, build(plan, x, *rest, dx, g), plan.bwd_ws, dev, ws_tag)
+        _call_native(entry, build(plan, x, *rest, dx, g), plan.bwd_ws, dev, ws_tag, *extra)
     else:
         ops(plan, x, *rest, dx, g)
     D, Dff = plan.dims.D, plan.dims.Dff
@@ -585,6 +589,98 @@ def _layer_backward(ctx, build, entry, ws_tag, ops, x, *rest):
     return (dx, g.get("dln1_w"), g.get("dln1_b"), *_qkv_grads(gw("dwqkv", (3 * D, D)), g.get("dbqkv"), need, D),
             gw("dwo", (D, D)), g.get("dbo"), g.get("dln2_w"), g.get("dln2_b"),
             gw("dw1", (Dff, D)), g.get("db1"), gw("dw2", (D, Dff)), g.get("db2"))
+
+
+# ---- a gradient that is zero outside one row per sample (the contrastive path reads token 0 of the last video layer) ---------------
+# GatherRowsFn.backward knows the scatter pattern of the tensor it returns and registers it here; EncoderLayerFn.backward looks its
+# incoming gradient up.  The claim is the tensor OBJECT at the version it was registered with: any second consumer of the layer
+# output makes autograd sum gradients (a new tensor, or an in-place add that bumps the version), a hook that rewrites the gradient
+# returns another tensor, an in-place write bumps the version -- the claim is then gone and the layer runs dense.  No data is read.
+_ROW_CLAIMS = {}            # id(tensor) -> (weakref, _version, data_ptr, (B, S, r0))
+_SUPPORTS = {}              # (device, B, S, r0, slabs) -> _Dx3Support (the lists depend on the shape only)
+sparse_last_bwd_calls = 0   # native layer backward calls that ran over tile lists (tests count them)
+
+
+def claim_row_support(t, B, S, r0):
+    """``t`` ([B*S, D]) is zero outside row ``b*S + r0`` of every sample ``b``."""
+    key = id(t)
+    _ROW_CLAIMS[key] = (weakref.ref(t, lambda _, key=key: _ROW_CLAIMS.pop(key, None)), t._version, t.data_ptr(), (int(B), int(S), int(r0)))
+
+
+def row_support_of(t):
+    """``(B, S, r0)`` if ``t`` is a tensor claim_row_support registered and nothing has written to it since, else None."""
+    c = _ROW_CLAIMS.get(id(t))
+    if c is None or c[0]() is not t or c[1] != t._version or c[2] != t.data_ptr():
+        return None
+    return c[3]
+
+
+def dx3_tile_lists(B, S, r0, slabs):
+    """The tile lists of a [B*S, .] gradient that is zero outside rows ``b*S + r0``: ``(m_tiles, [(k_tiles, k_tile_begin), ...])``,
+    one pair per ``(split, k_per_split)`` of ``slabs`` (a split-K weight gradient over those rows; k_per_split a multiple of 64).
+    k_tiles: per slab, ascending, the 64-row tiles that hold such a row; a slab with fewer than 2 (the GEMM pipeline's depth) is
+    padded with other 64-row tiles of its own range -- first those that share a 256-row tile with a listed one, then the slab's
+    first ones.  m_tiles: ascending, every 256-row tile that holds a k-tile of any list (padding included: the rows of a padding tile
+    are zero only where they were computed).  Pure host arithmetic."""
+    rows = B * S
+    active = sorted({(b * S + r0) // 64 for b in range(B)})
+    hot = {kt // 4 for kt in active}
+    m, lists = set(hot), []
+    for split, kps in slabs:
+        tiles, begin = [], [0]
+        for z in range(split):
+            k0, k1 = z * kps // 64, (min((z + 1) * kps, rows) + 63) // 64
+            mine = [kt for kt in active if k0 <= kt < k1]
+            spare = [kt for kt in range(k0, k1) if kt not in mine]
+            spare.sort(key=lambda kt: (kt // 4 not in hot, kt))
+            mine = sorted(mine + spare[:max(0, 2 - len(mine))])
+            if len(mine) < 2:
+                raise ValueError(f"dx3_tile_lists: slab {z} of {split} x {kps} rows has fewer than 2 k-tiles")
+            tiles += mine
+            begin.append(len(tiles))
+        m.update(kt // 4 for kt in tiles)
+        lists.append((tiles, begin))
+    return sorted(m), lists
+
+
+class _Dx3Support:
+    """XpDx3Support of one (device, shape): the device arrays, the host copies the library validates, the struct itself"""
+
+    def __init__(self, dev, m_tiles, lists, splits):
+        put = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)
+        self.keep = [put(m_tiles)]
+        s = self.struct = L.XpDx3Support()
+        s.m_tiles, s.n_m_tiles = self.keep[0].data_ptr(), len(m_tiles)
+        for w, ((tiles, begin), split) in enumerate(zip(lists, splits)):
+            host = (C.c_int32 * len(begin))(*begin)
+            self.keep += [put(tiles), put(begin), host]
+            s.k_tiles[w], s.k_tile_begin[w], s.k_tile_begin_host[w] = self.keep[-3].data_ptr(), self.keep[-2].data_ptr(), C.addressof(host)
+            s.split[w] = split
+
+
+def _dx3_support(plan, dev, claim):
+    """The XpDx3Support (xp_encoder_layer_bwd_listed) of a dense video layer whose dx3 carries ``claim`` = (B, S, r0); None where the
+    claim is for another shape or one of the six GEMMs of this shape is not planned on the 256-wide family (fp32, small shapes):
+    the layer then runs dense."""
+    d = plan.dims
+    if claim is None or (claim[0], claim[1]) != (d.B, d.S) or not 0 <= claim[2] < d.S:
+        return None
+    rows, D, Dff = d.rows, d.D, d.Dff
+    wg = ((D, Dff), (Dff, D), (D, D))                              # dW2, dW1, dWo as (n_out, n_in): csrc/layer.hip::mlp_out_proj_bwd
+    splits = tuple(_split_for(no, ni, rows, plan.dtype, (0, 0, 0), True) for no, ni in wg)
+    key = (dev, d.B, d.S, claim[2], D, Dff, plan.dtype, d.act, splits)
+    if key not in _SUPPORTS:
+        if torch.cuda.is_current_stream_capturing():              # (the lists are uploaded with blocking copies: not inside a capture)
+            return None
+        plans = [H.gemm_plan(no, ni, rows, plan.dtype, a_kstrided=True, b_kstrided=True, split_k=sp) for (no, ni), sp in zip(wg, splits)]
+        plans += [H.gemm_plan(rows, n, k, plan.dtype, b_kstrided=True, **kw)
+                  for n, k, kw in ((Dff, D, dict(epilogue=L.EPI_ACT_BWD[d.act], colsum=True)), (D, Dff, {}), (D, D, {}))]
+        sup = None
+        if all(p["family"] == L.GEMM_FAMILY_256 for p in plans) and plans[3]["colsum_rows"] > 0:
+            m_tiles, lists = dx3_tile_lists(d.B, d.S, claim[2], [(p["split"], p["k_per_split"]) for p in plans[:3]])
+            sup = _Dx3Support(dev, m_tiles, lists, splits)
+        _SUPPORTS[key] = sup
+    return _SUPPORTS[key]
 
 
 def _layer_bwd_args(plan, x, params, arena, dx3, pad_mask, side, side_x2, dx, grads):
@@ -772,9 +868,18 @@ class EncoderLayerFn(torch.autograd.Function):
         if dx3 is None:             # (set_materialize_grads(False): the layer output did not reach the loss)
             return (None,) * 26
         x, arena, *params, pad_mask, side, side_x2 = ctx.saved_tensors          # (params: _BWD_PARAMS)
+        claim = row_support_of(dx3)
         dx3 = _check_dx3("EncoderLayerFn", dx3, x, x.shape)
-        return _layer_backward(ctx, _layer_bwd_args, "xp_encoder_layer_bwd", "layer_bwd", _layer_bwd_ops, x, params, arena, dx3,
-                               pad_mask, side, side_x2) + (None,) * 9
+        entry, extra = "xp_encoder_layer_bwd", ()
+        if SPARSE_LAST_BWD and ctx.native and ctx.plan.size is not None and claim is not None:
+            # (video tower, native path: the op-by-op path stays dense on purpose -- it is the bit reference)
+            support = _dx3_support(ctx.plan, x.device, claim)
+            if support is not None:
+                global sparse_last_bwd_calls
+                sparse_last_bwd_calls += 1
+                entry, extra = "xp_encoder_layer_bwd_listed", (C.byref(support.struct),)
+        return _layer_backward(ctx, _layer_bwd_args, entry, "layer_bwd", _layer_bwd_ops, x, params, arena, dx3,
+                               pad_mask, side, side_x2, extra=extra) + (None,) * 9
 
 
 # ------------------------------------------------------------------------------------------ pooled last layer (video tower)
@@ -1085,7 +1190,10 @@ class GatherRowsFn(torch.autograd.Function):
     def backward(ctx, dout):
         (idx,) = ctx.saved_tensors
         B, S, D = ctx.meta
-        return H.scatter_rows(dout.contiguous(), idx, B, S, D), None, None, None
+        dx = H.scatter_rows(dout.contiguous(), idx, B, S, D)
+        if idx is None:             # token 0 of every sample: a host-known pattern (an EOS index is data: no claim)
+            claim_row_support(dx, B, S, 0)
+        return dx, None, None, None
 
 
 class ProjectionFn(torch.autograd.Function):

@@ -61,13 +61,17 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
          a_kstrided=False, b_kstrided=False, out_dtype=None, epilogue=L.EPI_NONE, bias=None, scale=1.0,
          scale_cols=0, resid=None, ldr=None, aux=None, ldaux=None, tab1=None, tab2=None, tab_L=0,
          a_remap=(0, 0, 0), c_remap=(0, 0, 0), split_k=1, out_rows=None, colsum_defer=None, colsum_name="gemm_colsum",
-         colsum_out=None, resid_side=None, out_side=None, side=None, frames=None, frame_patch=0, frame_norm=None, plan_only=False):
+         colsum_out=None, resid_side=None, out_side=None, side=None, frames=None, frame_patch=0, frame_norm=None, plan_only=False,
+         m_tiles=None, k_tiles=None, k_tile_begin=None):
     """C[M,N] = epilogue(sum_k A(m,k) B(n,k)); see include/xpretrain_hip.h::XpGemmDesc.
 
     ``plan_only``: launch nothing and return the plan xp_gemm would launch for this call's descriptor (``gemm_plan_of``).
 
     ``frames`` ([BT,3,H,W] fp32 or uint8, contiguous) with ``frame_patch`` = P: A is the patch matrix of the frames, gathered by the
     operand loader (no im2col pass; pass ``A=None``); uint8 frames need ``frame_norm = (mean3, std3)``.
+
+    ``m_tiles`` / ``k_tiles`` + ``k_tile_begin`` (sequences of int; XpGemmDesc's tile lists): uploaded per call -- the test and tool
+    interface of the lists (the layer backward keeps device copies per shape, functional._dx3_support).
 
     ``colsum_defer`` (a DeferredReduce): also return the column sums of C (a bias gradient), as ``(C, colsum)``; the
     sums come out of the GEMM epilogue where the library supports it, otherwise from a separate pass over C; either
@@ -119,6 +123,14 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
         if not (resid_side.is_contiguous() and out_side.is_contiguous()) or resid_side.numel() < need or out_side.numel() < need:
             raise ValueError("gemm: resid_side / out_side are too small or not contiguous")
         d.resid_side, d.out_side, d.side_S, d.side_M = resid_side.data_ptr(), out_side.data_ptr(), S_, M_
+    lists = [None if v is None else torch.tensor(list(v), dtype=torch.int32, device=B.device) for v in (m_tiles, k_tiles, k_tile_begin)]
+    if m_tiles is not None:
+        d.m_tiles, d.n_m_tiles = lists[0].data_ptr(), lists[0].numel()
+    if k_tiles is not None or k_tile_begin is not None:
+        if k_tiles is None or k_tile_begin is None or len(k_tile_begin) != max(split_k, 1) + 1:
+            raise ValueError("gemm: k_tiles and k_tile_begin go together, k_tile_begin with split_k + 1 entries")
+        begin_host = (C.c_int32 * len(k_tile_begin))(*k_tile_begin)
+        d.k_tiles, d.k_tile_begin, d.k_tile_begin_host = lists[1].data_ptr(), lists[2].data_ptr(), C.addressof(begin_host)
     if plan_only:
         if colsum_defer is not None and L.lib().xp_gemm_colsum_rows(C.byref(d)) > 0:
             d.colsum_partials = 1          # (the planner reads the pointer only as present / absent)
@@ -143,6 +155,22 @@ def gemm_plan_of(d: L.XpGemmDesc) -> dict:
     info = L.XpGemmPlanInfo()
     L.check(L.lib().xp_debug_gemm_plan(C.byref(d), C.byref(info)), "xp_debug_gemm_plan")
     return {f: (tuple(getattr(info, f)) if f == "grid" else getattr(info, f)) for f, _ in info._fields_ if f != "reserved"}
+
+
+def gemm_plan(M: int, N: int, K: int, dtype: torch.dtype, *, a_kstrided=False, b_kstrided=False, split_k=1, epilogue=L.EPI_NONE,
+              colsum=False) -> dict:
+    """The plan (gemm_plan_of) of a dense-operand problem described by its shape alone: no tensors, nothing launched.  ``colsum``: with
+    fused column sums where the library offers them.  Split-K problems write fp32 slabs, the others the compute dtype."""
+    d = L.XpGemmDesc()
+    d.M, d.N, d.K = M, N, K
+    d.lda, d.ldb, d.ldc, d.ldr, d.ldaux = (M if a_kstrided else K), (N if b_kstrided else K), N, N, N
+    d.a_kstrided, d.b_kstrided = int(a_kstrided), int(b_kstrided)
+    d.in_dtype, d.out_dtype = _DT[dtype], _DT[torch.float32 if split_k > 1 or (a_kstrided and b_kstrided) else dtype]
+    d.epilogue, d.split_k, d.scale = epilogue, split_k, 1.0
+    d.resid = int(epilogue in L.EPI_ACT_BWD)       # (the planner reads these pointers only as present / absent)
+    if colsum and L.lib().xp_gemm_colsum_rows(C.byref(d)) > 0:
+        d.colsum_partials = 1
+    return gemm_plan_of(d)
 
 
 def gemm_auto_split(M: int, N: int, K: int, dtype: torch.dtype, *, a_kstrided=True, b_kstrided=True, lda=None,
