@@ -743,8 +743,9 @@ size_t xp_encoder_layer_fwd_workspace_bytes(const XpLayerDims* dims);
 int xp_encoder_layer_fwd(const XpLayerFwd* args, void* stream);
 
 /* The rows of a layer's dx3 that can be non-zero, as tile lists (xp_encoder_layer_bwd_listed).  m_tiles: every 256-row tile that holds a listed k-tile of ANY of the three lists (padding tiles included: dW1 reads dpre, which is
- * written in those tiles only).  Weight gradient w (0: dW2, 1: dW1, 2: dWo): split[w] must be the split the library plans for it
- * (xp_gemm_auto_split_slack); k_tiles[w] / k_tile_begin[w] (device) and k_tile_begin_host[w] as in XpGemmDesc. */
+ * written in those tiles only).  Weight gradient w (0: dW2, 1: dW1, 2: dWo): split[w] must be the split the call will use -- split_k of
+ * entries XP_LAYER_GEMM_DW2 / _DW1 / _DWO of xp_debug_layer_bwd_gemms, whose plans (xp_debug_gemm_plan) give the slabs the lists are
+ * cut by; k_tiles[w] / k_tile_begin[w] (device) and k_tile_begin_host[w] as in XpGemmDesc. */
 typedef struct XpDx3Support {
   const int32_t* m_tiles; int32_t n_m_tiles; int32_t reserved;
   const int32_t* k_tiles[3]; const int32_t* k_tile_begin[3]; const int32_t* k_tile_begin_host[3];
@@ -899,6 +900,30 @@ typedef struct XpAttnPooledPlanInfo {
 } XpAttnPooledPlanInfo;
 int xp_debug_attn_pooled_plan(int64_t B, int64_t H, int64_t S, int32_t dtype, int32_t backward, int32_t cus,
                               XpAttnPooledPlanInfo* out);
+/* The GEMMs of xp_encoder_layer_bwd (pooled == 0) / xp_encoder_layer_pooled_bwd (pooled != 0) for `dims`, in issue order: the table
+ * the call sizes its workspace by and launches from (csrc/layer.hip), so what a caller plans from it is what runs.  Host only,
+ * launches nothing, needs no device; reads the CU budget and the planning switches as the call would.  Every out[i] is the launched
+ * descriptor without its operands: A, B, C, bias and the tile lists are NULL; resid and colsum_partials are non-NULL (never to be
+ * dereferenced) exactly where the launch passes them with every gradient asked for; a weight gradient's split_k is the split the
+ * call uses (>= 1; xp_gemm_auto_split_slack for dW2, dW1, dWo and the pooled dWq, xp_gemm_auto_split for dWqkv and dWkv).  Returns
+ * the number of descriptors written (XP_LAYER_GEMM_DENSE_COUNT / _POOLED_COUNT); XP_ERR_ARG, nothing written, for dims the call
+ * refuses or cap below that number. */
+enum { XP_LAYER_GEMM_DPRE = 0,        /* dpre = (dx3 . W2) * act'(pre), with fc1's bias-gradient partial rows where fused */
+       XP_LAYER_GEMM_DW2 = 1,         /* dW2 = dx3^T . act                                                                */
+       XP_LAYER_GEMM_DH2 = 2,         /* dh2 = dpre . W1                                                                  */
+       XP_LAYER_GEMM_DW1 = 3,         /* dW1 = dpre^T . h2                                                                */
+       XP_LAYER_GEMM_DATTN = 4,       /* dattn = dx2 . Wo                                                                 */
+       XP_LAYER_GEMM_DWO = 5,         /* dWo = dx2^T . attn_o                                                             */
+       XP_LAYER_GEMM_DH1 = 6,         /* dense: dh1 = dqkv . Wqkv                                                         */
+       XP_LAYER_GEMM_DWQKV = 7,       /* dense: dWqkv = dqkv^T . h1                                                       */
+       XP_LAYER_GEMM_DENSE_COUNT = 8,
+       XP_LAYER_GEMM_DH1_KV = 6,      /* pooled: dh1 = dkv . Wkv on every row                                             */
+       XP_LAYER_GEMM_DH1_Q = 7,       /* pooled: dh1[b*S] = dqkv[b*S] . Wqkv on the pooled rows                           */
+       XP_LAYER_GEMM_DWQ = 8,         /* pooled: dWq = dq^T . h1p                                                         */
+       XP_LAYER_GEMM_DWKV = 9,        /* pooled: dWkv = dkv^T . h1                                                        */
+       XP_LAYER_GEMM_POOLED_COUNT = 10,
+       XP_LAYER_GEMM_MAX = 10 };
+int32_t xp_debug_layer_bwd_gemms(const XpLayerDims* dims, int32_t pooled, XpGemmDesc* out, int32_t cap);
 int xp_probe_mfma_bf16(const void* a, const void* b, float* c, void* stream);
 int xp_probe_mfma_f32(const float* a, const float* b, float* c, void* stream);
 /* packed-fp32 self-check (csrc/probe.hip): err[(variant*64 + lane)*2 + half] += mismatches between one v_pk_*_f32 form and

@@ -8,11 +8,12 @@
 // The dense layer (xp_encoder_layer_fwd / _bwd) and the pooled last layer (xp_encoder_layer_pooled_fwd / _bwd) are the same
 // sequence from out_proj onward, over `rows` rows or over the B pooled rows: those stages (out_proj_mlp_fwd, mlp_out_proj_bwd,
 // finish_bwd) are written once and read the fields the argument structs have in common; LayerNorm 1, the projections, the
-// attention call and their backward stay with each entry point.
+// attention call and their backward stay with each entry point.  Every GEMM of a backward call is described once, as a row of
+// the call's BwdGemms table: the workspace carvers, the launch sites and xp_debug_layer_bwd_gemms (which functional._dx3_support
+// builds its tile lists from) all read that table.
 #include "common.h"
 #include <string.h>
 #include <stdlib.h>
-#include <initializer_list>
 #include <mutex>
 
 namespace {
@@ -21,7 +22,8 @@ inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 // Bump allocator over a layer call's workspace.  Every call has ONE carve_* function below: the *_workspace_bytes query runs it
 // with a null base (nothing is checked, bytes() is the answer), the call runs it over the caller's buffer, where every take is
-// checked against `cap` -- so the reported size and the pointers a call uses cannot drift apart.
+// checked against `cap` -- so the reported size and the pointers a call uses cannot drift apart; the GEMM shapes that decide the
+// sizes are the launched ones (BwdGemms below).
 struct Carver {
   char* base; size_t cap, off = 0;
   bool fits = true;          // false: a take went past cap (the pointers are then not to be used)
@@ -40,51 +42,60 @@ struct Carver {
 #define XP_REQUIRE_WORKSPACE(name, a, w)                                                                    \
   XP_REQUIRE((a)->workspace && (w).ws.fits, "%s: workspace too small (%zu < %zu)", name, (a)->workspace_bytes, (w).ws.bytes())
 
-XpGemmDesc gemm_desc(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int dtype) {
+// b_kstrided: the dX form, dX[M, N] = dY[M, K] . W[K, N] with W read k-strided
+XpGemmDesc gemm_desc(const void* A, const void* B, void* C, int64_t M, int64_t N, int64_t K, int dtype, bool b_kstrided = false) {
   XpGemmDesc d;
   memset(&d, 0, sizeof(d));
   d.A = A; d.B = B; d.C = C; d.M = M; d.N = N; d.K = K;
-  d.lda = K; d.ldb = K; d.ldc = N; d.ldr = N; d.ldaux = N;
+  d.lda = K; d.ldb = b_kstrided ? N : K; d.ldc = N; d.ldr = N; d.ldaux = N; d.b_kstrided = b_kstrided;
   d.in_dtype = dtype; d.out_dtype = dtype; d.split_k = 1; d.scale = 1.0f;
   return d;
 }
-
-// dW[n_out, n_in] = dY[k, n_out]^T . X[k, n_in], fp32: both operands k-strided (row pitches lddy / ldx), split-K chosen by the library
-XpGemmDesc wgrad_desc(const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t k, int64_t n_out, int64_t n_in,
-                      int dtype) {
-  XpGemmDesc d = gemm_desc(dy, x, dw, n_out, n_in, k, dtype);
-  d.a_kstrided = d.b_kstrided = 1; d.lda = lddy; d.ldb = ldx; d.out_dtype = XP_F32;
+// dW[n_out, n_in] = dY[k, n_out]^T . X[k, n_in], fp32: both operands k-strided (row pitches lddy / ldx; 0: dense)
+XpGemmDesc wgrad_desc(int64_t k, int64_t n_out, int64_t n_in, int dtype, int64_t lddy = 0, int64_t ldx = 0) {
+  XpGemmDesc d = gemm_desc(nullptr, nullptr, nullptr, n_out, n_in, k, dtype);
+  d.a_kstrided = d.b_kstrided = 1; d.lda = lddy ? lddy : n_out; d.ldb = ldx ? ldx : n_in; d.out_dtype = XP_F32;
   return d;
 }
-// slack: nothing waits for this launch soon (xp_gemm_auto_split_slack: fewer, longer slabs)
+
+// ---- the GEMMs of a backward call, described once: one table per call, on the stack ---------------------------------------------
+// Row XP_LAYER_GEMM_* is that product's descriptor without its operands.  Three functions write the rows (tail_bwd_gemms,
+// dense_bwd_gemms, pooled_bwd_gemms) and nothing else describes a backward GEMM: the carvers size the split-K slabs and fc1's
+// bias-gradient partial rows from the table, a launch site copies a row, binds its operands (`bound`) and launches it,
+// xp_debug_layer_bwd_gemms hands the table out.  A new product of the layer is one row.
+float present_[1];                       // an optional operand of a row: the planning queries test these pointers against null only
+struct BwdGemms {
+  XpGemmDesc g[XP_LAYER_GEMM_MAX] = {};
+  int n = 0;                             // rows in use: XP_LAYER_GEMM_DENSE_COUNT / _POOLED_COUNT
+  size_t max_slab_bytes = 0;             // split-K slab space that serves every weight gradient of the table under either split rule
+  int64_t db1_fused_rows = 0;            // partial rows of fc1's bias gradient out of dpre's epilogue, 0 = a column-sum pass over dpre
+  // a weight gradient's row carries the split its launch uses, asked for once per call.  slack: nothing waits for this launch soon
+  // (xp_gemm_auto_split_slack: fewer, longer slabs)
+  void wgrad(int i, XpGemmDesc d, bool slack) {
+    const int a = xp_gemm_auto_split(&d), b = xp_gemm_auto_split_slack(&d), split = slack ? b : a, most = a > b ? a : b;
+    const size_t s = most <= 1 ? 0 : (size_t)most * d.M * d.N * sizeof(float);
+    if (s > max_slab_bytes) max_slab_bytes = s;
+    d.split_k = split > 1 ? split : 1;
+    g[i] = d;
+  }
+};
+XpGemmDesc bound(XpGemmDesc d, const void* A, const void* B, void* C) { d.A = A; d.B = B; d.C = C; return d; }
+
 // sup / w: the k-tile lists of weight gradient w of xp_encoder_layer_bwd_listed (nullptr: dense)
-int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, bool slack, const XpDx3Support* sup = nullptr, int w = 0) {
-  const int split = slack ? xp_gemm_auto_split_slack(&d) : xp_gemm_auto_split(&d);
+int run_wgrad(XpGemmDesc d, float* slabs, size_t slab_bytes, void* st, const XpDx3Support* sup = nullptr, int w = 0) {
+  const int split = d.split_k;
   if (sup) {
-    XP_REQUIRE(sup->split[w] == (split > 1 ? split : 1), "encoder layer backward: dx3_support lists weight gradient %d for split %d, "
+    XP_REQUIRE(sup->split[w] == split, "encoder layer backward: dx3_support lists weight gradient %d for split %d, "
                "the library plans %d", w, sup->split[w], split);
     d.k_tiles = sup->k_tiles[w]; d.k_tile_begin = sup->k_tile_begin[w]; d.k_tile_begin_host = sup->k_tile_begin_host[w];
   }
   if (split <= 1) return xp_gemm(&d, st);
   XP_REQUIRE(slab_bytes >= (size_t)split * d.M * d.N * sizeof(float), "encoder layer backward: split-K slab space too small");
   float* dw = (float*)d.C;
-  d.C = slabs; d.split_k = split;
+  d.C = slabs;
   int rc = xp_gemm(&d, st);
   if (rc) return rc;
   return xp_splitk_reduce(slabs, dw, d.M * d.N, split, 0, st);
-}
-// both operands dense: dY[k, n_out], X[k, n_in]
-XpGemmDesc wgrad_desc(const void* dy, const void* x, float* dw, int64_t k, int64_t n_out, int64_t n_in, int dtype) {
-  return wgrad_desc(dy, n_out, x, n_in, dw, k, n_out, n_in, dtype);
-}
-// split-K slab space that serves every one of `ds` under either split rule (and at least `s` bytes)
-size_t max_slab_bytes(size_t s, std::initializer_list<XpGemmDesc> ds) {
-  for (XpGemmDesc d : ds) {
-    const int a = xp_gemm_auto_split(&d), b = xp_gemm_auto_split_slack(&d), split = a > b ? a : b;
-    const size_t t = split <= 1 ? 0 : (size_t)split * d.M * d.N * sizeof(float);
-    if (t > s) s = t;
-  }
-  return s;
 }
 
 struct Defer {             // the layer's deferred second-level reductions (bias / LayerNorm-parameter gradients)
@@ -191,23 +202,35 @@ int out_proj_mlp_fwd(const Args& a, int64_t n, int64_t ldr, const float* side_x,
 // fc1's bias-gradient partial rows, the second LayerNorm's partial rows, the batched-reduce scratch.
 struct TailBwd {
   void *dpre, *dh2, *dx2, *dattn, *red; float *cs_pre, *ln2_part;
-  size_t esz, cs_pre_bytes, ln2_bytes, red_bytes, slabs;    // slabs: what the stage's three dW GEMMs need (the caller carves them)
-  int64_t db1_fused_rows, cs_pre_rows, ln_rows;
+  size_t esz, cs_pre_bytes, ln2_bytes, red_bytes;
+  int64_t cs_pre_rows, ln_rows;
 };
-// db1_fused_rows: partial rows of fc1's bias gradient out of the dpre GEMM's epilogue (xp_gemm_colsum_rows), 0 = a separate
-// column-sum pass over dpre
-TailBwd carve_tail_bwd(Carver& ws, int64_t n, int64_t D, int64_t Dff, int dt, int64_t db1_fused_rows) {
+// the shared stages' rows of the table, over n rows.  fuse_db1: fc1's bias gradient comes out of the dpre GEMM's epilogue where the
+// library offers it (xp_gemm_colsum_rows), else -- and always without fuse_db1 -- from a column-sum pass over dpre
+void tail_bwd_gemms(BwdGemms& t, const XpLayerDims& d, int64_t n, bool fuse_db1) {
+  const int64_t D = d.D, Dff = d.Dff;
+  const int dt = d.dtype;
+  XpGemmDesc& g = t.g[XP_LAYER_GEMM_DPRE] = gemm_desc(nullptr, nullptr, nullptr, n, Dff, D, dt, true);      // (dx3 . W2) * act'(pre)
+  g.epilogue = epi_act_bwd(d); g.resid = present_;
+  t.db1_fused_rows = fuse_db1 ? xp_gemm_colsum_rows(&g) : 0;
+  if (t.db1_fused_rows > 0) g.colsum_partials = present_;
+  t.wgrad(XP_LAYER_GEMM_DW2, wgrad_desc(n, D, Dff, dt), true);
+  t.g[XP_LAYER_GEMM_DH2] = gemm_desc(nullptr, nullptr, nullptr, n, D, Dff, dt, true);                       // dpre . W1
+  t.wgrad(XP_LAYER_GEMM_DW1, wgrad_desc(n, Dff, D, dt), true);
+  t.g[XP_LAYER_GEMM_DATTN] = gemm_desc(nullptr, nullptr, nullptr, n, D, D, dt, true);                       // dx2 . Wo
+  t.wgrad(XP_LAYER_GEMM_DWO, wgrad_desc(n, D, D, dt), true);
+}
+TailBwd carve_tail_bwd(Carver& ws, const BwdGemms& gm) {
   TailBwd t;
-  t.esz = dt == XP_BF16 ? 2 : 4;
+  const XpGemmDesc& dpre = gm.g[XP_LAYER_GEMM_DPRE];
+  const int64_t n = dpre.M, Dff = dpre.N, D = dpre.K;
+  t.esz = dpre.in_dtype == XP_BF16 ? 2 : 4;
   t.dpre = ws.take(n * Dff * t.esz); t.dh2 = ws.take(n * D * t.esz); t.dx2 = ws.take(n * D * t.esz); t.dattn = ws.take(n * D * t.esz);
-  t.db1_fused_rows = db1_fused_rows;
-  t.cs_pre_rows = db1_fused_rows > 0 ? db1_fused_rows : xp_colsum_partial_rows(n, Dff);
+  t.cs_pre_rows = gm.db1_fused_rows > 0 ? gm.db1_fused_rows : xp_colsum_partial_rows(n, Dff);
   t.cs_pre = ws.take<float>(t.cs_pre_rows * Dff * sizeof(float), &t.cs_pre_bytes);
   t.ln_rows = xp_layernorm_bwd_partial_rows(n);
   t.ln2_part = ws.take<float>(xp_layernorm_bwd_workspace_bytes(n, D), &t.ln2_bytes);
   t.red = ws.take((size_t)XP_REDUCE_MAX_SEGS * 32 * (size_t)(3 * D > Dff ? 3 * D : Dff) * sizeof(float) + 16, &t.red_bytes);
-  t.slabs = max_slab_bytes(0, {wgrad_desc(nullptr, nullptr, nullptr, n, D, Dff, dt), wgrad_desc(nullptr, nullptr, nullptr, n, Dff, D, dt),
-                               wgrad_desc(nullptr, nullptr, nullptr, n, D, D, dt)});
   return t;
 }
 
@@ -218,7 +241,7 @@ TailBwd carve_tail_bwd(Carver& ws, int64_t n, int64_t D, int64_t Dff, int dt, in
 // dattn, fc1's bias-gradient partial rows -- is a fill on the launching stream in front of the listed launch.  dpre's unlisted
 // tiles are neither written nor read (dh2 and dW1 walk the same tiles).  LayerNorm 2' stays dense: it reads the filled dh2.
 template <class Args>
-int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwd& t, float* slabs, size_t slab_bytes, int64_t sS,
+int mlp_out_proj_bwd(const Args& a, int64_t n, const BwdGemms& gm, const TailBwd& t, float* slabs, size_t slab_bytes, int64_t sS,
                      int32_t sM, Defer& df, const WgradOrder& wg, void* st, const XpDx3Support* sup = nullptr) {
   const int64_t D = a.dims.D, Dff = a.dims.Dff;
   const int dt = a.dims.dtype;
@@ -232,22 +255,20 @@ int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwd& t, float* slabs, s
     }
     return XP_OK;
   };
-  XpGemmDesc g = gemm_desc(a.dx3, a.W2, t.dpre, n, Dff, D, dt);               // dpre = (dx3 . W2) * act'(pre)
-  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(a.dims); g.resid = a.pre; g.ldr = Dff;
-  if (a.db1 && t.db1_fused_rows > 0) g.colsum_partials = t.cs_pre;
+  XpGemmDesc g = bound(gm.g[XP_LAYER_GEMM_DPRE], a.dx3, a.W2, t.dpre);        // dpre = (dx3 . W2) * act'(pre)
+  g.resid = a.pre; g.colsum_partials = a.db1 && gm.db1_fused_rows > 0 ? t.cs_pre : nullptr;
   if ((rc = listed(g, g.colsum_partials, (size_t)t.cs_pre_rows * Dff * sizeof(float)))) return rc;
   if ((rc = xp_gemm(&g, st))) return rc;
   if (a.db1) {
-    if (t.db1_fused_rows == 0 && (rc = xp_colsum_partials(t.dpre, n, Dff, Dff, dt, t.cs_pre, t.cs_pre_bytes, st))) return rc;
+    if (gm.db1_fused_rows == 0 && (rc = xp_colsum_partials(t.dpre, n, Dff, Dff, dt, t.cs_pre, t.cs_pre_bytes, st))) return rc;
     df.add(t.cs_pre, a.db1, Dff, (int)t.cs_pre_rows, (int)Dff);
   }
-  if (a.dw2 && (rc = run_wgrad(wgrad_desc(a.dx3, a.act, a.dw2, n, D, Dff, dt), slabs, slab_bytes, wg.stream(), true, sup, 0))) return rc;
+  if (a.dw2 && (rc = run_wgrad(bound(gm.g[XP_LAYER_GEMM_DW2], a.dx3, a.act, a.dw2), slabs, slab_bytes, wg.stream(), sup, 0))) return rc;
   if ((rc = wg.mark(1))) return rc;                                           // dpre is ready for dW1
-  g = gemm_desc(t.dpre, a.W1, t.dh2, n, D, Dff, dt);                          // dh2 = dpre . W1
-  g.b_kstrided = 1; g.ldb = D;
+  g = bound(gm.g[XP_LAYER_GEMM_DH2], t.dpre, a.W1, t.dh2);                    // dh2 = dpre . W1
   if ((rc = listed(g, t.dh2, (size_t)n * D * t.esz))) return rc;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a.dw1 && (rc = run_wgrad(wgrad_desc(t.dpre, a.h2, a.dw1, n, Dff, D, dt), slabs, slab_bytes, wg.stream(), true, sup, 1))) return rc;
+  if (a.dw1 && (rc = run_wgrad(bound(gm.g[XP_LAYER_GEMM_DW1], t.dpre, a.h2, a.dw1), slabs, slab_bytes, wg.stream(), sup, 1))) return rc;
   // dx2 = dx3 + LN2'(dh2); partial rows [dgamma | dbeta | colsum(dx2) | colsum(dx3)] -- out_proj's and fc2's bias gradients
   if ((rc = xp_layernorm_bwd_partials_side(t.dh2, D, a.x2, D, a.ln2_w, a.mean2, a.rstd2, a.dx3, D, t.dx2, D, 2, n, D, dt,
                                            a.side_x2, sS, sM, sM, t.ln2_part, t.ln2_bytes, st))) return rc;
@@ -256,11 +277,10 @@ int mlp_out_proj_bwd(const Args& a, int64_t n, const TailBwd& t, float* slabs, s
   df.add(t.ln2_part + 2 * D, a.dbo, 4 * D, (int)t.ln_rows, (int)D);
   df.add(t.ln2_part + 3 * D, a.db2, 4 * D, (int)t.ln_rows, (int)D);
   if ((rc = wg.mark(2))) return rc;                                           // dx2 is ready for dWo
-  g = gemm_desc(t.dx2, a.Wo, t.dattn, n, D, D, dt);                           // dattn = dx2 . Wo
-  g.b_kstrided = 1; g.ldb = D;
+  g = bound(gm.g[XP_LAYER_GEMM_DATTN], t.dx2, a.Wo, t.dattn);                 // dattn = dx2 . Wo
   if ((rc = listed(g, t.dattn, (size_t)n * D * t.esz))) return rc;
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a.dwo && (rc = run_wgrad(wgrad_desc(t.dx2, a.attn_o, a.dwo, n, D, D, dt), slabs, slab_bytes, wg.stream(), true, sup, 2))) return rc;
+  if (a.dwo && (rc = run_wgrad(bound(gm.g[XP_LAYER_GEMM_DWO], t.dx2, a.attn_o, a.dwo), slabs, slab_bytes, wg.stream(), sup, 2))) return rc;
   return XP_OK;
 }
 
@@ -344,24 +364,31 @@ extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
 // LayerNorm's partial rows, the attention workspace
 namespace {
 struct BwdWs {
-  Carver ws; TailBwd t;
+  Carver ws; BwdGemms gm; TailBwd t;
   void *dqkv, *dh1, *attn; float *slabs, *cs_qkv, *ln1_part;
   size_t slab_bytes, cs_qkv_bytes, ln1_bytes, attn_bytes;
   int64_t cs_qkv_rows;
   bool cs_qkv_fused;
 };
+// the dense backward's table: the shared stages over every row, then dh1 = dqkv . Wqkv and dWqkv -- the last launch of the layer,
+// the one the join waits for: the general split rule
+BwdGemms dense_bwd_gemms(const XpLayerDims& d) {
+  BwdGemms t;
+  t.n = XP_LAYER_GEMM_DENSE_COUNT;
+  tail_bwd_gemms(t, d, d.rows, true);
+  t.g[XP_LAYER_GEMM_DH1] = gemm_desc(nullptr, nullptr, nullptr, d.rows, d.D, 3 * d.D, d.dtype, true);
+  t.wgrad(XP_LAYER_GEMM_DWQKV, wgrad_desc(d.rows, 3 * d.D, d.D, d.dtype), false);
+  return t;
+}
 BwdWs carve_bwd(const XpLayerDims& d, void* base, size_t cap) {
   BwdWs w;
   Carver& ws = w.ws = Carver{(char*)base, cap};
-  const int64_t rows = d.rows, D = d.D, Dff = d.Dff;
-  // fc1's bias gradient: fused into the dX GEMM epilogue where the library offers it, else a column-sum pass over dpre
-  XpGemmDesc g = gemm_desc(nullptr, nullptr, nullptr, rows, Dff, D, d.dtype);
-  g.b_kstrided = 1; g.ldb = Dff; g.epilogue = epi_act_bwd(d); g.ldr = Dff;
-  g.resid = &g;                          // (only tested for non-NULL by the planning queries)
-  w.t = carve_tail_bwd(ws, rows, D, Dff, d.dtype, xp_gemm_colsum_rows(&g));
+  const int64_t rows = d.rows, D = d.D;
+  w.gm = dense_bwd_gemms(d);
+  w.t = carve_tail_bwd(ws, w.gm);
   // (fc2's bias gradient = column sums of dx3: taken by the second LayerNorm's backward)
   w.dqkv = ws.take(rows * 3 * D * w.t.esz); w.dh1 = ws.take(rows * D * w.t.esz);
-  w.slabs = ws.take<float>(max_slab_bytes(w.t.slabs, {wgrad_desc(nullptr, nullptr, nullptr, rows, 3 * D, D, d.dtype)}), &w.slab_bytes);
+  w.slabs = ws.take<float>(w.gm.max_slab_bytes, &w.slab_bytes);
   // the q/k/v bias gradients: out of the attention backward kernels where they offer it, else a column-sum pass over dqkv
   w.cs_qkv_rows = xp_attn_bwd_colsum_rows(d.attn_mode, d.B, d.heads, d.S, d.M, d.N, d.L, d.dtype);
   w.cs_qkv_fused = w.cs_qkv_rows > 0;
@@ -406,20 +433,19 @@ static int encoder_layer_bwd(const XpLayerBwd* a, const XpDx3Support* sup, void*
   if ((rc = wg.mark(0))) return rc;
   // ---- MLP: x3 = x2 + fc2(act(fc1(LN2(x2)))), then dattn = dx2 . Wo of x2 = x + out_proj(attn(qkv(LN1(x))))
   if (sup) {
-    XP_REQUIRE(w.t.db1_fused_rows > 0 && sup->m_tiles && sup->n_m_tiles >= 1, "xp_encoder_layer_bwd: dx3_support needs the 256-wide "
+    XP_REQUIRE(w.gm.db1_fused_rows > 0 && sup->m_tiles && sup->n_m_tiles >= 1, "xp_encoder_layer_bwd: dx3_support needs the 256-wide "
                "GEMM plans of this shape (fused fc1 bias sums) and a non-empty m_tiles");
     for (int i = 0; i < 3; ++i)
       XP_REQUIRE(sup->k_tiles[i] && sup->k_tile_begin[i] && sup->k_tile_begin_host[i], "xp_encoder_layer_bwd: dx3_support list %d is null", i);
   }
-  if ((rc = mlp_out_proj_bwd(*a, rows, w.t, w.slabs, w.slab_bytes, a->side_S, a->side_M, df, wg, st, sup))) return rc;
+  if ((rc = mlp_out_proj_bwd(*a, rows, w.gm, w.t, w.slabs, w.slab_bytes, a->side_S, a->side_M, df, wg, st, sup))) return rc;
   // ---- attention
   if ((rc = xp_attn_bwd2(a->qkv, 3 * D, a->attn_o, w.t.dattn, D, a->stats, a->pad_mask, w.dqkv, d.q_scale, d.attn_mode, d.B, d.heads,
                          d.S, d.M, d.N, d.L, dt, w.attn, w.attn_bytes, (a->dbqkv && w.cs_qkv_fused) ? w.cs_qkv : nullptr, st))) return rc;
   if ((rc = wg.mark(3))) return rc;                                           // dqkv is ready for dWqkv
-  XpGemmDesc g = gemm_desc(w.dqkv, a->Wqkv, w.dh1, rows, D, 3 * D, dt);       // dh1 = dqkv . Wqkv
-  g.b_kstrided = 1; g.ldb = D;
+  const XpGemmDesc g = bound(w.gm.g[XP_LAYER_GEMM_DH1], w.dqkv, a->Wqkv, w.dh1);      // dh1 = dqkv . Wqkv
   if ((rc = xp_gemm(&g, st))) return rc;
-  if (a->dwqkv && (rc = run_wgrad(wgrad_desc(w.dqkv, a->h1, a->dwqkv, rows, 3 * D, D, dt), w.slabs, w.slab_bytes, wg.stream(), false))) return rc;
+  if (a->dwqkv && (rc = run_wgrad(bound(w.gm.g[XP_LAYER_GEMM_DWQKV], w.dqkv, a->h1, a->dwqkv), w.slabs, w.slab_bytes, wg.stream()))) return rc;
   if (a->dbqkv) {
     if (!w.cs_qkv_fused && (rc = xp_colsum_partials(w.dqkv, rows, 3 * D, 3 * D, dt, w.cs_qkv, w.cs_qkv_bytes, st))) return rc;
     df.add(w.cs_qkv, a->dbqkv, 3 * D, (int)w.cs_qkv_rows, (int)(3 * D));
@@ -460,21 +486,38 @@ PooledFwdWs carve_pooled_fwd(const XpLayerDims& d, void* base, size_t cap) {
 // workspace of the pooled backward: the shared stages over the B pooled rows (TailBwd), [dqkv | dh1] over every row, split-K slabs,
 // the q and k/v bias-gradient partial rows, LayerNorm 1's partial rows of both passes, the attention partials
 struct PooledBwdWs {
-  Carver ws; TailBwd t;
+  Carver ws; BwdGemms gm; TailBwd t;
   char* dqkv; void *dh1, *attn; float *slabs, *cs_q, *cs_kv, *ln1_part, *ln1p_part;
   size_t slab_bytes, cs_q_bytes, ln1_bytes, ln1p_bytes, attn_bytes;
   int64_t cs_q_rows, ln_rows;
 };
+// the pooled backward's table: the shared stages over the B pooled rows (fc1's bias gradient: always a column-sum pass over dpre),
+// then, over dqkv[rows, 3D] (row pitch 3D): dh1 = dkv . Wkv on every row, the pooled rows again with their q columns (row b*S
+// through the row remaps), dWq of the pooled rows and dWkv of every row -- the last launch, the general split rule
+BwdGemms pooled_bwd_gemms(const XpLayerDims& d) {
+  BwdGemms t;
+  const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
+  t.n = XP_LAYER_GEMM_POOLED_COUNT;
+  tail_bwd_gemms(t, d, B, false);
+  t.g[XP_LAYER_GEMM_DH1_KV] = gemm_desc(nullptr, nullptr, nullptr, rows, D, 2 * D, d.dtype, true);        // dh1 = dkv . Wkv
+  t.g[XP_LAYER_GEMM_DH1_KV].lda = 3 * D;
+  XpGemmDesc& g = t.g[XP_LAYER_GEMM_DH1_Q] = gemm_desc(nullptr, nullptr, nullptr, B, D, 3 * D, d.dtype, true);   // dh1[b*S] = dqkv[b*S] . Wqkv
+  g.a_grp = 1; g.a_grp_stride = S; g.c_grp = 1; g.c_grp_stride = S;
+  XpGemmDesc gq = wgrad_desc(B, D, D, d.dtype, 3 * D, D);                     // dWq = dq^T . h1p: dq of the pooled rows of dqkv
+  gq.a_grp = 1; gq.a_grp_stride = S;
+  t.wgrad(XP_LAYER_GEMM_DWQ, gq, true);
+  t.wgrad(XP_LAYER_GEMM_DWKV, wgrad_desc(rows, 2 * D, D, d.dtype, 3 * D, D), false);
+  return t;
+}
 PooledBwdWs carve_pooled_bwd(const XpLayerDims& d, void* base, size_t cap) {
   PooledBwdWs w;
   Carver& ws = w.ws = Carver{(char*)base, cap};
   const int64_t rows = d.rows, D = d.D, B = d.B, S = d.S;
   const int dt = d.dtype;
-  w.t = carve_tail_bwd(ws, B, D, d.Dff, dt, 0);      // fc1's bias gradient: always a column-sum pass over dpre
+  w.gm = pooled_bwd_gemms(d);
+  w.t = carve_tail_bwd(ws, w.gm);
   w.dqkv = ws.take<char>(rows * 3 * D * w.t.esz); w.dh1 = ws.take(rows * D * w.t.esz);
-  XpGemmDesc gq = wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, B, D, D, dt);       // dWq: dq of the pooled rows of dqkv
-  gq.a_grp = 1; gq.a_grp_stride = S;
-  w.slabs = ws.take<float>(max_slab_bytes(w.t.slabs, {gq, wgrad_desc(nullptr, 3 * D, nullptr, D, nullptr, rows, 2 * D, D, dt)}), &w.slab_bytes);
+  w.slabs = ws.take<float>(w.gm.max_slab_bytes, &w.slab_bytes);
   w.cs_q_rows = xp_colsum_partial_rows(B, D);
   w.cs_q = ws.take<float>(w.cs_q_rows * D * sizeof(float), &w.cs_q_bytes);
   w.cs_kv = ws.take<float>(xp_attn_pooled_colsum_rows_max(B, S) * 2 * D * sizeof(float));
@@ -529,6 +572,16 @@ extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) 
   return out_proj_mlp_fwd(*a, B, S * D, side0, side_x2, a->side_out, s1, s1, st);
 }
 
+extern "C" int32_t xp_debug_layer_bwd_gemms(const XpLayerDims* d, int32_t pooled, XpGemmDesc* out, int32_t cap) {
+  XP_REQUIRE(d && out, "xp_debug_layer_bwd_gemms: null argument");
+  int rc = pooled ? check_pooled_dims("xp_debug_layer_bwd_gemms", *d) : check_dims("xp_debug_layer_bwd_gemms", *d);
+  if (rc) return rc;
+  const BwdGemms t = pooled ? pooled_bwd_gemms(*d) : dense_bwd_gemms(*d);
+  XP_REQUIRE(cap >= t.n, "xp_debug_layer_bwd_gemms: room for %d descriptors, the table has %d", cap, t.n);
+  memcpy(out, t.g, t.n * sizeof(XpGemmDesc));
+  return t.n;
+}
+
 extern "C" size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* d) {
   if (!d || d->rows <= 0 || d->B <= 0 || d->D <= 0 || d->Dff <= 0 || d->S <= 0 || d->heads <= 0) return 0;
   return carve_pooled_bwd(*d, nullptr, 0).ws.bytes();
@@ -557,23 +610,19 @@ extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) 
   const WgradOrder wg{rows >= 4096 ? wgrad_side() : nullptr, (hipStream_t)st, "xp_encoder_layer_pooled_bwd"};
   if ((rc = wg.mark(0))) return rc;
   // ---- MLP and dattn = dx2 . Wo on the pooled rows
-  if ((rc = mlp_out_proj_bwd(*a, B, w.t, w.slabs, w.slab_bytes, s1, s1, df, wg, st))) return rc;
+  if ((rc = mlp_out_proj_bwd(*a, B, w.gm, w.t, w.slabs, w.slab_bytes, s1, s1, df, wg, st))) return rc;
   // ---- attention: dq lands in the q columns of the pooled rows of dqkv, dk / dv in the k / v columns of every row
   if ((rc = xp_attn_pooled_bwd(a->q, a->kv, 2 * D, a->attn_o, w.t.dattn, a->stats, dqkv, S * 3 * D, dkv, 3 * D, d.q_scale, B, d.heads,
                                S, dt, w.attn, w.attn_bytes, a->dbqkv ? w.cs_kv : nullptr, st))) return rc;
   if ((rc = wg.mark(3))) return rc;
   // dh1 = dkv . Wkv on every row, then the pooled rows again with their q columns: dqkv[b*S] . Wqkv
-  XpGemmDesc g = gemm_desc(dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * w.t.esz, w.dh1, rows, D, 2 * D, dt);
-  g.lda = 3 * D; g.b_kstrided = 1; g.ldb = D;
+  XpGemmDesc g = bound(w.gm.g[XP_LAYER_GEMM_DH1_KV], dkv, static_cast<const char*>(a->Wqkv) + (size_t)D * D * w.t.esz, w.dh1);
   if ((rc = xp_gemm(&g, st))) return rc;
-  g = gemm_desc(dqkv, a->Wqkv, w.dh1, B, D, 3 * D, dt);
-  g.a_grp = 1; g.a_grp_stride = S; g.b_kstrided = 1; g.ldb = D; g.c_grp = 1; g.c_grp_stride = S;
+  g = bound(w.gm.g[XP_LAYER_GEMM_DH1_Q], dqkv, a->Wqkv, w.dh1);
   if ((rc = xp_gemm(&g, st))) return rc;
   if (a->dwqkv) {
-    g = wgrad_desc(dqkv, 3 * D, a->h1p, D, a->dwqkv, B, D, D, dt);            // dWq = dq^T . h1p
-    g.a_grp = 1; g.a_grp_stride = S;
-    if ((rc = run_wgrad(g, w.slabs, w.slab_bytes, wg.stream(), true))) return rc;
-    if ((rc = run_wgrad(wgrad_desc(dkv, 3 * D, a->h1, D, a->dwqkv + D * D, rows, 2 * D, D, dt), w.slabs, w.slab_bytes, wg.stream(), false))) return rc;
+    if ((rc = run_wgrad(bound(w.gm.g[XP_LAYER_GEMM_DWQ], dqkv, a->h1p, a->dwqkv), w.slabs, w.slab_bytes, wg.stream()))) return rc;
+    if ((rc = run_wgrad(bound(w.gm.g[XP_LAYER_GEMM_DWKV], dkv, a->h1, a->dwqkv + D * D), w.slabs, w.slab_bytes, wg.stream()))) return rc;
   }
   if (a->dbqkv) {
     const int64_t kv_rows = xp_attn_pooled_colsum_rows(B, d.heads, S, dt);

@@ -597,7 +597,7 @@ def _layer_backward(ctx, build, entry, ws_tag, ops, x, *rest, extra=()):
 # output makes autograd sum gradients (a new tensor, or an in-place add that bumps the version), a hook that rewrites the gradient
 # returns another tensor, an in-place write bumps the version -- the claim is then gone and the layer runs dense.  No data is read.
 _ROW_CLAIMS = {}            # id(tensor) -> (weakref, _version, data_ptr, (B, S, r0))
-_SUPPORTS = {}              # (device, B, S, r0, slabs) -> _Dx3Support (the lists depend on the shape only)
+_SUPPORTS = {}              # (device, layer plan, r0, CU budget) -> _Dx3Support (the lists depend on the shape and the splits only)
 sparse_last_bwd_calls = 0   # native layer backward calls that ran over tile lists (tests count them)
 
 
@@ -658,28 +658,31 @@ class _Dx3Support:
             s.split[w] = split
 
 
+def _dx3_lists(dims, r0):
+    """The host half of _dx3_support: ``(m_tiles, lists, splits)`` of a dense layer of ``dims`` whose dx3 is zero outside row ``r0`` of
+    every sample, from the library's own table of the backward's GEMMs (H.layer_bwd_gemms) and their plans; None where one of the
+    six is not planned on the 256-wide family or fc1's bias sums are not fused (fp32, small shapes).  No device, no upload."""
+    table = H.layer_bwd_gemms(dims)
+    dw = [table[i] for i in (L.XP_LAYER_GEMM_DW2, L.XP_LAYER_GEMM_DW1, L.XP_LAYER_GEMM_DWO)]
+    plans = [H.gemm_plan_of(g) for g in dw + [table[i] for i in (L.XP_LAYER_GEMM_DPRE, L.XP_LAYER_GEMM_DH2, L.XP_LAYER_GEMM_DATTN)]]
+    if not all(p["family"] == L.GEMM_FAMILY_256 for p in plans) or plans[3]["colsum_rows"] <= 0:
+        return None
+    m_tiles, lists = dx3_tile_lists(dims.B, dims.S, r0, [(p["split"], p["k_per_split"]) for p in plans[:3]])
+    return m_tiles, lists, tuple(g.split_k for g in dw)
+
+
 def _dx3_support(plan, dev, claim):
     """The XpDx3Support (xp_encoder_layer_bwd_listed) of a dense video layer whose dx3 carries ``claim`` = (B, S, r0); None where the
-    claim is for another shape or one of the six GEMMs of this shape is not planned on the 256-wide family (fp32, small shapes):
-    the layer then runs dense."""
+    claim is for another shape or _dx3_lists has none for this one: the layer then runs dense."""
     d = plan.dims
     if claim is None or (claim[0], claim[1]) != (d.B, d.S) or not 0 <= claim[2] < d.S:
         return None
-    rows, D, Dff = d.rows, d.D, d.Dff
-    wg = ((D, Dff), (Dff, D), (D, D))                              # dW2, dW1, dWo as (n_out, n_in): csrc/layer.hip::mlp_out_proj_bwd
-    splits = tuple(_split_for(no, ni, rows, plan.dtype, (0, 0, 0), True) for no, ni in wg)
-    key = (dev, d.B, d.S, claim[2], D, Dff, plan.dtype, d.act, splits)
+    key = (dev, plan, claim[2], L.lib().xp_get_cu_budget())       # (the CU budget moves the splits)
     if key not in _SUPPORTS:
         if torch.cuda.is_current_stream_capturing():              # (the lists are uploaded with blocking copies: not inside a capture)
             return None
-        plans = [H.gemm_plan(no, ni, rows, plan.dtype, a_kstrided=True, b_kstrided=True, split_k=sp) for (no, ni), sp in zip(wg, splits)]
-        plans += [H.gemm_plan(rows, n, k, plan.dtype, b_kstrided=True, **kw)
-                  for n, k, kw in ((Dff, D, dict(epilogue=L.EPI_ACT_BWD[d.act], colsum=True)), (D, Dff, {}), (D, D, {}))]
-        sup = None
-        if all(p["family"] == L.GEMM_FAMILY_256 for p in plans) and plans[3]["colsum_rows"] > 0:
-            m_tiles, lists = dx3_tile_lists(d.B, d.S, claim[2], [(p["split"], p["k_per_split"]) for p in plans[:3]])
-            sup = _Dx3Support(dev, m_tiles, lists, splits)
-        _SUPPORTS[key] = sup
+        host = _dx3_lists(d, claim[2])
+        _SUPPORTS[key] = None if host is None else _Dx3Support(dev, *host)
     return _SUPPORTS[key]
 
 

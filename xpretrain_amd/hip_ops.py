@@ -57,6 +57,24 @@ def workspace(nbytes: int, device, tag: str = "ws") -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------- GEMM
+def _gemm_desc(M, N, K, in_dtype, out_dtype, a_kstrided=False, b_kstrided=False, *, lda=None, ldb=None, ldc=None, ldr=None, ldaux=None,
+               epilogue=L.EPI_NONE, split_k=1, a_remap=(0, 0, 0), c_remap=(0, 0, 0), scale=1.0, scale_cols=0) -> L.XpGemmDesc:
+    """An XpGemmDesc without operands: shape, layouts, dtype codes, epilogue, split, row remaps -- and THE leading-dimension defaults
+    (an operand's extent along its contiguous dimension; N for the output, resid and aux)."""
+    d = L.XpGemmDesc()
+    d.M, d.N, d.K = M, N, K
+    d.lda = lda if lda is not None else (M if a_kstrided else K)
+    d.ldb = ldb if ldb is not None else (N if b_kstrided else K)
+    d.ldc, d.ldr, d.ldaux = (N if v is None else v for v in (ldc, ldr, ldaux))
+    d.a_kstrided, d.b_kstrided = int(a_kstrided), int(b_kstrided)
+    d.in_dtype, d.out_dtype = in_dtype, out_dtype
+    d.epilogue, d.split_k = epilogue, split_k
+    d.a_grp, d.a_grp_stride, d.a_off = a_remap
+    d.c_grp, d.c_grp_stride, d.c_off = c_remap
+    d.scale, d.scale_cols = float(scale), scale_cols
+    return d
+
+
 def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, ldb=None, out=None, ldc=None,
          a_kstrided=False, b_kstrided=False, out_dtype=None, epilogue=L.EPI_NONE, bias=None, scale=1.0,
          scale_cols=0, resid=None, ldr=None, aux=None, ldaux=None, tab1=None, tab2=None, tab_L=0,
@@ -90,7 +108,8 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
         out_dtype = torch.float32
     elif out is None:
         out = torch.empty((out_rows or M, N), dtype=out_dtype, device=A.device)
-    d = L.XpGemmDesc()
+    d = _gemm_desc(M, N, K, _dt(A), _DT[out_dtype], a_kstrided, b_kstrided, lda=lda, ldb=ldb, ldc=ldc, ldr=ldr, ldaux=ldaux,
+                   epilogue=epilogue, split_k=split_k, a_remap=a_remap, c_remap=c_remap, scale=scale, scale_cols=scale_cols)
     d.A, d.B, d.C = (0 if frames is not None else A.data_ptr()), B.data_ptr(), out.data_ptr()
     if frames is not None:
         d.a_frames, d.a_frames_u8 = frames.data_ptr(), int(frames.dtype == torch.uint8)
@@ -98,21 +117,9 @@ def gemm(A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, *, lda=None, 
         if frame_norm is not None:
             for c in range(3):
                 d.fr_mean[c], d.fr_std[c] = float(frame_norm[0][c]), float(frame_norm[1][c])
-    d.M, d.N, d.K = M, N, K
-    d.lda = lda if lda is not None else (M if a_kstrided else K)
-    d.ldb = ldb if ldb is not None else (N if b_kstrided else K)
-    d.ldc = ldc if ldc is not None else N
-    d.a_kstrided, d.b_kstrided = int(a_kstrided), int(b_kstrided)
-    d.in_dtype, d.out_dtype = _dt(A), _DT[out_dtype]
-    d.epilogue, d.split_k = epilogue, split_k
-    d.a_grp, d.a_grp_stride, d.a_off = a_remap
-    d.c_grp, d.c_grp_stride, d.c_off = c_remap
     d.bias = 0 if bias is None else _chk(bias, "bias", torch.float32).data_ptr()
-    d.scale, d.scale_cols = float(scale), scale_cols
     d.resid = 0 if resid is None else _chk(resid, "resid", A.dtype).data_ptr()
-    d.ldr = ldr if ldr is not None else N
     d.aux = 0 if aux is None else _chk(aux, "aux", out_dtype).data_ptr()       # BIAS_GELU without aux: forward-only
-    d.ldaux = ldaux if ldaux is not None else N
     d.tab1 = 0 if tab1 is None else _chk(tab1, "tab1", torch.float32).data_ptr()
     d.tab2 = 0 if tab2 is None else _chk(tab2, "tab2", torch.float32).data_ptr()
     d.tab_L = tab_L
@@ -161,12 +168,8 @@ def gemm_plan(M: int, N: int, K: int, dtype: torch.dtype, *, a_kstrided=False, b
               colsum=False) -> dict:
     """The plan (gemm_plan_of) of a dense-operand problem described by its shape alone: no tensors, nothing launched.  ``colsum``: with
     fused column sums where the library offers them.  Split-K problems write fp32 slabs, the others the compute dtype."""
-    d = L.XpGemmDesc()
-    d.M, d.N, d.K = M, N, K
-    d.lda, d.ldb, d.ldc, d.ldr, d.ldaux = (M if a_kstrided else K), (N if b_kstrided else K), N, N, N
-    d.a_kstrided, d.b_kstrided = int(a_kstrided), int(b_kstrided)
-    d.in_dtype, d.out_dtype = _DT[dtype], _DT[torch.float32 if split_k > 1 or (a_kstrided and b_kstrided) else dtype]
-    d.epilogue, d.split_k, d.scale = epilogue, split_k, 1.0
+    d = _gemm_desc(M, N, K, _DT[dtype], _DT[torch.float32 if split_k > 1 or (a_kstrided and b_kstrided) else dtype], a_kstrided, b_kstrided,
+                   epilogue=epilogue, split_k=split_k)
     d.resid = int(epilogue in L.EPI_ACT_BWD)       # (the planner reads these pointers only as present / absent)
     if colsum and L.lib().xp_gemm_colsum_rows(C.byref(d)) > 0:
         d.colsum_partials = 1
@@ -176,15 +179,17 @@ def gemm_plan(M: int, N: int, K: int, dtype: torch.dtype, *, a_kstrided=False, b
 def gemm_auto_split(M: int, N: int, K: int, dtype: torch.dtype, *, a_kstrided=True, b_kstrided=True, lda=None,
                     ldb=None, a_remap=(0, 0, 0), slack=False) -> int:
     """Split-K factor for a weight-gradient GEMM (see include/xpretrain_hip.h::xp_gemm_auto_split / _slack)."""
-    d = L.XpGemmDesc()
-    d.M, d.N, d.K = M, N, K
-    d.lda = lda if lda is not None else (M if a_kstrided else K)
-    d.ldb = ldb if ldb is not None else (N if b_kstrided else K)
-    d.ldc = N
-    d.a_kstrided, d.b_kstrided = int(a_kstrided), int(b_kstrided)
-    d.in_dtype, d.out_dtype = _DT[dtype], _DT[torch.float32]
-    d.a_grp, d.a_grp_stride, d.a_off = a_remap
+    d = _gemm_desc(M, N, K, _DT[dtype], L.XP_F32, a_kstrided, b_kstrided, lda=lda, ldb=ldb, a_remap=a_remap)
     return int((L.lib().xp_gemm_auto_split_slack if slack else L.lib().xp_gemm_auto_split)(C.byref(d)))
+
+
+def layer_bwd_gemms(dims: L.XpLayerDims, pooled=False) -> list:
+    """The GEMMs of a layer backward for ``dims`` as the native call describes, sizes and launches them (xp_debug_layer_bwd_gemms: host
+    only, nothing launched): XpGemmDesc's without operands, indexed by L.XP_LAYER_GEMM_*, each weight gradient at its split."""
+    out = (L.XpGemmDesc * L.XP_LAYER_GEMM_MAX)()
+    n = L.lib().xp_debug_layer_bwd_gemms(C.byref(dims), int(pooled), out, len(out))
+    L.check(min(n, 0), "xp_debug_layer_bwd_gemms")
+    return list(out[:n])
 
 
 def splitk_reduce(slabs: torch.Tensor, out: torch.Tensor, accumulate=False, splits=None) -> torch.Tensor:
