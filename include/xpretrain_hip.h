@@ -626,7 +626,9 @@ int xp_contrastive_loss(int32_t kind, const float* vis, const float* txt, const 
  *                    cs_ij = max(0, margin + S_ij - S_ii), ci_ij = max(0, margin + S_ij - S_jj), both diagonals cleared
  *                    loss = sum cs + sum ci (sums, not means); with max_violation  sum_i max_j cs_ij + sum_j max_i ci_ij.
  *                    A hinge is active where its cost is > 0.  The gradient of a maximum goes to ONE element, on an exact tie
- *                    to the lowest index; a line without a positive cost has no gradient.
+ *                    to the lowest index; a line without a positive cost has no gradient.  A NaN cost counts as active and as
+ *                    the largest of its line, and max(0, x) keeps a NaN, as torch's clamp(min=0) and max() do: a non-finite
+ *                    feature makes the loss non-finite instead of vanishing in a comparison that is false for NaN.
  *                    Order measure: dS_ij/dv_i = max(0, t_j - v_i) / (-S_ij) = -dS_ij/dt_j, a kernel of its own (no GEMM).  A
  *                    pair at distance exactly 0 contributes ZERO gradient -- the one deliberate deviation: torch gives NaN there.
  *   XP_PAIR_HARDNEG  S = T V^T (no temperature).  Each row of S and each row of S^T keeps its k = hard_negative_num largest

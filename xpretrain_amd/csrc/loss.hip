@@ -612,6 +612,12 @@ __device__ __forceinline__ int wave_sum_int(int v) {
   return v;
 }
 
+// max(x, 0) as torch.clamp(min=0) has it: a NaN stays a NaN (fmaxf would return the 0), so that a non-finite feature reaches the loss
+__device__ __forceinline__ float relu_nan(float x) { return !(x <= 0.f) ? x : 0.f; }
+
+// a > b in the order in which a NaN is the largest value, as torch.max() has it: a line that holds a NaN has it for its maximum
+__device__ __forceinline__ bool gt_nan(float a, float b) { return a != a ? b == b : a > b; }
+
 // S_ij = -|max(0, t_j - v_i)|_2 (order_sim, loss.py:13-19): one wave per (i, j), a fixed butterfly
 __global__ __launch_bounds__(256) void order_sim_kernel(const float* __restrict__ V, const float* __restrict__ T,
                                                         float* __restrict__ S, int n, int d) {
@@ -623,7 +629,7 @@ __global__ __launch_bounds__(256) void order_sim_kernel(const float* __restrict_
   const float* t = T + (int64_t)j * d;
   float s = 0.f;
   for (int k = lane; k < d; k += 64) {
-    const float r = fmaxf(t[k] - v[k], 0.f);
+    const float r = relu_nan(t[k] - v[k]);
     s += r * r;
   }
   s = wave_sum(s);
@@ -647,7 +653,7 @@ __global__ void order_bwd_kernel(const float* __restrict__ V, const float* __res
       const float g = G[o], s = S[o];
       if (g != 0.f && s != 0.f) {                                             // (uniform over the block)
         const float y = other[(int64_t)b * d + k];
-        const float r = fmaxf(col ? x - y : y - x, 0.f);                      // max(0, t_j - v_i)
+        const float r = relu_nan(col ? x - y : y - x);                        // max(0, t_j - v_i)
         acc += g * r / (col ? s : -s);
       }
     }
@@ -683,7 +689,8 @@ __global__ void pair_nce_kernel(const float* __restrict__ A, float* __restrict__
 }
 
 // TripletContrastiveLoss: the costs of line idx against ITS diagonal entry -- row i: cs_ij = margin + S_ij - S_ii (j != i),
-// column j: ci_ij = margin + S_ij - S_jj (i != j); active where > 0.  G share: +1 on every active entry (max_violation: on the
+// column j: ci_ij = margin + S_ij - S_jj (i != j); active where > 0 -- or NaN: the reference's clamp(min=0) and max() hand a NaN on to
+// the loss, and so does this kernel (a NaN cost counts as active, and as the largest).  G share: +1 on every active entry (max_violation: on the
 // largest one only, lowest index on a tie) and minus their number on the diagonal entry.
 template <bool COL>
 __global__ void pair_triplet_kernel(const float* __restrict__ S, float* __restrict__ G, float* __restrict__ part, int n, PairArgs p) {
@@ -695,13 +702,14 @@ __global__ void pair_triplet_kernel(const float* __restrict__ S, float* __restri
     int bi = -1;
     for (int t = lane; t < n; t += 64) {
       const float cst = base + S[line_off<COL>(idx, t, n)];
-      if (t != idx && cst > best) { best = cst; bi = t; }                     // (t ascending per lane: the first of equals stays)
+      if (t != idx && gt_nan(cst, best)) { best = cst; bi = t; }              // (t ascending per lane: the first of equals stays)
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       const float ob = __shfl_xor(best, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (ob > best || (ob == best && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
+      const bool same = ob == best || (ob != ob && best != best);
+      if (gt_nan(ob, best) || (same && oi >= 0 && (bi < 0 || oi < bi))) { best = ob; bi = oi; }
     }
     for (int t = lane; t < n; t += 64) {
       const int64_t o = line_off<COL>(idx, t, n);
@@ -716,7 +724,7 @@ __global__ void pair_triplet_kernel(const float* __restrict__ S, float* __restri
       if (t == idx) continue;                                                 // (lane 0 writes the diagonal entry below)
       const int64_t o = line_off<COL>(idx, t, n);
       const float cst = base + S[o];
-      const bool act = cst > 0.f;
+      const bool act = !(cst <= 0.f);                                         // (true for a NaN)
       sum += act ? cst : 0.f;
       cnt += act;
       const float g = act ? 1.0f : 0.f;
