@@ -370,6 +370,26 @@ def join_late_weights():
         lu.join()
 
 
+# ---- streams on which a backward pass allocates parameter gradients -----------------------------------------------------------------
+# Autograd replays a node's backward on the stream of its forward, so the text tower's parameter gradients are allocated on the text
+# tower's stream -- and the caching allocator hands a freed block back at once, but only to the stream that allocated it.  An
+# optimizer reads those gradients on ITS stream; zero_grad(set_to_none=True) right behind the step would return them to the text
+# stream's pool while the update kernel may still read them, and whatever allocates on that stream next (the shared stream also
+# carries utils.prefetch.PrefetchLoader's copies) could overwrite them: only CLIPModel.forward's own fork orders that stream behind
+# the caller's.  So the step orders every such stream behind its reads: one event per step, on a stream that is idle until the next
+# forward forks from the caller's stream anyway.  (distributed.GradBucketReducer's pack path and the late update record_stream their
+# gradients for the same reason; found by tests/stream_ledger.py)
+GRADIENT_STREAMS = {}           # device index -> stream; CLIPModel.shared_text_stream registers the text tower's
+
+
+def order_gradient_streams_behind(reader):
+    """Every registered gradient stream of ``reader``'s device waits for what ``reader`` has enqueued so far (an optimizer step's
+    reads of the gradients).  Not under capture: a wait would pull the other stream into the capture."""
+    st = GRADIENT_STREAMS.get(reader.device.index)
+    if st is not None and st != reader and not torch.cuda.is_current_stream_capturing():
+        st.wait_stream(reader)
+
+
 # XPRETRAIN_FWD_SPLIT=0: the whole batch as one chain (A/B switch for the two half-batch chains of the video tower's forward)
 FWD_SPLIT = os.environ.get("XPRETRAIN_FWD_SPLIT", "1") != "0"
 FWD_SPLIT_MIN_ROWS = 8192          # below this a half-batch launch no longer fills the chip beside its twin

@@ -698,6 +698,7 @@ class CLIPModel(CLIPPreTrainedModel):
         st = CLIPModel._text_streams.get(key)
         if st is None:
             st = CLIPModel._text_streams[key] = torch.cuda.Stream(device=torch.device("cuda", key))
+            XF.GRADIENT_STREAMS[key] = st       # the tower's backward allocates its parameter gradients there
         return st
 
     def _text_stream(self, device):

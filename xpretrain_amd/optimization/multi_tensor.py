@@ -240,7 +240,7 @@ class MultiTensorOptimizer(Optimizer):
         act = self._active()
         if not act:
             return loss
-        from ..functional import WEIGHTS
+        from ..functional import WEIGHTS, order_gradient_streams_behind
         name, (sm, sv) = type(self).__name__, self._STATE
         plan = self._plan
         # steady state: the same parameters and state tensors with the same storage as when the plan was built, and no change in the
@@ -322,6 +322,9 @@ class MultiTensorOptimizer(Optimizer):
         for la in plan["launches"]:
             if not (overlap and la["late"]):
                 run(la, stream)
+        # gradients another stream's backward allocated (the text tower's) go back to THAT stream's pool when they are freed:
+        # it must not reuse them before the launches above have read them
+        order_gradient_streams_behind(torch.cuda.current_stream(dev))
         if guard:
             # What happened reaches the host behind the step, with no wait here: the next step() (or whoever reads the counts first)
             # waits for this event, a forward and a backward later, and takes the increments above back if the step was skipped.
