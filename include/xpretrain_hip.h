@@ -691,9 +691,30 @@ int xp_retrieval_ranks(const float* sim, const int64_t* labels, int64_t n, int64
  * workspace below *_workspace_bytes (which return 0 and set xp_last_error for shapes they refuse).
  * xp_retrieval_stream_plan: the tiling the calls use, for tests that place rows on its boundaries: scores are computed in tiles of
  *   XP_RETRIEVAL_TILE x XP_RETRIEVAL_TILE; the DSL statistics split the query tiles into runs of *stat_tiles_per_split, the top-k
- *   search splits the gallery tiles into runs of *topk_tiles_per_split. */
+ *   search splits the gallery tiles into runs of *topk_tiles_per_split.
+ *
+ * DSL-weighted search: top-k on the re-ranked score x = s * exp(theta s - mx) / sum, the statistics as a call of their own.
+ * xp_retrieval_dsl_stats: for every row j of `of` [n_of, d], over the rows i of `over` [n_over, d]:  mx[j] = max_i theta (over_i .
+ *   of_j),  sum[j] = sum_i exp(theta (over_i . of_j) - mx[j]).  The split plan is that of xp_retrieval_ranks_streamed(nq = n_over,
+ *   ng = n_of, dsl = 1), and with accumulate == 0 the outputs are bit for bit the statistics that call forms internally for
+ *   q = over, g = of.  accumulate != 0: the incoming (mx, sum) -- an earlier call's result for other rows of `over` -- lead the fold
+ *   of this call's splits under (m, s) + (m', s') = (max, s e^(m - max) + s' e^(m' - max)): an `over` set that arrives in shards
+ *   folds in shard order.  mx is exact either way (a maximum of the same products); the bits of sum depend on (n_over, n_of) through
+ *   the plan and on the shard boundaries of an accumulated fold (each changes the order of the sum, not its terms).
+ * xp_retrieval_topk_dsl: xp_retrieval_topk on x_ij = s_ij * exp(theta s_ij - mx_.) / sum_. -- the one expression the rank counts use
+ *   -- with the statistics of the candidate's gallery row (stats_of == XP_DSL_OF_GALLERY: mx, sum [ng]; the t2v direction of
+ *   validate(), statistics from xp_retrieval_dsl_stats(over = q, of = g)) or of the query row (XP_DSL_OF_QUERIES: mx, sum [nq]; the
+ *   v2t direction, queries = videos, statistics from xp_retrieval_dsl_stats(over = g, of = q) over the WHOLE gallery).  Workspace:
+ *   xp_retrieval_topk_workspace_bytes.  The result is EXACT GIVEN THE STATISTICS: the bits of x_ij depend on row i, row j, d, theta
+ *   and the two statistics alone, the order is total (x descending, index ascending) -- a gallery fed shard by shard gives the
+ *   one-shot result bit for bit when each shard is fed its slice of a per-gallery (mx, sum), or every shard the same per-query
+ *   (mx, sum).  How close x is to the real-valued re-rank is the statistics' matter (sum: see above).
+ * Both return XP_ERR_ARG before any launch for whatever xp_retrieval_topk refuses, null statistics, a theta that is not finite,
+ * a stats_of that is neither constant or a workspace below its *_workspace_bytes. */
 #define XP_RETRIEVAL_TILE 128
 #define XP_RETRIEVAL_MAX_K 128
+#define XP_DSL_OF_GALLERY 1
+#define XP_DSL_OF_QUERIES 2
 int xp_retrieval_stream_plan(int64_t nq, int64_t ng, int32_t k, int32_t* stat_tiles_per_split, int32_t* topk_tiles_per_split);
 size_t xp_retrieval_ranks_streamed_workspace_bytes(int64_t nq, int64_t ng, int64_t d, int32_t dsl);
 int xp_retrieval_ranks_streamed(const float* q, const float* g, const int64_t* labels_q, const int64_t* labels_g, int64_t nq,
@@ -702,6 +723,12 @@ int xp_retrieval_ranks_streamed(const float* q, const float* g, const int64_t* l
 size_t xp_retrieval_topk_workspace_bytes(int64_t nq, int64_t ng, int64_t d, int32_t k);
 int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
                       int32_t accumulate, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+size_t xp_retrieval_dsl_stats_workspace_bytes(int64_t n_over, int64_t n_of, int64_t d);
+int xp_retrieval_dsl_stats(const float* over, const float* of, int64_t n_over, int64_t n_of, int64_t d, float theta,
+                           int32_t accumulate, float* mx, float* sum, void* workspace, size_t workspace_bytes, void* stream);
+int xp_retrieval_topk_dsl(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
+                          int32_t accumulate, float theta, int32_t stats_of, const float* mx, const float* sum, float* vals,
+                          int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------ Encoder layer
  * One CLIPEncoderLayer.forward / backward per call (modeling/CLIP_ViP.py:444-460: x + Attn(LN1(x)), then x + MLP(LN2(x));

@@ -1,6 +1,13 @@
-// Retrieval at gallery scale (xp_retrieval_ranks_streamed / xp_retrieval_topk; include/xpretrain_hip.h states the contract, the
-// numpy reference is tests/retrieval_stream_ref.py).  One fp32 score core, s_ij = sum_k q[i,k] g[j,k], and three consumers that
-// never write a score to global memory: column statistics of the dual-softmax re-rank, rank counts in both directions, top-k.
+// Retrieval at gallery scale (xp_retrieval_ranks_streamed / xp_retrieval_topk / xp_retrieval_dsl_stats / xp_retrieval_topk_dsl;
+// include/xpretrain_hip.h states the contract, the numpy references are tests/retrieval_stream_ref.py and retrieval_dsl_ref.py).
+// One fp32 score core, s_ij = sum_k q[i,k] g[j,k], and three consumers that never write a score to global memory: column
+// statistics of the dual-softmax re-rank, rank counts in both directions, top-k.
+//
+// DSL-weighted search connects them: the statistics are an entry of their own (launch_col_stats: the launches the rank call makes,
+// so the bits it forms internally; an earlier result may lead the fold), and topk_kernel's MODE turns the score into
+// x = dsl_x(s, theta, mx, sum) -- the function the counting kernels use -- with the statistics of the candidate's gallery row or of
+// the query row, at the one place where the accumulators go to the LDS score tile.  The list is exact GIVEN the statistics: x
+// depends on the two rows, d, theta and (mx, sum) alone, so shards fed the same statistics give the one-shot bits.
 //
 // Score core: a 128 x 128 tile of scores per 256-thread workgroup; both operand tiles are staged in LDS in 32-column chunks
 // (rows of 36 floats: 16-byte aligned rows, a stride of 36 banks), the next chunk's global loads are in flight while the current
@@ -231,13 +238,14 @@ XP_NO_PK_F32 __global__ __launch_bounds__(THREADS) void col_stats_kernel(const f
   }
 }
 
-// the query splits of column j, ascending
+// the query splits of column j, ascending; `prev_mx` / `prev_sum` (null, or an earlier call's result: they may BE col_mx / col_sum)
+// lead the fold as one more operand -- an `over` set that arrives in shards folds in shard order
 __global__ void col_stats_combine_kernel(const float* __restrict__ part_mx, const float* __restrict__ part_sum, int64_t ng, int splits,
-                                         float* __restrict__ col_mx, float* __restrict__ col_sum) {
+                                         const float* prev_mx, const float* prev_sum, float* col_mx, float* col_sum) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= ng) return;
-  float m = part_mx[j], s = part_sum[j];
-  for (int y = 1; y < splits; ++y) stat_merge(m, s, part_mx[(int64_t)y * ng + j], part_sum[(int64_t)y * ng + j]);
+  float m = prev_mx ? prev_mx[j] : part_mx[j], s = prev_mx ? prev_sum[j] : part_sum[j];
+  for (int y = prev_mx ? 0 : 1; y < splits; ++y) stat_merge(m, s, part_mx[(int64_t)y * ng + j], part_sum[(int64_t)y * ng + j]);
   col_mx[j] = m;
   col_sum[j] = s;
 }
@@ -364,13 +372,22 @@ struct TopList {
 // of a tile go to LDS, wave w then owns rows 32 w .. 32 w + 31: a row's 128 candidates are tested against the row's k-th best
 // (lane rr of the wave keeps it for row rr), and only for a row with a candidate that passes is the list fetched (split 0: the
 // output itself, so that `accumulate` is "do not clear it"; split y > 0: lists in the workspace), updated in registers and put back.
-template <bool VEC>
+//
+// MODE: what a candidate's value is.  PLAIN: the score s.  DSL_GALLERY / DSL_QUERIES: dsl_x(s, theta, mx, sum) with the statistics
+// of the candidate's gallery row (mx / sum [ng]: a lane's two columns, loaded per gallery tile) or of the query row (mx / sum [nq]:
+// the block's 128 queries, loaded once into LDS).  The mode acts where the accumulators go to the LDS score tile and nowhere else:
+// thresholds, the first tile's ranking, the lists and their merge see x.
+enum { PLAIN = 0, DSL_GALLERY = XP_DSL_OF_GALLERY, DSL_QUERIES = XP_DSL_OF_QUERIES };
+template <bool VEC, int MODE>
 XP_NO_PK_F32 __global__ __launch_bounds__(THREADS) void topk_kernel(const float* __restrict__ q, const float* __restrict__ g, int64_t nq,
                                                                     int64_t ng, int d, int k, int64_t index_base, int accumulate,
                                                                     int tiles_per_split, float* __restrict__ vals, int64_t* __restrict__ idx,
-                                                                    float* __restrict__ ws_vals, int64_t* __restrict__ ws_idx) {
+                                                                    float* __restrict__ ws_vals, int64_t* __restrict__ ws_idx, float theta,
+                                                                    const float* __restrict__ dsl_mx, const float* __restrict__ dsl_sum) {
   __shared__ __attribute__((aligned(16))) float lds[TILE * TILE];     // staging (STAGE_FLOATS), then the tile's scores
   static_assert(STAGE_FLOATS <= TILE * TILE, "the staging area lies inside the score tile");
+  __shared__ float q_mx[MODE == DSL_QUERIES ? TILE : 1], q_sum[MODE == DSL_QUERIES ? TILE : 1];
+  static_assert(sizeof(lds) + 2 * TILE * sizeof(float) <= 80 << 10, "two workgroups per CU (TOPK_TARGET_BLOCKS) on 160 KiB of LDS");
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w >> 1, wn = w & 1, r = lane & 31, h = lane >> 5;
   const int64_t i0 = (int64_t)blockIdx.x * TILE;
   const int split = blockIdx.y;
@@ -390,18 +407,39 @@ XP_NO_PK_F32 __global__ __launch_bounds__(THREADS) void topk_kernel(const float*
       thr_i = li[i * k + k - 1];
     }
   }
+  if (MODE == DSL_QUERIES && t < TILE) {          // rows beyond nq: the neutral pair (score_tile's barriers are in front of the reads)
+    q_mx[t] = i0 + t < nq ? dsl_mx[i0 + t] : 0.f;
+    q_sum[t] = i0 + t < nq ? dsl_sum[i0 + t] : 1.f;
+  }
   const int64_t gtiles = cdiv_dev(ng);
   const int64_t t0 = (int64_t)split * tiles_per_split, t1 = min(t0 + tiles_per_split, gtiles);
   f32x16 acc[2][2];
   for (int64_t gt = t0; gt < t1; ++gt) {
     const int64_t j0 = gt * TILE;
+    float cmx[2] = {0.f, 0.f}, csum[2] = {1.f, 1.f};        // DSL_GALLERY: this lane's two columns (the neutral pair beyond ng)
+    if (MODE == DSL_GALLERY) {
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int64_t j = j0 + wn * 64 + b * 32 + r;
+        if (j < ng) { cmx[b] = dsl_mx[j]; csum[b] = dsl_sum[j]; }
+      }
+    }
     score_tile<VEC>(q, g, i0, j0, nq, ng, d, lds, acc);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-      for (int b = 0; b < 2; ++b)
+      for (int e = 0; e < 16; ++e) {
+        const int row = wm * 64 + acc_row(a, e, h);
+        float rmx = 0.f, rsum = 1.f;
+        if (MODE == DSL_QUERIES) { rmx = q_mx[row]; rsum = q_sum[row]; }
 #pragma unroll
-        for (int e = 0; e < 16; ++e) lds[(wm * 64 + acc_row(a, e, h)) * TILE + wn * 64 + b * 32 + r] = acc[a][b][e];
+        for (int b = 0; b < 2; ++b) {
+          const float s = acc[a][b][e];
+          lds[row * TILE + wn * 64 + b * 32 + r] = MODE == PLAIN         ? s
+                                                   : MODE == DSL_GALLERY ? dsl_x(s, theta, cmx[b], csum[b])
+                                                                         : dsl_x(s, theta, rmx, rsum);
+        }
+      }
     __syncthreads();
     for (int rr = 0; rr < 32; ++rr) {
       const int row = w * 32 + rr;
@@ -558,6 +596,28 @@ int prepare_labels(const char* fn, const char* name, const int64_t* labels, int6
   return XP_OK;
 }
 
+// the column statistics of g's rows over q's rows under plan p -> col_mx / col_sum [ng]: the ONE launch sequence of
+// xp_retrieval_ranks_streamed and xp_retrieval_dsl_stats.  `part`: the per-split (mx, then sum) partials, 2 * part_bytes(p, ng) bytes,
+// touched when the plan splits the query tiles or `merge` is set.  merge: col_mx / col_sum hold an earlier result, which leads the
+// fold of this call's splits.
+size_t part_bytes(const RanksPlan& p, int64_t ng) { return pad256((size_t)p.stat_splits * ng * 4); }
+int launch_col_stats(const char* fn, const float* q, const float* g, int64_t nq, int64_t ng, int D, float theta, bool vec, const RanksPlan& p,
+                     float* part, bool merge, float* col_mx, float* col_sum, hipStream_t st) {
+  const bool direct = p.stat_splits == 1 && !merge;
+  float* const pm = direct ? col_mx : part;
+  float* const ps = direct ? col_sum : (float*)((char*)part + part_bytes(p, ng));
+  dim3 grid((unsigned)tiles(ng), (unsigned)p.stat_splits);
+  if (vec) col_stats_kernel<true><<<grid, THREADS, 0, st>>>(q, g, nq, ng, D, theta, (int)p.stat_tiles_per_split, pm, ps);
+  else col_stats_kernel<false><<<grid, THREADS, 0, st>>>(q, g, nq, ng, D, theta, (int)p.stat_tiles_per_split, pm, ps);
+  XP_CHECK_LAUNCH(fn);
+  if (!direct) {
+    col_stats_combine_kernel<<<(unsigned)cdiv(ng, 256), 256, 0, st>>>(pm, ps, ng, (int)p.stat_splits, merge ? col_mx : nullptr,
+                                                                      merge ? col_sum : nullptr, col_mx, col_sum);
+    XP_CHECK_LAUNCH(fn);
+  }
+  return XP_OK;
+}
+
 }  // namespace
 
 extern "C" int xp_retrieval_stream_plan(int64_t nq, int64_t ng, int32_t k, int32_t* stat_tiles_per_split, int32_t* topk_tiles_per_split) {
@@ -604,18 +664,8 @@ extern "C" int xp_retrieval_ranks_streamed(const float* q, const float* g, const
   float* const col_sum = dsl ? (float*)(ws + p.off_sum) : nullptr;
   const bool vec = d % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)g & 15) == 0;
   const int D = (int)d;
-  if (dsl) {
-    float* pm = p.stat_splits > 1 ? (float*)(ws + p.off_part) : col_mx;
-    float* ps = p.stat_splits > 1 ? (float*)(ws + p.off_part + pad256((size_t)p.stat_splits * ng * 4)) : col_sum;
-    dim3 grid((unsigned)tiles(ng), (unsigned)p.stat_splits);
-    if (vec) col_stats_kernel<true><<<grid, THREADS, 0, st>>>(q, g, nq, ng, D, theta, (int)p.stat_tiles_per_split, pm, ps);
-    else col_stats_kernel<false><<<grid, THREADS, 0, st>>>(q, g, nq, ng, D, theta, (int)p.stat_tiles_per_split, pm, ps);
-    XP_CHECK_LAUNCH(fn);
-    if (p.stat_splits > 1) {
-      col_stats_combine_kernel<<<(unsigned)cdiv(ng, 256), 256, 0, st>>>(pm, ps, ng, (int)p.stat_splits, col_mx, col_sum);
-      XP_CHECK_LAUNCH(fn);
-    }
-  }
+  if (dsl)
+    if (int rc = launch_col_stats(fn, q, g, nq, ng, D, theta, vec, p, (float*)(ws + p.off_part), false, col_mx, col_sum, st)) return rc;
   const int nbq = greater_q ? (int)cdiv(nq, 32) : 0, nbg = greater_g ? (int)cdiv(ng, 32) : 0;
   if (vec) label_scores_kernel<true><<<(unsigned)(nbq + nbg), 64, 0, st>>>(q, g, lq, lgl, nq, ng, D, nbq, dsl, theta, col_mx, col_sum, xlab_q, xlab_g);
   else label_scores_kernel<false><<<(unsigned)(nbq + nbg), 64, 0, st>>>(q, g, lq, lgl, nq, ng, D, nbq, dsl, theta, col_mx, col_sum, xlab_q, xlab_g);
@@ -652,14 +702,21 @@ extern "C" size_t xp_retrieval_topk_workspace_bytes(int64_t nq, int64_t ng, int6
   return topk_plan(nq, ng, k).bytes;
 }
 
-extern "C" int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
-                                 int32_t accumulate, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* fn = "xp_retrieval_topk";
+// both top-k entries: every refusal, the plan, the launches.  mode PLAIN: theta, mx and sum are not looked at
+static int topk_call(const char* fn, const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
+                     int32_t accumulate, int mode, float theta, const float* mx, const float* sum, float* vals, int64_t* idx, void* workspace,
+                     size_t workspace_bytes, void* stream) {
   XP_REQUIRE(q && g && vals && idx, "%s: q, g, vals or idx is null", fn);
   if (int rc = check_shape(fn, nq, ng, d)) return rc;
   XP_REQUIRE(k >= 1 && k <= XP_RETRIEVAL_MAX_K && k <= ng, "%s: k=%d is not in 1..min(%d, ng=%lld)", fn, k, XP_RETRIEVAL_MAX_K, (long long)ng);
   XP_REQUIRE(index_base >= 0 && index_base <= INT64_MAX - ng - 1, "%s: index_base=%lld out of range", fn, (long long)index_base);
   XP_REQUIRE(tiles(ng) <= MAX_FIXED_TILES * (int64_t)MAX_FIXED_TILES, "%s: ng=%lld beyond one launch", fn, (long long)ng);
+  if (mode != PLAIN) {
+    XP_REQUIRE(mode == DSL_GALLERY || mode == DSL_QUERIES, "%s: stats_of=%d is neither XP_DSL_OF_GALLERY (%d) nor XP_DSL_OF_QUERIES (%d)", fn,
+               mode, XP_DSL_OF_GALLERY, XP_DSL_OF_QUERIES);
+    XP_REQUIRE(mx && sum, "%s: mx or sum is null", fn);
+    XP_REQUIRE(std::isfinite(theta), "%s: theta is not finite", fn);
+  }
   const TopkPlan p = topk_plan(nq, ng, k);
   XP_REQUIRE(p.splits <= MAX_FIXED_TILES, "%s: ng=%lld beyond one launch", fn, (long long)ng);
   XP_REQUIRE(workspace && workspace_bytes >= p.bytes, "%s: workspace of %zu bytes, %zu needed", fn, workspace ? workspace_bytes : (size_t)0,
@@ -669,8 +726,11 @@ extern "C" int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int
   int64_t* const ws_idx = (int64_t*)((char*)workspace + p.off_idx);
   const bool vec = d % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)g & 15) == 0;
   dim3 grid((unsigned)tiles(nq), (unsigned)p.splits);
-  if (vec) topk_kernel<true><<<grid, THREADS, 0, st>>>(q, g, nq, ng, (int)d, k, index_base, accumulate, (int)p.tiles_per_split, vals, idx, ws_vals, ws_idx);
-  else topk_kernel<false><<<grid, THREADS, 0, st>>>(q, g, nq, ng, (int)d, k, index_base, accumulate, (int)p.tiles_per_split, vals, idx, ws_vals, ws_idx);
+#define XP_TOPK(V, M) topk_kernel<V, M><<<grid, THREADS, 0, st>>>(q, g, nq, ng, (int)d, k, index_base, accumulate, (int)p.tiles_per_split, vals, idx, ws_vals, ws_idx, theta, mx, sum)
+  if (mode == PLAIN) { if (vec) XP_TOPK(true, PLAIN); else XP_TOPK(false, PLAIN); }
+  else if (mode == DSL_GALLERY) { if (vec) XP_TOPK(true, DSL_GALLERY); else XP_TOPK(false, DSL_GALLERY); }
+  else { if (vec) XP_TOPK(true, DSL_QUERIES); else XP_TOPK(false, DSL_QUERIES); }
+#undef XP_TOPK
   XP_CHECK_LAUNCH(fn);
   if (p.splits > 1) {
     topk_merge_kernel<<<(unsigned)nq, 64, 0, st>>>(nq, k, (int)p.splits, vals, idx, ws_vals, ws_idx);
@@ -678,3 +738,37 @@ extern "C" int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int
   }
   return XP_OK;
 }
+
+extern "C" int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
+                                 int32_t accumulate, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+  return topk_call("xp_retrieval_topk", q, g, nq, ng, d, k, index_base, accumulate, PLAIN, 0.f, nullptr, nullptr, vals, idx, workspace,
+                   workspace_bytes, stream);
+}
+
+extern "C" int xp_retrieval_topk_dsl(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
+                                     int32_t accumulate, float theta, int32_t stats_of, const float* mx, const float* sum, float* vals,
+                                     int64_t* idx, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "xp_retrieval_topk_dsl";
+  XP_REQUIRE(stats_of == XP_DSL_OF_GALLERY || stats_of == XP_DSL_OF_QUERIES, "%s: stats_of=%d is neither XP_DSL_OF_GALLERY (%d) nor "
+             "XP_DSL_OF_QUERIES (%d)", fn, stats_of, XP_DSL_OF_GALLERY, XP_DSL_OF_QUERIES);
+  return topk_call(fn, q, g, nq, ng, d, k, index_base, accumulate, stats_of, theta, mx, sum, vals, idx, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t xp_retrieval_dsl_stats_workspace_bytes(int64_t n_over, int64_t n_of, int64_t d) {
+  if (check_shape("xp_retrieval_dsl_stats_workspace_bytes", n_over, n_of, d)) return 0;
+  return std::max<size_t>(256, 2 * part_bytes(ranks_plan(n_over, n_of, 1), n_of));
+}
+
+extern "C" int xp_retrieval_dsl_stats(const float* over, const float* of, int64_t n_over, int64_t n_of, int64_t d, float theta,
+                                      int32_t accumulate, float* mx, float* sum, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* fn = "xp_retrieval_dsl_stats";
+  XP_REQUIRE(over && of && mx && sum, "%s: over, of, mx or sum is null", fn);
+  if (int rc = check_shape(fn, n_over, n_of, d)) return rc;
+  XP_REQUIRE(std::isfinite(theta), "%s: theta is not finite", fn);
+  const RanksPlan p = ranks_plan(n_over, n_of, 1);
+  const size_t need = std::max<size_t>(256, 2 * part_bytes(p, n_of));
+  XP_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", fn, workspace ? workspace_bytes : (size_t)0, need);
+  const bool vec = d % 4 == 0 && ((uintptr_t)over & 15) == 0 && ((uintptr_t)of & 15) == 0;
+  return launch_col_stats(fn, over, of, n_over, n_of, (int)d, theta, vec, p, (float*)workspace, accumulate != 0, mx, sum, (hipStream_t)stream);
+}
+

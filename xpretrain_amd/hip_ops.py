@@ -997,13 +997,57 @@ def retrieval_ranks_streamed(q: torch.Tensor, g: torch.Tensor, labels_q=None, la
     return gq, eq, gg, eg
 
 
-def retrieval_topk(q: torch.Tensor, g: torch.Tensor, k: int, index_base: int = 0, out=None):
+DSL_OF = {"gallery": L.XP_DSL_OF_GALLERY, "queries": L.XP_DSL_OF_QUERIES}
+
+
+def _stat_pair(pair, name, n, what, device):
+    """``pair`` = (mx, sum): two contiguous fp32 GPU vectors of length n"""
+    if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+        raise TypeError(f"{name}: expected the pair (mx, sum) of fp32 GPU vectors of length {n} ({what}), got {type(pair).__name__}")
+    for t, part in zip(pair, ("mx", "sum")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+            raise TypeError(f"{name}[{part}]: expected a contiguous fp32 GPU vector of length {n} ({what}), got "
+                            f"{f'{t.dtype} on {t.device}' if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if t.dim() != 1 or t.numel() != n or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{name}[{part}]: expected a contiguous fp32 vector of length {n} ({what}) on {device}, got "
+                             f"{tuple(t.shape)} on {t.device}")
+    return pair
+
+
+def retrieval_dsl_stats(over: torch.Tensor, of: torch.Tensor, theta: float = 100.0, out=None):
+    """(mx, sum) [rows of ``of``]: mx[j] = max_i theta over_i . of_j, sum[j] = sum_i exp(theta over_i . of_j - mx[j]) -- the dual
+    softmax's statistics xp_retrieval_ranks_streamed(q=over, g=of, dsl=1) forms internally, bit for bit.  ``out`` = (mx, sum) of an
+    earlier call over other rows of ``over``: they lead the fold and the pair is updated in place (include/xpretrain_hip.h)"""
+    _feature_rows(over, "over")
+    _feature_rows(of, "of", over.shape[1])
+    n_over, n_of, d = over.shape[0], of.shape[0], over.shape[1]
+    need = L.lib().xp_retrieval_dsl_stats_workspace_bytes(n_over, n_of, d)
+    if need == 0:
+        raise ValueError(f"xp_retrieval_dsl_stats_workspace_bytes: {L.lib().xp_last_error().decode()}")
+    if out is None:
+        mx, sm = (torch.empty(n_of, dtype=torch.float32, device=of.device) for _ in range(2))
+    else:
+        mx, sm = _stat_pair(out, "out", n_of, "one entry per row of `of`", of.device)
+    ws = workspace(need, of.device, "retrieval_dsl_stats")
+    L.check(L.lib().xp_retrieval_dsl_stats(_p(over), _p(of), n_over, n_of, d, float(theta), int(out is not None), _p(mx), _p(sm), _p(ws),
+                                           ws.numel(), _stream()), "xp_retrieval_dsl_stats")
+    return mx, sm
+
+
+def retrieval_topk(q: torch.Tensor, g: torch.Tensor, k: int, index_base: int = 0, out=None, *, dsl=None, dsl_of="gallery", theta=100.0):
     """(vals [nq, k] fp32, idx [nq, k] int64): each query's k best gallery rows, score descending, ties to the lowest index;
-    ``out`` = (vals, idx) of an earlier call: its entries compete as candidates and the pair is updated in place"""
+    ``out`` = (vals, idx) of an earlier call: its entries compete as candidates and the pair is updated in place.
+    ``dsl`` = (mx, sum): rank by s * exp(theta s - mx) / sum with the statistics of the gallery row (``dsl_of="gallery"``, length ng)
+    or of the query row (``dsl_of="queries"``, length nq) -- xp_retrieval_topk_dsl; None: the plain call"""
     _feature_rows(q, "q")
     _feature_rows(g, "g", q.shape[1])
     nq, ng, d = q.shape[0], g.shape[0], q.shape[1]
     k = int(k)
+    if dsl is not None:
+        if dsl_of not in DSL_OF:
+            raise ValueError(f"dsl_of: expected 'gallery' or 'queries', got {dsl_of!r}")
+        n, what = (ng, "dsl_of='gallery': one entry per gallery row") if dsl_of == "gallery" else (nq, "dsl_of='queries': one entry per query")
+        mx, sm = _stat_pair(dsl, "dsl", n, what, q.device)
     need = L.lib().xp_retrieval_topk_workspace_bytes(nq, ng, d, k)
     if need == 0:
         raise ValueError(f"xp_retrieval_topk_workspace_bytes: {L.lib().xp_last_error().decode()}")
@@ -1017,6 +1061,11 @@ def retrieval_topk(q: torch.Tensor, g: torch.Tensor, k: int, index_base: int = 0
         if tuple(vals.shape) != (nq, k) or tuple(idx.shape) != (nq, k) or not (vals.is_contiguous() and idx.is_contiguous()):
             raise ValueError(f"out: expected contiguous ([{nq}, {k}] fp32, [{nq}, {k}] int64), got {tuple(vals.shape)}, {tuple(idx.shape)}")
     ws = workspace(need, q.device, "retrieval_topk")
-    L.check(L.lib().xp_retrieval_topk(_p(q), _p(g), nq, ng, d, k, int(index_base), int(out is not None), _p(vals), _p(idx), _p(ws),
-                                      ws.numel(), _stream()), "xp_retrieval_topk")
+    if dsl is None:
+        L.check(L.lib().xp_retrieval_topk(_p(q), _p(g), nq, ng, d, k, int(index_base), int(out is not None), _p(vals), _p(idx), _p(ws),
+                                          ws.numel(), _stream()), "xp_retrieval_topk")
+    else:
+        L.check(L.lib().xp_retrieval_topk_dsl(_p(q), _p(g), nq, ng, d, k, int(index_base), int(out is not None), float(theta),
+                                              DSL_OF[dsl_of], _p(mx), _p(sm), _p(vals), _p(idx), _p(ws), ws.numel(), _stream()),
+                "xp_retrieval_topk_dsl")
     return vals, idx

@@ -122,19 +122,58 @@ def retrieval_metrics_streamed(text_feats, vis_feats, labels=None, v2t_labels=No
     return out
 
 
-def topk(query_feats, gallery_feats, k, index_base=0, out=None):
+def dsl_stats(over_feats, of_feats, theta=100.0, out=None):
+    """(mx, sum), fp32 GPU vectors with one entry per row of ``of_feats``: the dual softmax's statistics over the rows of
+    ``over_feats`` -- ``mx[j] = max_i theta s_ij``, ``sum[j] = sum_i exp(theta s_ij - mx[j])`` with ``s = cal_cossim(over_feats,
+    of_feats)``, i.e. ``np_softmax(s * theta, axis=0) = exp(theta s - mx) / sum``.  ``out`` = (mx, sum) of an earlier call over other
+    rows of ``over_feats``: they lead the fold and the pair is updated in place, so an ``over`` set can arrive in shards."""
+    return H.retrieval_dsl_stats(_feats(over_feats, "over_feats"), _feats(of_feats, "of_feats"), theta, out)
+
+
+def topk(query_feats, gallery_feats, k, index_base=0, out=None, dsl=None, dsl_of="gallery", theta=100.0):
     """(values [n_query, k] fp32, indices [n_query, k] int64): each query's k best gallery rows by dot product, best first, ties to
     the lowest index; ``index_base`` is added to every index.  ``out`` = (values, indices) of an earlier call: its entries compete
-    with this gallery's and the pair is updated in place -- shard by shard gives exactly the one-shot result."""
-    return H.retrieval_topk(_feats(query_feats, "query_feats"), _feats(gallery_feats, "gallery_feats"), k, index_base, out)
+    with this gallery's and the pair is updated in place -- shard by shard gives exactly the one-shot result.
+
+    ``dsl`` = (mx, sum) from ``dsl_stats``: rank by the DSL setting of ``validate`` instead (run_video_retrieval.py:157-171), exact
+    given those statistics.
+    ``dsl_of="gallery"`` (t2v, queries = texts; statistics of length n_gallery from ``dsl_stats(query_feats, gallery_feats)``): the
+    rows of ``sim * np_softmax(sim*theta, axis=0)`` with ``sim = cal_cossim(query_feats, gallery_feats)``.
+    ``dsl_of="queries"`` (v2t, queries = videos; statistics of length n_query from ``dsl_stats(gallery_feats, query_feats)`` over
+    the WHOLE gallery): the rows of the transpose of that expression with ``sim = cal_cossim(gallery_feats, query_feats)``."""
+    return H.retrieval_topk(_feats(query_feats, "query_feats"), _feats(gallery_feats, "gallery_feats"), k, index_base, out, dsl=dsl,
+                            dsl_of=dsl_of, theta=theta)
 
 
-def search(query_feats, shards, k):
+def search(query_feats, shards, k, dsl_of=None, theta=100.0):
     """``topk`` over a gallery that arrives as an iterable of [rows, d] shards; indices count rows across the shards.  Every shard
-    needs at least k rows (a shard's own best k are what it can contribute)."""
+    needs at least k rows (a shard's own best k are what it can contribute).
+
+    ``dsl_of="gallery"``: the rows of ``sim * np_softmax(sim*theta, axis=0)`` with ``sim = cal_cossim(query_feats, gallery)`` (the
+    reference's t2v).  One walk: a gallery row's statistics need the queries only, so each shard gets its own from ``dsl_stats``.
+    ``dsl_of="queries"``: the rows of the transpose of that expression with ``sim = cal_cossim(gallery, query_feats)`` (the
+    reference's v2t).  Two walks: a query's statistics run over the whole gallery and must be complete before any candidate can be
+    ranked, so ``shards`` must be re-iterable -- a sequence, or a zero-argument callable that returns a fresh iterator."""
+    if dsl_of not in (None, "gallery", "queries"):
+        raise ValueError(f"search: dsl_of must be None, 'gallery' or 'queries', got {dsl_of!r}")
+    walk = shards if callable(shards) else (lambda: shards)
+    if dsl_of == "queries" and not callable(shards) and iter(shards) is shards:
+        raise TypeError("search: dsl_of='queries' walks the gallery twice (each query's statistics over the whole gallery, then the "
+                        "ranking) and a one-shot iterator cannot be rewound: pass a sequence, or a zero-argument callable that returns "
+                        "a fresh iterator")
+    stats = None
+    if dsl_of == "queries":
+        for shard in walk():
+            stats = dsl_stats(shard, query_feats, theta, out=stats)
+        if stats is None:
+            raise ValueError("search: no gallery shards")
     out, base = None, 0
-    for shard in shards:
-        out = topk(query_feats, shard, k, index_base=base, out=out)
+    for shard in walk():
+        if dsl_of is None:
+            out = topk(query_feats, shard, k, index_base=base, out=out)
+        else:
+            st = stats if dsl_of == "queries" else dsl_stats(query_feats, shard, theta)
+            out = topk(query_feats, shard, k, index_base=base, out=out, dsl=st, dsl_of=dsl_of, theta=theta)
         base += shard.shape[0]
     if out is None:
         raise ValueError("search: no gallery shards")
