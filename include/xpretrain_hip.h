@@ -567,28 +567,11 @@ int xp_optim_step_guarded(int32_t kind, const XpAdamTensor* table, const int32_t
                           int32_t n_norm_partials, float max_norm, float* grad_norm_out,
                           const XpStepVerdict* verdict, void* stream);
 
-/* ------------------------------------------------------------------------------------------- Loss
- * NCELearnableTempLoss.forward (optimization/loss.py:134-141) on gathered unit-norm features
- * vis[n,d], txt[n,d] (fp32) and the LOG scale parameter: loss = CE(s V T^T, diag) + CE(s T V^T, diag).
- * One launch computes the loss AND d loss / d{vis, txt, log_scale} (the backward just scales them).
- */
-size_t xp_nce_loss_workspace_bytes(int64_t n, int64_t d);
-int xp_nce_loss(const float* vis, const float* txt, const float* log_scale, float* loss,
-                float* d_vis, float* d_txt, float* d_log_scale, int64_t n, int64_t d,
-                void* workspace, size_t workspace_bytes, void* stream);
-
-/* NCELearnableTempLoss_vsc_fc.forward (optimization/loss.py:296-324, the pre-training default,
- * pretrain_vip_base_16.json:75) on gathered unit-norm features vis/txt/img/cap [n,d] (fp32): six cross-entropies
- * over video-subtitle, video-caption (off-diagonal negatives of both re-packed behind either positive, :307-314)
- * and frame-caption logits.  One call computes the loss and d loss / d{vis, txt, img, cap, log_scale}. */
-size_t xp_vsc_fc_loss_workspace_bytes(int64_t n, int64_t d);
-int xp_vsc_fc_loss(const float* vis, const float* txt, const float* img, const float* cap, const float* log_scale,
-                   float* loss, float* d_vis, float* d_txt, float* d_img, float* d_cap, float* d_log_scale,
-                   int64_t n, int64_t d, void* workspace, size_t workspace_bytes, void* stream);
-
-/* The whole family of learnable-temperature contrastive losses of optimization/loss.py behind one entry: loss and every
- * gradient in one call, fp32, fixed reduction order (bit-reproducible), all launches on `stream`.
- * vis, txt [n,d]; img, cap [m,d]: gathered unit-norm features.  With s = exp(*log_scale), S1 = s V T^T, S2 = s V C^T,
+/* ------------------------------------------------------------------------------------------- Loss (csrc/loss_family.hip)
+ * The whole family of learnable-temperature contrastive losses of optimization/loss.py behind one entry: loss and every
+ * gradient in one call (the backward just scales them), fp32, fixed reduction order (bit-reproducible), all launches on `stream`.
+ * vis, txt [n,d]; img, cap [m,d]: gathered unit-norm features; log_scale: the LOG scale parameter (a device scalar).
+ * With s = exp(*log_scale), S1 = s V T^T, S2 = s V C^T,
  * S3 = s I C^T, "rows(S)" = mean over i of (lse_j S_ij - S_ii) and "cols(S)" the same over columns:
  *   XP_LOSS_NCE            rows(S1) + cols(S1)                                         NCELearnableTempLoss          :134-141
  *   XP_LOSS_VS_VC          rows + cols of S1 and of S2                                 NCELearnableTempLoss_vs_vc    :212-225
@@ -607,10 +590,11 @@ int xp_vsc_fc_loss(const float* vis, const float* txt, const float* img, const f
  * Every gradient follows the same way: d loss / d S* from the softmaxes, then two GEMMs per logit matrix and
  * d log_scale = sum over the matrices of sum(G o S).
  * A kind that does not read an operand takes NULL for it and for its gradient (they are ignored): NCE and DSL read neither
- * img nor cap; VS_VC and VSC do not read img.  Only VIDIMG and VIDIMG_DIVIDE accept m != n.  n, m (n + m for VIDIMG) <= 16384.
- * xp_nce_loss and xp_vsc_fc_loss are this entry with their kind: same kernels, same bits. */
+ * img nor cap; VS_VC and VSC do not read img: xp_contrastive_loss_operands says which of the two a kind reads (1 / 0; an unknown
+ * kind is refused).  Only VIDIMG and VIDIMG_DIVIDE accept m != n.  n, m (n + m for VIDIMG) <= 16384. */
 enum XpLossKind { XP_LOSS_NCE, XP_LOSS_VSC_FC, XP_LOSS_DSL, XP_LOSS_VS_VC, XP_LOSS_VS_VC_FC,
                   XP_LOSS_VSC, XP_LOSS_VIDIMG, XP_LOSS_VIDIMG_DIVIDE };
+int xp_contrastive_loss_operands(int32_t kind, int32_t* reads_img, int32_t* reads_cap);
 size_t xp_contrastive_loss_workspace_bytes(int32_t kind, int64_t n, int64_t m, int64_t d);
 int xp_contrastive_loss(int32_t kind, const float* vis, const float* txt, const float* img, const float* cap,
                         const float* log_scale, float* loss, float* d_vis, float* d_txt, float* d_img, float* d_cap,

@@ -101,7 +101,7 @@ def dsl64(s, theta):
 
 
 def dsl_restated_f32(q, g, theta):
-    """dsl_rerank_kernel's formula (csrc/loss.hip) in numpy float32 on the float32 product of the same features:
+    """dsl_rerank_kernel's formula (csrc/retrieval.hip) in numpy float32 on the float32 product of the same features:
     mx = max_i s theta; sum = sum_i exp(s theta - mx); x = s * (exp(s theta - mx) / sum)"""
     s = (q @ g.T).astype(np.float32)
     th = np.float32(theta)

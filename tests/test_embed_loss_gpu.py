@@ -131,7 +131,7 @@ def test_nce_loss_against_reference_fixtures(golden):
     for c in golden("loss.pt"):
         v, t = c["feats"][0].cuda(), c["feats"][1].cuda()
         ls = torch.tensor(c["log_scale"], device="cuda")
-        loss, dv, dt, dls = H.nce_loss(v, t, ls)
+        loss, dv, dt, _, _, dls = H.contrastive_loss(H.L.XP_LOSS_NCE, v, t, log_scale=ls)
         tag = f"nce n={c['n']} ls={c['log_scale']:.2f}"
         assert abs(loss.item() - c["nce"].item()) <= 1e-3 * max(1.0, abs(c["nce"].item())), tag
         assert report(tag + " dV", dv, c["nce_grads"][0], 1e-3) <= 1e-3
@@ -146,7 +146,7 @@ def test_nce_loss_large_n_fp64():
     v = torch.nn.functional.normalize(torch.randn(n, d, device="cuda"), dim=-1)
     t = torch.nn.functional.normalize(torch.randn(n, d, device="cuda"), dim=-1)
     ls = torch.tensor(4.6, device="cuda")
-    loss, dv, dt, dls = H.nce_loss(v, t, ls)
+    loss, dv, dt, _, _, dls = H.contrastive_loss(H.L.XP_LOSS_NCE, v, t, log_scale=ls)
     vd, td, lsd = v.double().requires_grad_(), t.double().requires_grad_(), ls.double().requires_grad_()
     A = vd @ td.t() * lsd.exp()
     lbl = torch.arange(n, device="cuda")
@@ -186,7 +186,7 @@ def test_vsc_fc_loss_large_n_fp64():
     ls = torch.tensor(3.7, dtype=torch.float64, requires_grad=True)
     ref = O.nce_vsc_fc_loss(*feats, ls)
     rg = torch.autograd.grad(ref, feats + [ls])
-    out = H.vsc_fc_loss(*[f.detach().float().cuda() for f in feats], ls.detach().float().cuda())
+    out = H.contrastive_loss(H.L.XP_LOSS_VSC_FC, *[f.detach().float().cuda() for f in feats], log_scale=ls.detach().float().cuda())
     assert abs(out[0].item() - ref.item()) <= 1e-4 * abs(ref.item())
     for name, g, r in zip(("dV", "dT", "dI", "dC"), out[1:5], rg[:4]):
         assert report(f"vsc_fc200 {name}", g, r, 1e-4) <= 1e-4

@@ -31,12 +31,13 @@ def test_binding_declares_the_family_entry_and_kinds():
     from xpretrain_amd import _lib as L
     assert "xp_contrastive_loss" in L.SIGNATURES and "xp_contrastive_loss_workspace_bytes" in L.SIGNATURES
     assert len(L.SIGNATURES["xp_contrastive_loss"][1]) == 18 and len(L.SIGNATURES["xp_contrastive_loss_workspace_bytes"][1]) == 4
+    assert len(L.SIGNATURES["xp_contrastive_loss_operands"][1]) == 3
+    assert not [name for name in L.SIGNATURES if "loss" in name and not name.startswith(("xp_contrastive_loss", "xp_pair_loss"))]
     ids = {k: getattr(L, "XP_LOSS_" + k.upper()) for k in R.KINDS}
     assert ids == R.KIND_IDS                                      # the header's enum order
     from xpretrain_amd import optimization as opt
     for k, (name, _, _) in R.KINDS.items():
-        if k not in ("nce", "vsc_fc"):
-            assert getattr(opt, name).kind == ids[k]
+        assert getattr(opt, name).kind == ids[k]                  # every class of the family is its kind and nothing else
 
 
 def test_vsc_asserts_equal_text_and_caption_rows():

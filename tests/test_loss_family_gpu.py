@@ -1,6 +1,6 @@
 """GPU: the learnable-temperature loss family behind xp_contrastive_loss -- the six kinds beside NCELearnableTempLoss and
 NCELearnableTempLoss_vsc_fc -- against the reference's fixtures (tests/golden/loss_family.pt), against fp64 autograd of
-tests/loss_family_ref.py, bitwise against the two older entry points, and through VidCLIP's backward."""
+tests/loss_family_ref.py, the library's operand table against the helper's, and through VidCLIP's backward."""
 import functools
 
 import pytest
@@ -82,22 +82,27 @@ def test_family_against_fp64(kind, shape):
     _check_fp64(f"{kind} fp64 n={shape[0]} m={shape[1]} d={shape[2]}", out, ref, shape[3])
 
 
-@pytest.mark.parametrize("n,d", [(8, 512), (70, 32), (200, 96)])
-def test_old_entry_points_equal_the_family_bitwise(n, d):
-    """3. xp_nce_loss / xp_vsc_fc_loss are the family path with their kind: identical bits on every output"""
-    from xpretrain_amd import _lib as L
+def test_operands_query_is_the_kind_table():
+    """3. which operands a kind reads is the library's to say (xp_contrastive_loss_operands): it agrees with the helper's table for
+    every kind, refuses an unknown kind, and the wrapper hands out gradients for exactly those operands.  (The bits of every
+    kind, nce and vsc_fc through their former entries included, are pinned by tests/test_loss_bits_gpu.py.)"""
+    import ctypes as C
     from xpretrain_amd import hip_ops as H
-    feats = [f.float().cuda() for f in R.unit_feats(n, n, d, seed=n + d)]
-    ls = torch.tensor(4.6, device="cuda")
-    old = H.nce_loss(feats[0], feats[1], ls)
-    new = H.contrastive_loss(L.XP_LOSS_NCE, feats[0], feats[1], log_scale=ls)
-    assert new[3] is None and new[4] is None
-    for a, b in zip(old, (new[0], new[1], new[2], new[5])):
-        assert torch.equal(a, b)
-    old = H.vsc_fc_loss(*feats, ls)
-    new = H.contrastive_loss(L.XP_LOSS_VSC_FC, *feats, log_scale=ls)
-    for a, b in zip(old, new):
-        assert torch.equal(a, b)
+    query = H.L.lib().xp_contrastive_loss_operands
+    feats = [f.float().cuda() for f in R.unit_feats(6, 6, 32, seed=5)]
+    for kind in list(R.KINDS) + [len(R.KINDS), -1, 1000]:
+        img, cap = C.c_int32(-1), C.c_int32(-1)
+        rc = query(R.KIND_IDS.get(kind, kind), C.byref(img), C.byref(cap))
+        if kind in R.KINDS:
+            use = R.KINDS[kind][1:]
+            assert rc == 0 and (img.value, cap.value) == use and H.loss_operands(R.KIND_IDS[kind]) == use, kind
+            out = H.contrastive_loss(R.KIND_IDS[kind], *feats, log_scale=torch.tensor(1.0, device="cuda"))
+            assert [g is not None for g in out] == [True, True, True, *use, True], kind
+        else:
+            assert rc != 0 and (img.value, cap.value) == (-1, -1) and H.L.lib().xp_last_error().startswith(b"xp_contrastive_loss: unknown kind")
+            with pytest.raises(RuntimeError, match=r"xp_contrastive_loss: unknown kind"):
+                H.loss_operands(kind)
+    assert query(0, None, None) != 0
 
 
 @pytest.mark.parametrize("kind", NEW)

@@ -163,8 +163,8 @@ def test_partial_row_counts_and_workspaces():
     # attention: forward partials / backward (delta + proxy partials) share one workspace
     assert lib.xp_attn_workspace_bytes(L.ATTN_PROXY, 8, 12, 4, 12, 196) >= 8 * 12 * 2356 * 4
     assert lib.xp_attn_workspace_bytes(L.ATTN_CAUSAL, 8, 8, 0, 1, 32) == 8 * 8 * 32 * 4
-    assert lib.xp_nce_loss_workspace_bytes(64, 512) >= 2 * 64 * 64 * 4
-    assert lib.xp_vsc_fc_loss_workspace_bytes(64, 512) >= 6 * 64 * 64 * 4
+    assert lib.xp_contrastive_loss_workspace_bytes(L.XP_LOSS_NCE, 64, 64, 512) >= 2 * 64 * 64 * 4
+    assert lib.xp_contrastive_loss_workspace_bytes(L.XP_LOSS_VSC_FC, 64, 64, 512) >= 6 * 64 * 64 * 4
 
 
 def _dims(rows, D, Dff, B, S, heads, size, dtype=L.XP_BF16):

@@ -1,4 +1,4 @@
-"""GPU: the three retrieval-evaluation kernels of csrc/loss.hip, called through the C ABI with every output in a guard buffer, and
+"""GPU: the three retrieval-evaluation kernels of csrc/small_gemm.hip and csrc/retrieval.hip, called through the C ABI with every output in a guard buffer, and
 the functions of xpretrain_amd.utils.metrics built on them.
 
 Covered:

@@ -20,7 +20,7 @@ by reading every kernel's use of its workspace (before this file first ran on a 
     order by a second launch; no counter, no atomics.
   * xp_reduce_rows_batch / xp_colsum (reduce.hip), xp_layernorm_bwd* (layernorm.hip), xp_vip_embed_bwd (embed.hip): partial rows
     written by level 1, read by level 2; segments of <= 64 rows skip level 1 and do not touch the workspace.  No such word.
-  * loss.hip: logits, statistics, G matrices and part[] are each written by one launch and read by the following ones.
+  * loss_family.hip and the pair losses' file: logits, statistics, G matrices and part[] are each written by one launch and read by the following ones.
   * layer.hip: a bump allocator over the caller's workspace that checks every take against ``workspace_bytes``; the regions are
     the ones above plus GEMM outputs and split-K slabs (every slab element is written by its k-slice).
 Nothing relies on previous contents."""
@@ -199,10 +199,16 @@ def test_contrastive_loss(kind, shape):
 
 @pytest.mark.parametrize("n,d", [(9, 30), (200, 96)])
 def test_nce_and_vsc_fc_entry_points(n, d):
-    from xpretrain_amd import hip_ops as H
-    feats = [f.float().cuda() for f in R.unit_feats(n, n, d, seed=n + d)]
-    ls = torch.tensor(4.6, device="cuda")
-    twice(lambda: (H.nce_loss(feats[0], feats[1], ls), H.vsc_fc_loss(*feats, ls)), tags=["loss"])
+    """the two losses that once had entries of their own, through their modules and autograd (the benchmark's route to the family
+    entry): the loss and every gradient"""
+    from xpretrain_amd.optimization import NCELearnableTempLoss, NCELearnableTempLoss_vsc_fc
+    feats = [f.float().cuda().requires_grad_() for f in R.unit_feats(n, n, d, seed=n + d)]
+    ls = torch.tensor(4.6, device="cuda", requires_grad=True)
+
+    def run(fn, ops):
+        loss = fn(*ops, ls)
+        return loss.detach(), torch.autograd.grad(loss, ops + [ls])
+    twice(lambda: (run(NCELearnableTempLoss(), feats[:2]), run(NCELearnableTempLoss_vsc_fc(), feats)), tags=["loss"])
 
 
 # ------------------------------------------------------------------------------------------------ dense attention

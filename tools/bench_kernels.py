@@ -1,8 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmarks of the individual HIP kernels at BASELINE cfg #2 shapes (B=8, T=12, 224^2, ViT-B/16).
 Run on the GPU box:  python tools/bench_kernels.py [gemm|gemmfwd|ln|attn|all]  -> prints one line per kernel.
-`python tools/bench_kernels.py loss [n] [d]`: each kind of xp_contrastive_loss (and the two older entry points) back to back,
-loss + all gradients per call, at n = m pairs of width d (default 64 x 512: 8 GPUs x 8 pairs).
+`python tools/bench_kernels.py loss [n] [d]`: each kind of xp_contrastive_loss back to back, loss + all gradients per call, at n = m pairs of width d (default 64 x 512: 8 GPUs x 8 pairs).
 `python tools/bench_kernels.py act [rounds]`: the two GEMMs that carry the MLP activation (fc1 forward with both outputs, dpre with
 fused column sums), quick_gelu (epilogue kinds 3 / 5) against erf GELU (kinds 8 / 9), interleaved.
 `python tools/bench_kernels.py probs`: xp_attn_probs (the attention weights of one layer, output_attentions) at cfg #2, bf16 and fp32
@@ -146,8 +145,7 @@ def bench_loss(n=64, d=512):
     feats = [torch.nn.functional.normalize(torch.randn(n, d, device="cuda"), dim=-1) for _ in range(4)]
     ls = torch.tensor(4.6, device="cuda")
     kinds = ("NCE", "VSC_FC", "DSL", "VS_VC", "VS_VC_FC", "VSC", "VIDIMG", "VIDIMG_DIVIDE")
-    runs = [("xp_nce_loss", lambda: H.nce_loss(feats[0], feats[1], ls)), ("xp_vsc_fc_loss", lambda: H.vsc_fc_loss(*feats, ls))]
-    runs += [(f"xp_contrastive_loss {k}", lambda k=k: H.contrastive_loss(getattr(L, "XP_LOSS_" + k), *feats, log_scale=ls)) for k in kinds]
+    runs = [(f"xp_contrastive_loss {k}", lambda k=k: H.contrastive_loss(getattr(L, "XP_LOSS_" + k), *feats, log_scale=ls)) for k in kinds]
     for name, fn in runs:
         print(f"loss n={n} d={d} {name:36s} {timeit(fn):8.1f} us per call (launches back to back, host call included)")
 

@@ -41,6 +41,13 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // in[nrows][width], for every y < ceil(nrows / nsum), in that file's fixed order (tree A).  The caller checks the launch.
 void xp_launch_rows_reduce(const float* in, float* out, int nrows, int nsum, int width, int accumulate, hipStream_t st);
 
+// small_gemm.hip: C[i][j] (+)= alpha * sum_k X[i * sxi + k * sxk] Y[k * syk + j * syj] for i < I, j < J over K terms, fp32, with
+// alpha = exp(*log_scale), or 1 where log_scale is null; xp_launch_logits: A[n][n] = alpha * vis txt^T of two [n,d] operands, by the
+// kernel that suits n and d.  The caller checks the launch.
+void xp_launch_small_gemm(const float* X, int64_t sxi, int64_t sxk, const float* Y, int64_t syk, int64_t syj, float* C, int64_t ldc,
+                          int I, int J, int K, const float* log_scale, int accumulate, hipStream_t st);
+void xp_launch_logits(const float* vis, const float* txt, float* A, int64_t n, int64_t d, const float* log_scale, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------ scalars
 template <typename T> struct DT;
 template <> struct DT<bf16_t> { static constexpr int id = XP_BF16; };

@@ -1259,12 +1259,7 @@ class L2NormFn(torch.autograd.Function):
         return H.l2norm_bwd(dy.contiguous().float(), y, inv, rows, D, ctx.dtype)
 
 
-def _sim(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """a . b^T in fp32 through xp_sim_matrix (csrc/loss.hip) -- the package launches no vendor GEMM"""
-    a, b = a.contiguous().float(), b.contiguous().float()
-    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-    L.check(L.lib().xp_sim_matrix(H._p(a), H._p(b), H._p(out), a.shape[0], b.shape[0], a.shape[1], H._stream()), "xp_sim_matrix")
-    return out
+_sim = H.sim_matrix      # a . b^T in fp32 through xp_sim_matrix (csrc/small_gemm.hip) -- the package launches no vendor GEMM
 
 
 class SimLogitsFn(torch.autograd.Function):
@@ -1290,39 +1285,24 @@ class SimLogitsFn(torch.autograd.Function):
         return dt, di, dls
 
 
-class NCELossFn(torch.autograd.Function):
-    """NCELearnableTempLoss.forward (optimization/loss.py:134-141).  The kernel produces the loss and its
-    gradients in one pass; backward only applies the incoming scalar."""
+class _FusedLossFn(torch.autograd.Function):
+    """A loss whose library call produces the loss and its gradients in one pass; backward only applies the incoming scalar.
+    A subclass's forward returns ``_keep(ctx, loss, slots)``, ``slots`` holding one entry per forward argument: its gradient, or
+    ``None`` (an argument that is no tensor, or an operand the loss does not read)."""
 
     @staticmethod
-    def forward(ctx, vis, txt, log_scale):
-        loss, dv, dt, dls = H.nce_loss(vis.contiguous().float(), txt.contiguous().float(),
-                                       log_scale.detach().float().reshape(()))
-        ctx.save_for_backward(dv, dt, dls)
+    def _keep(ctx, loss, slots):
+        ctx.has = [g is not None for g in slots]
+        ctx.save_for_backward(*[g for g in slots if g is not None])
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        dv, dt, dls = ctx.saved_tensors
-        return dv * g, dt * g, dls * g
+        saved = iter(ctx.saved_tensors)
+        return tuple(next(saved) * g if h else None for h in ctx.has)
 
 
-class VscFcLossFn(torch.autograd.Function):
-    """NCELearnableTempLoss_vsc_fc.forward (optimization/loss.py:296-324); loss and gradients in one kernel pass."""
-
-    @staticmethod
-    def forward(ctx, vis, txt, img, cap, log_scale):
-        loss, *grads = H.vsc_fc_loss(vis.contiguous().float(), txt.contiguous().float(), img.contiguous().float(),
-                                     cap.contiguous().float(), log_scale.detach().float().reshape(()))
-        ctx.save_for_backward(*grads)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        return tuple(t * g for t in ctx.saved_tensors)
-
-
-class ContrastiveLossFn(torch.autograd.Function):
+class ContrastiveLossFn(_FusedLossFn):
     """Any loss of the learnable-temperature family (optimization/loss.py:126-324) by its ``XP_LOSS_*`` kind; loss and
     gradients in one kernel pass.  An operand the kind does not read gets no gradient (``None``): with ``vs_vc`` / ``vsc`` the
     frame pass of the video tower has no backward at all, as in the reference."""
@@ -1332,30 +1312,17 @@ class ContrastiveLossFn(torch.autograd.Function):
         def f(t):
             return None if t is None else t.contiguous().float()
         loss, *grads = H.contrastive_loss(kind, f(vis), f(txt), f(img), f(cap), log_scale=log_scale.detach().float().reshape(()))
-        ctx.has = [g is not None for g in grads]
-        ctx.save_for_backward(*[g for g in grads if g is not None])
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        saved = iter(ctx.saved_tensors)
-        return (None, *[next(saved) * g if h else None for h in ctx.has])
+        return _FusedLossFn._keep(ctx, loss, (None, *grads))
 
 
-class PairLossFn(torch.autograd.Function):
+class PairLossFn(_FusedLossFn):
     """One of the fixed-temperature losses (optimization/loss.py:22-124) by its ``XP_PAIR_*`` kind; loss and both feature
     gradients in one library call.  ``params``: the keyword arguments of ``hip_ops.pair_loss``."""
 
     @staticmethod
     def forward(ctx, kind, vis, txt, params):
         loss, dv, dt = H.pair_loss(kind, vis.contiguous().float(), txt.contiguous().float(), **params)
-        ctx.save_for_backward(dv, dt)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        dv, dt = ctx.saved_tensors
-        return None, dv * g, dt * g, None
+        return _FusedLossFn._keep(ctx, loss, (None, dv, dt, None))
 
 
 def _layer_params(layer):

@@ -8,6 +8,7 @@ Nothing here computes with torch ops.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 from typing import NamedTuple, Optional
 
@@ -675,54 +676,22 @@ def cast_back(src: torch.Tensor, out=None, accumulate=False) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------- loss
-def nce_loss(vis: torch.Tensor, txt: torch.Tensor, log_scale: torch.Tensor):
-    """Returns (loss, d_vis, d_txt, d_log_scale) -- fp32 device tensors."""
-    _chk(vis, "vis", torch.float32); _chk(txt, "txt", torch.float32); _chk(log_scale, "log_scale", torch.float32)
-    n, d = vis.shape
-    dev = vis.device
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dls = torch.empty((), dtype=torch.float32, device=dev)
-    dv, dt = torch.empty_like(vis), torch.empty_like(txt)
-    nb = L.lib().xp_nce_loss_workspace_bytes(n, d)
-    ws = workspace(nb, dev, "loss")
-    L.check(L.lib().xp_nce_loss(_p(vis), _p(txt), _p(log_scale), _p(loss), _p(dv), _p(dt), _p(dls), n, d, _p(ws),
-                                ws.numel(), _stream()), "xp_nce_loss")
-    return loss, dv, dt, dls
-
-
-def vsc_fc_loss(vis, txt, img, cap, log_scale):
-    """Returns (loss, d_vis, d_txt, d_img, d_cap, d_log_scale) -- fp32 device tensors."""
-    for t, name in ((vis, "vis"), (txt, "txt"), (img, "img"), (cap, "cap"), (log_scale, "log_scale")):
-        _chk(t, name, torch.float32)
-    n, d = vis.shape
-    if not (txt.shape == img.shape == cap.shape == vis.shape):
-        raise ValueError(f"vsc_fc_loss: feature shapes differ: {tuple(vis.shape)}, {tuple(txt.shape)}, "
-                         f"{tuple(img.shape)}, {tuple(cap.shape)}")          # loss.py:297 asserts text/cap only
-    dev = vis.device
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    dls = torch.empty((), dtype=torch.float32, device=dev)
-    grads = [torch.empty_like(vis) for _ in range(4)]
-    nb = L.lib().xp_vsc_fc_loss_workspace_bytes(n, d)
-    ws = workspace(nb, dev, "loss")
-    L.check(L.lib().xp_vsc_fc_loss(_p(vis), _p(txt), _p(img), _p(cap), _p(log_scale), _p(loss), _p(grads[0]),
-                                   _p(grads[1]), _p(grads[2]), _p(grads[3]), _p(dls), n, d, _p(ws), ws.numel(),
-                                   _stream()), "xp_vsc_fc_loss")
-    return (loss, *grads, dls)
-
-
-# XpLossKind -> (reads img, reads cap); an operand the kind does not read goes to the library as NULL
-_LOSS_OPERANDS = {L.XP_LOSS_NCE: (False, False), L.XP_LOSS_VSC_FC: (True, True), L.XP_LOSS_DSL: (False, False),
-                  L.XP_LOSS_VS_VC: (False, True), L.XP_LOSS_VS_VC_FC: (True, True), L.XP_LOSS_VSC: (False, True),
-                  L.XP_LOSS_VIDIMG: (True, True), L.XP_LOSS_VIDIMG_DIVIDE: (True, True)}
+@functools.lru_cache(maxsize=None)
+def loss_operands(kind: int):
+    """(reads img, reads cap) of an ``L.XP_LOSS_*`` kind, from the library's kind table (asked once per kind); an unknown kind is
+    refused"""
+    img, cap = C.c_int32(), C.c_int32()
+    L.check(L.lib().xp_contrastive_loss_operands(kind, C.byref(img), C.byref(cap)), "xp_contrastive_loss_operands")
+    return bool(img.value), bool(cap.value)
 
 
 def contrastive_loss(kind: int, vis, txt, img=None, cap=None, *, log_scale):
     """xp_contrastive_loss: any loss of the learnable-temperature family (``L.XP_LOSS_*``) and all its gradients in one call.
     vis/txt [n,d], img/cap [m,d].  Returns (loss, d_vis, d_txt, d_img, d_cap, d_log_scale) -- fp32 device tensors, ``None``
-    where the kind has no such operand (an ``img`` / ``cap`` it does not read is ignored).  What the kind itself rules out
-    (m != n, a missing operand, an unknown kind) is refused by the library before anything is launched."""
+    where the kind has no such operand (an ``img`` / ``cap`` it does not read is ignored; it goes to the library as NULL).  What
+    the kind itself rules out (m != n, a missing operand, an unknown kind) is refused by the library before anything is launched."""
     kind = int(kind)
-    use_img, use_cap = _LOSS_OPERANDS.get(kind, (img is not None, cap is not None))
+    use_img, use_cap = loss_operands(kind)
     img, cap = img if use_img else None, cap if use_cap else None
     ops = [(vis, "vis"), (txt, "txt"), (img, "img"), (cap, "cap")]
     for t, name in ops + [(log_scale, "log_scale")]:
@@ -771,6 +740,15 @@ def pair_loss(kind: int, vis, txt, *, temp=1.0, margin=0.0, max_violation=False,
     L.check(L.lib().xp_pair_loss(kind, C.byref(prm), _p(vis), _p(txt), _p(loss), _p(dv), _p(dt), n, d, _p(ws), ws.numel(), _stream()),
             "xp_pair_loss")
     return loss, dv, dt
+
+
+def sim_matrix(a: torch.Tensor, b: torch.Tensor, out=None) -> torch.Tensor:
+    """xp_sim_matrix: out[i][j] = a[i] . b[j] in fp32 of a [na, d] and b [nb, d], any device dtype (converted) and layout
+    (made contiguous); ``out``: a contiguous fp32 [na, nb] buffer to write into."""
+    a, b = _chk(a, "a").contiguous().float(), _chk(b, "b").contiguous().float()
+    out = _dest("sim_matrix", out, "out", torch.float32, (a.shape[0], b.shape[0]), a.device)
+    L.check(L.lib().xp_sim_matrix(_p(a), _p(b), _p(out), a.shape[0], b.shape[0], a.shape[1], _stream()), "xp_sim_matrix")
+    return out
 
 
 # --------------------------------------------------------------------------------------- attention

@@ -729,7 +729,7 @@ class CLIPModel(CLIPPreTrainedModel):
         logits_per_image = _Lazy(lambda: XF.SimLogitsFn.apply(text_embeds, image_embeds, self.logit_scale).T)
         loss = None          # the reference returns None as well unless return_loss (:1160-1162)
         if return_loss:      # clip_loss (:70-73) == NCELearnableTempLoss / 2, through the fused HIP loss kernel
-            loss = XF.NCELossFn.apply(image_embeds, text_embeds, self.logit_scale) * 0.5
+            loss = XF.ContrastiveLossFn.apply(XF.L.XP_LOSS_NCE, image_embeds, text_embeds, None, None, self.logit_scale) * 0.5
         out = CLIPOutput(loss=loss, logits_per_image=logits_per_image, logits_per_text=logits_per_text,
                          text_embeds=text_embeds, image_embeds=image_embeds, text_model_output=text_outputs,
                          vision_model_output=vision_outputs)

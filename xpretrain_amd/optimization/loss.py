@@ -1,9 +1,9 @@
 """Contrastive loss surface (reference: src/optimization/loss.py).
 
-``NCELearnableTempLoss`` (loss.py:126-141) is the hot-path loss: fused HIP kernel computing
+``NCELearnableTempLoss`` (loss.py:126-141) is the hot-path loss: fused HIP kernels computing
 exp(temp) * vis @ text^T, both cross-entropies and all gradients in one call
-(csrc/loss.hip).  The other learnable-temperature losses the reference drivers name (run_pretrain.py:355-363,
-run_video_retrieval.py:333) run through the same library path, one ``XP_LOSS_*`` kind each (xp_contrastive_loss).
+(csrc/loss_family.hip).  It and the other learnable-temperature losses the reference drivers name (run_pretrain.py:355-363,
+run_video_retrieval.py:333) run through one library path, one ``XP_LOSS_*`` kind each (xp_contrastive_loss).
 The four two-argument, fixed-temperature losses (loss.py:22-124, reached through the drivers' ``else: loss_func(vis_feat, text_feat)``
 branch) run through xp_pair_loss, one ``XP_PAIR_*`` kind each.
 ``build_loss_func(cfg)`` keeps the reference's factory signature (loss.py:326-328).
@@ -14,28 +14,6 @@ from torch import nn
 
 from .. import _lib as L
 from .. import functional as XF
-
-
-class NCELearnableTempLoss(nn.Module):
-    """loss = CE(exp(temp) * V T^T, diag) + CE(exp(temp) * T V^T, diag); `temp` is the LOG-scale parameter."""
-
-    def __init__(self, cfg=None):
-        super().__init__()
-
-    def forward(self, vis_feat, text_feat, temp):
-        return XF.NCELossFn.apply(vis_feat, text_feat, temp)
-
-
-class NCELearnableTempLoss_vsc_fc(nn.Module):
-    """Pre-training default (loss.py:288-324, pretrain_vip_base_16.json:75): video-(subtitle, caption) and
-    frame-caption contrast, six cross-entropy terms; same call signature as the reference."""
-
-    def __init__(self, cfg=None):
-        super().__init__()
-
-    def forward(self, vis_feat, text_feat, img_feat, cap_feat, temp):
-        assert text_feat.shape[0] == cap_feat.shape[0]                       # loss.py:297
-        return XF.VscFcLossFn.apply(vis_feat, text_feat, img_feat, cap_feat, temp)
 
 
 class _FamilyLoss(nn.Module):
@@ -49,6 +27,24 @@ class _FamilyLoss(nn.Module):
         return XF.ContrastiveLossFn.apply(self.kind, vis_feat, text_feat, img_feat, cap_feat, temp)
 
 
+class NCELearnableTempLoss(_FamilyLoss):
+    """loss = CE(exp(temp) * V T^T, diag) + CE(exp(temp) * T V^T, diag) (loss.py:126-141)."""
+    kind = L.XP_LOSS_NCE
+
+    def forward(self, vis_feat, text_feat, temp):
+        return XF.ContrastiveLossFn.apply(self.kind, vis_feat, text_feat, None, None, temp)
+
+
+class NCELearnableTempLoss_vsc_fc(_FamilyLoss):
+    """Pre-training default (loss.py:288-324, pretrain_vip_base_16.json:75): video-(subtitle, caption) and
+    frame-caption contrast, six cross-entropy terms; same call signature as the reference."""
+    kind = L.XP_LOSS_VSC_FC
+
+    def forward(self, vis_feat, text_feat, img_feat, cap_feat, temp):
+        assert text_feat.shape[0] == cap_feat.shape[0]                       # loss.py:297
+        return super().forward(vis_feat, text_feat, img_feat, cap_feat, temp)
+
+
 class VidImgNCELearnableTempLoss(_FamilyLoss):
     """loss.py:143-160: NCELearnableTempLoss over the concatenations [vis; img] and [text; cap] (img/cap may have another
     row count than vis/text)."""
@@ -60,13 +56,11 @@ class VidImgDivideNCELearnableTempLoss(_FamilyLoss):
     kind = L.XP_LOSS_VIDIMG_DIVIDE
 
 
-class NCELearnableTempDSLLoss(_FamilyLoss):
+class NCELearnableTempDSLLoss(NCELearnableTempLoss):
     """loss.py:185-202, the retrieval finetuning loss with the dual-softmax prior: each direction's logits are multiplied by
-    their softmax over the OTHER axis before the cross-entropy; the prior is not detached (its Jacobian is in the gradient)."""
+    their softmax over the OTHER axis before the cross-entropy; the prior is not detached (its Jacobian is in the gradient).
+    Two operands, as NCELearnableTempLoss."""
     kind = L.XP_LOSS_DSL
-
-    def forward(self, vis_feat, text_feat, temp):
-        return XF.ContrastiveLossFn.apply(self.kind, vis_feat, text_feat, None, None, temp)
 
 
 class NCELearnableTempLoss_vs_vc(_FamilyLoss):

@@ -21,10 +21,7 @@ def _f32(t, name):
 
 def cal_cossim(feats1: torch.Tensor, feats2: torch.Tensor) -> torch.Tensor:
     """sim[i][j] = feats1[i] . feats2[j]   (metrics.py:3-5)"""
-    a, b = _f32(feats1, "feats1"), _f32(feats2, "feats2")
-    sim = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
-    L.check(L.lib().xp_sim_matrix(H._p(a), H._p(b), H._p(sim), a.shape[0], b.shape[0], a.shape[1], H._stream()), "xp_sim_matrix")
-    return sim
+    return H.sim_matrix(_f32(feats1, "feats1"), _f32(feats2, "feats2"))
 
 
 def _col_softmax(sim: torch.Tensor, theta: float, multiply: bool) -> torch.Tensor:
