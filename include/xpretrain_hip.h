@@ -449,6 +449,26 @@ int xp_text_embed_fwd(const int64_t* ids, const float* tok, const float* pos, vo
  * written, in either mode: a longer position table keeps its other rows.  ids are not range-checked on the device. */
 int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_tok, float* d_pos,
                       int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, int32_t accumulate, void* stream);
+/* The same two with caller-given position_ids (:221-227, position_embedding(position_ids)); csrc/text_embed_pos.hip.  pos_ids is
+ * int64 [pos_B, Lt] with pos_B == 1 (one map shared by every sample) or pos_B == B (a map per sample); pos is the fp32 table
+ * [n_pos, D].  Lt is not bound by n_pos: only the ids are.
+ *     x[b,t] = tok[ids[b,t]] + pos[pos_ids[b % pos_B, t]]        one fp32 add, one rounding to `dtype`: xp_text_embed_fwd's
+ * so pos_ids[., t] == t gives xp_text_embed_fwd's bits.  A position id outside [0, n_pos) is decided on the device (no host
+ * synchronisation, no read outside the table): every element of that output row is NaN and the other rows are not affected; in
+ * the backward such a row adds to no row of d_pos and writes nowhere in it (d_tok does not look at pos_ids).  Token ids are not
+ * range-checked on the device, as in xp_text_embed_fwd / _bwd.
+ *     d_tok: the contract and the bits of xp_text_embed_bwd (all `vocab` rows cleared first with accumulate == 0)
+ *     d_pos[p] (+)= sum of dx[b,t] over the occurrences of p in pos_ids as the rows read it, in (b,t) row order: the first row that
+ *                  holds p adds all of p's rows, found 256 rows at a time -- fixed order, no atomics: bit-reproducible.
+ * accumulate == 0: all n_pos rows of d_pos are written (one hipMemsetAsync on `stream` clears them; the rows no id names stay
+ * zero); accumulate != 0: the rows no id names are untouched, the others take one add of the ordered sum.
+ * Refused before any launch (or memset): a null pointer, B / Lt / vocab < 1, pos_B not in {1, B}, D not a positive multiple of 4,
+ * n_pos < 1, B * Lt > INT32_MAX, a bad dtype. */
+int xp_text_embed_fwd_pos(const int64_t* ids, const int64_t* pos_ids, int64_t pos_B, const float* tok, const float* pos, void* x,
+                          int64_t B, int64_t Lt, int64_t D, int64_t vocab, int64_t n_pos, int32_t dtype, void* stream);
+int xp_text_embed_bwd_pos(const int64_t* ids, const int64_t* pos_ids, int64_t pos_B, const void* dx, float* d_tok, float* d_pos,
+                          int64_t B, int64_t Lt, int64_t D, int64_t vocab, int64_t n_pos, int32_t dtype, int32_t accumulate,
+                          void* stream);
 /* pooled[b] = x[b, idx[b]] (text: idx = ids.argmax(-1), :776 ; vision: idx = 0, :892) and its scatter */
 int xp_argmax_rows(const int64_t* ids, int64_t* idx, int64_t B, int64_t Lt, void* stream);
 int xp_gather_rows(const void* x, const int64_t* idx, void* out, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream);

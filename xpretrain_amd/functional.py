@@ -1170,6 +1170,27 @@ class TextEmbedFn(torch.autograd.Function):
         return None, d_tok, d_pos, None
 
 
+class TextEmbedPosFn(torch.autograd.Function):
+    """CLIPTextEmbeddings.forward with caller-given ``position_ids`` (modeling/CLIP_ViP.py:221-227):
+    token_embedding[ids] + position_embedding[pos_ids], ``pos_ids`` int64 ``[1 | B, Lt]`` on the GPU.  The position table's gradient
+    is a scatter with repeated indices, summed by the kernel in row order (bit-reproducible); ids equal to ``arange(Lt)`` give
+    TextEmbedFn's bits, forward and backward."""
+
+    @staticmethod
+    def forward(ctx, ids, pos_ids, tok_w, pos_w, dtype):
+        ids, pos_ids = ids.contiguous(), pos_ids.contiguous()
+        x = H.text_embed_fwd_pos(ids, pos_ids, tok_w.detach(), pos_w.detach(), dtype)
+        ctx.save_for_backward(ids, pos_ids)
+        ctx.meta = (tok_w.shape[0], pos_w.shape[0])
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        ids, pos_ids = ctx.saved_tensors
+        d_tok, d_pos = H.text_embed_bwd_pos(ids, pos_ids, dx.contiguous(), *ctx.meta)
+        return None, None, d_tok, d_pos, None
+
+
 # ------------------------------------------------------------------------------------------ small blocks
 class LayerNormFn(torch.autograd.Function):
     """nn.LayerNorm (pre_layrnorm :881, post_layernorm :893, final_layer_norm :772)."""

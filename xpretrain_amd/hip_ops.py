@@ -629,6 +629,39 @@ def text_embed_bwd(ids, dx, vocab, npos):
     return d_tok, d_pos
 
 
+def _pos_ids(pos_ids, B, Lt):
+    """pos_ids as the ``_pos`` entries read them: a contiguous int64 GPU tensor [pos_B, Lt], pos_B 1 or B; returns pos_B"""
+    _chk(pos_ids, "pos_ids", torch.int64)
+    if pos_ids.dim() != 2 or pos_ids.shape[1] != Lt or pos_ids.shape[0] not in (1, B) or not pos_ids.is_contiguous():
+        raise ValueError(f"pos_ids must be a contiguous [1, {Lt}] or [{B}, {Lt}] tensor, got {tuple(pos_ids.shape)}")
+    return pos_ids.shape[0]
+
+
+def text_embed_fwd_pos(ids, pos_ids, tok, pos, dtype):
+    """text_embed_fwd with caller-given position ids [1 | B, Lt] (xp_text_embed_fwd_pos): a row whose id is outside the table is NaN"""
+    _chk(ids, "ids", torch.int64)
+    B, Lt = ids.shape
+    pos_B = _pos_ids(pos_ids, B, Lt)
+    vocab, D = tok.shape
+    x = torch.empty((B * Lt, D), dtype=dtype, device=ids.device)
+    L.check(L.lib().xp_text_embed_fwd_pos(_p(ids), _p(pos_ids), pos_B, _p(tok), _p(pos), _p(x), B, Lt, D, vocab, pos.shape[0],
+                                          _DT[dtype], _stream()), "xp_text_embed_fwd_pos")
+    return x
+
+
+def text_embed_bwd_pos(ids, pos_ids, dx, vocab, npos):
+    """(d_tok [vocab, D], d_pos [npos, D]) of text_embed_fwd_pos (xp_text_embed_bwd_pos): ordered fp32 sums, every row written"""
+    _chk(ids, "ids", torch.int64)
+    B, Lt = ids.shape
+    pos_B = _pos_ids(pos_ids, B, Lt)
+    D = dx.shape[-1]
+    d_tok = torch.empty((vocab, D), dtype=torch.float32, device=dx.device)
+    d_pos = torch.empty((npos, D), dtype=torch.float32, device=dx.device)
+    L.check(L.lib().xp_text_embed_bwd_pos(_p(ids), _p(pos_ids), pos_B, _p(dx), _p(d_tok), _p(d_pos), B, Lt, D, vocab, npos, _dt(dx), 0,
+                                          _stream()), "xp_text_embed_bwd_pos")
+    return d_tok, d_pos
+
+
 def argmax_rows(ids):
     B, Lt = ids.shape
     idx = torch.empty(B, dtype=torch.int64, device=ids.device)

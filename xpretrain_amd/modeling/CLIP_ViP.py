@@ -179,9 +179,36 @@ class CLIPTextEmbeddings(nn.Module):
         self.position_embedding = nn.Embedding(config.max_position_embeddings, embed_dim)
         self.register_buffer("position_ids", torch.arange(config.max_position_embeddings).expand((1, -1)))
 
+    def position_rows(self, position_ids, B: int, Lt: int, device):
+        """Caller-given ``position_ids`` (reference :221-227) as the kernels read them: int64 ``[1 | B, Lt]`` on ``device``.
+        Accepted: ``[Lt]``, ``[1, Lt]`` (one map for every sample) or ``[B, Lt]`` (a map per sample), a list or a tensor of any
+        integer dtype, on the CPU or the GPU.  The shape is always checked; the values of a list or CPU tensor are checked against
+        the table here (ValueError); a GPU tensor's values are not read on the host -- the kernel decides, and a row whose id is
+        outside the table comes out NaN (xp_text_embed_fwd_pos)."""
+        n_pos = self.position_embedding.weight.shape[0]
+        try:
+            ids = position_ids if isinstance(position_ids, torch.Tensor) else torch.as_tensor(position_ids)
+        except (TypeError, ValueError, RuntimeError) as e:
+            raise ValueError(f"position_ids: not an integer array ({e})")
+        if ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
+            raise ValueError(f"position_ids: expected an integer dtype, got {ids.dtype}")
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(0)
+        if ids.dim() != 2 or ids.shape[1] != Lt or ids.shape[0] not in (1, B):
+            raise ValueError(f"position_ids: expected shape [{Lt}], [1, {Lt}] or [{B}, {Lt}] (input_ids is [{B}, {Lt}]), got "
+                             f"{tuple(position_ids.shape) if isinstance(position_ids, torch.Tensor) else tuple(ids.shape)}")
+        if not ids.is_cuda:
+            lo, hi = int(ids.min()), int(ids.max())
+            if lo < 0 or hi >= n_pos:
+                raise ValueError(f"position_ids: values span [{lo}, {hi}], outside the position table [0, {n_pos})")
+        return ids.to(device=device, dtype=torch.int64).contiguous()
+
     def forward(self, input_ids, position_ids=None, dtype=torch.bfloat16):
+        """``position_ids=None``: position t for column t, at most max_position_embeddings columns.  Given: ``position_rows``;
+        the sequence may then be longer than the table, as in the reference, as long as every id is inside it."""
         if position_ids is not None:
-            raise NotImplementedError("custom position_ids are not on the CLIP-ViP path (run_pretrain.py never passes them)")
+            rows = self.position_rows(position_ids, input_ids.shape[0], input_ids.shape[1], input_ids.device)
+            return XF.TextEmbedPosFn.apply(input_ids, rows, self.token_embedding.weight, self.position_embedding.weight, dtype)
         if input_ids.shape[-1] > self.position_embedding.weight.shape[0]:
             raise ValueError("sequence longer than max_position_embeddings")
         return XF.TextEmbedFn.apply(input_ids, self.token_embedding.weight, self.position_embedding.weight, dtype)
@@ -357,6 +384,14 @@ class CLIPTextTransformer(nn.Module):
         input_ids = input_ids.view(-1, input_ids.shape[-1]).contiguous()
         B, Lt = input_ids.shape
         D = self.config.hidden_size
+        if position_ids is not None:
+            # checked once, in front of every launch (ValueError): the ids themselves, and -- position_ids lift the bound of Lt by
+            # the table -- the sequence length against what the causal attention plan accepts, in the planner's own words
+            position_ids = self.embeddings.position_rows(position_ids, B, Lt, input_ids.device)
+            try:
+                XF.H.attn_plan(B, Lt, self.config.num_attention_heads, pad_mask=attention_mask, dtype=self.compute_dtype)
+            except RuntimeError as e:
+                raise ValueError(f"position_ids: a sequence of {Lt} tokens is not one the causal attention runs: {e}")
         x = self.embeddings(input_ids, position_ids, self.compute_dtype)
         pad = None if attention_mask is None else attention_mask.to(torch.int64).contiguous()
         idx = XF.H.argmax_rows(input_ids)
@@ -366,7 +401,9 @@ class CLIPTextTransformer(nn.Module):
             # the text tower is 256 rows: its WHOLE residual stream is kept in fp32 beside the bf16 rows the kernels read (the same
             # side-row mechanism as the video tower's proxy tokens, with every row a side row)
             emb = self.embeddings
-            side = XF.H.text_embed_fwd(input_ids, emb.token_embedding.weight.detach(), emb.position_embedding.weight.detach(), torch.float32)
+            tok_w, pos_w = emb.token_embedding.weight.detach(), emb.position_embedding.weight.detach()
+            side = (XF.H.text_embed_fwd(input_ids, tok_w, pos_w, torch.float32) if position_ids is None else
+                    XF.H.text_embed_fwd_pos(input_ids, position_ids, tok_w, pos_w, torch.float32))
             hs, hside = ([x], [side]) if output_hidden_states else (None, None)
             x, side = self.encoder(x, B, Lt, None, pad, hs, side, hside, collect_attn=attn)
             pooled = XF.LayerNormFn.apply(XF.GatherRowsFn.apply(x, idx, B, Lt), ln.weight, ln.bias,
