@@ -21,6 +21,23 @@
  *     directly from the fp32 master copy (biases, LayerNorm affine, embedding tables) are always float.
  *     Every bf16 store of an fp32 value is one round-to-nearest-even, subnormals included (see xp_cast).
  *   - sizes are int64_t elements; `ld*` are row strides in elements.
+ *   - Pointer alignment.  Every device pointer -- parameters and the pointer fields of the argument structs alike -- has one of two
+ *     classes per (entry, operand), stated in the `align[entry]` comment in front of each prototype:
+ *       need N   (N = 4, 8 or 16; `need 8/16`: 8 with bf16 storage, 16 with fp32 -- four elements per access)  the widest access a
+ *                kernel of the entry makes through that pointer, LDS-DMA loads included.  A base that is not N-byte aligned is
+ *                refused with XP_ERR_ARG on the host before anything is launched or written; xp_last_error() reads
+ *                "<entry>: <operand>=<address> is not N-byte aligned".  A NULL pointer is aligned; whether an operand may be
+ *                absent is the entry's own rule.
+ *       any      every element-aligned base is served: the kernels behind that operand touch it one element at a time, or choose a
+ *                wider path per call (per chunk, in the optimizer) only where every address involved allows it.  These are the
+ *                operands the host side itself hands over at arbitrary element offsets: the optimizer's tensors and gradients
+ *                (views of flat buffers), a launch table's slice of the norm partials, the rows xp_reduce_rows_batch sums,
+ *                xp_sim_matrix and the streamed retrieval's features (and the statistics slice a gallery shard is searched with),
+ *                the frame transforms' source bytes and output.
+ *     `all need 16` stands for every operand the comment does not name.  No kernel issues a vector access at an address that is not
+ *     a multiple of its width: what the hardware does with one is not something this library depends on.  Row pitches keep their
+ *     own rules (`ld % 4`, `% 8`): base and pitch together decide the alignment of every row.  tests/alignment_cases.py is this
+ *     table as data; tests/test_alignment_cpu.py holds the two together.
  */
 #ifndef XPRETRAIN_HIP_H
 #define XPRETRAIN_HIP_H
@@ -118,6 +135,9 @@ typedef struct XpGemmDesc {
   const int32_t* k_tiles; const int32_t* k_tile_begin; const int32_t* k_tile_begin_host;
 } XpGemmDesc;
 
+/* align[xp_gemm]: all need 16 */
+/* (every pointer field of the descriptor, under the name "desc.<field>"; desc.a_frames of decoded uint8 frames, a_frames_u8 = 1,
+ * need 8 as xp_im2col_u8's; k_tile_begin_host is host memory) */
 int xp_gemm(const XpGemmDesc* desc, void* stream);
 
 /* Split-K factor xp_gemm should be given for a weight-gradient-shaped problem (dW = dY^T X as computed by the
@@ -145,16 +165,19 @@ int64_t xp_gemm_colsum_rows(const XpGemmDesc* desc);
 int32_t xp_gemm_tile_rows(const XpGemmDesc* desc);
 
 /* out[i] (+)= sum_z slabs[z*n + i], fp32; accumulate != 0 adds into out (gradient accumulation). */
+/* align[xp_splitk_reduce]: all need 16 */
 int xp_splitk_reduce(const float* slabs, float* out, int64_t n, int32_t splits, int32_t accumulate, void* stream);
 
 /* Bias gradient: out[n] (+)= sum_m X[m*ldx + n]; workspace >= xp_colsum_workspace_bytes(). */
 size_t xp_colsum_workspace_bytes(int64_t rows, int64_t cols);
+/* align[xp_colsum]: all need 16 */
 int xp_colsum(const void* X, int64_t rows, int64_t cols, int64_t ldx, int32_t dtype, float* out,
               int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Deferred form: first level only.  partials[r*cols + n] = sum over the r-th chunk of rows of X[.][n];
  * xp_colsum_partial_rows(rows, cols) chunks.  Finish with xp_reduce_rows_batch. */
 int64_t xp_colsum_partial_rows(int64_t rows, int64_t cols);
+/* align[xp_colsum_partials]: all need 16 */
 int xp_colsum_partials(const void* X, int64_t rows, int64_t cols, int64_t ldx, int32_t dtype, float* partials,
                        size_t partials_bytes, void* stream);
 
@@ -169,17 +192,20 @@ typedef struct {
   int32_t accumulate, reserved;
 } XpReduceSeg;
 size_t xp_reduce_rows_batch_workspace_bytes(const XpReduceSeg* segs_host, int32_t n);
+/* align[xp_reduce_rows_batch]: any: segs_host[].in segs_host[].out workspace */
 int xp_reduce_rows_batch(const XpReduceSeg* segs_host, int32_t n, void* workspace, size_t workspace_bytes, void* stream);
 
 /* --------------------------------------------------------------------------------------- LayerNorm
  * nn.LayerNorm(eps=1e-5) of modeling/CLIP_ViP.py:404-406,855-857,720 (pre_layrnorm, layer_norm1/2,
  * post_layernorm, final_layer_norm).  Statistics in fp32; mean/rstd saved for the backward.
  */
+/* align[xp_layernorm_fwd]: need 8/16: x y; all need 16 */
 int xp_layernorm_fwd(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy,
                      float* mean, float* rstd, int64_t rows, int64_t cols, float eps, int32_t dtype, void* stream);
 /* The same with fp32 side rows of the residual stream (see XpGemmDesc::resid_side): row r with r % side_S < side_M is READ from
  * x_side[((r / side_S) * side_stride + r % side_S) * cols] (fp32) instead of x when x_side != NULL, and its fp32 result is ALSO
  * written to y_side (same indexing) when y_side != NULL (pre_layrnorm, CLIP_ViP.py:881: its output is the residual stream). */
+/* align[xp_layernorm_fwd_side]: need 8/16: x y; all need 16 */
 int xp_layernorm_fwd_side(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy,
                           float* mean, float* rstd, int64_t rows, int64_t cols, float eps, int32_t dtype,
                           const float* x_side, float* y_side, int64_t side_S, int32_t side_M, int32_t side_stride, void* stream);
@@ -193,11 +219,13 @@ size_t xp_layernorm_bwd_workspace_bytes(int64_t rows, int64_t cols);
  * colsum(dx) sums the fp32 values of dx BEFORE they are rounded to `dtype` (as the GEMM's fused column sums do): with bf16 it is
  * not the column sum of the stored dx.  dres may alias dx here too (same pointer and pitch: every row is read before it is written). */
 int64_t xp_layernorm_bwd_partial_rows(int64_t rows);
+/* align[xp_layernorm_bwd_partials]: need 8/16: dy x dres dx; all need 16 */
 int xp_layernorm_bwd_partials(const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* gamma,
                               const float* mean, const float* rstd, const void* dres, int64_t lddres,
                               void* dx, int64_t lddx, int32_t with_dx_colsum, int64_t rows, int64_t cols,
                               int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 /* dx = (dres ? dres : 0) + LN'(dy);  dgamma/dbeta (+)= column sums.  dres may alias dx. */
+/* align[xp_layernorm_bwd]: need 8/16: dy x dres dx; all need 16 */
 int xp_layernorm_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* gamma,
                      const float* mean, const float* rstd, const void* dres, int64_t lddres,
                      void* dx, int64_t lddx, float* dgamma, float* dbeta, int32_t accumulate,
@@ -205,11 +233,13 @@ int xp_layernorm_bwd(const void* dy, int64_t lddy, const void* x, int64_t ldx, c
                      void* workspace, size_t workspace_bytes, void* stream);
 /* The two backward forms with the fp32 side rows of x the forward normalised (xp_layernorm_fwd_side's x_side, same indexing): those
  * rows' x-hat is recomputed from the fp32 values, so the backward differentiates exactly the function the forward computed. */
+/* align[xp_layernorm_bwd_partials_side]: need 8/16: dy x dres dx; all need 16 */
 int xp_layernorm_bwd_partials_side(const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* gamma,
                                    const float* mean, const float* rstd, const void* dres, int64_t lddres,
                                    void* dx, int64_t lddx, int32_t with_dx_colsum, int64_t rows, int64_t cols,
                                    int32_t dtype, const float* x_side, int64_t side_S, int32_t side_M, int32_t side_stride,
                                    void* workspace, size_t workspace_bytes, void* stream);
+/* align[xp_layernorm_bwd_side]: need 8/16: dy x dres dx; all need 16 */
 int xp_layernorm_bwd_side(const void* dy, int64_t lddy, const void* x, int64_t ldx, const float* gamma,
                           const float* mean, const float* rstd, const void* dres, int64_t lddres,
                           void* dx, int64_t lddx, float* dgamma, float* dbeta, int32_t accumulate,
@@ -235,6 +265,7 @@ int xp_layernorm_bwd_side(const void* dy, int64_t lddy, const void* x, int64_t l
  */
 enum { XP_ATTN_PROXY = 0, XP_ATTN_CAUSAL = 1 };
 size_t xp_attn_workspace_bytes(int32_t mode, int64_t B, int64_t H, int64_t M, int64_t N, int64_t L);
+/* align[xp_attn_fwd]: all need 16 */
 int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, float* stats,
                 const int64_t* pad_mask, int32_t mode, int64_t B, int64_t H, int64_t S,
                 int64_t M, int64_t N, int64_t L, int32_t dtype,
@@ -245,6 +276,7 @@ int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ldo, float* s
  * a 4-byte device counter at the end of `workspace`, which this call resets with hipMemsetAsync on `stream` (the one operation of the
  * library besides kernel launches, event records and waits).  Everything else runs the dQ kernel, then the dK/dV kernel -- unless
  * the wide one-launch backward is switched on (below). */
+/* align[xp_attn_bwd]: all need 16 */
 int xp_attn_bwd(const void* qkv, int64_t ldqkv, const void* out, const void* dout, int64_t ldo,
                 const float* stats, const int64_t* pad_mask, void* dqkv, float q_scale,
                 int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
@@ -261,6 +293,7 @@ int32_t xp_get_attn_bwd_wide(void);
  * as one partial row: dqkv_colsum_partials[r * 3*H*64 + c], r < xp_attn_bwd_colsum_rows(...) -- finish with xp_reduce_rows_batch.
  * Saves the separate pass over dqkv.  xp_attn_bwd_colsum_rows() == 0 (fp32 mode): not available, pass NULL. */
 int64_t xp_attn_bwd_colsum_rows(int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype);
+/* align[xp_attn_bwd2]: all need 16 */
 int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, const void* dout, int64_t ldo,
                  const float* stats, const int64_t* pad_mask, void* dqkv, float q_scale,
                  int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
@@ -277,6 +310,7 @@ int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, const void* do
  *                  that column order), probs_proxy[B,H,M,S] = its second (:365-370: proxy queries over all keys).  The reference
  *                  computes both and drops them.  pad_mask must be NULL.
  * `dtype` is the storage of qkv; arithmetic is fp32.  No workspace; launches only on `stream`. */
+/* align[xp_attn_probs]: all need 16 */
 int xp_attn_probs(const void* qkv, int64_t ldqkv, const float* stats, const int64_t* pad_mask,
                   float* probs, float* probs_proxy, int32_t mode, int64_t B, int64_t H, int64_t S,
                   int64_t M, int64_t N, int64_t L, int32_t dtype, void* stream);
@@ -290,6 +324,7 @@ int xp_attn_probs(const void* qkv, int64_t ldqkv, const float* stats, const int6
  * arithmetic either way.  head_dim 64; no padding mask, no XP_ATTN_CAUSAL (the text tower pools at a per-sample EOS index and
  * is 0.6 % of the step's FLOPs). */
 size_t xp_attn_pooled_workspace_bytes(int64_t B, int64_t H, int64_t S, int32_t dtype);
+/* align[xp_attn_pooled_fwd]: all need 16 */
 int xp_attn_pooled_fwd(const void* q, const void* kv, int64_t ldkv, void* out, float* stats, int64_t B, int64_t H, int64_t S,
                        int32_t dtype, void* workspace, size_t workspace_bytes, void* stream);
 /* dq[b*lddq + h*64 + d] (already multiplied by q_scale, as xp_attn_bwd defines dq) and dkv[B, S, 2, H, 64] (row stride lddkv) for
@@ -298,6 +333,7 @@ int xp_attn_pooled_fwd(const void* q, const void* kv, int64_t ldkv, void* out, f
  * than xp_attn_pooled_colsum_rows_max(); finish with xp_reduce_rows_batch (the k_proj / v_proj bias gradients). */
 int64_t xp_attn_pooled_colsum_rows(int64_t B, int64_t H, int64_t S, int32_t dtype);
 int64_t xp_attn_pooled_colsum_rows_max(int64_t B, int64_t S);
+/* align[xp_attn_pooled_bwd]: all need 16 */
 int xp_attn_pooled_bwd(const void* q, const void* kv, int64_t ldkv, const void* out, const void* dout, const float* stats,
                        void* dq, int64_t lddq, void* dkv, int64_t lddkv, float q_scale, int64_t B, int64_t H, int64_t S,
                        int32_t dtype, void* workspace, size_t workspace_bytes, float* dkv_colsum_partials, void* stream);
@@ -306,11 +342,13 @@ int xp_attn_pooled_bwd(const void* q, const void* kv, int64_t ldkv, const void* 
  * CLIPVisionViPEmbeddings.forward (modeling/CLIP_ViP.py:168-197).
  */
 /* frames fp32 [BT,3,H,W] -> patch matrix [BT*gh*gw, 3*P*P] (dtype), k = (c,py,px): the conv-as-GEMM A operand */
+/* align[xp_im2col]: all need 16 */
 int xp_im2col(const float* video, void* patches, int64_t BT, int64_t H, int64_t W, int64_t P, int32_t dtype, void* stream);
 /* Same patch matrix straight from DECODED uint8 frames [BT,3,H,W]: (x/255 - mean[c]) / std[c] -- the host collate's
  * /255 + transforms.Normalize (datasets/dataloader.py:209-233) resp. ImageNorm on the device
  * (datasets/data_utils.py:256-281) -- fused with the cast and the patch gather.  mean/std: HOST
  * float[3]. */
+/* align[xp_im2col_u8]: need 8: frames; all need 16 */
 int xp_im2col_u8(const uint8_t* frames, const float* mean3_host, const float* std3_host, void* patches, int64_t BT,
                  int64_t H, int64_t W, int64_t P, int32_t dtype, void* stream);
 /* Raw decoded uint8 frames of ANY source resolution -> the fp32 model input, in one launch for a batch of videos: the CPU-worker
@@ -341,6 +379,7 @@ typedef struct {
   int32_t top, left;                            /* where the oh x ow output window sits in the resized image     */
   int32_t flip;                                 /* != 0: output column x shows resized column left + ow-1-x      */
 } XpFrameSrc;
+/* align[xp_frames_resize_norm]: any: videos_host[].src out */
 int xp_frames_resize_norm(const XpFrameSrc* videos_host, int32_t n_videos, const float* mean3_host,
                           const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream);
 /* The same launch with a choice of filter and an optional colour stage: the other two transform factories of the reference
@@ -382,6 +421,7 @@ typedef struct {
   int32_t color_op[3];                          /* XP_FRAMES_COLOR_*, in the order of application                */
   float color_factor[3];                        /* the factor of color_op[k]                                     */
 } XpFrameTransform;
+/* align[xp_frames_transform]: any: videos_host[].src out */
 int xp_frames_transform(const XpFrameTransform* videos_host, int32_t n_videos, const float* mean3_host,
                         const float* std3_host, float* out, int32_t oh, int32_t ow, void* stream);
 /* xp_frames_transform with an antialias filter: what torchvision >= 0.17 computes for Resize / RandomResizedCrop on a float tensor
@@ -409,10 +449,12 @@ int xp_frames_transform(const XpFrameTransform* videos_host, int32_t n_videos, c
  * BILINEAR2 the composite's, ceil(scale1 (taps2 - 1)) + taps1.  3840 -> 224 bicubic has 71. */
 #define XP_FRAMES_AA_MAX_TAPS 128
 size_t xp_frames_transform_aa_workspace_bytes(const XpFrameTransform* videos_host, int32_t n_videos, int32_t oh, int32_t ow);
+/* align[xp_frames_transform_aa]: any: videos_host[].src out; need 4: workspace */
 int xp_frames_transform_aa(const XpFrameTransform* videos_host, int32_t n_videos, const float* mean3_host,
                            const float* std3_host, float* out, int32_t oh, int32_t ow, void* workspace, size_t workspace_bytes,
                            void* stream);
 /* proxy rows: x[b, 0] = class_emb + pos[0]; x[b, 1+i] = added_cls[i] + pos[0]   (:187-191) */
+/* align[xp_vip_proxy_rows]: all need 16 */
 int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const float* pos, void* x,
                       int64_t B, int64_t S, int64_t M, int64_t D, int32_t dtype, void* stream);
 /* gradients of class_embedding, added_cls, position_embedding[1+L], time table [T,D] from dx[B,S,D], S = M + T*L; each is an
@@ -421,6 +463,7 @@ int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const floa
  * d_added may be NULL when M == 1; d_time may be NULL (then no workspace is needed), otherwise `workspace` holds at least
  * xp_vip_embed_bwd_workspace_bytes(B, T, L, D) bytes.  Every refusal comes before the first launch: a refused call writes nothing. */
 size_t xp_vip_embed_bwd_workspace_bytes(int64_t B, int64_t T, int64_t L, int64_t D);
+/* align[xp_vip_embed_bwd]: all need 16 */
 int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, float* d_pos, float* d_time,
                      int64_t B, int64_t M, int64_t T, int64_t L, int64_t D, int32_t dtype, int32_t accumulate,
                      void* workspace, size_t workspace_bytes, void* stream);
@@ -438,15 +481,19 @@ int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, float* d_po
  * weights skipped, one thread per element, no atomics: bit-reproducible.  gh == gw == g0 is an exact identity (weights 0, 1, 0, 0),
  * but callers are expected not to launch it.  No workspace.  Refused before any launch: a null or not 16-byte aligned pointer,
  * g0 / gh / gw outside [1, 16384], D not a positive multiple of 4. */
+/* align[xp_pos_resample_fwd]: all need 16 */
 int xp_pos_resample_fwd(const float* pos, float* out, int32_t g0, int32_t gh, int32_t gw, int32_t D, void* stream);
+/* align[xp_pos_resample_bwd]: all need 16 */
 int xp_pos_resample_bwd(const float* d_out, float* d_pos, int32_t g0, int32_t gh, int32_t gw, int32_t D, void* stream);
 /* CLIPTextEmbeddings.forward (:210-227): x[b,t] = tok[ids[b,t]] + pos[t] */
+/* align[xp_text_embed_fwd]: all need 16 */
 int xp_text_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void* x,
                       int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, void* stream);
 /* d_tok[id] (+)= sum of dx[b,t] over the occurrences of id in (b,t) order (fixed order, no atomics: bit-reproducible);
  * d_pos[t] (+)= sum_b dx[b,t].  The rows of d_tok whose id does not occur in ids are zero with accumulate == 0 (all `vocab` rows
  * are cleared by one hipMemsetAsync on `stream`) and are left untouched with accumulate != 0.  Only rows 0 .. Lt-1 of d_pos are
  * written, in either mode: a longer position table keeps its other rows.  ids are not range-checked on the device. */
+/* align[xp_text_embed_bwd]: all need 16 */
 int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_tok, float* d_pos,
                       int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, int32_t accumulate, void* stream);
 /* The same two with caller-given position_ids (:221-227, position_embedding(position_ids)); csrc/text_embed_pos.hip.  pos_ids is
@@ -464,26 +511,35 @@ int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_tok, float* d
  * zero); accumulate != 0: the rows no id names are untouched, the others take one add of the ordered sum.
  * Refused before any launch (or memset): a null pointer, B / Lt / vocab < 1, pos_B not in {1, B}, D not a positive multiple of 4,
  * n_pos < 1, B * Lt > INT32_MAX, a bad dtype. */
+/* align[xp_text_embed_fwd_pos]: all need 16 */
 int xp_text_embed_fwd_pos(const int64_t* ids, const int64_t* pos_ids, int64_t pos_B, const float* tok, const float* pos, void* x,
                           int64_t B, int64_t Lt, int64_t D, int64_t vocab, int64_t n_pos, int32_t dtype, void* stream);
+/* align[xp_text_embed_bwd_pos]: all need 16 */
 int xp_text_embed_bwd_pos(const int64_t* ids, const int64_t* pos_ids, int64_t pos_B, const void* dx, float* d_tok, float* d_pos,
                           int64_t B, int64_t Lt, int64_t D, int64_t vocab, int64_t n_pos, int32_t dtype, int32_t accumulate,
                           void* stream);
 /* pooled[b] = x[b, idx[b]] (text: idx = ids.argmax(-1), :776 ; vision: idx = 0, :892) and its scatter */
+/* align[xp_argmax_rows]: all need 16 */
 int xp_argmax_rows(const int64_t* ids, int64_t* idx, int64_t B, int64_t Lt, void* stream);
+/* align[xp_gather_rows]: all need 16 */
 int xp_gather_rows(const void* x, const int64_t* idx, void* out, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream);
+/* align[xp_scatter_rows]: all need 16 */
 int xp_scatter_rows(const void* dout, const int64_t* idx, void* dx, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream);
 /* x / ||x||_2 per row (:1148-1149); in `dtype`, out fp32 features; inv_norm saved.  No epsilon, like the reference's
  * x / x.norm(dim=-1, keepdim=True): a row of zeros gives inv_norm = +inf and a row of NaN in y (and in xp_l2norm_bwd's dx); the
  * other rows are not affected. */
+/* align[xp_l2norm_fwd]: all need 16 */
 int xp_l2norm_fwd(const void* x, float* y, float* inv_norm, int64_t rows, int64_t cols, int32_t dtype, void* stream);
+/* align[xp_l2norm_bwd]: all need 16 */
 int xp_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, void* dx, int64_t rows, int64_t cols,
                   int32_t dtype, void* stream);
 /* fp32 master -> compute dtype copy (n % 4 == 0).  To bf16 it is round-to-nearest-even: ties to the even mantissa, a carry may
  * reach the exponent, values from 0x7F7F8000 up round to infinity, infinities and the sign of zero are kept, a NaN stays a NaN, and
  * fp32 subnormals are NOT flushed: they round onto the bf16 subnormals (measured on MI355X, tests/test_embed_contract_gpu.py).
  * xp_cast_back widens exactly; with accumulate != 0 it is dst = src + dst, one add per element. */
+/* align[xp_cast]: all need 16 */
 int xp_cast(const float* src, void* dst, int64_t n, int32_t dtype, void* stream);
+/* align[xp_cast_back]: all need 16 */
 int xp_cast_back(const void* src, float* dst, int64_t n, int32_t dtype, int32_t accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------- Optimizer
@@ -515,10 +571,12 @@ typedef struct {
   float step_size;                      /* lr * sqrt(1-beta2^t) / (1-beta1^t) (or lr if !correct_bias)  */
 } XpAdamGroup;
 /* partials[c] = sum of squares of chunk c's gradient elements (fixed order, deterministic). */
+/* align[xp_grad_sqnorm_partials]: any: table[].p table[].m table[].v table[].shadow grads_host[] partials; all need 16 */
 int xp_grad_sqnorm_partials(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                             const void* const* grads_host, int32_t n_tensors, float* partials, void* stream);
 /* norm_partials (nullable): ALL chunks' partial sums of squares (n_norm_partials of them); max_norm <= 0: no
  * clipping; grad_norm_out (nullable): receives ||g||_2 before clipping. */
+/* align[xp_adamw_step]: any: table[].p table[].m table[].v table[].shadow grads_host[]; all need 16 */
 int xp_adamw_step(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                   const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                   const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
@@ -544,6 +602,7 @@ typedef struct {
   float one_minus_beta1;                /* 1-beta1 formed in double, then rounded: the weight torch's lerp_ gets (1 - 0.8f is not 0.2f) */
 } XpOptGroup;
 /* Arguments as for xp_adamw_step.  An unknown kind is refused before any launch. */
+/* align[xp_optim_step]: any: table[].p table[].m table[].v table[].shadow grads_host[]; all need 16 */
 int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                   const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                   const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
@@ -566,6 +625,7 @@ typedef struct {
   int32_t reserved;
   int64_t applied, skipped;             /* monotonic: each xp_step_verdict call adds 1 to exactly one of them                 */
 } XpStepVerdict;
+/* align[xp_step_verdict]: all need 16 */
 int xp_step_verdict(const float* partials, int32_t n_partials, XpStepVerdict* verdict, void* stream);
 /* Arguments as for xp_adamw_step / xp_optim_step, plus the verdict (device pointer, written by an earlier launch on an ordered stream).
  *   finite == 1: the twin's arithmetic, element for element, in the same rounding order; coef = min(1, max_norm / (verdict->norm + 1e-6)),
@@ -576,11 +636,13 @@ int xp_step_verdict(const float* partials, int32_t n_partials, XpStepVerdict* ve
  * grad_norm_out (nullable) receives verdict->norm in both cases.  The step count behind XpAdamGroup::step_size / XpOptGroup's bias
  * factors is the caller's: a skipped step must not count (optimization/multi_tensor.py takes the increment back).
  * A null verdict, an unknown kind and every argument error of the twin are refused before any launch. */
+/* align[xp_adamw_step_guarded]: any: table[].p table[].m table[].v table[].shadow grads_host[]; all need 16 */
 int xp_adamw_step_guarded(const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                           const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                           const XpAdamGroup* groups_host, int32_t n_groups, const float* norm_partials,
                           int32_t n_norm_partials, float max_norm, float* grad_norm_out,
                           const XpStepVerdict* verdict, void* stream);
+/* align[xp_optim_step_guarded]: any: table[].p table[].m table[].v table[].shadow grads_host[]; all need 16 */
 int xp_optim_step_guarded(int32_t kind, const XpAdamTensor* table, const int32_t* chunk_map, int32_t n_chunks,
                           const void* const* grads_host, const uint8_t* group_of_host, int32_t n_tensors,
                           const XpOptGroup* groups_host, int32_t n_groups, const float* norm_partials,
@@ -616,6 +678,7 @@ enum XpLossKind { XP_LOSS_NCE, XP_LOSS_VSC_FC, XP_LOSS_DSL, XP_LOSS_VS_VC, XP_LO
                   XP_LOSS_VSC, XP_LOSS_VIDIMG, XP_LOSS_VIDIMG_DIVIDE };
 int xp_contrastive_loss_operands(int32_t kind, int32_t* reads_img, int32_t* reads_cap);
 size_t xp_contrastive_loss_workspace_bytes(int32_t kind, int64_t n, int64_t m, int64_t d);
+/* align[xp_contrastive_loss]: all need 16 */
 int xp_contrastive_loss(int32_t kind, const float* vis, const float* txt, const float* img, const float* cap,
                         const float* log_scale, float* loss, float* d_vis, float* d_txt, float* d_img, float* d_cap,
                         float* d_log_scale, int64_t n, int64_t m, int64_t d,
@@ -655,6 +718,7 @@ typedef struct {
   int32_t max_violation, order_measure, hard_negative_num, bag;
 } XpPairLossParams;
 size_t xp_pair_loss_workspace_bytes(int32_t kind, const XpPairLossParams* params, int64_t n, int64_t d);
+/* align[xp_pair_loss]: all need 16 */
 int xp_pair_loss(int32_t kind, const XpPairLossParams* params, const float* vis, const float* txt, float* loss,
                  float* d_vis, float* d_txt, int64_t n, int64_t d, void* workspace, size_t workspace_bytes, void* stream);
 
@@ -667,8 +731,11 @@ int xp_pair_loss(int32_t kind, const XpPairLossParams* params, const float* vis,
  * xp_retrieval_ranks: query i = row i (transpose = 0) or column i (transpose != 0, the v2t direction, which the
  * reference evaluates on sim.T); label = labels[i] or i; greater[i] / equal[i] = number of candidates with a score
  * above / equal to the labelled one (the label sits at sorted positions greater .. greater+equal-1). */
+/* align[xp_sim_matrix]: any: a b sim */
 int xp_sim_matrix(const float* a, const float* b, float* sim, int64_t na, int64_t nb, int64_t d, void* stream);
+/* align[xp_dsl_rerank]: all need 16 */
 int xp_dsl_rerank(float* sim, int64_t n, int64_t m, float theta, int32_t multiply, void* stream);
+/* align[xp_retrieval_ranks]: all need 16 */
 int xp_retrieval_ranks(const float* sim, const int64_t* labels, int64_t n, int64_t m, int32_t transpose,
                        int32_t* greater, int32_t* equal, void* stream);
 
@@ -721,15 +788,19 @@ int xp_retrieval_ranks(const float* sim, const int64_t* labels, int64_t n, int64
 #define XP_DSL_OF_QUERIES 2
 int xp_retrieval_stream_plan(int64_t nq, int64_t ng, int32_t k, int32_t* stat_tiles_per_split, int32_t* topk_tiles_per_split);
 size_t xp_retrieval_ranks_streamed_workspace_bytes(int64_t nq, int64_t ng, int64_t d, int32_t dsl);
+/* align[xp_retrieval_ranks_streamed]: any: q g; all need 16 */
 int xp_retrieval_ranks_streamed(const float* q, const float* g, const int64_t* labels_q, const int64_t* labels_g, int64_t nq,
                                 int64_t ng, int64_t d, int32_t dsl, float theta, int32_t* greater_q, int32_t* equal_q,
                                 int32_t* greater_g, int32_t* equal_g, void* workspace, size_t workspace_bytes, void* stream);
 size_t xp_retrieval_topk_workspace_bytes(int64_t nq, int64_t ng, int64_t d, int32_t k);
+/* align[xp_retrieval_topk]: any: q g; all need 16 */
 int xp_retrieval_topk(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
                       int32_t accumulate, float* vals, int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
 size_t xp_retrieval_dsl_stats_workspace_bytes(int64_t n_over, int64_t n_of, int64_t d);
+/* align[xp_retrieval_dsl_stats]: any: over of; all need 16 */
 int xp_retrieval_dsl_stats(const float* over, const float* of, int64_t n_over, int64_t n_of, int64_t d, float theta,
                            int32_t accumulate, float* mx, float* sum, void* workspace, size_t workspace_bytes, void* stream);
+/* align[xp_retrieval_topk_dsl]: any: q g mx sum; all need 16 */
 int xp_retrieval_topk_dsl(const float* q, const float* g, int64_t nq, int64_t ng, int64_t d, int32_t k, int64_t index_base,
                           int32_t accumulate, float theta, int32_t stats_of, const float* mx, const float* sum, float* vals,
                           int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
@@ -773,6 +844,7 @@ typedef struct XpLayerFwd {
   float* side_x2;
 } XpLayerFwd;
 size_t xp_encoder_layer_fwd_workspace_bytes(const XpLayerDims* dims);
+/* align[xp_encoder_layer_fwd]: all need 16 */
 int xp_encoder_layer_fwd(const XpLayerFwd* args, void* stream);
 
 /* The rows of a layer's dx3 that can be non-zero, as tile lists (xp_encoder_layer_bwd_listed).  m_tiles: every 256-row tile that holds a listed k-tile of ANY of the three lists (padding tiles included: dW1 reads dpre, which is
@@ -801,6 +873,7 @@ typedef struct XpLayerBwd {
   const float* side_in; const float* side_x2; int64_t side_S; int32_t side_M; int32_t reserved;
 } XpLayerBwd;
 size_t xp_encoder_layer_bwd_workspace_bytes(const XpLayerDims* dims);
+/* align[xp_encoder_layer_bwd]: all need 16 */
 int xp_encoder_layer_bwd(const XpLayerBwd* args, void* stream);
 /* xp_encoder_layer_bwd for a dx3 that is zero outside a few rows, given as tile lists.  The caller vouches that args->dx3 is +-0
  * outside the 64-row k-tiles listed; the MLP / out_proj part of the backward then runs its three dX GEMMs (dpre, dh2, dattn) over
@@ -809,6 +882,7 @@ int xp_encoder_layer_bwd(const XpLayerBwd* args, void* stream);
  * product 0 * Inf poisons a weight gradient; the listed one never forms it.)  LayerNorm 2', attention', dh1, dWqkv, LayerNorm 1'
  * and the reductions stay dense.  Same workspace.  Needs the 256-wide-family plans of all six GEMMs (bf16, large shapes): an
  * error otherwise, nothing is launched dense in its place. */
+/* align[xp_encoder_layer_bwd_listed]: all need 16 */
 int xp_encoder_layer_bwd_listed(const XpLayerBwd* args, const XpDx3Support* dx3_support, void* stream);
 /* The LAST video-tower layer when only the pooled feature (token 0 of every sample, a proxy row) leaves the tower: the same
  * function of x as row b*S of xp_encoder_layer_fwd's x3, computed without the dead rows.  LayerNorm 1 and the K/V projection
@@ -834,6 +908,7 @@ typedef struct XpLayerPooledFwd {
   const float* side_in; float* side_out; float* side_x2;
 } XpLayerPooledFwd;
 size_t xp_encoder_layer_pooled_fwd_workspace_bytes(const XpLayerDims* dims);
+/* align[xp_encoder_layer_pooled_fwd]: all need 16 */
 int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* args, void* stream);
 
 typedef struct XpLayerPooledBwd {
@@ -851,6 +926,7 @@ typedef struct XpLayerPooledBwd {
   const float* side_in; const float* side_x2;
 } XpLayerPooledBwd;
 size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims* dims);
+/* align[xp_encoder_layer_pooled_bwd]: all need 16 */
 int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* args, void* stream);
 /* The library's second stream of the current device (the one xp_encoder_layer_bwd and xp_encoder_layer_pooled_bwd issue the
  * weight-gradient GEMMs on; created at the DEFAULT priority on first use -- a high-priority queue starves the critical chain as soon
@@ -863,6 +939,7 @@ void* xp_side_stream(void);
  * Hardware-layout probes used by tests/test_probe_gpu.py to pin the MFMA / LDS-transpose lane maps
  * this library relies on (out buffers are small device arrays; see csrc/probe.hip). */
 /* cycle-stamp trace of the 128x128 GEMM main loop (tools/gemm_trace.py); pass NULL to disable.  buffer: >= 1 KiB */
+/* align[xp_debug_set_gemm_trace]: all need 16 */
 int xp_debug_set_gemm_trace(void* device_buffer);
 /* In-step timing of ONE GEMM shape: while armed, every xp_gemm call with these (M, N, K, epilogue, operand layouts, split_k) is
  * bracketed by a pair of HIP events on the stream it is launched on (up to max_launches calls); ..._read disarms, waits for the events and
@@ -872,6 +949,7 @@ int xp_debug_gemm_timer_arm(int64_t M, int64_t N, int64_t K, int32_t epilogue, i
                             int32_t max_launches);
 int32_t xp_debug_gemm_timer_read(float* ms, int32_t cap);
 /* cycle stamps of one attention-forward workgroup (start, loads issued, loads landed, loop end); NULL disables */
+/* align[xp_debug_set_attn_trace]: all need 16 */
 int xp_debug_set_attn_trace(void* device_buffer);
 /* resident workgroups per CU of the default bf16 GEMM kernel at `lds_bytes` of dynamic LDS (occupancy API) */
 int xp_debug_gemm_occupancy(int lds_bytes);
@@ -957,16 +1035,22 @@ enum { XP_LAYER_GEMM_DPRE = 0,        /* dpre = (dx3 . W2) * act'(pre), with fc1
        XP_LAYER_GEMM_POOLED_COUNT = 10,
        XP_LAYER_GEMM_MAX = 10 };
 int32_t xp_debug_layer_bwd_gemms(const XpLayerDims* dims, int32_t pooled, XpGemmDesc* out, int32_t cap);
+/* align[xp_probe_mfma_bf16]: all need 16 */
 int xp_probe_mfma_bf16(const void* a, const void* b, float* c, void* stream);
+/* align[xp_probe_mfma_f32]: all need 16 */
 int xp_probe_mfma_f32(const float* a, const float* b, float* c, void* stream);
 /* packed-fp32 self-check (csrc/probe.hip): err[(variant*64 + lane)*2 + half] += mismatches between one v_pk_*_f32 form and
  * the same arithmetic in unpacked VALU instructions; 15 variants */
+/* align[xp_probe_pk_f32]: all need 16 */
 int xp_probe_pk_f32(void* err /*15*64*2 u32, zeroed by the caller*/, int32_t iters, int32_t blocks, uint32_t seed, void* stream);
 /* memory-bound copy of nbytes (multiple of 16) repeated iters times by `blocks` 256-thread workgroups: a one-GPU stand-in for a
  * collective's channel kernels beside the backward pass (hvd.DistributedOptimizer's all-reduce, run_pretrain.py:224-227) */
+/* align[xp_probe_stream_copy]: all need 16 */
 int xp_probe_stream_copy(void* dst, const void* src, int64_t nbytes, int32_t blocks, int32_t iters, void* stream);
 /* the same copy in a kernel with the register / LDS footprint of RCCL's gfx950 collective kernel (one wave per SIMD, 19,744 B LDS) */
+/* align[xp_probe_stream_copy_fat]: all need 16 */
 int xp_probe_stream_copy_fat(void* dst, const void* src, int64_t nbytes, int32_t blocks, int32_t iters, void* stream);
+/* align[xp_probe_tr16]: all need 16 */
 int xp_probe_tr16(const void* in /*4096 u16*/, const int32_t* lane_byte_off /*64*/, void* out /*64*4 u16*/, void* stream);
 
 #ifdef __cplusplus

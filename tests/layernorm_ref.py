@@ -141,8 +141,9 @@ BWD_WIDTHS = (8, 260, 512, 768, 1024)          # NJ = 1, 2, 2, 3, 4 (768: the on
 SIDES = ((60, (10, 3, 5)), (8, (1, 1, 1)))
 # a case with fewer rows than families (1 row; the pooled form's 5) starts at this family, so that over the widths of a sweep the
 # one-row cases meet every family: forward 4 .. 1024 -> normal, const, tight, offset, large, tight, outlier, offset;
-# backward 8, 260, 512, 768, 1024 -> const, large, tight, outlier, offset (normal: every longer case)
-SHORT_FIRST = {4: "normal", 8: "const", 252: "tight", 256: "offset", 260: "large", 512: "tight", 768: "outlier", 1020: "outlier",
+# backward 8, 260, 512, 768, 1024 -> const, large, tight, outlier, offset (normal: every longer case).  128 (in no sweep: the
+# five-row cases of tests/test_alignment_gpu.py at the alignment floor) -> offset
+SHORT_FIRST = {4: "normal", 8: "const", 128: "offset", 252: "tight", 256: "offset", 260: "large", 512: "tight", 768: "outlier", 1020: "outlier",
                1024: "offset"}
 BIG = 16395                                   # beyond both grid caps (forward 16384 rows, backward 8192)
 

@@ -1861,7 +1861,11 @@ int xp_attn_f32_bwd(const void* qkv, int64_t ldqkv, const void* out, const void*
                     int64_t M, int64_t N, int64_t L, float* delta_ws, hipStream_t st);
 
 static void* g_attn_trace = nullptr;
-extern "C" int xp_debug_set_attn_trace(void* device_buffer) { g_attn_trace = device_buffer; return XP_OK; }
+extern "C" int xp_debug_set_attn_trace(void* device_buffer) {
+  XP_REQUIRE_ALIGNED("xp_debug_set_attn_trace", 16, XP_P(device_buffer));
+  g_attn_trace = device_buffer;
+  return XP_OK;
+}
 
 extern "C" int xp_set_attn_bwd_wide(int32_t on) { g_attn_bwd_wide = on != 0; return XP_OK; }
 extern "C" int32_t xp_get_attn_bwd_wide(void) { return g_attn_bwd_wide; }
@@ -1878,6 +1882,7 @@ extern "C" int xp_attn_fwd(const void* qkv, int64_t ldqkv, void* out, int64_t ld
                            int64_t M, int64_t N, int64_t L, int32_t dtype,
                            void* workspace, size_t workspace_bytes, void* stream) {
   XP_REQUIRE(qkv && out && stats, "xp_attn_fwd: null pointer");
+  XP_REQUIRE_ALIGNED("xp_attn_fwd", 16, XP_P(qkv), XP_P(out), XP_P(stats), XP_P(pad_mask), XP_P(workspace));
   if (mode == XP_ATTN_CAUSAL) { M = 0; N = 1; L = S; }
   int rc = check_common("xp_attn_fwd", mode, B, H, S, M, N, L, ldqkv, ldo, dtype);
   if (rc) return rc;
@@ -1909,6 +1914,7 @@ extern "C" int xp_attn_bwd(const void* qkv, int64_t ldqkv, const void* out, cons
                            const float* stats, const int64_t* pad_mask, void* dqkv, float q_scale,
                            int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
                            void* workspace, size_t workspace_bytes, void* stream) {
+  XP_REQUIRE_ALIGNED("xp_attn_bwd", 16, XP_P(qkv), XP_P(out), XP_P(dout), XP_P(stats), XP_P(pad_mask), XP_P(dqkv), XP_P(workspace));
   return xp_attn_bwd2(qkv, ldqkv, out, dout, ldo, stats, pad_mask, dqkv, q_scale, mode, B, H, S, M, N, L, dtype, workspace,
                       workspace_bytes, nullptr, stream);
 }
@@ -1918,6 +1924,8 @@ extern "C" int xp_attn_bwd2(const void* qkv, int64_t ldqkv, const void* out, con
                             int32_t mode, int64_t B, int64_t H, int64_t S, int64_t M, int64_t N, int64_t L, int32_t dtype,
                             void* workspace, size_t workspace_bytes, float* dqkv_colsum_partials, void* stream) {
   XP_REQUIRE(qkv && out && dout && stats && dqkv, "xp_attn_bwd: null pointer");
+  XP_REQUIRE_ALIGNED("xp_attn_bwd2", 16, XP_P(qkv), XP_P(out), XP_P(dout), XP_P(stats), XP_P(pad_mask), XP_P(dqkv), XP_P(workspace),
+                     XP_P(dqkv_colsum_partials));
   XP_REQUIRE(!dqkv_colsum_partials || xp_attn_bwd_colsum_rows(mode, B, H, S, M, N, L, dtype) > 0,
              "xp_attn_bwd2: fused column sums are not available for this problem (xp_attn_bwd_colsum_rows() == 0)");
   if (mode == XP_ATTN_CAUSAL) { M = 0; N = 1; L = S; }

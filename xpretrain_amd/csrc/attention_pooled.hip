@@ -337,10 +337,10 @@ extern "C" int xp_attn_pooled_fwd(const void* q, const void* kv, int64_t ldkv, v
   XP_REQUIRE(q && kv && out && stats, "xp_attn_pooled_fwd: null pointer");
   int rc = check_pooled("xp_attn_pooled_fwd", B, H, S, ldkv, dtype);
   if (rc) return rc;
-  XP_REQUIRE(((uintptr_t)q | (uintptr_t)kv | (uintptr_t)out) % 16 == 0, "xp_attn_pooled_fwd: operands must be 16-byte aligned");
+  XP_REQUIRE_ALIGNED("xp_attn_pooled_fwd", 16, XP_P(q), XP_P(kv), XP_P(out), XP_P(stats), XP_P(workspace));
   PooledPlan pl;
   if ((rc = plan_pooled_for(B, H, S, false, 0, pl))) return rc;
-  XP_REQUIRE(workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= (size_t)pl.ws_bytes, "xp_attn_pooled_fwd: workspace too small");
+  XP_REQUIRE(workspace && workspace_bytes >= (size_t)pl.ws_bytes, "xp_attn_pooled_fwd: workspace too small");
   PP p{};
   p.q = q; p.kv = kv; p.ldkv = ldkv; p.out = out; p.stats = stats;
   p.ws_ml = reinterpret_cast<float*>(static_cast<char*>(workspace) + pl.ml.off);
@@ -365,11 +365,11 @@ extern "C" int xp_attn_pooled_bwd(const void* q, const void* kv, int64_t ldkv, c
   if (rc) return rc;
   if ((rc = check_pooled("xp_attn_pooled_bwd(dkv)", B, H, S, lddkv, dtype))) return rc;
   XP_REQUIRE(lddq >= H * DH, "xp_attn_pooled_bwd: dq row stride %lld < H*64", (long long)lddq);
-  XP_REQUIRE(((uintptr_t)q | (uintptr_t)kv | (uintptr_t)out | (uintptr_t)dout | (uintptr_t)dkv) % 16 == 0,
-             "xp_attn_pooled_bwd: operands must be 16-byte aligned");
+  XP_REQUIRE_ALIGNED("xp_attn_pooled_bwd", 16, XP_P(q), XP_P(kv), XP_P(out), XP_P(dout), XP_P(stats), XP_P(dq), XP_P(dkv), XP_P(workspace),
+                     XP_P(dkv_colsum_partials));
   PooledPlan pl;
   if ((rc = plan_pooled_for(B, H, S, true, 0, pl))) return rc;
-  XP_REQUIRE(workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= (size_t)pl.ws_bytes, "xp_attn_pooled_bwd: workspace too small");
+  XP_REQUIRE(workspace && workspace_bytes >= (size_t)pl.ws_bytes, "xp_attn_pooled_bwd: workspace too small");
   PP p{};
   p.q = q; p.kv = kv; p.ldkv = ldkv; p.out = const_cast<void*>(out); p.stats = const_cast<float*>(stats); p.dout = dout;
   p.dq = dq; p.lddq = lddq; p.dkv = dkv; p.lddkv = lddkv; p.cs = dkv_colsum_partials; p.q_scale = q_scale;

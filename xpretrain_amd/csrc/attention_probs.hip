@@ -131,6 +131,7 @@ extern "C" int xp_attn_probs(const void* qkv, int64_t ldqkv, const float* stats,
                              float* probs, float* probs_proxy, int32_t mode, int64_t B, int64_t H, int64_t S,
                              int64_t M, int64_t N, int64_t L, int32_t dtype, void* stream) {
   XP_REQUIRE(qkv && stats && probs, "xp_attn_probs: null pointer");
+  XP_REQUIRE_ALIGNED("xp_attn_probs", 16, XP_P(qkv), XP_P(stats), XP_P(pad_mask), XP_P(probs), XP_P(probs_proxy));
   XP_REQUIRE(dtype == XP_BF16 || dtype == XP_F32, "xp_attn_probs: bad dtype %d", dtype);
   XP_REQUIRE(mode == XP_ATTN_PROXY || mode == XP_ATTN_CAUSAL, "xp_attn_probs: bad mode %d", mode);
   XP_REQUIRE(B > 0 && H > 0 && S > 0, "xp_attn_probs: empty problem");

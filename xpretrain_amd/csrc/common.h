@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <initializer_list>
 #include "../../include/xpretrain_hip.h"
 
 typedef __bf16 bf16_t;
@@ -24,6 +25,25 @@ int xp_device_cus(const void* kernel = nullptr, int lds_bytes = 0);     // CUs o
 #define XP_REQUIRE(cond, ...)                                  \
   do {                                                         \
     if (!(cond)) { xp_set_error(__VA_ARGS__); return XP_ERR_ARG; } \
+  } while (0)
+
+// The pointer-alignment rule of the ABI (include/xpretrain_hip.h, "Pointer alignment"): every device pointer an entry receives is
+// checked on the host before the entry's first HIP call.  `bytes` is the operand's class there (need 4 / 8 / 16: the widest access
+// any kernel of the entry makes through that pointer); operands of class `any` are not checked, their kernels are element-wide.
+// A null pointer passes: whether an operand may be absent is the entry's own check.  The message names entry, operand and bytes.
+struct XpPtrName { const char* name; const void* ptr; };
+inline int xp_check_aligned(const char* fn, unsigned bytes, std::initializer_list<XpPtrName> ptrs) {
+  for (const XpPtrName& p : ptrs)
+    if (((uintptr_t)p.ptr & (bytes - 1)) != 0) {
+      xp_set_error("%s: %s=%p is not %u-byte aligned", fn, p.name, p.ptr, bytes);
+      return XP_ERR_ARG;
+    }
+  return XP_OK;
+}
+#define XP_P(p) XpPtrName{#p, (const void*)(p)}                    /* a parameter, under its header name */
+#define XP_REQUIRE_ALIGNED(fn, bytes, ...)                                           \
+  do {                                                                               \
+    if (int rc_al__ = xp_check_aligned(fn, bytes, {__VA_ARGS__})) return rc_al__;    \
   } while (0)
 
 #define XP_CHECK_LAUNCH(name)                                                   \

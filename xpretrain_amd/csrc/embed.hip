@@ -296,6 +296,7 @@ __global__ void cast_back_kernel(const T* __restrict__ src, float* __restrict__ 
 
 extern "C" int xp_im2col(const float* video, void* patches, int64_t BT, int64_t H, int64_t W, int64_t P, int32_t dtype, void* stream) {
   XP_REQUIRE(video && patches && BT > 0, "xp_im2col: null/empty");
+  XP_REQUIRE_ALIGNED("xp_im2col", 16, XP_P(video), XP_P(patches));
   XP_REQUIRE(P % 8 == 0 && H % P == 0 && W % P == 0, "xp_im2col: need P%%8==0 and H,W multiples of P (H=%lld W=%lld P=%lld)",
              (long long)H, (long long)W, (long long)P);
   hipStream_t st = (hipStream_t)stream;
@@ -311,7 +312,8 @@ extern "C" int xp_im2col_u8(const uint8_t* frames, const float* mean3_host, cons
   XP_REQUIRE(frames && patches && mean3_host && std3_host && BT > 0, "xp_im2col_u8: null/empty");
   XP_REQUIRE(P % 8 == 0 && H % P == 0 && W % P == 0, "xp_im2col_u8: need P%%8==0 and H,W multiples of P (H=%lld W=%lld P=%lld)",
              (long long)H, (long long)W, (long long)P);
-  XP_REQUIRE(((uintptr_t)frames & 7) == 0, "xp_im2col_u8: frames must be 8-byte aligned");
+  XP_REQUIRE_ALIGNED("xp_im2col_u8", 8, XP_P(frames));          // 8 pixels of a patch row per load
+  XP_REQUIRE_ALIGNED("xp_im2col_u8", 16, XP_P(patches));
   Norm3 nm;
   for (int c = 0; c < 3; ++c) {
     XP_REQUIRE(std3_host[c] > 0.f, "xp_im2col_u8: std[%d] must be positive", c);
@@ -328,6 +330,7 @@ extern "C" int xp_im2col_u8(const uint8_t* frames, const float* mean3_host, cons
 extern "C" int xp_vip_proxy_rows(const float* class_emb, const float* added_cls, const float* pos, void* x,
                                  int64_t B, int64_t S, int64_t M, int64_t D, int32_t dtype, void* stream) {
   XP_REQUIRE(class_emb && pos && x && (M == 1 || added_cls), "xp_vip_proxy_rows: null pointer");
+  XP_REQUIRE_ALIGNED("xp_vip_proxy_rows", 16, XP_P(class_emb), XP_P(added_cls), XP_P(pos), XP_P(x));
   XP_REQUIRE(B > 0 && M >= 1 && M <= S && D % 4 == 0, "xp_vip_proxy_rows: bad sizes");
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(B * M * D / 4);
@@ -346,6 +349,7 @@ extern "C" int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, 
                                 int64_t B, int64_t M, int64_t T, int64_t L, int64_t D, int32_t dtype, int32_t accumulate,
                                 void* workspace, size_t workspace_bytes, void* stream) {
   XP_REQUIRE(dx && d_class && d_pos && (M == 1 || d_added), "xp_vip_embed_bwd: null pointer");
+  XP_REQUIRE_ALIGNED("xp_vip_embed_bwd", 16, XP_P(dx), XP_P(d_class), XP_P(d_added), XP_P(d_pos), XP_P(d_time), XP_P(workspace));
   XP_REQUIRE(D % 4 == 0 && D <= 1024 && B > 0 && T > 0 && L > 0 && M >= 1, "xp_vip_embed_bwd: bad sizes (D<=1024, D%%4==0)");
   // every refusal comes before the first launch: a refused call writes nothing
   XP_REQUIRE(dtype == XP_BF16 || dtype == XP_F32, "xp_vip_embed_bwd: bad dtype %d", (int)dtype);
@@ -372,6 +376,7 @@ extern "C" int xp_vip_embed_bwd(const void* dx, float* d_class, float* d_added, 
 extern "C" int xp_text_embed_fwd(const int64_t* ids, const float* tok, const float* pos, void* x,
                                  int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, void* stream) {
   XP_REQUIRE(ids && tok && pos && x && B > 0 && Lt > 0 && D % 4 == 0 && vocab > 0, "xp_text_embed_fwd: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_text_embed_fwd", 16, XP_P(ids), XP_P(tok), XP_P(pos), XP_P(x));
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(B * Lt * D / 4);
   DISPATCH(dtype, (text_embed_fwd_kernel<bf16_t><<<g, TPB, 0, st>>>(ids, tok, pos, (bf16_t*)x, B * Lt, (int)Lt, (int)D)),
@@ -383,6 +388,7 @@ extern "C" int xp_text_embed_fwd(const int64_t* ids, const float* tok, const flo
 extern "C" int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_tok, float* d_pos,
                                  int64_t B, int64_t Lt, int64_t D, int64_t vocab, int32_t dtype, int32_t accumulate, void* stream) {
   XP_REQUIRE(ids && dx && d_tok && d_pos && B > 0 && Lt > 0 && D % 4 == 0 && vocab > 0, "xp_text_embed_bwd: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_text_embed_bwd", 16, XP_P(ids), XP_P(dx), XP_P(d_tok), XP_P(d_pos));
   XP_REQUIRE(dtype == XP_BF16 || dtype == XP_F32, "xp_text_embed_bwd: bad dtype %d", (int)dtype);     // before the memset: a refused call writes nothing
   hipStream_t st = (hipStream_t)stream;
   if (!accumulate) {
@@ -402,6 +408,7 @@ extern "C" int xp_text_embed_bwd(const int64_t* ids, const void* dx, float* d_to
 
 extern "C" int xp_argmax_rows(const int64_t* ids, int64_t* idx, int64_t B, int64_t Lt, void* stream) {
   XP_REQUIRE(ids && idx && B > 0 && Lt > 0, "xp_argmax_rows: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_argmax_rows", 16, XP_P(ids), XP_P(idx));
   argmax_rows_kernel<<<(unsigned)cdiv(B, 64), 64, 0, (hipStream_t)stream>>>(ids, idx, B, (int)Lt);
   XP_CHECK_LAUNCH("xp_argmax_rows");
   return XP_OK;
@@ -409,6 +416,7 @@ extern "C" int xp_argmax_rows(const int64_t* ids, int64_t* idx, int64_t B, int64
 
 extern "C" int xp_gather_rows(const void* x, const int64_t* idx, void* out, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream) {
   XP_REQUIRE(x && out && B > 0 && S > 0 && D % 4 == 0, "xp_gather_rows: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_gather_rows", 16, XP_P(x), XP_P(idx), XP_P(out));
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(B * D / 4);
   DISPATCH(dtype, (gather_rows_kernel<bf16_t><<<g, TPB, 0, st>>>((const bf16_t*)x, idx, (bf16_t*)out, B, S, (int)D)),
@@ -419,6 +427,7 @@ extern "C" int xp_gather_rows(const void* x, const int64_t* idx, void* out, int6
 
 extern "C" int xp_scatter_rows(const void* dout, const int64_t* idx, void* dx, int64_t B, int64_t S, int64_t D, int32_t dtype, void* stream) {
   XP_REQUIRE(dout && dx && B > 0 && S > 0 && D % 4 == 0, "xp_scatter_rows: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_scatter_rows", 16, XP_P(dout), XP_P(idx), XP_P(dx));
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(B * S * D / 4);
   DISPATCH(dtype, (scatter_rows_kernel<bf16_t><<<g, TPB, 0, st>>>((const bf16_t*)dout, idx, (bf16_t*)dx, B, S, (int)D)),
@@ -429,6 +438,7 @@ extern "C" int xp_scatter_rows(const void* dout, const int64_t* idx, void* dx, i
 
 extern "C" int xp_l2norm_fwd(const void* x, float* y, float* inv_norm, int64_t rows, int64_t cols, int32_t dtype, void* stream) {
   XP_REQUIRE(x && y && inv_norm && rows > 0 && cols > 0 && cols % 4 == 0, "xp_l2norm_fwd: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_l2norm_fwd", 16, XP_P(x), XP_P(y), XP_P(inv_norm));
   hipStream_t st = (hipStream_t)stream;
   const unsigned g = (unsigned)cdiv(rows, 4);
   DISPATCH(dtype, (l2norm_fwd_kernel<bf16_t><<<g, 256, 0, st>>>((const bf16_t*)x, y, inv_norm, rows, (int)cols)),
@@ -440,6 +450,7 @@ extern "C" int xp_l2norm_fwd(const void* x, float* y, float* inv_norm, int64_t r
 extern "C" int xp_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, void* dx, int64_t rows, int64_t cols,
                              int32_t dtype, void* stream) {
   XP_REQUIRE(dy && y && inv_norm && dx && rows > 0 && cols > 0 && cols % 4 == 0, "xp_l2norm_bwd: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_l2norm_bwd", 16, XP_P(dy), XP_P(y), XP_P(inv_norm), XP_P(dx));
   hipStream_t st = (hipStream_t)stream;
   const unsigned g = (unsigned)cdiv(rows, 4);
   DISPATCH(dtype, (l2norm_bwd_kernel<bf16_t><<<g, 256, 0, st>>>(dy, y, inv_norm, (bf16_t*)dx, rows, (int)cols)),
@@ -450,6 +461,7 @@ extern "C" int xp_l2norm_bwd(const float* dy, const float* y, const float* inv_n
 
 extern "C" int xp_cast(const float* src, void* dst, int64_t n, int32_t dtype, void* stream) {
   XP_REQUIRE(src && dst && n > 0 && n % 4 == 0, "xp_cast: need n %% 4 == 0 (n=%lld)", (long long)n);
+  XP_REQUIRE_ALIGNED("xp_cast", 16, XP_P(src), XP_P(dst));
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(n / 4);
   DISPATCH(dtype, (cast_kernel<bf16_t><<<g, TPB, 0, st>>>(src, (bf16_t*)dst, n / 4)),
@@ -460,6 +472,7 @@ extern "C" int xp_cast(const float* src, void* dst, int64_t n, int32_t dtype, vo
 
 extern "C" int xp_cast_back(const void* src, float* dst, int64_t n, int32_t dtype, int32_t accumulate, void* stream) {
   XP_REQUIRE(src && dst && n > 0 && n % 4 == 0, "xp_cast_back: need n %% 4 == 0");
+  XP_REQUIRE_ALIGNED("xp_cast_back", 16, XP_P(src), XP_P(dst));
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(n / 4);
   DISPATCH(dtype, (cast_back_kernel<bf16_t><<<g, TPB, 0, st>>>((const bf16_t*)src, dst, n / 4, accumulate)),

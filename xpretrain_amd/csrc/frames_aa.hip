@@ -384,7 +384,7 @@ extern "C" int xp_frames_transform_aa(const XpFrameTransform* videos_host, int32
   AaPlan p;
   if (int rc = aa_plan(fn, videos_host, n_videos, oh, ow, &p)) return rc;
   XP_REQUIRE(workspace, "%s: workspace is null", fn);
-  XP_REQUIRE(((uintptr_t)workspace & 3) == 0, "%s: workspace=%p is not 4-byte aligned", fn, workspace);
+  XP_REQUIRE_ALIGNED(fn, 4, XP_P(workspace));           // the tables are dwords; (src and out: class `any`, bytes / one float per access)
   XP_REQUIRE(workspace_bytes >= (size_t)p.words * 4, "%s: workspace_bytes=%zu is below the %lld bytes "
              "xp_frames_transform_aa_workspace_bytes reports", fn, workspace_bytes, (long long)p.words * 4);
 

@@ -486,7 +486,11 @@ extern "C" int xp_debug_gemm_occupancy(int lds_bytes) {
 }
 
 static unsigned long long* g_gemm_trace = nullptr;
-extern "C" int xp_debug_set_gemm_trace(void* device_buffer) { g_gemm_trace = (unsigned long long*)device_buffer; return XP_OK; }
+extern "C" int xp_debug_set_gemm_trace(void* device_buffer) {
+  XP_REQUIRE_ALIGNED("xp_debug_set_gemm_trace", 16, XP_P(device_buffer));
+  g_gemm_trace = (unsigned long long*)device_buffer;
+  return XP_OK;
+}
 
 // ---- in-step timing of ONE GEMM shape (bench.py's roofline: the dominant kernel timed where it runs, inside training steps) ----
 // While armed, every xp_gemm call whose (M, N, K, epilogue, operand layout, split) match is bracketed by a pair of HIP events on
@@ -616,15 +620,21 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
   XP_REQUIRE(a_contig % epc == 0 && b_contig % epc == 0 && d->lda % epc == 0 && d->ldb % epc == 0,
              "xp_gemm: contiguous extents / leading dims must be multiples of %d elements", epc);
   XP_REQUIRE(d->N % 4 == 0 && d->ldc % 4 == 0, "xp_gemm: N and ldc must be multiples of 4");
-  XP_REQUIRE(((uintptr_t)d->A | (uintptr_t)d->B | (uintptr_t)d->C) % 16 == 0, "xp_gemm: operands must be 16-byte aligned");
+  // every operand loader and epilogue moves 16 bytes per lane (LDS-DMA, buffer loads, 4- / 8-column epilogue rows); the uint8 frame
+  // gather moves 8 pixels
+#define XP_D(f) XpPtrName{"desc." #f, (const void*)d->f}
+  XP_REQUIRE_ALIGNED("xp_gemm", 16, XP_D(A), XP_D(B), XP_D(C), XP_D(bias), XP_D(resid), XP_D(aux), XP_D(tab1), XP_D(tab2), XP_D(colsum_partials),
+                     XP_D(resid_side), XP_D(out_side), XP_D(m_tiles), XP_D(k_tiles), XP_D(k_tile_begin));
+  XP_REQUIRE_ALIGNED("xp_gemm", d->a_frames_u8 ? 8u : 16u, XP_D(a_frames));
+#undef XP_D
   if (d->a_frames) {
     const int64_t P = d->fr_P, gh = P > 0 ? d->fr_H / P : 0, gw = P > 0 ? d->fr_W / P : 0;
     XP_REQUIRE(d->in_dtype == XP_BF16 && !d->a_kstrided && !d->b_kstrided && d->a_grp == 0 && (d->split_k <= 1),
                "xp_gemm: a_frames needs bf16 compute, k-contiguous operands, no row remap of A, no split-K");
     XP_REQUIRE(P > 0 && P % 8 == 0 && d->fr_H % P == 0 && d->fr_W % P == 0 && d->K == 3 * P * P && gh * gw > 0 && d->M % (gh * gw) == 0,
                "xp_gemm: a_frames needs P %% 8 == 0, H and W multiples of P, K == 3*P*P and M a multiple of the patches per frame");
-    XP_REQUIRE(((uintptr_t)d->a_frames & (d->a_frames_u8 ? 7 : 15)) == 0 && (d->a_frames_u8 ? d->fr_W % 8 == 0 : d->fr_W % 4 == 0),
-               "xp_gemm: a_frames must be 16-byte (fp32) / 8-byte (uint8) aligned with a row pitch that keeps 8-pixel strips aligned");
+    XP_REQUIRE(d->a_frames_u8 ? d->fr_W % 8 == 0 : d->fr_W % 4 == 0,
+               "xp_gemm: a_frames needs a row pitch that keeps 8-pixel strips aligned (fr_W %% 8 == 0 for uint8, %% 4 for fp32)");
     if (d->a_frames_u8) for (int c = 0; c < 3; ++c) XP_REQUIRE(d->fr_std[c] > 0.f, "xp_gemm: fr_std[%d] must be positive", c);
   }
   XP_REQUIRE(d->epilogue >= XP_EPI_NONE && d->epilogue <= XP_EPI_GELU_ERF_BWD, "xp_gemm: bad epilogue %d", d->epilogue);
@@ -647,12 +657,12 @@ extern "C" int xp_gemm(const XpGemmDesc* d, void* stream) {
     XP_REQUIRE(!(mlist && klist), "xp_gemm: m_tiles and k_tiles are for different operand layouts");
     if (mlist) {
       XP_REQUIRE(!d->a_kstrided && d->b_kstrided && split == 1, "xp_gemm: m_tiles is for the dX form (A k-contiguous, B k-strided, no split-K)");
-      XP_REQUIRE(d->m_tiles && d->n_m_tiles >= 1 && d->n_m_tiles <= plan.tiles_m && (uintptr_t)d->m_tiles % 4 == 0,
+      XP_REQUIRE(d->m_tiles && d->n_m_tiles >= 1 && d->n_m_tiles <= plan.tiles_m,
                  "xp_gemm: m_tiles needs 1..%d entries, got %d", plan.tiles_m, d->n_m_tiles);
       plan.grid = dim3(d->n_m_tiles * plan.tiles_n, 1, 1);
     } else {
       XP_REQUIRE(d->a_kstrided && d->b_kstrided && ep == XP_EPI_NONE, "xp_gemm: k_tiles is for the dW form (both operands k-strided, EPI_NONE)");
-      XP_REQUIRE(d->k_tiles && d->k_tile_begin && d->k_tile_begin_host && ((uintptr_t)d->k_tiles | (uintptr_t)d->k_tile_begin) % 4 == 0,
+      XP_REQUIRE(d->k_tiles && d->k_tile_begin && d->k_tile_begin_host,
                  "xp_gemm: k_tiles needs k_tile_begin and k_tile_begin_host");
       const int32_t* kb = d->k_tile_begin_host;
       XP_REQUIRE(kb[0] >= 0, "xp_gemm: k_tile_begin_host[0] is negative");

@@ -305,6 +305,10 @@ int check_dims(const char* name, const XpLayerDims& d) {
 
 }  // namespace
 
+// Every device pointer of a layer call's argument struct is 16-byte aligned (the GEMM, attention and LayerNorm entries the call
+// sequences ask it of their operands; checked here once, under the struct's field names, before anything is launched).
+#define XP_A(f) XpPtrName{"args." #f, (const void*)a->f}
+
 extern "C" void* xp_side_stream(void) {
   WgradSide* w = wgrad_side();
   return w ? (void*)w->side : nullptr;
@@ -330,6 +334,7 @@ extern "C" size_t xp_encoder_layer_fwd_workspace_bytes(const XpLayerDims* d) {
 
 extern "C" int xp_encoder_layer_fwd(const XpLayerFwd* a, void* st) {
   XP_REQUIRE(a, "xp_encoder_layer_fwd: null argument");
+  XP_REQUIRE_ALIGNED("xp_encoder_layer_fwd", 16, XP_A(x), XP_A(Wqkv), XP_A(Wo), XP_A(W1), XP_A(W2), XP_A(ln1_w), XP_A(ln1_b), XP_A(bqkv), XP_A(bo), XP_A(ln2_w), XP_A(ln2_b), XP_A(b1), XP_A(b2), XP_A(pad_mask), XP_A(h1), XP_A(qkv), XP_A(attn_o), XP_A(x2), XP_A(h2), XP_A(pre), XP_A(act), XP_A(x3), XP_A(mean1), XP_A(rstd1), XP_A(mean2), XP_A(rstd2), XP_A(stats), XP_A(workspace), XP_A(side_in), XP_A(side_out), XP_A(side_x2));
   const XpLayerDims& d = a->dims;
   int rc = check_dims("xp_encoder_layer_fwd", d);
   if (rc) return rc;
@@ -414,6 +419,13 @@ extern "C" int xp_encoder_layer_bwd_listed(const XpLayerBwd* a, const XpDx3Suppo
 
 static int encoder_layer_bwd(const XpLayerBwd* a, const XpDx3Support* sup, void* st) {
   XP_REQUIRE(a, "xp_encoder_layer_bwd: null argument");
+  const char* const fn = sup ? "xp_encoder_layer_bwd_listed" : "xp_encoder_layer_bwd";
+  XP_REQUIRE_ALIGNED(fn, 16, XP_A(x), XP_A(h1), XP_A(qkv), XP_A(attn_o), XP_A(x2), XP_A(h2), XP_A(pre), XP_A(act), XP_A(Wqkv), XP_A(Wo), XP_A(W1), XP_A(W2), XP_A(ln1_w), XP_A(ln2_w), XP_A(mean1), XP_A(rstd1), XP_A(mean2), XP_A(rstd2), XP_A(stats), XP_A(pad_mask), XP_A(dx3), XP_A(dx), XP_A(dln1_w), XP_A(dln1_b), XP_A(dwqkv), XP_A(dbqkv), XP_A(dwo), XP_A(dbo), XP_A(dln2_w), XP_A(dln2_b), XP_A(dw1), XP_A(db1), XP_A(dw2), XP_A(db2), XP_A(workspace), XP_A(side_in), XP_A(side_x2));
+  if (sup)
+    XP_REQUIRE_ALIGNED(fn, 16, XpPtrName{"dx3_support.m_tiles", sup->m_tiles}, XpPtrName{"dx3_support.k_tiles[0]", sup->k_tiles[0]},
+                       XpPtrName{"dx3_support.k_tiles[1]", sup->k_tiles[1]}, XpPtrName{"dx3_support.k_tiles[2]", sup->k_tiles[2]},
+                       XpPtrName{"dx3_support.k_tile_begin[0]", sup->k_tile_begin[0]}, XpPtrName{"dx3_support.k_tile_begin[1]", sup->k_tile_begin[1]},
+                       XpPtrName{"dx3_support.k_tile_begin[2]", sup->k_tile_begin[2]});
   const XpLayerDims& d = a->dims;
   int rc = check_dims("xp_encoder_layer_bwd", d);
   if (rc) return rc;
@@ -537,6 +549,7 @@ extern "C" size_t xp_encoder_layer_pooled_fwd_workspace_bytes(const XpLayerDims*
 
 extern "C" int xp_encoder_layer_pooled_fwd(const XpLayerPooledFwd* a, void* st) {
   XP_REQUIRE(a, "xp_encoder_layer_pooled_fwd: null argument");
+  XP_REQUIRE_ALIGNED("xp_encoder_layer_pooled_fwd", 16, XP_A(x), XP_A(Wqkv), XP_A(Wo), XP_A(W1), XP_A(W2), XP_A(ln1_w), XP_A(ln1_b), XP_A(bqkv), XP_A(bo), XP_A(ln2_w), XP_A(ln2_b), XP_A(b1), XP_A(b2), XP_A(h1), XP_A(kv), XP_A(mean1), XP_A(rstd1), XP_A(h1p), XP_A(q), XP_A(attn_o), XP_A(x2), XP_A(h2), XP_A(pre), XP_A(act), XP_A(x3), XP_A(mean1p), XP_A(rstd1p), XP_A(mean2), XP_A(rstd2), XP_A(stats), XP_A(workspace), XP_A(side_in), XP_A(side_out), XP_A(side_x2));
   const XpLayerDims& d = a->dims;
   int rc = check_pooled_dims("xp_encoder_layer_pooled_fwd", d);
   if (rc) return rc;
@@ -589,6 +602,7 @@ extern "C" size_t xp_encoder_layer_pooled_bwd_workspace_bytes(const XpLayerDims*
 
 extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) {
   XP_REQUIRE(a, "xp_encoder_layer_pooled_bwd: null argument");
+  XP_REQUIRE_ALIGNED("xp_encoder_layer_pooled_bwd", 16, XP_A(x), XP_A(h1), XP_A(kv), XP_A(h1p), XP_A(q), XP_A(attn_o), XP_A(x2), XP_A(h2), XP_A(pre), XP_A(act), XP_A(Wqkv), XP_A(Wo), XP_A(W1), XP_A(W2), XP_A(ln1_w), XP_A(ln2_w), XP_A(mean1), XP_A(rstd1), XP_A(mean1p), XP_A(rstd1p), XP_A(mean2), XP_A(rstd2), XP_A(stats), XP_A(dx3), XP_A(dx), XP_A(dln1_w), XP_A(dln1_b), XP_A(dwqkv), XP_A(dbqkv), XP_A(dwo), XP_A(dbo), XP_A(dln2_w), XP_A(dln2_b), XP_A(dw1), XP_A(db1), XP_A(dw2), XP_A(db2), XP_A(workspace), XP_A(side_in), XP_A(side_x2));
   const XpLayerDims& d = a->dims;
   int rc = check_pooled_dims("xp_encoder_layer_pooled_bwd", d);
   if (rc) return rc;
@@ -641,3 +655,4 @@ extern "C" int xp_encoder_layer_pooled_bwd(const XpLayerPooledBwd* a, void* st) 
                                            a->side_in, s1, s1, sM, w.ln1p_part, w.ln1p_bytes, st))) return rc;
   return finish_bwd(df, w.t.red, w.t.red_bytes, wg, st);
 }
+#undef XP_A

@@ -292,9 +292,29 @@ inline int bwd_blocks(int64_t rows) { int64_t b = cdiv(rows, WAVES * 4); return 
 
 }  // namespace
 
+namespace {
+// x and y are moved four elements per lane by the narrowest forward kernel (ln_fwd_kernel: 8 bytes in bf16, 16 in fp32; the 16-byte
+// bf16 kernel is chosen only where they are 16-byte aligned); gamma, beta and the side rows are read as float4 by every kernel
+int ln_fwd_aligned(const char* fn, const void* x, const float* gamma, const float* beta, const void* y, const float* mean,
+                   const float* rstd, const float* x_side, const float* y_side, int32_t dtype) {
+  XP_REQUIRE_ALIGNED(fn, dtype == XP_BF16 ? 8u : 16u, XP_P(x), XP_P(y));
+  XP_REQUIRE_ALIGNED(fn, 16, XP_P(gamma), XP_P(beta), XP_P(mean), XP_P(rstd), XP_P(x_side), XP_P(y_side));
+  return XP_OK;
+}
+// every backward kernel moves four elements per lane through dy, x, dres and dx, float4 through everything else
+int ln_bwd_aligned(const char* fn, const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
+                   const void* dres, const void* dx, const float* dgamma, const float* dbeta, const float* x_side, const void* workspace,
+                   int32_t dtype) {
+  XP_REQUIRE_ALIGNED(fn, dtype == XP_BF16 ? 8u : 16u, XP_P(dy), XP_P(x), XP_P(dres), XP_P(dx));
+  XP_REQUIRE_ALIGNED(fn, 16, XP_P(gamma), XP_P(mean), XP_P(rstd), XP_P(dgamma), XP_P(dbeta), XP_P(x_side), XP_P(workspace));
+  return XP_OK;
+}
+}  // namespace
+
 extern "C" int xp_layernorm_fwd(const void* x, int64_t ldx, const float* gamma, const float* beta, void* y, int64_t ldy,
                                 float* mean, float* rstd, int64_t rows, int64_t cols, float eps, int32_t dtype,
                                 void* stream) {
+  if (int rc = ln_fwd_aligned("xp_layernorm_fwd", x, gamma, beta, y, mean, rstd, nullptr, nullptr, dtype)) return rc;
   return xp_layernorm_fwd_side(x, ldx, gamma, beta, y, ldy, mean, rstd, rows, cols, eps, dtype, nullptr, nullptr, 0, 0, 0, stream);
 }
 
@@ -303,6 +323,7 @@ extern "C" int xp_layernorm_fwd_side(const void* x, int64_t ldx, const float* ga
                                      const float* x_side, float* y_side, int64_t side_S, int32_t side_M, int32_t side_stride,
                                      void* stream) {
   XP_REQUIRE(x && gamma && beta && y && mean && rstd, "xp_layernorm_fwd: null pointer");
+  if (int rc = ln_fwd_aligned("xp_layernorm_fwd_side", x, gamma, beta, y, mean, rstd, x_side, y_side, dtype)) return rc;
   XP_REQUIRE((!x_side && !y_side) || (side_S > 0 && side_M > 0 && side_M <= side_S && side_stride >= side_M && rows < ((int64_t)1 << 31) &&
                                       side_S < ((int64_t)1 << 31)),
              "xp_layernorm_fwd_side: side rows need 0 < side_M <= side_S and side_stride >= side_M");
@@ -313,8 +334,8 @@ extern "C" int xp_layernorm_fwd_side(const void* x, int64_t ldx, const float* ga
   const int blocks = (int)(cdiv(rows, WAVES) < 4096 ? cdiv(rows, WAVES) : 4096);
   hipStream_t st = (hipStream_t)stream;
   const bool half_rows = true;
-  const bool wide16 = dtype == XP_BF16 && cols % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 &&
-                      (((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)x_side | (uintptr_t)y_side) & 15) == 0;
+  // (gamma, beta and the side rows are 16-byte aligned here: ln_fwd_aligned refused anything else)
+  const bool wide16 = dtype == XP_BF16 && cols % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
   if (half_rows && wide16) {
     const int hb = (int)(cdiv(rows, 2 * WAVES) < 2048 ? cdiv(rows, 2 * WAVES) : 2048);
     const int nj = (int)cdiv(cols, 256);
@@ -373,6 +394,7 @@ extern "C" int xp_layernorm_bwd(const void* dy, int64_t lddy, const void* x, int
                                 void* dx, int64_t lddx, float* dgamma, float* dbeta, int32_t accumulate,
                                 int64_t rows, int64_t cols, int32_t dtype,
                                 void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ln_bwd_aligned("xp_layernorm_bwd", dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, nullptr, workspace, dtype)) return rc;
   return xp_layernorm_bwd_side(dy, lddy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, dgamma, dbeta, accumulate, rows, cols, dtype,
                                nullptr, 0, 0, 0, workspace, workspace_bytes, stream);
 }
@@ -384,6 +406,7 @@ extern "C" int xp_layernorm_bwd_side(const void* dy, int64_t lddy, const void* x
                                      const float* x_side, int64_t side_S, int32_t side_M, int32_t side_stride,
                                      void* workspace, size_t workspace_bytes, void* stream) {
   XP_REQUIRE(dgamma && dbeta, "xp_layernorm_bwd: null pointer");
+  if (int rc = ln_bwd_aligned("xp_layernorm_bwd_side", dy, x, gamma, mean, rstd, dres, dx, dgamma, dbeta, x_side, workspace, dtype)) return rc;
   hipStream_t st = (hipStream_t)stream;
   int rc = ln_bwd_launch("xp_layernorm_bwd", dy, lddy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, rows, cols, dtype, 0,
                          workspace, workspace_bytes, st, x_side, side_S, side_M, side_stride);
@@ -409,6 +432,7 @@ extern "C" int xp_layernorm_bwd_partials(const void* dy, int64_t lddy, const voi
                                          const float* mean, const float* rstd, const void* dres, int64_t lddres,
                                          void* dx, int64_t lddx, int32_t with_dx_colsum, int64_t rows, int64_t cols,
                                          int32_t dtype, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ln_bwd_aligned("xp_layernorm_bwd_partials", dy, x, gamma, mean, rstd, dres, dx, nullptr, nullptr, nullptr, workspace, dtype)) return rc;
   return ln_bwd_launch("xp_layernorm_bwd_partials", dy, lddy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, rows, cols, dtype,
                        with_dx_colsum, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -418,6 +442,8 @@ extern "C" int xp_layernorm_bwd_partials_side(const void* dy, int64_t lddy, cons
                                               void* dx, int64_t lddx, int32_t with_dx_colsum, int64_t rows, int64_t cols,
                                               int32_t dtype, const float* x_side, int64_t side_S, int32_t side_M, int32_t side_stride,
                                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ln_bwd_aligned("xp_layernorm_bwd_partials_side", dy, x, gamma, mean, rstd, dres, dx, nullptr, nullptr, x_side, workspace, dtype))
+    return rc;
   return ln_bwd_launch("xp_layernorm_bwd_partials_side", dy, lddy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, rows, cols, dtype,
                        with_dx_colsum, workspace, workspace_bytes, (hipStream_t)stream, x_side, side_S, side_M, side_stride);
 }

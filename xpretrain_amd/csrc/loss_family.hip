@@ -400,6 +400,8 @@ extern "C" int xp_contrastive_loss(int32_t kind, const float* vis, const float* 
   XP_REQUIRE(vis && txt && log_scale && loss && d_vis && d_txt && d_log_scale, "xp_contrastive_loss(%s): null pointer", k.name);
   XP_REQUIRE((!k.reads_img || (img && d_img)) && (!k.reads_cap || (cap && d_cap)),
              "xp_contrastive_loss(%s): null pointer (this kind reads %s)", k.name, k.reads_img ? "img and cap" : "cap");
+  XP_REQUIRE_ALIGNED("xp_contrastive_loss", 16, XP_P(vis), XP_P(txt), XP_P(img), XP_P(cap), XP_P(log_scale), XP_P(loss), XP_P(d_vis), XP_P(d_txt),
+                     XP_P(d_img), XP_P(d_cap), XP_P(d_log_scale), XP_P(workspace));
   XP_REQUIRE(n > 0 && m > 0 && d > 0 && (k.concat ? n + m : (n > m ? n : m)) <= 16384,
              "xp_contrastive_loss(%s): bad sizes n=%lld m=%lld d=%lld", k.name, (long long)n, (long long)m, (long long)d);
   XP_REQUIRE(m == n || k.concat || k.divide, "xp_contrastive_loss(%s): this kind needs m == n, got n=%lld m=%lld", k.name,

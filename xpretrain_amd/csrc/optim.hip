@@ -263,6 +263,9 @@ int check_and_fill(const char* name, const UpdateCall<Group>& u, bool guarded, U
   XP_REQUIRE(!guarded || u.verdict, "%s: null verdict (xp_step_verdict writes it, behind the partials of the whole step)", name);
   XP_REQUIRE(u.table && u.chunk_map && u.grads_host && u.group_of_host && u.groups_host && u.n_chunks > 0, "%s: null argument", name);
   XP_REQUIRE(u.n_tensors > 0 && u.n_tensors <= MAXT, "%s: n_tensors=%d not in 1..%d", name, u.n_tensors, MAXT);
+  if (int rc = xp_check_aligned(name, 16, {XpPtrName{"table", u.table}, XpPtrName{"chunk_map", u.chunk_map}, XpPtrName{"norm_partials", u.norm_partials},
+                                           XpPtrName{"grad_norm_out", u.grad_norm_out}, XpPtrName{"verdict", u.verdict}}))
+    return rc;
   XP_REQUIRE(u.n_groups > 0 && u.n_groups <= MAXG, "%s: n_groups=%d not in 1..%d", name, u.n_groups, MAXG);
   XP_REQUIRE(u.norm_partials || u.max_norm <= 0.f, "%s: max_norm > 0 needs the gradient-norm partials", name);
   XP_REQUIRE(!u.norm_partials || u.n_norm_partials > 0, "%s: n_norm_partials must be positive", name);
@@ -302,6 +305,10 @@ extern "C" int xp_grad_sqnorm_partials(const XpAdamTensor* table, const int32_t*
                                        const void* const* grads_host, int32_t n_tensors, float* partials, void* stream) {
   XP_REQUIRE(table && chunk_map && grads_host && partials && n_chunks > 0, "xp_grad_sqnorm_partials: null argument");
   XP_REQUIRE(n_tensors > 0 && n_tensors <= MAXT, "xp_grad_sqnorm_partials: n_tensors=%d not in 1..%d", n_tensors, MAXT);
+  // (the gradients and the tensors the table names: alignment class `any` -- the kernels take their 16-byte path per chunk only where
+  //  every pointer of the chunk allows it, else one float per access; partials: one float per workgroup, and a launch table of
+  //  optimization/multi_tensor.py writes its slice of the step's array from an arbitrary chunk on)
+  XP_REQUIRE_ALIGNED("xp_grad_sqnorm_partials", 16, XP_P(table), XP_P(chunk_map));
   NormArgs a;
   for (int i = 0; i < n_tensors; ++i) {
     XP_REQUIRE(grads_host[i], "xp_grad_sqnorm_partials: gradient %d is null", i);
@@ -333,6 +340,7 @@ extern "C" int xp_optim_step(int32_t kind, const XpAdamTensor* table, const int3
 extern "C" int xp_step_verdict(const float* partials, int32_t n_partials, XpStepVerdict* verdict, void* stream) {
   XP_REQUIRE(partials && verdict, "xp_step_verdict: null argument");
   XP_REQUIRE(n_partials > 0, "xp_step_verdict: n_partials=%d must be positive", n_partials);
+  XP_REQUIRE_ALIGNED("xp_step_verdict", 16, XP_P(partials), XP_P(verdict));
   verdict_kernel<<<1, NT, 0, (hipStream_t)stream>>>(partials, n_partials, verdict);
   XP_CHECK_LAUNCH("xp_step_verdict");
   return XP_OK;

@@ -290,6 +290,7 @@ extern "C" int xp_pair_loss(int32_t kind, const XpPairLossParams* params, const 
   const char* name = kind >= 0 && kind < kNumPairKinds ? kPairKinds[kind] : "?";
   XP_REQUIRE(!why, "xp_pair_loss(%s): %s (kind=%d n=%lld d=%lld)", name, why, (int)kind, (long long)n, (long long)d);
   XP_REQUIRE(vis && txt && loss && d_vis && d_txt, "xp_pair_loss(%s): null pointer", name);
+  XP_REQUIRE_ALIGNED("xp_pair_loss", 16, XP_P(vis), XP_P(txt), XP_P(loss), XP_P(d_vis), XP_P(d_txt), XP_P(workspace));
   const int64_t bag = params->bag, m = n * bag;
   const PairPlan plan = pair_plan(kind, n, bag);
   XP_REQUIRE(workspace && workspace_bytes >= plan.bytes, "xp_pair_loss(%s): workspace too small", name);

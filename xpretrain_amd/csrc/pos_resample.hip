@@ -107,8 +107,7 @@ int check_args(const char* fn, const void* in, const char* in_name, const void* 
                int D, int64_t rows, unsigned* blocks, int64_t* total) {
   XP_REQUIRE(in, "%s: %s is null", fn, in_name);
   XP_REQUIRE(out, "%s: %s is null", fn, out_name);
-  XP_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0, "%s: %s and %s must be 16-byte aligned (float4 rows)", fn,
-             in_name, out_name);
+  if (int rc = xp_check_aligned(fn, 16, {XpPtrName{in_name, in}, XpPtrName{out_name, out}})) return rc;      // float4 rows
   XP_REQUIRE(g0 >= 1 && g0 <= MAX_GRID, "%s: g0=%d not in 1..%d", fn, g0, MAX_GRID);
   XP_REQUIRE(gh >= 1 && gh <= MAX_GRID, "%s: gh=%d not in 1..%d", fn, gh, MAX_GRID);
   XP_REQUIRE(gw >= 1 && gw <= MAX_GRID, "%s: gw=%d not in 1..%d", fn, gw, MAX_GRID);

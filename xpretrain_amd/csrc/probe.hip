@@ -106,6 +106,7 @@ __global__ __launch_bounds__(256) void probe_stream_copy_kernel(u32x4* dst, cons
 }
 extern "C" int xp_probe_stream_copy(void* dst, const void* src, int64_t nbytes, int32_t blocks, int32_t iters, void* stream) {
   XP_REQUIRE(dst && src && nbytes >= 16 && blocks > 0 && iters > 0, "xp_probe_stream_copy: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_probe_stream_copy", 16, XP_P(dst), XP_P(src));
   probe_stream_copy_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>((u32x4*)dst, (const u32x4*)src, nbytes / 16, iters);
   XP_CHECK_LAUNCH("xp_probe_stream_copy");
   return XP_OK;
@@ -126,28 +127,33 @@ __global__ __launch_bounds__(256) void probe_stream_copy_fat_kernel(u32x4* dst, 
 }
 extern "C" int xp_probe_stream_copy_fat(void* dst, const void* src, int64_t nbytes, int32_t blocks, int32_t iters, void* stream) {
   XP_REQUIRE(dst && src && nbytes >= 16 && blocks > 0 && iters > 0, "xp_probe_stream_copy_fat: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_probe_stream_copy_fat", 16, XP_P(dst), XP_P(src));
   probe_stream_copy_fat_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>((u32x4*)dst, (const u32x4*)src, nbytes / 16, iters);
   XP_CHECK_LAUNCH("xp_probe_stream_copy_fat");
   return XP_OK;
 }
 
 extern "C" int xp_probe_pk_f32(void* err, int32_t iters, int32_t blocks, uint32_t seed, void* stream) {
+  XP_REQUIRE_ALIGNED("xp_probe_pk_f32", 16, XP_P(err));
   probe_pk_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>((unsigned*)err, iters, seed);
   XP_CHECK_LAUNCH("xp_probe_pk_f32");
   return XP_OK;
 }
 
 extern "C" int xp_probe_mfma_bf16(const void* a, const void* b, float* c, void* stream) {
+  XP_REQUIRE_ALIGNED("xp_probe_mfma_bf16", 16, XP_P(a), XP_P(b), XP_P(c));
   probe_mfma_bf16_kernel<<<1, 64, 0, (hipStream_t)stream>>>((const bf16x8*)a, (const bf16x8*)b, (f32x4*)c);
   XP_CHECK_LAUNCH("xp_probe_mfma_bf16");
   return XP_OK;
 }
 extern "C" int xp_probe_mfma_f32(const float* a, const float* b, float* c, void* stream) {
+  XP_REQUIRE_ALIGNED("xp_probe_mfma_f32", 16, XP_P(a), XP_P(b), XP_P(c));
   probe_mfma_f32_kernel<<<1, 64, 0, (hipStream_t)stream>>>(a, b, (f32x4*)c);
   XP_CHECK_LAUNCH("xp_probe_mfma_f32");
   return XP_OK;
 }
 extern "C" int xp_probe_tr16(const void* in, const int32_t* lane_byte_off, void* out, void* stream) {
+  XP_REQUIRE_ALIGNED("xp_probe_tr16", 16, XP_P(in), XP_P(lane_byte_off), XP_P(out));
   probe_tr16_kernel<<<1, 64, 0, (hipStream_t)stream>>>((const unsigned short*)in, lane_byte_off, (i16x4*)out);
   XP_CHECK_LAUNCH("xp_probe_tr16");
   return XP_OK;

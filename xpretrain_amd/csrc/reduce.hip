@@ -155,6 +155,7 @@ void xp_launch_rows_reduce(const float* in, float* out, int nrows, int nsum, int
 extern "C" int xp_splitk_reduce(const float* slabs, float* out, int64_t n, int32_t splits, int32_t accumulate,
                                 void* stream) {
   XP_REQUIRE(slabs && out && n > 0 && n % 4 == 0 && splits >= 1, "xp_splitk_reduce: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_splitk_reduce", 16, XP_P(slabs), XP_P(out));
   const int64_t n4 = n / 4;
   int blocks = (int)(cdiv(n4, 256) < 8192 ? cdiv(n4, 256) : 8192);
   splitk_reduce_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(slabs, out, n4, splits, accumulate);
@@ -167,6 +168,7 @@ extern "C" int64_t xp_colsum_partial_rows(int64_t rows, int64_t cols) { return c
 extern "C" int xp_colsum_partials(const void* X, int64_t rows, int64_t cols, int64_t ldx, int32_t dtype, float* partials,
                                   size_t partials_bytes, void* stream) {
   XP_REQUIRE(X && partials && rows > 0 && cols > 0 && cols % 4 == 0 && ldx % 4 == 0, "xp_colsum_partials: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_colsum_partials", 16, XP_P(X), XP_P(partials));
   const int csr = cs_rows(rows, cols), chunks = (int)cdiv(rows, csr);
   XP_REQUIRE(partials_bytes >= (size_t)chunks * cols * sizeof(float), "xp_colsum_partials: partials buffer too small");
   dim3 grid((unsigned)cdiv(cols, 256), chunks);
@@ -185,6 +187,7 @@ extern "C" size_t xp_colsum_workspace_bytes(int64_t rows, int64_t cols) {
 extern "C" int xp_colsum(const void* X, int64_t rows, int64_t cols, int64_t ldx, int32_t dtype, float* out,
                          int32_t accumulate, void* workspace, size_t workspace_bytes, void* stream) {
   XP_REQUIRE(X && out && rows > 0 && cols > 0 && cols % 4 == 0 && ldx % 4 == 0, "xp_colsum: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_colsum", 16, XP_P(X), XP_P(out), XP_P(workspace));
   XP_REQUIRE(workspace && workspace_bytes >= xp_colsum_workspace_bytes(rows, cols), "xp_colsum: workspace too small");
   const int csr = cs_rows(rows, cols), chunks = (int)cdiv(rows, csr);
   dim3 grid((unsigned)cdiv(cols, 256), chunks);
@@ -217,6 +220,7 @@ extern "C" int xp_reduce_rows_batch(const XpReduceSeg* segs_host, int32_t n, voi
   BatchArgs a;
   a.n = n;
   float* ws = (float*)workspace;
+  // (alignment class `any` for workspace, in and out: reduce_batch_kernel<1, .> moves one float per lane and access)
   // four columns per lane when every segment allows 16-byte accesses (widths, pitches and addresses multiples of 4 floats: every
   // segment the encoder layers pass); XPRETRAIN_DEBUG=rows_reduce_scalar keeps the one-column kernels (bit-identity test)
   bool vec = ((uintptr_t)workspace & 15) == 0 && !xp_debug_flag("rows_reduce_scalar");

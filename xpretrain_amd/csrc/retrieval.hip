@@ -42,6 +42,7 @@ __global__ void retrieval_ranks_kernel(const float* __restrict__ sim, const int6
 
 extern "C" int xp_dsl_rerank(float* sim, int64_t n, int64_t m, float theta, int32_t multiply, void* stream) {
   XP_REQUIRE(sim && n > 0 && m > 0, "xp_dsl_rerank: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_dsl_rerank", 16, XP_P(sim));
   dsl_rerank_kernel<<<(unsigned)m, 64, 0, (hipStream_t)stream>>>(sim, (int)n, (int)m, theta, multiply);
   XP_CHECK_LAUNCH("xp_dsl_rerank");
   return XP_OK;
@@ -50,6 +51,7 @@ extern "C" int xp_dsl_rerank(float* sim, int64_t n, int64_t m, float theta, int3
 extern "C" int xp_retrieval_ranks(const float* sim, const int64_t* labels, int64_t n, int64_t m, int32_t transpose,
                                   int32_t* greater, int32_t* equal, void* stream) {
   XP_REQUIRE(sim && greater && equal && n > 0 && m > 0 && n < (1 << 24) && m < (1 << 24), "xp_retrieval_ranks: bad arguments");
+  XP_REQUIRE_ALIGNED("xp_retrieval_ranks", 16, XP_P(sim), XP_P(labels), XP_P(greater), XP_P(equal));
   XP_REQUIRE(labels || n == m || (transpose ? m <= n : n <= m), "xp_retrieval_ranks: diagonal labels need a label for every query");
   const int64_t queries = transpose ? m : n;
   retrieval_ranks_kernel<<<(unsigned)queries, 64, 0, (hipStream_t)stream>>>(sim, labels, (int)n, (int)m, transpose, greater, equal);

@@ -638,6 +638,8 @@ extern "C" int xp_retrieval_ranks_streamed(const float* q, const float* g, const
                                            int32_t* greater_g, int32_t* equal_g, void* workspace, size_t workspace_bytes, void* stream) {
   const char* fn = "xp_retrieval_ranks_streamed";
   XP_REQUIRE(q && g, "%s: q or g is null", fn);
+  // (q and g: alignment class `any` -- load_row4<false> reads one float per access wherever `vec` below is false)
+  XP_REQUIRE_ALIGNED(fn, 16, XP_P(labels_q), XP_P(labels_g), XP_P(greater_q), XP_P(equal_q), XP_P(greater_g), XP_P(equal_g), XP_P(workspace));
   if (int rc = check_shape(fn, nq, ng, d)) return rc;
   XP_REQUIRE((greater_q != nullptr) == (equal_q != nullptr) && (greater_g != nullptr) == (equal_g != nullptr),
              "%s: a direction's greater and equal outputs come together", fn);
@@ -707,6 +709,9 @@ static int topk_call(const char* fn, const float* q, const float* g, int64_t nq,
                      int32_t accumulate, int mode, float theta, const float* mx, const float* sum, float* vals, int64_t* idx, void* workspace,
                      size_t workspace_bytes, void* stream) {
   XP_REQUIRE(q && g && vals && idx, "%s: q, g, vals or idx is null", fn);
+  // (q, g: class `any`, as above; mx, sum too: topk_kernel reads them one float per lane, and a gallery fed shard by shard gets
+  //  its slice of the per-gallery statistics -- utils/metrics.py callers pass st[a:b])
+  XP_REQUIRE_ALIGNED(fn, 16, XP_P(vals), XP_P(idx), XP_P(workspace));
   if (int rc = check_shape(fn, nq, ng, d)) return rc;
   XP_REQUIRE(k >= 1 && k <= XP_RETRIEVAL_MAX_K && k <= ng, "%s: k=%d is not in 1..min(%d, ng=%lld)", fn, k, XP_RETRIEVAL_MAX_K, (long long)ng);
   XP_REQUIRE(index_base >= 0 && index_base <= INT64_MAX - ng - 1, "%s: index_base=%lld out of range", fn, (long long)index_base);
@@ -763,6 +768,7 @@ extern "C" int xp_retrieval_dsl_stats(const float* over, const float* of, int64_
                                       int32_t accumulate, float* mx, float* sum, void* workspace, size_t workspace_bytes, void* stream) {
   const char* fn = "xp_retrieval_dsl_stats";
   XP_REQUIRE(over && of && mx && sum, "%s: over, of, mx or sum is null", fn);
+  XP_REQUIRE_ALIGNED(fn, 16, XP_P(mx), XP_P(sum), XP_P(workspace));                              // (over, of: class `any`, as above)
   if (int rc = check_shape(fn, n_over, n_of, d)) return rc;
   XP_REQUIRE(std::isfinite(theta), "%s: theta is not finite", fn);
   const RanksPlan p = ranks_plan(n_over, n_of, 1);

@@ -77,6 +77,9 @@ void xp_launch_small_gemm(const float* X, int64_t sxi, int64_t sxk, const float*
 }
 
 // logits A[n][n] = e^ls V T^T: the small form up to n = 128 (d a multiple of 4, 16-byte aligned rows), the tiled form beyond
+// (Both callers, xp_contrastive_loss and xp_pair_loss, refuse a vis / txt off 16 bytes before they get here, and their concatenated
+// operands are 256-byte aligned workspace pieces: the two address terms are always true today.  They stay as the kernel's own
+// precondition, next to d % 4, for a caller inside the library that does not come through those checks.)
 void xp_launch_logits(const float* vis, const float* txt, float* A, int64_t n, int64_t d, const float* log_scale, hipStream_t st) {
   if (n <= 128 && d % 4 == 0 && ((uintptr_t)vis & 15) == 0 && ((uintptr_t)txt & 15) == 0) {
     logits_small_kernel<<<(unsigned)cdiv(n * n, 4), 256, 0, st>>>(vis, txt, A, (int)n, (int)d, log_scale);
@@ -87,6 +90,7 @@ void xp_launch_logits(const float* vis, const float* txt, float* A, int64_t n, i
 
 extern "C" int xp_sim_matrix(const float* a, const float* b, float* sim, int64_t na, int64_t nb, int64_t d, void* stream) {
   XP_REQUIRE(a && b && sim && na > 0 && nb > 0 && d > 0, "xp_sim_matrix: bad arguments");
+  // alignment class `any` for a, b and sim: sgemm_strided_kernel reads and writes one float per lane and access
   xp_launch_small_gemm(a, d, 1, b, 1, d, sim, nb, (int)na, (int)nb, (int)d, nullptr, 0, (hipStream_t)stream);
   XP_CHECK_LAUNCH("xp_sim_matrix");
   return XP_OK;

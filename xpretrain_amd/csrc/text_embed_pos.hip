@@ -98,6 +98,7 @@ extern "C" int xp_text_embed_fwd_pos(const int64_t* ids, const int64_t* pos_ids,
                                      void* x, int64_t B, int64_t Lt, int64_t D, int64_t vocab, int64_t n_pos, int32_t dtype,
                                      void* stream) {
   if (int rc = check_args("xp_text_embed_fwd_pos", ids && pos_ids && tok && pos && x, pos_B, B, Lt, D, vocab, n_pos, dtype)) return rc;
+  XP_REQUIRE_ALIGNED("xp_text_embed_fwd_pos", 16, XP_P(ids), XP_P(pos_ids), XP_P(tok), XP_P(pos), XP_P(x));
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(B * Lt * D / 4);
   if (dtype == XP_BF16)
@@ -112,6 +113,7 @@ extern "C" int xp_text_embed_bwd_pos(const int64_t* ids, const int64_t* pos_ids,
                                      float* d_pos, int64_t B, int64_t Lt, int64_t D, int64_t vocab, int64_t n_pos, int32_t dtype,
                                      int32_t accumulate, void* stream) {
   if (int rc = check_args("xp_text_embed_bwd_pos", ids && pos_ids && dx && d_tok && d_pos, pos_B, B, Lt, D, vocab, n_pos, dtype)) return rc;
+  XP_REQUIRE_ALIGNED("xp_text_embed_bwd_pos", 16, XP_P(ids), XP_P(pos_ids), XP_P(dx), XP_P(d_tok), XP_P(d_pos));
   hipStream_t st = (hipStream_t)stream;
   if (!accumulate) {
     hipError_t e = hipMemsetAsync(d_tok, 0, (size_t)vocab * D * sizeof(float), st);

@@ -537,8 +537,14 @@ def grad_sink_key(params16):
 
 
 def _claim_sink(key, sink, numel, device, params):
-    """The sink of ``key`` if this layer call may write its gradients straight into it, else None (private buffer)."""
+    """The sink of ``key`` if this layer call may write its gradients straight into it, else None (private buffer).  A sink that
+    does not start on a 16-byte boundary is declined: the native layer backward asks
+    that of every gradient pointer (include/xpretrain_hip.h, "Pointer alignment"), and a reducer whose bucket holds an odd-sized
+    parameter -- the one-element logit_scale -- in front of a layer group puts the group's slice 4 bytes off.  The private buffer
+    and the reducer's pack copy take over: the same gradients."""
     if sink is None or sink.numel() != numel or sink.device != device or not all(p.grad is None for p in params):
+        return None
+    if sink.data_ptr() % 16:
         return None
     task = torch._C._current_graph_task_id()
     if task < 0 or _SINK_CLAIMS.get(key) == task:      # outside a backward pass / second application in this pass
